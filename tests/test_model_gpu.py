@@ -1034,6 +1034,23 @@ def test_engine_refuses_to_step_under_other_planning_options():
     eng.step_eager(); torch.cuda.synchronize()
 
 
+def test_engine_refuses_to_step_under_another_pwx_policy():
+    """Option pwx decides at plan time whether a stage's first block runs its shortcut and branch2c -- and its two input gradients -- as one
+    launch (hip.conv_pointwise2_ok): an engine planned under one value and stepped under another raises the plan-option error before any
+    launch, instead of reaching urso_conv_pointwise2 with a form it no longer takes."""
+    from ursonet_amd import hip
+    from ursonet_amd.engine import Engine
+    cfg = make_config("resnet50", 64, 128, batch=2, regress_ori=False, ori_bins=4, dtype="bfloat16")
+    img, loc, ori, _ = synthetic_batch(cfg, 2, seed=2)
+    eng = Engine(cfg, "training", seed=7, randomize_bn=True)
+    eng.load_batch(img, loc, ori)
+    with hip.options(pwx=0):
+        with pytest.raises(RuntimeError, match=r"options changed .*pwx \d+ -> 0") as e:
+            eng.step_eager()
+    assert not isinstance(e.value, hip.UrsoHipError)
+    eng.step_eager(); torch.cuda.synchronize()
+
+
 def test_urso_comm_bucket_averaging_one_rank(monkeypatch):
     """The C-ABI exchange step (urso_comm_*: RCCL bound at run time) with one rank: the average over one rank is the identity, the
     collective runs on the communicator's own stream ordered after the producer kernel, and urso_comm_wait orders the consumer
