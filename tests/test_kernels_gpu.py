@@ -298,7 +298,7 @@ def test_halo_conv_stream_k_schedule(shape, dt):
     z = _ref_conv(x, rnd(w, dt), 1, (1, 1), H, W) + bias
     ws = torch.zeros(hip.conv_igemm_halo_ws_bytes() // 4 + 16, dtype=torch.float32, device="cuda")
     xd, md = dev(x, dt), dev(msk, dt)
-    with hip.options(hconv=2, grid_cap=cap, c3=0):
+    with hip.options(hconv=2, hconv2=0, grid_cap=cap, c3=0):          # hconv2's cost model would take some of these shapes
         assert hip.conv_igemm_halo_ok(g, dt, hip.EPI_RELU)
         y0 = torch.empty(B, H, W, N, dtype=tdt, device="cuda")
         hip.conv_igemm(g, dt, hip.EPI_RELU, xd, wf, biasf, None, None, y0)                       # whole tiles per block
@@ -1114,7 +1114,7 @@ C3W_CASES = [
     (3, 17, 45, 128, 128, 3, 1, (1, 1), "c3w_ragged"),
     (2, 64, 96, 128, 128, 3, 1, (1, 1), "c3w_multi_tile"),
     (8, 64, 80, 128, 128, 3, 1, (1, 1), "c3w_stage3_rows"),
-    (2, 21, 50, 128, 128, 3, 1, (1, 1), "c3w_ragged_16"),          # 8 x 16 tiles with partial rows and columns on both borders
+    (2, 21, 50, 128, 128, 3, 1, (1, 1), "c3w_ragged_16"),          # both tile forms cover 68 % of the image: runs on 4 x 32 tiles (c3w_best_tw)
 ]
 
 

@@ -1120,7 +1120,8 @@ class Engine(object):
           * the producer's own data gradient is the compact-scatter form (GEMM over the sampled pixels, zeros elsewhere), and the 3x3
             layer below it takes that tensor as a scattered dz operand: its weight gradient runs over the even pixels only;
           * the residual branch hands the compact tensor to the fused backward pair (urso_conv_pair, add_h / add_w).
-        Where the residual side is not a fused pair (stages 4-5, pair option off) the dense form is produced once by urso_rows_expand2.
+        Where the residual side is not a fused pair (stages 4-5, pair option off) the dense form lives in a buffer zeroed once at
+        planning; each step writes only its even pixels with urso_rows_scatter2 (_plan_residual_handover).
         URSO_COMPACT_GRAD=0 keeps the dense path everywhere."""
         g, dt, B, dev = self.graph, self.dt, self.B, self.device
         if dt == hip.F32 or not getattr(self.config, "COMPACT_GRADIENTS", True) or not self._env_compact_grad:
@@ -1147,7 +1148,7 @@ class Engine(object):
             rc = [c for c in convs if c.src is R]
             if len(rc) != 1 or sum(1 for c in convs if c.res is R) != 1:
                 continue
-            X.residual_needs_dense = self.pair_first.get(rc[0].name) is None or R.bits is None     # stages 4-5: expanded (urso_rows_expand2)
+            X.residual_needs_dense = self.pair_first.get(rc[0].name) is None or R.bits is None     # stages 4-5: scattered into a dense buffer (urso_rows_scatter2)
             H, W = X.spec.h, X.spec.w
             gd_ok = True
             for c in cons:

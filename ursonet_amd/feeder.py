@@ -6,8 +6,8 @@ images through a queue.  At ~2,800 images/s per GPU that design cannot keep up (
 PCIe alone is 2.3 ms of an 11.4 ms step).  Here:
   * workers (threads: image decode / synthesis and NumPy release the GIL) only produce the RAW sample -- uint8 frame + pose;
   * everything per-pixel runs batched on the GPU: sim2real stages, camera / in-plane rotation warps (one urso_warp_perspective for
-    the minibatch), target re-encoding (urso_encode_ori), zero padding (urso_pad_images_u8); mean subtraction + cast are the
-    engine's first kernel (urso_mold_images reads uint8);
+    the minibatch) and target re-encoding (urso_encode_ori); resize / zero padding stay on the host (finish_sample:
+    utils.resize_image); mean subtraction + cast are the engine's first kernel (urso_mold_images reads uint8);
   * uint8 frames go host -> device from PINNED memory on a side stream into a double buffer while the previous step computes:
     31 MB instead of 126 MB per step, off the critical path.
 `data_generator` keeps the reference's signature and yield format on top of the same pieces.
