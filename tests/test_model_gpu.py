@@ -1130,13 +1130,14 @@ def test_bench_under_torchrun_with_forced_collectives_one_rank():
     --gpus 1` with URSO_DP_FORCE_COLLECTIVES=1 runs the REAL data-parallel path (rendezvous on 127.0.0.1, RCCL communicator, weight
     broadcast, segmented hipGraphs, one RCCL all-reduce per gradient bucket, join before the optimizer).  The JSON line must carry the
     dp record (exposed_comm_ms, bucket_bytes summing to 4 bytes x parameters) and a throughput within 5 % of the plain single-process
-    run (a one-rank all-reduce is a copy: the segmentation itself must cost next to nothing)."""
+    run (a one-rank all-reduce is a copy: the segmentation itself must cost next to nothing).  Both runs pass --full: a plain run leaves
+    the dp record out."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--pcie-steps", "0", "--profile-steps", "1"]
+    common = ["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--pcie-steps", "0", "--profile-steps", "1"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("URSO_DP_FORCE_COLLECTIVES", None)
     env["URSO_WGRAD_STREAM"] = "0"        # like with like: data-parallel plans keep the single chain (Engine._fork_weight_gradients)
@@ -1162,6 +1163,41 @@ def test_bench_under_torchrun_with_forced_collectives_one_rank():
                    if wn not in ("moving_mean", "moving_variance"))
     assert sum(d["dp"]["bucket_bytes"]) == 4 * n_params
     assert abs(d["value"] / p["value"] - 1.0) < 0.05, (d["value"], p["value"])
+
+
+def test_bench_plain_run_leaves_the_full_records_out(tmp_path):
+    """A plain `bench.py` run does only what its headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  The
+    records that take runs of their own (fork_check, roofline, kernels, pcie_inclusive, dp, cpu_baseline) are null there and present
+    with --full.  The forked-against-single-chain check that --full runs before timing leaves what the timed steps compute unchanged:
+    both runs dump the same arrays, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("URSO_WGRAD_STREAM", "URSO_DP_FORCE_COLLECTIVES", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    common = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--pcie-steps", "2", "--profile-steps", "1"])):
+        r = subprocess.run([sys.executable] + common + extra + ["--dump-outputs", str(tmp_path / mode)], cwd=root, env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines[mode] = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    p, f = lines["plain"], lines["full"]
+    for d in (p, f):
+        assert d["metric"] == "images/sec fwd+bwd ResNet50 640x512 bs32/GPU" and d["unit"] == "images/sec" and d["dtype"] == "bf16"
+        assert d["higher_is_better"] is True and d["steps"] == 3 and d["warmup"] == 1
+        assert d["value"] > 0 and abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+        assert d["dumped_outputs"] is not None and d["dp"] is None and d["cpu_baseline"] is None
+    assert p["full"] is False and f["full"] is True
+    assert p["roofline"] is None and p["kernels"] is None and p["pcie_inclusive"] is None and p["config"]["fork_check"] is None
+    assert f["roofline"]["top5"] and f["kernels"] and f["pcie_inclusive"]["steps"] == 2
+    assert f["config"]["fork_check"]["steps"] == 3
+    assert p["dumped_outputs"]["arrays"] == f["dumped_outputs"]["arrays"]
+    for name in p["dumped_outputs"]["arrays"]:
+        a, b = np.load(str(tmp_path / "plain" / (name + ".npy"))), np.load(str(tmp_path / "full" / (name + ".npy")))
+        assert a.shape == b.shape and np.array_equal(a, b), name
 
 
 @pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
