@@ -571,6 +571,26 @@ int urso_quat_wavg_decode(int B, int K, const float* logits_d, const float* hqua
                           float* q_d, float* a_d, void* stream);
 
 /*
+ * EM fit of a mixture of "Gaussians on the rotation group" to orientation PMFs (pose_estimator.py:42-154,
+ * fit_GMM_to_orientation), batched on the GPU: B independent fits, one workgroup each.  in_d = logits (in_is_pmf = 0,
+ * stable_softmax utils.py:26-28 inside) or PMFs [B][K] fp32; hquat_d fp32 [K][4], 16-byte aligned; M = nr_max_modes - 1 (1..4).
+ *   d(a,b) = 2 acos(clip(|a.b|, 0, 1)) / pi.  Initial means (:60-79): mode k = the highest-PMF bin that is not a previous
+ *   pick and not within d^2 < 9 var of one (ties: lowest bin index; none left: the zero quaternion); priors 1/N, variances var.
+ *   EM (:82-127), N = 1 .. M, nr_iterations each (N = 1 stops after two): p_k = 1e-18 + exp(-d^2 / 2 s_k^2) / sqrt(2 pi s_k^2),
+ *   r_k = p_k pi_k / p_X, W_k = r_k pmf, Z_k = sum W_k; mu_k = unit eigenvector of lambda_max(sum W_k/Z_k q q^T),
+ *   s_k^2 = sum W_k/Z_k d(q, mu_k)^2 with the new mean, pi_k = Z_k.  Model selection (:129-141): score_N = sum pmf log p_X of
+ *   the last E-step; the first model is accepted, a larger one only if score_N > last accepted score + 0.005, the first
+ *   rejection stops.  Bins are evaluated in fp32, reductions accumulated in fp64.
+ * Outputs, all [B][M] row-major, modes sorted by prior (descending), slots past n_modes filled with mean 0 / var 0 / prior 0 /
+ * score NaN: mean_d fp32 [B][M][4] (sign: largest-magnitude component positive), var_d, prior_d, score_d fp32 [B][M]
+ * (accepted scores in order), nmodes_d int32 [B].  A mode whose Z_k is 0 gets NaN mean and variance (the reference's 0/0).
+ * No workspace, no allocation.
+ */
+int urso_quat_gmm_fit(int B, int K, const float* in_d, int in_is_pmf, const float* hquat_d, float var,
+                      int nr_iterations, int nr_max_modes, float* mean_d, float* var_d, float* prior_d,
+                      float* score_d, int* nmodes_d, void* stream);
+
+/*
  * Rotation augmentation on the GPU ("next" scope row f-1; reference: utils.rotate_cam / rotate_image utils.py:30-86 called
  * from load_image_gt net.py:415-438, and utils.encode_ori_fast utils.py:319-346 for the re-encoded target).
  *   urso_warp_perspective: OpenCV warpPerspective arithmetic on uint8 images [B,H,W,C], constant-0 border.  M [B][9]

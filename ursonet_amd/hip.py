@@ -140,6 +140,7 @@ _SIGS = {
     "urso_adam_amsgrad_clip": (_i, [_sz, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
     "urso_scale_f32": (_i, [_sz, _fp, _f, _vp]),
     "urso_quat_wavg_decode": (_i, [_i, _i, _fp, _fp, _fp, _fp, _vp]),
+    "urso_quat_gmm_fit": (_i, [_i, _i, _fp, _i, _fp, _f, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp]),
     "urso_warp_perspective": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "urso_encode_ori": (_i, [_i, _i, _vp, _fp, _vp, C.c_double, _fp, _vp]),
     "urso_encode_loc": (_i, [_i, _i, _vp, _vp, C.c_double, _fp, _vp]),
@@ -622,6 +623,11 @@ def scale_f32(n, x, s, stream=None):
 def quat_wavg_decode(B, K, logits, hquat, q, a=None, stream=None):
     _chk(_lib.urso_quat_wavg_decode(B, K, ptr(logits), ptr(hquat), ptr(q), ptr(a), stream_ptr(stream)),
          "urso_quat_wavg_decode")
+
+
+def quat_gmm_fit(B, K, x, is_pmf, hquat, var, nr_iterations, nr_max_modes, mean, var_out, prior, score, n_modes, stream=None):
+    _chk(_lib.urso_quat_gmm_fit(B, K, ptr(x), int(bool(is_pmf)), ptr(hquat), float(var), int(nr_iterations), int(nr_max_modes), ptr(mean),
+                                ptr(var_out), ptr(prior), ptr(score), ptr(n_modes), stream_ptr(stream)), "urso_quat_gmm_fit")
 
 
 def warp_perspective(B, H, W, Cc, interp, src, m, dst, stream=None):

@@ -4,7 +4,8 @@ Host side mirrors the reference's L1 helpers that datasets call when they are lo
 (utils.encode_ori utils.py:246-317, encode_ori_fast :319-346, encode_loc :349-396,
 stable_softmax :26-28, se3lib.euler2quat se3lib.py:53-67); the decode replaces the per-image
 Python loop of se3lib.quat_weighted_avg (se3lib.py:217-260, 40-318 ms per image) with one
-kernel launch for the whole batch (urso_quat_wavg_decode).  No CPU decode path is provided.
+kernel launch for the whole batch (urso_quat_wavg_decode), and the EM fit of multimodal orientation PMFs
+(pose_estimator.fit_GMM_to_orientation :42-154) the same way (urso_quat_gmm_fit).  No CPU decode path is provided.
 """
 import itertools
 
@@ -125,6 +126,50 @@ def decode_orientations(ori_logits, H_quat):
     q = torch.empty(z.shape[0], 4, dtype=torch.float32, device=z.device)
     hip.quat_wavg_decode(z.shape[0], z.shape[1], z, hq, q)
     return q.cpu().numpy()
+
+
+def fit_orientation_modes(ori, H_quat, var, nr_iterations=5, nr_max_modes=4, pmf=False):
+    """Batched EM fit of up to nr_max_modes - 1 orientation modes (pose_estimator.py:42-154) on the GPU, one launch
+    (urso_quat_gmm_fit).  ori: [B, n^3] logits (softmaxed inside) or, with pmf=True, PMFs; device tensor or array.
+    var as the reference's callers compute it, (BETA / ORI_BINS_PER_DIM)**2 / 12 (:333-334).  Returns NumPy arrays
+    (mean [B,M,4] float32, var [B,M], prior [B,M], score [B,M], n_modes [B] int32) with M = nr_max_modes - 1: per image the
+    accepted model's modes sorted by prior (descending) and its accepted scores; slots past n_modes hold 0 (score NaN)."""
+    import torch
+    from . import hip
+    x = torch.as_tensor(ori, dtype=torch.float32).cuda()
+    x = (x[None] if x.dim() == 1 else x).contiguous()
+    hq = torch.as_tensor(np.ascontiguousarray(H_quat), dtype=torch.float32).cuda().contiguous()
+    B, K = x.shape
+    if hq.shape != (K, 4):
+        raise ValueError("H_quat must be [%d, 4] for %d bins, got %s" % (K, K, tuple(hq.shape)))
+    M = max(int(nr_max_modes) - 1, 1)
+    mean = torch.empty(B, M, 4, dtype=torch.float32, device=x.device)
+    v, pri, sc = (torch.empty(B, M, dtype=torch.float32, device=x.device) for _ in range(3))
+    nm = torch.empty(B, dtype=torch.int32, device=x.device)
+    hip.quat_gmm_fit(B, K, x, pmf, hq, var, nr_iterations, nr_max_modes, mean, v, pri, sc, nm)
+    return mean.cpu().numpy(), v.cpu().numpy(), pri.cpu().numpy(), sc.cpu().numpy(), nm.cpu().numpy()
+
+
+def fit_GMM_to_orientation(q_map, pmf, nr_iterations, var, nr_max_modes=4):
+    """Drop-in for pose_estimator.fit_GMM_to_orientation (:42-154): one GPU launch with B = 1.  Returns, with the reference's
+    types, (Q_mean [m,4] float32, Q_var [m] float32, Q_priors [m] float64, scores: list of np.float64) for the m modes found,
+    sorted by prior (the values are the kernel's fp32 results).  Unlike the reference it prints nothing, and each mean's sign
+    is normalised (largest-magnitude component positive)."""
+    mean, v, pri, sc, nm = fit_orientation_modes(np.asarray(pmf, dtype=np.float32)[None], q_map, var, nr_iterations, nr_max_modes,
+                                                 pmf=True)
+    m = int(nm[0])
+    return mean[0, :m], v[0, :m], pri[0, :m].astype(np.float64), [np.float64(s) for s in sc[0, :m]]
+
+
+def mode_errors(mean, n_modes, q_gt):
+    """Angular error [deg] of every fitted mode against the ground truth (the comparison of pose_estimator.py:414-425):
+    mean [B,M,4], n_modes [B], q_gt [B,4] -> [B,M] float64, NaN past n_modes."""
+    mean = np.asarray(mean, dtype=np.float64)
+    q_gt = np.atleast_2d(np.asarray(q_gt, dtype=np.float64))
+    d = np.minimum(1.0, np.abs((mean * q_gt[:, None, :]).sum(-1)))
+    err = 2 * np.arccos(d) * 180 / np.pi
+    err[np.arange(mean.shape[1])[None, :] >= np.asarray(n_modes).reshape(-1, 1)] = np.nan
+    return err
 
 
 def pose_errors(loc_est, q_est, loc_gt, q_gt):
