@@ -591,6 +591,58 @@ int urso_quat_gmm_fit(int B, int K, const float* in_d, int in_is_pmf, const floa
                       float* score_d, int* nmodes_d, void* stream);
 
 /*
+ * Decode and score of one batch of head outputs against ground truth (pose_estimator.py:321-460, evaluate), batched on the
+ * GPU: one workgroup per valid row b < n writes row row0 + b of the fp64 table [rows][URSO_EVAL_COLS]; rows past n are not
+ * touched.  Decoding and metrics run in fp64 from the fp32 outputs.  All pointers are device pointers; loc / ori / ori2 rows
+ * are loc_ld / ori_ld floats apart.
+ *   location   URSO_EVAL_LOC_REGRESS: loc[b, 0:3].  URSO_EVAL_LOC_CLASS: softmax(loc[b, 0:loc_bins]) @ loc_map
+ *              (loc_map fp64 [loc_map_rows][3], dataset.histogram_3D_map; :380-383).
+ *   ori_mode   URSO_EVAL_ORI_QUAT: ori[b, 0:4] (the engine's normalised q_out).  _EULER: SO32quat(euler2SO3_left(pitch, yaw,
+ *              roll)) (se3lib.py:38-51, 77-115).  _ANGLE_AXIS: theta = |v|, axis 0 if theta < 1e-6, [axis sin(theta/2),
+ *              cos(theta/2)] (:397-403).  _SOFT: ori[b, 0:4] = urso_quat_wavg_decode's output on the orientation logits,
+ *              used as it is.  _KEYPOINTS: pose_3Dto3D(P1, [k1 | k2 | loc]) + SO32quat(R.T) (:355-366) with k1 = ori,
+ *              k2 = ori2, P1 = columns (0,0,3), (0,3,0), (0,0,0); the rotation by Horn's quaternion method (the same proper
+ *              rotation as the reference's reflection-corrected SVD when the two nonzero singular values differ).
+ *   enc_loc    optional, LOC_CLASS only: PMF [B][loc_bins]; LOC_ENC_ERR = || enc_loc @ loc_map - loc_gt || (:386-387).
+ *   enc_ori    optional, _SOFT only: PMF [B][ori_bins] over ori_map (fp32 [ori_map_rows][4], 16-byte aligned);
+ *              ORI_ENC_ERR = 2 acos|quat_weighted_avg(ori_map, enc_ori) . q_gt| * 180/pi (:429-430), fp64 reduction.
+ *   gmm_mean   optional, _SOFT only: urso_quat_gmm_fit's means [B][gmm_modes][4] and gmm_nmodes [B] on the same logits.
+ *              q_est = mode 0 if gmm_nmodes == 1 or err0 < err1, else mode 1 (the commented rule of :420-424); MODE holds
+ *              the pick and ORI_ERR_SOFT the soft-argmax error.  Without it both columns are NaN.
+ *   metrics    loc_gt fp64 [B][3], q_gt fp64 [B][4]: ORI_ERR = 2 acos(min(1, |q_est . q_gt|)) * 180/pi, LOC_ERR =
+ *              ||loc_est - loc_gt||, ESA = LOC_ERR / ||loc_gt|| + 2 acos(min(1, |q_est . q_gt|)), DIST = loc_gt[2] (:434-449).
+ *              The clip to 1 is this project's convention (the reference's arccos returns NaN past 1); a NaN input gives NaN.
+ *              Undefined columns (encoded errors without their input) are NaN; the last column is 0.
+ * No workspace, no allocation, no host synchronisation; n = 0 launches nothing.  Bad arguments return URSO_EINVAL before any
+ * launch: a null required pointer, B <= 0, n outside [0, B], row0 < 0, an unknown mode, loc_bins != loc_map_rows or
+ * ori_bins != ori_map_rows, a row stride below the row width, an optional input in a mode that does not define it.
+ */
+enum { URSO_EVAL_LOC_REGRESS = 0, URSO_EVAL_LOC_CLASS = 1 };
+enum { URSO_EVAL_ORI_QUAT = 0, URSO_EVAL_ORI_EULER = 1, URSO_EVAL_ORI_ANGLE_AXIS = 2, URSO_EVAL_ORI_SOFT = 3, URSO_EVAL_ORI_KEYPOINTS = 4 };
+enum { URSO_EVAL_LOC_EST = 0, URSO_EVAL_Q_EST = 3, URSO_EVAL_LOC_ERR = 7, URSO_EVAL_ORI_ERR = 8, URSO_EVAL_ESA = 9, URSO_EVAL_DIST = 10,
+       URSO_EVAL_LOC_ENC_ERR = 11, URSO_EVAL_ORI_ENC_ERR = 12, URSO_EVAL_ORI_ERR_SOFT = 13, URSO_EVAL_MODE = 14, URSO_EVAL_COLS = 16 };
+typedef struct urso_pose_eval_args {
+    int32_t B, n;                    /* rows of the batch buffers, valid rows (0 <= n <= B) */
+    int64_t row0;                    /* table row of batch row 0 */
+    int32_t loc_mode, ori_mode;
+    int32_t loc_ld, ori_ld;          /* floats between rows of loc / ori / ori2 */
+    int32_t loc_bins, loc_map_rows, ori_bins, ori_map_rows, gmm_modes, pad0;
+    const float* loc;
+    const float* ori;
+    const float* ori2;               /* k2 in keypoint mode, else NULL */
+    const double* loc_map;
+    const float* ori_map;
+    const float* enc_loc;
+    const float* enc_ori;
+    const double* loc_gt;
+    const double* q_gt;
+    const float* gmm_mean;
+    const int32_t* gmm_nmodes;
+    double* table;
+} urso_pose_eval_args;
+int urso_pose_eval(const urso_pose_eval_args* args, void* stream);
+
+/*
  * Rotation augmentation on the GPU ("next" scope row f-1; reference: utils.rotate_cam / rotate_image utils.py:30-86 called
  * from load_image_gt net.py:415-438, and utils.encode_ori_fast utils.py:319-346 for the re-encoded target).
  *   urso_warp_perspective: OpenCV warpPerspective arithmetic on uint8 images [B,H,W,C], constant-0 border.  M [B][9]

@@ -81,6 +81,7 @@ class SyntheticPoses(Dataset):
             # classification location head: soft labels over the (x/z, y/z, z) grid, as urso.py:85-93 builds them with utils.encode_loc
             xyz = np.stack([t[:, 0] / t[:, 2], t[:, 1] / t[:, 2], t[:, 2]], axis=1)
             loc_enc, self.loc_histogram_map = utils.encode_loc(xyz, config.LOC_BINS_PER_DIM, config.BETA, xyz.max(0), xyz.min(0))
+            self.histogram_3D_map = self.loc_histogram_map          # the name evaluate reads (pose_estimator.py:383)
         for i in range(n):
             self.add_image("SYN", image_id=i, path="synthetic://%d" % i, location=t[i], quaternion=q[i],
                            pyr=np.zeros(3, dtype=np.float32), angleaxis=np.zeros(3, dtype=np.float32),

@@ -304,3 +304,136 @@ class DeviceFeeder(object):
                 self.q.get_nowait()
         except queue.Empty:
             pass
+
+
+def eval_batch_plan(image_ids, batch_size):
+    """The batches of one evaluation pass over `image_ids`, in order: [(row0, n, slot_ids)], where table rows row0 .. row0 + n - 1
+    receive the n valid images and slot_ids lists the image of every one of the batch_size slots -- the tail batch repeats its last
+    valid image in the padding slots (n < batch_size), which are computed and not scored.  No images: no batches."""
+    ids = list(image_ids)
+    out = []
+    for row0 in range(0, len(ids), batch_size):
+        chunk = ids[row0:row0 + batch_size]
+        out.append((row0, len(chunk), chunk + [chunk[-1]] * (batch_size - len(chunk))))
+    return out
+
+
+class EvalBatch(object):
+    """One uploaded evaluation batch: table rows [row0, row0 + n), device tensors `images` (uint8 frames, or molded float32 where the
+    dataset's frames are not uint8 RGB), `loc_gt` fp64 [B,3], `q_gt` fp64 [B,4] and, where a classification head needs them, the
+    stored encoded targets `enc_loc` / `enc_ori` fp32 [B,K] (else None)."""
+    __slots__ = ("row0", "n", "images", "loc_gt", "q_gt", "enc_loc", "enc_ori")
+
+    def __init__(self, row0, n, tensors):
+        self.row0, self.n = row0, n
+        self.images, self.loc_gt, self.q_gt, self.enc_loc, self.enc_ori = tensors
+
+
+class EvalFeeder(object):
+    """Finite, ordered, augmentation-free input of evaluate(): walks dataset.image_ids once in order (eval_batch_plan).  Loader
+    threads load every image with load_sample / finish_sample (host resize / pad, no augmentation: ROT_AUG, ROT_IMAGE_AUG and
+    SIM2REAL_AUG are ignored, and the encoded targets are the dataset's stored ones); a producer thread assembles each batch in
+    pinned memory (under hip.capture_lock, as DeviceFeeder does); iterating uploads batch k+1 on a side stream into the other half
+    of a double buffer while batch k is used.  A batch's staging slot is reused only after the work the consumer put on the current
+    stream while holding it (the forward pass and the scoring kernels) has run.  `loc_dtype` is the dtype of the dataset's locations."""
+
+    def __init__(self, model, dataset, config, enc_loc=False, enc_ori=False, workers=4, depth=3):
+        import torch
+        from concurrent.futures import ThreadPoolExecutor
+        self.torch, self.eng = torch, model._engine
+        self.plan = eval_batch_plan(dataset.image_ids, self.eng.B)
+        self.q = queue.Queue(maxsize=depth)
+        self.stop, self.err, self.loc_dtype = False, None, None
+        self.side = torch.cuda.Stream(device=self.eng.device)
+        self.stage = [None, None]
+        self.events = [torch.cuda.Event(), torch.cuda.Event()]
+        self.consumed = [None, None]
+        self.k = 0
+        pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
+
+        def load(image_id):
+            image = dataset.load_image(image_id)
+            loc = np.asarray(dataset.load_location(image_id))
+            q = np.asarray(dataset.load_quaternion(image_id), dtype=np.float64)
+            el = np.asarray(dataset.load_location_encoded(image_id), dtype=np.float32) if enc_loc else None
+            eo = np.asarray(dataset.load_orientation_encoded(image_id), dtype=np.float32) if enc_ori else None
+            if getattr(image, "dtype", None) == np.uint8 and image.ndim == 3 and image.shape[-1] == 3:
+                image = finish_sample(Sample(image_id, image, None, None), config)[0]
+                return True, image, loc, q, el, eo
+            return False, image, loc, q, el, eo
+
+        def produce():
+            from . import hip
+            try:
+                for row0, n, slots in self.plan:
+                    if self.stop:
+                        return
+                    got = dict(zip(slots[:n], pool.map(load, slots[:n])))
+                    rows = [got[i] for i in slots]
+                    if self.loc_dtype is None:
+                        self.loc_dtype = rows[0][2].dtype
+                    if all(r[0] for r in rows):
+                        images = np.stack([r[1] for r in rows])
+                    else:                                       # not uint8 RGB: molded on the host, as detect does for such frames
+                        images = model.mold_inputs([r[1] for r in rows])[0].astype(np.float32)
+                    arrays = [images, np.stack([r[2] for r in rows]).astype(np.float64), np.stack([r[3] for r in rows])]
+                    arrays += [np.stack([r[k] for r in rows]) if rows[0][k] is not None else None for k in (4, 5)]
+                    arrays = [None if a is None else np.ascontiguousarray(a) for a in arrays]
+                    with hip.capture_lock:
+                        host = [None if a is None else torch.from_numpy(a).pin_memory() for a in arrays]
+                    self.q.put((row0, n, host))
+                self.q.put(None)
+            except BaseException as e:                         # surfaced by the consumer
+                self.err = e
+                self.q.put(None)
+            finally:
+                pool.shutdown(wait=False)
+        self.thread = threading.Thread(target=produce, daemon=True)
+        self.thread.start()
+
+    def _upload(self):
+        """Starts the upload of the next batch on the side stream; returns False at the end of the plan."""
+        torch = self.torch
+        item = self.q.get()
+        if item is None:
+            if self.err is not None:
+                raise self.err
+            self._pending = None
+            return False
+        row0, n, host = item
+        slot = self.k & 1
+        with torch.cuda.stream(self.side):
+            if self.consumed[slot] is not None:
+                self.side.wait_event(self.consumed[slot])      # the work that read this slot two batches ago must have run first
+            st = self.stage[slot]
+            if st is None or any((d is None) != (h is None) or (h is not None and (d.shape != h.shape or d.dtype != h.dtype))
+                                 for d, h in zip(st, host)):
+                st = self.stage[slot] = [None if h is None else torch.empty(h.shape, dtype=h.dtype, device=self.eng.device) for h in host]
+            for d, h in zip(st, host):
+                if h is not None:
+                    d.copy_(h, non_blocking=True)
+            self.events[slot].record(self.side)
+        self._pending = (slot, row0, n, host)                  # the pinned tensors stay alive until their copy has been waited for
+        self.k += 1
+        return True
+
+    def __iter__(self):
+        torch = self.torch
+        cur = torch.cuda.current_stream(self.eng.device)
+        more = self._upload()
+        while more:
+            slot, row0, n, _host = self._pending
+            cur.wait_event(self.events[slot])
+            more = self._upload()                               # batch k+1 goes up while batch k is used
+            yield EvalBatch(row0, n, self.stage[slot])
+            if self.consumed[slot] is None:
+                self.consumed[slot] = torch.cuda.Event()
+            self.consumed[slot].record(cur)
+
+    def close(self):
+        self.stop = True
+        try:
+            while True:
+                self.q.get_nowait()
+        except queue.Empty:
+            pass

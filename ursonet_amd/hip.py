@@ -75,6 +75,22 @@ class DenseLayer(C.Structure):
                 [(n, C.c_int32) for n in ("M", "N", "K0", "K1", "flags")])
 
 
+class PoseEvalArgs(C.Structure):
+    """urso_pose_eval_args (include/ursonet_hip.h): one batch of urso_pose_eval."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] +
+                [(n, C.c_int32) for n in ("loc_mode", "ori_mode", "loc_ld", "ori_ld", "loc_bins", "loc_map_rows", "ori_bins", "ori_map_rows",
+                                          "gmm_modes", "pad0")] +
+                [(n, C.c_void_p) for n in ("loc", "ori", "ori2", "loc_map", "ori_map", "enc_loc", "enc_ori", "loc_gt", "q_gt", "gmm_mean",
+                                           "gmm_nmodes", "table")])
+
+
+# urso_pose_eval modes and table columns (include/ursonet_hip.h)
+EVAL_LOC_REGRESS, EVAL_LOC_CLASS = 0, 1
+EVAL_ORI_QUAT, EVAL_ORI_EULER, EVAL_ORI_ANGLE_AXIS, EVAL_ORI_SOFT, EVAL_ORI_KEYPOINTS = range(5)
+EVAL_LOC_EST, EVAL_Q_EST, EVAL_LOC_ERR, EVAL_ORI_ERR, EVAL_ESA, EVAL_DIST = 0, 3, 7, 8, 9, 10
+EVAL_LOC_ENC_ERR, EVAL_ORI_ENC_ERR, EVAL_ORI_ERR_SOFT, EVAL_MODE, EVAL_COLS = 11, 12, 13, 14, 16
+
+
 class DenseWgradLayer(C.Structure):
     """urso_dense_wgrad_layer (include/ursonet_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("x", "dz", "part", "colpart")] + [(n, C.c_int32) for n in ("M", "K", "N")]
@@ -141,6 +157,7 @@ _SIGS = {
     "urso_scale_f32": (_i, [_sz, _fp, _f, _vp]),
     "urso_quat_wavg_decode": (_i, [_i, _i, _fp, _fp, _fp, _fp, _vp]),
     "urso_quat_gmm_fit": (_i, [_i, _i, _fp, _i, _fp, _f, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp]),
+    "urso_pose_eval": (_i, [C.POINTER(PoseEvalArgs), _vp]),
     "urso_warp_perspective": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "urso_encode_ori": (_i, [_i, _i, _vp, _fp, _vp, C.c_double, _fp, _vp]),
     "urso_encode_loc": (_i, [_i, _i, _vp, _vp, C.c_double, _fp, _vp]),
@@ -628,6 +645,34 @@ def quat_wavg_decode(B, K, logits, hquat, q, a=None, stream=None):
 def quat_gmm_fit(B, K, x, is_pmf, hquat, var, nr_iterations, nr_max_modes, mean, var_out, prior, score, n_modes, stream=None):
     _chk(_lib.urso_quat_gmm_fit(B, K, ptr(x), int(bool(is_pmf)), ptr(hquat), float(var), int(nr_iterations), int(nr_max_modes), ptr(mean),
                                 ptr(var_out), ptr(prior), ptr(score), ptr(n_modes), stream_ptr(stream)), "urso_quat_gmm_fit")
+
+
+def _rows(t):
+    """(device pointer, row stride in elements) of a 2-D tensor whose rows are contiguous (None -> (NULL, 0))."""
+    if t is None:
+        return None, 0
+    assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1, "expected a device tensor with contiguous rows"
+    return t.data_ptr(), t.stride(0)
+
+
+def pose_eval(B, n, row0, loc_mode, ori_mode, loc, ori, loc_gt, q_gt, table, ori2=None, loc_map=None, ori_map=None, enc_loc=None,
+              enc_ori=None, gmm_mean=None, gmm_nmodes=None, stream=None):
+    """urso_pose_eval on one batch: loc / ori / ori2 are fp32 device tensors [B, width] with contiguous rows (views of the engine's
+    outputs are fine), the rest contiguous; table is fp64 [rows, EVAL_COLS]."""
+    a = PoseEvalArgs()
+    a.B, a.n, a.row0, a.loc_mode, a.ori_mode = int(B), int(n), int(row0), int(loc_mode), int(ori_mode)
+    a.loc, a.loc_ld = _rows(loc)
+    a.ori, a.ori_ld = _rows(ori)
+    a.ori2 = _rows(ori2)[0]
+    a.loc_map, a.ori_map = ptr(loc_map), ptr(ori_map)
+    a.loc_map_rows = 0 if loc_map is None else loc_map.shape[0]
+    a.ori_map_rows = 0 if ori_map is None else ori_map.shape[0]
+    a.loc_bins = loc.shape[1] if loc_mode == EVAL_LOC_CLASS else 0
+    a.ori_bins = 0 if enc_ori is None else enc_ori.shape[1]
+    a.enc_loc, a.enc_ori, a.loc_gt, a.q_gt, a.table = ptr(enc_loc), ptr(enc_ori), ptr(loc_gt), ptr(q_gt), ptr(table)
+    a.gmm_mean, a.gmm_nmodes = ptr(gmm_mean), ptr(gmm_nmodes)
+    a.gmm_modes = 0 if gmm_mean is None else gmm_mean.shape[1]
+    _chk(_lib.urso_pose_eval(C.byref(a), stream_ptr(stream)), "urso_pose_eval")
 
 
 def warp_perspective(B, H, W, Cc, interp, src, m, dst, stream=None):
