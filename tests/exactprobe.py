@@ -10,13 +10,16 @@ Two ways to compare a kernel with a float64 reference of the same operation, bot
   the fp32 accumulation error (assert_rounded_once).  A truncating store, a double rounding or 16-bit partial sums
   break that bound (tests/test_exactprobe_cpu.py shows it on simulated kernels).
 
-int_operands() / int_plan() make the integer data; ran() asserts which kernel a call actually launched.
+int_operands() / int_plan() make the integer data; ran() asserts which kernel a call actually launched.  The references of the
+packed stem (stem_taps, stem_conv64), of the max-pool's gradient routing (pool_route), of weight gradients (wgrad64) and of
+two-segment reductions (two_segment) live here too, each with a CPU test that it rejects the fault it is there to expose.
 """
 import contextlib
 import math
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 # storage types by the library's dtype codes (URSO_F32 / URSO_BF16 / URSO_F16) or by torch dtype
 _TDT = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
@@ -186,3 +189,96 @@ def ran(symbol_substring):
     syms = [r[5] for r in recs]
     assert syms, "no library call was profiled (expected %s)" % symbol_substring
     assert all(all(u in s for u in subs) for s in syms), "expected every call to launch %s, launched %s" % (" + ".join(subs), syms)
+
+
+def round_to(t, dt):
+    """float64 t rounded once to the storage type (round to nearest even), back in float64."""
+    return t.to(torch.float64).to(tdtype(dt)).to(torch.float64)
+
+
+def pack_bits(keep):
+    """Bit-mask bytes of a 0 / 1 tensor in element order (bit i of byte j = element 8 j + i): the ReLU bit masks of the library."""
+    k = keep.reshape(-1, 8).to(torch.int32)
+    return (k << torch.arange(8, dtype=torch.int32)).sum(1).to(torch.uint8)
+
+
+def assert_zero_columns(y, n, what="output"):
+    """The padded output columns n.. of y (last dimension) are exactly 0 (zero filter rows, zero bias)."""
+    pad = _host64(y)[..., n:]
+    bad = pad != 0
+    assert not bool(bad.any()), "%s: %d values of the padded columns %d.. are not 0 (max |v| %g)" % (
+        what, int(bad.sum()), n, float(pad.abs().max()))
+
+
+# ---- the packed stem (urso_stem_weight_pack / conv_stem.hip): 7x7 taps of 3 channels as 7 rows x 4 pixel pairs x 8 (pixel, channel)
+def stem_taps(w):
+    """[7][7][3][N] filter -> the packed 7 x 8 x 4 tap grid [7][8][4][N]: window pixel q = kx + 1 (q = 0 is a pad tap) and channel
+    c (c = 3 is the molded zero channel); pad taps are 0.  Permuted to [N][7][8][4] and reshaped to [N][7][4][8] it is the layout
+    of urso_stem_weight_pack's filter (pixel pair kp = q >> 1, cp = 4 (q & 1) + c)."""
+    N = w.shape[3]
+    t = torch.zeros(7, 8, 4, N, dtype=torch.float64)
+    t[:, 1:, :3] = w.to(torch.float64)
+    return t
+
+
+def stem_untaps(t):
+    """The 147 real taps [7][7][3][N] of a [7][8][4][N] tap grid (urso_stem_wgrad_unpack)."""
+    return t[:, 1:, :3]
+
+
+def stem_conv64(x4, taps):
+    """float64 stem on the molded input [B][H][W][4] with a [7][8][4][N] tap grid: stride 2, ZeroPadding2D(3) -- window pixel q of
+    output column ox is input column 2 ox - 4 + q -- so the real taps give the 7x7 / s2 / pad-3 conv of the 3 channels.  [B][H/2][W/2][N]."""
+    B, H, W, _ = x4.shape
+    xp = F.pad(x4.to(torch.float64).permute(0, 3, 1, 2), (4, 3, 3, 3))
+    y = F.conv2d(xp, taps.to(torch.float64).permute(3, 2, 0, 1), stride=2)
+    return y[:, :, :H // 2, :W // 2].permute(0, 2, 3, 1)
+
+
+def stem_wgrad64(x4, dz):
+    """float64 gradient of stem_conv64 with respect to its [7][8][4][N] tap grid (x^T dz over the B * H/2 * W/2 pixels)."""
+    taps = torch.zeros(7, 8, 4, dz.shape[3], dtype=torch.float64, requires_grad=True)
+    (stem_conv64(x4, taps) * dz.to(torch.float64)).sum().backward()
+    return taps.grad
+
+
+def pool_route(dpool, am, H, W):
+    """The max-pool 3x3 / s2 / SAME gradient in float64: every pooled element goes to the conv pixel its arg-max byte names (tap in
+    bits 0-3 = 3 ky + kx of window (2 py, 2 px)); a byte with bit 4 set (window maximum <= 0: the ReLU in front) routes nothing.
+    Returns (sum reaching each conv pixel [B][H][W][C], the same sum of magnitudes) -- unrounded: the kernels store it rounded ONCE."""
+    B, PH, PW, C = dpool.shape
+    dp = dpool.to(torch.float64)
+    a = am.to("cpu").to(torch.int64)
+    live = (a & 16) == 0
+    out = torch.zeros(B, 2 * PH + 1, 2 * PW + 1, C, dtype=torch.float64)
+    mag = torch.zeros_like(out)
+    for ky in range(3):
+        for kx in range(3):
+            sel = (live & ((a & 15) == 3 * ky + kx)).to(torch.float64)
+            out[:, ky:ky + 2 * PH:2, kx:kx + 2 * PW:2] += sel * dp
+            mag[:, ky:ky + 2 * PH:2, kx:kx + 2 * PW:2] += sel * dp.abs()
+    assert float(mag[:, H:].abs().sum()) == 0 and float(mag[:, :, W:].abs().sum()) == 0, "an arg-max byte points outside the conv output"
+    return out[:, :H, :W], mag[:, :H, :W]
+
+
+# ---- weight gradients and two-segment reductions
+def wgrad64(x, dz, k, s, pad):
+    """float64 filter gradient x^T dz of a k x k / stride-s conv with top / left padding pad (bottom / right as far as the output grid
+    needs): [k][k][C][N].  Runs on the operands' device (float64 GEMMs; exact for integer data below 2^53)."""
+    B, H, W, C = x.shape
+    _, OH, OW, N = dz.shape
+    pb = max((OH - 1) * s + k - H - pad[0], 0)
+    pr = max((OW - 1) * s + k - W - pad[1], 0)
+    xp = F.pad(x.to(torch.float64).permute(0, 3, 1, 2), (pad[1], pr, pad[0], pb))
+    cols = F.unfold(xp, k, stride=s)                                     # [B][C k k][L], L >= OH OW
+    L = cols.shape[2]
+    nw = (xp.shape[3] - k) // s + 1
+    cols = cols.reshape(B, C * k * k, L // nw, nw)[:, :, :OH, :OW].reshape(B, C * k * k, OH * OW)
+    g = torch.einsum("bkl,bln->kn", cols, dz.to(torch.float64).reshape(B, OH * OW, N))
+    return g.reshape(C, k, k, N).permute(1, 2, 0, 3)
+
+
+def two_segment(x0, w0, x1, w1):
+    """(x0 w0^T + x1 w1^T, |x0| |w0|^T + |x1| |w1|^T) in float64: ONE reduction of K0 + K1 terms, rounded once when stored."""
+    d = lambda t: t.to(torch.float64)
+    return d(x0) @ d(w0).T + d(x1) @ d(w1).T, d(x0).abs() @ d(w0).abs().T + d(x1).abs() @ d(w1).abs().T

@@ -244,3 +244,160 @@ def test_exact_refuses_a_reference_of_another_layout():
         X.assert_exact(ref.T.contiguous().float(), ref)
     with pytest.raises(AssertionError, match="shape"):
         X.assert_rounded_once(ref.T.contiguous().float(), ref, ref.abs(), torch.bfloat16, 4)
+
+
+# ---- the packed stem, the max-pool's gradient routing, padded filter columns, two-segment reductions
+SB, SH, SW, SN = 2, 12, 20, 8                  # molded input [SB][SH][SW][4], conv output [SB][SH/2][SW/2][SN]
+
+
+def stem_case(t, exact, seed=11, up=1):
+    """Molded input [SB][up SH][up SW][4] and a [7][7][3][SN] filter (up = 2: the conv output is SH x SW)."""
+    g = torch.Generator().manual_seed(seed)
+    x4 = torch.zeros(SB, up * SH, up * SW, 4)
+    if exact:
+        x4[..., :3] = X.int_operands((SB, up * SH, up * SW, 3), t, 3, 0.6, seed)
+        w = X.int_operands((7, 7, 3, SN), t, 3, 0.6, seed + 1)
+    else:
+        x4[..., :3] = torch.randn(SB, up * SH, up * SW, 3, generator=g).to(t).float()
+        w = (torch.randn(7, 7, 3, SN, generator=g) / 12).to(t).float()
+    return x4, w
+
+
+def test_stem_taps_match_the_kernel_pack_and_a_plain_7x7_conv():
+    """stem_taps is the layout of urso_stem_weight_pack (its index formula, element by element) and stem_conv64 with it is the 7x7 /
+    s2 / ZeroPadding2D(3) conv of the 3 real channels; stem_untaps inverts stem_taps."""
+    x4, w = stem_case(torch.bfloat16, exact=True)
+    packed = X.stem_taps(w).permute(3, 0, 1, 2).reshape(-1)
+    for i in range(packed.numel()):                    # prep.hip stem_pack_kernel: i = ((n * 7 + ky) * 4 + kp) * 8 + cp
+        cp, kp, ky, n = i & 7, (i >> 3) & 3, (i >> 5) % 7, i // 224
+        q, c = 2 * kp + (cp >> 2), cp & 3
+        want = float(w[ky, q - 1, c, n]) if q >= 1 and c < 3 else 0.0
+        assert float(packed[i]) == want, i
+    plain = F.conv2d(F.pad(x4[..., :3].double().permute(0, 3, 1, 2), (3, 3, 3, 3)), w.double().permute(3, 2, 0, 1), stride=2)
+    assert torch.equal(X.stem_conv64(x4, X.stem_taps(w)), plain[:, :, :SH // 2, :SW // 2].permute(0, 2, 3, 1))
+    assert torch.equal(X.stem_untaps(X.stem_taps(w)), w.double())
+
+
+@pytest.mark.parametrize("t", DTS, ids=["bf16", "fp16"])
+def test_stem_unpack_counting_a_pad_tap_is_rejected(t):
+    """A weight-gradient unpack that reads window pixel q = kx (the pad tap q = 0 counted, the last real tap dropped) instead of kx + 1."""
+    for exact in (True, False):
+        x4, _ = stem_case(t, exact)
+        g = torch.Generator().manual_seed(3)
+        dz = (X.int_operands((SB, SH // 2, SW // 2, SN), t, 3, 0.8, 4) if exact else torch.randn(SB, SH // 2, SW // 2, SN, generator=g).to(t)).double()
+        gt, mag = X.stem_wgrad64(x4, dz), X.stem_wgrad64(x4.abs(), dz.abs())
+        got = gt.float().double()                       # fp32 output of a correct kernel
+        assert float(gt[:, :, 3].abs().max()) == 0 and float(gt[:, 0].abs().max()) > 0    # the zero channel; the pad tap sees pixels
+        ref, rmag = X.stem_untaps(gt), X.stem_untaps(mag)
+        if exact:
+            X.assert_exact(X.stem_untaps(got), ref)
+            with pytest.raises(AssertionError, match="elements wrong"):
+                X.assert_exact(got[:, :7, :3], ref)
+        else:
+            X.assert_rounded_once(X.stem_untaps(got), ref, rmag, torch.float32, SB * SH * SW // 4)
+            with pytest.raises(AssertionError, match="rounded-once bound"):
+                X.assert_rounded_once(got[:, :7, :3], ref, rmag, torch.float32, SB * SH * SW // 4)
+
+
+def pool_case(t, seed=21):
+    """Post-ReLU conv output with ties and all-zero windows, its pooled gradient and arg-max bytes (urso_maxpool3x3s2_fwd's encoding)."""
+    g = torch.Generator().manual_seed(seed)
+    y = torch.relu(X.int_operands((SB, SH, SW, SN), t, 3, 0.5, seed))
+    best = torch.full((SB, SH // 2, SW // 2, SN), -math.inf, dtype=torch.float64)
+    arg = torch.zeros(best.shape, dtype=torch.int64)
+    yp = torch.full((SB, SH + 1, SW + 1, SN), -math.inf, dtype=torch.float64)
+    yp[:, :SH, :SW] = y.double()
+    for ky in range(3):
+        for kx in range(3):
+            v = yp[:, ky:ky + SH:2, kx:kx + SW:2]
+            take = v > best
+            best, arg = torch.where(take, v, best), torch.where(take, torch.full_like(arg, 3 * ky + kx), arg)
+    am = (arg + 16 * (best <= 0).long()).to(torch.uint8)
+    dpool = torch.randn(best.shape, generator=g).to(t).double()
+    return am, dpool
+
+
+def route_neighbour(dpool, am):
+    """A router that sends a window's gradient to the pixel right of its arg-max where that is kx = 0 (always inside the image)."""
+    a = am.to(torch.int64)
+    tap = a & 15
+    return X.pool_route(dpool, (tap + (tap % 3 == 0).long() + (a & 16)).to(torch.uint8), SH, SW)[0]
+
+
+def route_rounding_every_add(dpool, am, t):
+    """A router that rounds to the storage type after every window it adds (instead of once per conv pixel)."""
+    B_, PH, PW, C_ = dpool.shape
+    out = torch.zeros(B_, SH + 1, SW + 1, C_, dtype=torch.float64)
+    a = am.to(torch.int64)
+    for ky in range(3):
+        for kx in range(3):
+            sel = (((a & 16) == 0) & ((a & 15) == 3 * ky + kx)).double()
+            out[:, ky:ky + 2 * PH:2, kx:kx + 2 * PW:2] = X.round_to(out[:, ky:ky + 2 * PH:2, kx:kx + 2 * PW:2] + sel * dpool, t)
+    return out[:, :SH, :SW]
+
+
+@pytest.mark.parametrize("t", DTS, ids=["bf16", "fp16"])
+def test_pool_route_and_its_faults(t):
+    """pool_route: every live window's gradient reaches its arg-max pixel, dead windows (bit 4) nothing; the stem's weight gradient from
+    the routed gradient rounded once rejects a router that picks a neighbouring tap, a gradient left unrounded and one rounded twice."""
+    am, dpool = pool_case(t)
+    routed, mag = X.pool_route(dpool, am, SH, SW)
+    live = (am.long() & 16) == 0
+    assert 0.05 < float((~live).double().mean()) < 0.95
+    assert abs(float(routed.sum()) - float((dpool * live).sum())) < 1e-9 and torch.equal(mag.sum(), (dpool.abs() * live).sum())
+    dz = X.round_to(routed, t)
+    assert not torch.equal(dz, routed) and int((mag > 0).sum()) > int((routed != 0).sum()) // 2
+    x4, _ = stem_case(t, exact=False, up=2)
+    ref, rmag = X.stem_wgrad64(x4, dz), X.stem_wgrad64(x4.abs(), dz.abs())
+    K = SB * SH * SW
+    X.assert_rounded_once(X.stem_wgrad64(x4, dz).float(), ref, rmag, torch.float32, K)
+    for bad in (X.round_to(route_neighbour(dpool, am), t), routed, route_rounding_every_add(dpool, am, t)):
+        assert not torch.equal(bad, dz)
+        with pytest.raises(AssertionError, match="rounded-once bound"):
+            X.assert_rounded_once(X.stem_wgrad64(x4, bad).float(), ref, rmag, torch.float32, K)
+    with pytest.raises(AssertionError, match="elements wrong"):
+        X.assert_exact(route_neighbour(dpool.round(), am), X.pool_route(dpool.round(), am, SH, SW)[0])
+
+
+def test_padded_filter_columns_must_be_zero():
+    y = torch.zeros(2, 3, 4, 32)
+    y[..., :24] = torch.randn(2, 3, 4, 24)
+    X.assert_zero_columns(y, 24)
+    y[1, 2, 3, 30] = 2.0 ** -20
+    with pytest.raises(AssertionError, match="padded columns"):
+        X.assert_zero_columns(y, 24)
+
+
+def test_pack_bits_element_order():
+    keep = (torch.rand(64, generator=torch.Generator().manual_seed(2)) > 0.5).to(torch.int32)
+    bits = X.pack_bits(keep)
+    assert torch.equal(((bits.to(torch.int32).reshape(-1, 1) >> torch.arange(8)) & 1).reshape(-1), keep)
+
+
+@pytest.mark.parametrize("t", DTS, ids=["bf16", "fp16"])
+def test_two_segment_rounded_between_segments_is_rejected(t):
+    """Two reduction segments summed in one fp32 accumulator and rounded once pass; rounding segment 1 to the storage type before adding
+    segment 2 (the two-launch form) does not."""
+    g = torch.Generator().manual_seed(8)
+    Mr, K0, K1, Nn = 32, 1024, 1024, 256
+    x0, x1 = (torch.randn(Mr, K0, generator=g).to(t).float(), torch.randn(Mr, K1, generator=g).to(t).float())
+    w0, w1 = ((torch.randn(Nn, K0, generator=g) / 32).to(t).float(), (torch.randn(Nn, K1, generator=g) / 32).to(t).float())
+    ref, mag = X.two_segment(x0, w0, x1, w1)
+    s0, s1 = (x0 @ w0.T).double(), (x1 @ w1.T).double()                  # fp32 segment sums
+    X.assert_rounded_once(rne((s0 + s1).float().double(), t), ref, mag, t, K0 + K1)
+    with pytest.raises(AssertionError, match="rounded-once bound"):
+        X.assert_rounded_once(rne(rne(s0, t) + s1, t), ref, mag, t, K0 + K1)
+
+
+def test_wgrad64_is_the_filter_gradient_of_a_strided_padded_conv():
+    g = torch.Generator().manual_seed(9)
+    for (Bq, Hq, Wq, Cq, Nq, k, s, pad) in [(2, 9, 11, 5, 7, 3, 2, (1, 1)), (2, 8, 10, 4, 6, 3, 2, (0, 0)), (1, 6, 6, 3, 4, 1, 2, (0, 0)),
+                                            (2, 5, 7, 3, 5, 3, 1, (1, 1))]:
+        OH, OW = ((Hq + 2 * pad[0] - k) // s + 1, (Wq + 2 * pad[1] - k) // s + 1) if pad[0] or s == 1 else (-(-Hq // s), -(-Wq // s))
+        x = torch.randn(Bq, Hq, Wq, Cq, generator=g, dtype=torch.float64)
+        dz = torch.randn(Bq, OH, OW, Nq, generator=g, dtype=torch.float64)
+        w = torch.zeros(k, k, Cq, Nq, dtype=torch.float64, requires_grad=True)
+        pb, pr = max((OH - 1) * s + k - Hq - pad[0], 0), max((OW - 1) * s + k - Wq - pad[1], 0)
+        y = F.conv2d(F.pad(x.permute(0, 3, 1, 2), (pad[1], pr, pad[0], pb)), w.permute(3, 2, 0, 1), stride=s).permute(0, 2, 3, 1)
+        (y * dz).sum().backward()
+        assert float((X.wgrad64(x, dz, k, s, pad) - w.grad).abs().max()) < 1e-12

@@ -6,7 +6,14 @@ can expose a wrong tap, channel or store), and with real operands pre-rounded to
 within half an ulp + the fp32 accumulation error of the float64 reference: one rounding, after the fused epilogue --
 the model oracle.graph_ref.StorageRounding assumes).  Weights come from urso_conv_weight_prep without BatchNorm (scale 1,
 so the folded filter is the pre-rounded one); outputs are filled with a sentinel first; a probe that forces a kernel
-through an option asserts with ran() that the kernel it names actually ran."""
+through an option asserts with ran() that the kernel it names actually ran.
+
+Families: the generic implicit GEMM, pointwise, halo, register-filter and big-tile pointwise kernels, the Dense head, the
+max-pool, the weight-gradient variants, the fused pointwise pairs and the two-segment pointwise launch; the stem (weight
+pack with a BatchNorm fold, unpooled, fused with ReLU + max-pool, weight gradient from dz and from the pool's gradient);
+bottleneck_layer's forward and parity-class data gradient; the Dense heads in one launch (forward and weight gradients);
+the batched weight gradients (grouped layers, two 3x3 layers in one launch, dz on a coarser grid).  The references of the
+larger layers are float64 on the device."""
 import math
 
 import pytest
@@ -29,16 +36,18 @@ def dev(t, dt):
     return t.contiguous().to(X.tdtype(dt)).cuda()
 
 
-def prep_weights(w_hwio, dt, bias):
-    """urso_conv_weight_prep with bn = None: wf [N][kh][kw][C], wd [C][kh][kw][N] (flipped data-gradient filter), biasf."""
+def prep_weights(w_hwio, dt, bias, npad=None):
+    """urso_conv_weight_prep with bn = None: wf [npad][kh][kw][C], wd [C][kh][kw][npad] (flipped data-gradient filter), biasf; filters
+    N.. npad - 1 zero (npad defaults to N)."""
     hip = _hip()
     KH, KW, Ci, N = w_hwio.shape
+    npad = npad or N
     tdt = X.tdtype(dt)
-    wf = torch.empty(N * KH * KW * Ci, dtype=tdt, device="cuda")
-    wd = torch.empty(Ci * KH * KW * N, dtype=tdt, device="cuda")
-    biasf = torch.empty(N, dtype=torch.float32, device="cuda")
-    scale = torch.empty(N, dtype=torch.float32, device="cuda")
-    hip.conv_weight_prep(KH, KW, Ci, N, N, dt, w_hwio.contiguous().cuda(), bias.contiguous().cuda(),
+    wf = torch.empty(npad * KH * KW * Ci, dtype=tdt, device="cuda")
+    wd = torch.empty(Ci * KH * KW * npad, dtype=tdt, device="cuda")
+    biasf = torch.empty(npad, dtype=torch.float32, device="cuda")
+    scale = torch.empty(npad, dtype=torch.float32, device="cuda")
+    hip.conv_weight_prep(KH, KW, Ci, N, npad, dt, w_hwio.contiguous().cuda(), bias.contiguous().cuda(),
                          None, None, None, None, 1e-3, wf, wd, biasf, scale)
     return wf, wd, biasf
 
@@ -792,3 +801,430 @@ def test_pointwise2(shape, form, dt, exact):
         _record("pointwise2", X.assert_rounded_once(dst, ref, mag, dt, K + 1, "pointwise2 " + form))
     if form == "forward_emit":
         assert torch.equal(_unpack_bits(bits, M, N), (dst.cpu().float() > 0).to(torch.int32)), "emitted bits differ from (dst > 0)"
+
+
+# ---------------------------------------------------------------- the stem (conv_stem.hip, conv_stemw.hip, prep.hip)
+# pooled 10 x 17: partial 8 x 15 pool tiles and partial 8 x 32 conv tiles; pooled 17 x 31 on 18 tiles under grid_cap = 8: windows across
+# the tile seams (stride 16 x 30, 17 x 32 conv pixels per tile), every block walks several tiles; conv grid 17 x 21: odd, the fused
+# pool refuses it (unpooled path only)
+STEM_CASES = [(2, 40, 68, 0, "partial_tiles"), (2, 68, 124, 8, "seams_capped"), (1, 34, 42, 0, "odd_grid")]
+STEM_N = 64
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("case", STEM_CASES, ids=[c[-1] for c in STEM_CASES])
+def test_stem_kernels(case, dt, exact):
+    """urso_stem_weight_pack with a BatchNorm fold that is exact but not the identity (scale 1 / sqrt(3 + 1) = 1/2), the unpooled stem
+    (stem_kernel, bias + ReLU), the fused stem + ReLU + max-pool (stem_pool_kernel: values and arg-max bytes) and the weight gradient from
+    the pool's gradient (stemw_kernel, pooled form) and from dz (urso_conv_wgrad) + urso_stem_wgrad_unpack -- against a float64 7x7 / s2 /
+    pad-3 conv of the 3 real channels.  The pooled weight gradient's dz is the routed pool gradient rounded ONCE to the storage type: the
+    kernel's LDS dz tile is bit for bit what urso_maxpool3x3s2_bwd writes (conv_stemw.hip)."""
+    hip = _hip()
+    B, H, W, cap, name = case
+    N, OH, OW = STEM_N, H // 2, W // 2
+    seed = H + W + 13 * dt
+    if exact:
+        a, d = X.int_plan(147, dt, share=24)
+        x, w = X.int_operands((B, H, W, 3), dt, a, d, seed), X.int_operands((7, 7, 3, N), dt, a, d, seed + 1)
+    else:
+        x = _operands((B, H, W, 3), dt, False, 0, seed)
+        w = 2 * _operands((7, 7, 3, N), dt, False, 0, seed + 1, 0.5 / 147 ** 0.5)     # w / 2 representable (fp16: not subnormal-cut)
+    b = _operands((N,), dt, exact, 0, seed + 2, 0.3, small=True)
+    beta = X.int_operands((N,), None, 3, 0.8, seed + 3) / 2            # folded bias b / 2 + beta - mean / 2: halves (exact in fp32)
+    mean = X.int_operands((N,), None, 3, 0.8, seed + 4)
+    x4 = torch.zeros(B, H, W, 4)
+    x4[..., :3] = x                                                         # the molded input: RGB + a zero channel
+    # ---- weight pack: BN with gamma 1, var 3, eps 1
+    wf, biasf, scale = full((N * 224,), dt), full((N,), 0), full((N,), 0)
+    hip.stem_weight_pack(N, dt, w.cuda(), b.cuda(), torch.ones(N, device="cuda"), beta.cuda(), mean.cuda(), torch.full((N,), 3.0, device="cuda"),
+                         1.0, wf, biasf, scale)
+    torch.cuda.synchronize()
+    taps = X.stem_taps(w.double() * 0.5)
+    bias64 = b.double() * 0.5 + beta.double() - mean.double() * 0.5
+    X.premise(dt, stored=[("packed stem filter", taps)])
+    X.premise(0, stored=[("folded stem bias", bias64)])
+    X.assert_exact(scale, torch.full((N,), 0.5, dtype=torch.float64), "folded BN scale")
+    X.assert_exact(wf.reshape(N, 7, 4, 8), taps.permute(3, 0, 1, 2).reshape(N, 7, 4, 8), "packed stem filter")
+    X.assert_exact(biasf, bias64, "folded stem bias")
+    # ---- forward, unpooled: the packed 7 x 4-pair geometry
+    g = hip.geom(B, H, W // 2, 8, OH, OW, N, 7, 4, 2, 1, 3, 2)
+    x4d = dev(x4, dt)
+    z = X.stem_conv64(x4, taps) + bias64
+    mag = X.stem_conv64(x4.abs(), taps.abs()) + bias64.abs()
+    ref = F.relu(z)
+    y = full((B, OH, OW, N), dt)
+    with hip.options(stem=1, grid_cap=cap), X.ran("stem_kernel"):
+        hip.conv_igemm(g, dt, hip.EPI_RELU, x4d, wf, biasf, None, None, y)
+    torch.cuda.synchronize()
+    if exact:
+        x0 = x4.clone()
+        x0[..., 2] = 0                                                      # the last REAL channel (channel 3 is the molded zero)
+        X.premise(dt, stored=[("stem", ref)], mags=[("stem", mag)])
+        X.assert_sensitive(ref, F.relu(X.stem_conv64(x0, taps) + bias64), z, "stem")
+        X.assert_exact(y, ref, "stem")
+    else:
+        _record("stem", X.assert_rounded_once(y, ref, mag, dt, 148, "stem"))
+    # ---- forward fused with ReLU + max-pool 3x3 / s2 / SAME (even grid: SAME pads the bottom and the right only)
+    with hip.options(stem=1, stem_pool=1):
+        pool_ok = hip.stem_conv_pool_ok(g, dt)
+    assert pool_ok == (OH % 2 == 0 and OW % 2 == 0), "urso_stem_conv_pool_ok: %s for a %d x %d conv grid" % (pool_ok, OH, OW)
+    ws = torch.full((hip.conv_wgrad_ws_bytes(g, dt) // 4 + 16,), float("nan"), device="cuda")
+    Kw = B * OH * OW
+    if pool_ok:
+        PH, PW = OH // 2, OW // 2
+        best, arg = _pool_ref(ref)
+        pooled = full((B, PH, PW, N), dt)
+        am = torch.full((B, PH, PW, N), 0xEE, dtype=torch.uint8, device="cuda")
+        with hip.options(stem=1, stem_pool=1, grid_cap=cap), X.ran("stem_pool_kernel"):
+            hip.stem_conv_pool(g, dt, x4d, wf, biasf, pooled, am)
+        torch.cuda.synchronize()
+        if exact:
+            X.assert_exact(pooled, best, "fused stem + pool")
+            X.assert_exact(am.cpu().double(), (arg + 16 * (best <= 0).long()).double(), "fused stem + pool arg-max bytes")
+        else:          # rounding is monotone: the rounded maximum is the maximum of the rounded values (arg-max: ties, not compared)
+            _record("stem_pool", X.assert_rounded_once(pooled, best, _pool_ref(mag)[0], dt, 148, "fused stem + pool"))
+        dpool = _operands((B, PH, PW, N), dt, exact, 0, seed + 5, small=True)
+        routed, _ = X.pool_route(dpool, am, OH, OW)
+        dz = X.round_to(routed, dt)
+        assert float((dz != 0).double().mean()) > 0.1
+    else:
+        dz = _operands((B, OH, OW, N), dt, exact, 0, seed + 5, small=True).double()
+    # ---- weight gradient: packed [224][N] (pad taps included), unpacked [7][7][3][N], column sums
+    gt = X.stem_wgrad64(x4, dz)
+    gmag = X.stem_wgrad64(x4.abs(), dz.abs())
+    cs_ref, cs_mag = dz.sum((0, 1, 2)), dz.abs().sum((0, 1, 2))
+
+    def check(dwp, cs, what):
+        dw = full((7, 7, 3, N), 0)
+        hip.stem_wgrad_unpack(N, dwp, dw)
+        torch.cuda.synchronize()
+        for part, got, r, m in (("packed", dwp.reshape(7, 8, 4, N), gt, gmag), ("unpacked", dw, X.stem_untaps(gt), X.stem_untaps(gmag)),
+                                ("column sums", cs, cs_ref, cs_mag)):
+            if exact:
+                X.premise(0, stored=[(part, r)], mags=[(part, m)])
+                X.assert_exact(got, r, "%s %s" % (what, part))
+            else:
+                _record("stemw", X.assert_rounded_once(got, r, m, 0, Kw, "%s %s" % (what, part)))
+
+    if pool_ok:
+        dwp, cs = full((224 * N,), 0), full((N,), 0)
+        with hip.options(stem=1, grid_cap=cap), X.ran("stemw_kernel"):
+            hip.stem_wgrad_pooled(g, dt, x4d, dev(dpool, dt), am, ws, dwp, cs)
+        torch.cuda.synchronize()
+        check(dwp, cs, "pooled stem weight gradient")
+        ws.fill_(float("nan"))
+    dwp, cs = full((224 * N,), 0), full((N,), 0)
+    with hip.options(stem=1, grid_cap=cap), X.ran("stemw_kernel"):
+        hip.conv_wgrad(g, dt, x4d, dev(dz, dt), ws, dwp, cs)
+    torch.cuda.synchronize()
+    check(dwp, cs, "stem weight gradient")
+
+
+# ---------------------------------------------------------------- bottleneck_layer (conv_bneck.hip, option bneck = 3)
+BNECK_CASES = [(3, 16, 20, 128, 32, 0, "tfsame_small"), (32, 16, 20, 2048, 32, 0, "cfg2_full"), (2, 20, 30, 256, 32, 0, "cfg5_grid"),
+               (2, 9, 11, 64, 32, 1, "odd_grid_pad1"), (2, 4, 4, 512, 32, 0, "cfg1_r18"), (2, 16, 20, 64, 24, 0, "n24")]
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("case", BNECK_CASES, ids=[c[-1] for c in BNECK_CASES])
+def test_bneck_kernels(case, dt, exact):
+    """3x3 / s2 / SAME (or pad 1), <= 32 filters padded to 32: the forward (bias, with and without ReLU; bneck_fwd_kernel where C % 512 == 0,
+    the general kernel otherwise) with its padded output columns exactly 0, and the data gradient by parity class (bneck_dgrad_kernel: no
+    mask, ReLU bit mask, mask tensor) with nonzero values in dz's padded columns, which the zero filter rows must keep out of dx.  References
+    in float64 on the device."""
+    hip = _hip()
+    B, H, W, Ci, N, p, name = case
+    npad, pad = 32, (p, p)
+    OH, OW = _out_hw(H, W, 3, 2, pad, "tfsame" if p == 0 else name)
+    seed = B + H + Ci + N + 3 * dt
+    if exact:                                                     # 32 filters: smaller sums, so that >= 1 % of them are exactly 0
+        a, d = X.int_plan(9 * Ci, dt, share=24)
+        x, w = X.int_operands((B, H, W, Ci), dt, a, d, seed), X.int_operands((3, 3, N, Ci), dt, a, d, seed + 1)
+        x, w = X.fill_last_channel(x, seed + 6), X.fill_last_channel(w, seed + 7).transpose(2, 3).contiguous()   # long sparse sums: see the last channel
+    else:
+        x, w = _operands((B, H, W, Ci), dt, False, 0, seed), _operands((3, 3, Ci, N), dt, False, 0, seed + 1, (9 * Ci) ** -0.5)
+    bias = _operands((N,), 0, exact, 0, seed + 2, 0.3, small=True)
+    dz = _operands((B, OH, OW, N), dt, exact, 9 * N, seed + 3)
+    dzpad = X.int_operands((B, OH, OW, npad - N), dt, 3, 1.0, seed + 4)           # never 0
+    mk = _operands((B, H, W, Ci), dt, exact, 0, seed + 5, small=True, density=0.9)
+    wf, wd, biasf = prep_weights(w, dt, bias, npad)
+    c = lambda t: t.cuda().double()
+    conv = lambda a, b: _conv64(a, b, 2, pad, OH, OW)
+    zc = conv(c(x), c(w))
+    z, mag = zc + c(bias), conv(c(x).abs(), c(w).abs()) + c(bias).abs()
+    x0 = c(x).clone()
+    x0[..., -1] = 0
+    z0 = conv(x0, c(w)) + c(bias)
+    # ---- forward
+    g = hip.geom(B, H, W, Ci, OH, OW, npad, 3, 3, 2, 2, p, p)
+    ws = torch.empty(hip.conv_igemm_ws_bytes(g, dt) // 4 + 4, dtype=torch.float32, device="cuda")
+    xd = dev(x, dt)
+    for relu in (0, hip.EPI_RELU):
+        y = full((B, OH, OW, npad), dt)
+        with hip.options(bneck=3), (X.ran("bneck_fwd_kernel") if Ci % 512 == 0 else _nullctx()):
+            hip.conv_igemm_ex(g, dt, relu, xd, wf, biasf, None, None, y, None, ws)
+        torch.cuda.synchronize()
+        X.assert_zero_columns(y, N, "bneck forward")
+        ref, ref0 = (F.relu(z), F.relu(z0)) if relu else (z, z0)
+        what = "bneck forward relu=%d" % bool(relu)
+        if exact:
+            X.premise(dt, stored=[(what, ref)], mags=[(what, mag)])
+            X.assert_sensitive(ref.cpu(), ref0.cpu(), z.cpu() if relu else None, what)
+            X.assert_exact(y[..., :N], ref.cpu(), what)
+        else:
+            _record("bneck_fwd", X.assert_rounded_once(y[..., :N], ref.cpu(), mag.cpu(), dt, 9 * Ci + 1, what))
+    # ---- data gradient: dz [B, OH, OW, 32] -> dx [B, H, W, Ci], gather form with dilation 2
+    xr, xa = c(x).requires_grad_(True), c(x).abs().requires_grad_(True)
+    (conv(xr, c(w)) * c(dz)).sum().backward()
+    (conv(xa, c(w).abs()) * c(dz).abs()).sum().backward()
+    dz0 = c(dz).clone()
+    dz0[..., -1] = 0                                                                # the last real filter's gradient
+    x0r = c(x).requires_grad_(True)
+    (conv(x0r, c(w)) * dz0).sum().backward()
+    gx, mgx, gx0 = xr.grad.cpu(), xa.grad.cpu(), x0r.grad.cpu()
+    gd = hip.geom(B, OH, OW, npad, H, W, Ci, 3, 3, 1, 1, 2 - p, 2 - p, 2, 2)
+    dzd = dev(torch.cat([dz, dzpad], -1), dt)
+    keep = (mk > 0).double()
+    for mb in (0, 1, 2):                                  # no mask, ReLU bit mask, mask tensor (the destination's own activation)
+        kp = keep if mb else torch.ones_like(keep)
+        mask = (None, X.pack_bits(keep).cuda(), dev(mk, dt))[mb]
+        dx = full((B, H, W, Ci), dt)
+        with hip.options(bneck=3), X.ran("bneck_dgrad_kernel"):
+            hip.conv_igemm_ex(gd, dt, hip.EPI_MASK_BITS if mb == 1 else 0, dzd, wd, None, None, mask, dx)
+        torch.cuda.synchronize()
+        what = "bneck data gradient mask=%s" % ("none", "bits", "tensor")[mb]
+        if exact:
+            X.premise(dt, stored=[(what, gx * kp)], mags=[(what, mgx * kp)])
+            X.assert_sensitive(gx * kp, gx0 * kp, None, what)
+            X.assert_exact(dx, gx * kp, what)
+        else:
+            _record("bneck_dgrad", X.assert_rounded_once(dx, gx * kp, mgx * kp, dt, 9 * N, what))
+
+
+# ---------------------------------------------------------------- Dense heads in one launch (conv_dense.hip: urso_dense_multi / _wgrad_multi)
+def _dense_operands(M, K, N, dt, exact, seed):
+    if exact:                                                     # few outputs: smaller sums, so that >= 1 % are exactly 0
+        a, d = X.int_plan(K, dt, share=24)
+        x, w = X.int_operands((M, K), dt, a, d, seed), X.int_operands((N, K), dt, a, d, seed + 1)
+        return X.fill_last_channel(x, seed + 5), X.fill_last_channel(w, seed + 6)
+    return _operands((M, K), dt, False, K, seed), _operands((N, K), dt, False, K, seed + 1, K ** -0.5)
+
+
+# (K0, K1, N, form): "relu" / "relu_shared" (bias + ReLU; _shared: the previous layer's input), "final" (fp32 output, bias, 8 outputs of
+# which 6 real: zero filter rows and bias behind), "add_mask" (data gradient + add, masked), "two" (two reduction segments, no epilogue)
+DENSE_LAUNCHES = {
+    "four_heads": [(2560, 0, 1024, "relu"), (2560, 0, 1024, "relu_shared"), (1024, 0, 8, "final"), (4096, 0, 1024, "add_mask")],
+    "short": [(1024, 0, 8, "final"), (512, 256, 264, "two"), (1024, 0, 520, "add_mask")],
+    "two_segment": [(1024, 1024, 2560, "two")],
+}
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("M", [32, 5])
+@pytest.mark.parametrize("launch", list(DENSE_LAUNCHES))
+def test_dense_multi_kernel(launch, M, dt, exact):
+    """hip.DenseMulti: every layer of one launch against float64.  A launch whose longest reduction is >= 2048 runs 16 waves per block,
+    8 otherwise (asserted through the kernel's template argument); a two-segment layer (dZ_ori Wd_ori^T + dZ_loc Wd_loc^T) sums both
+    segments in one fp32 accumulator and rounds once, K = K0 + K1."""
+    hip = _hip()
+    layers, checks = [], []
+    for i, (K0, K1, N, form) in enumerate(DENSE_LAUNCHES[launch]):
+        seed = 100 * i + M + K0 + N + dt
+        x0, w0 = _dense_operands(M, K0, N, dt, exact, seed)
+        if form == "final":
+            w0[6:] = 0
+        if form == "relu_shared":                                           # loc_dense_0 / ori_dense_0: the same input tensor
+            x0 = layers[-1]["x0"]
+        L = dict(x0=x0, src0=layers[-1]["src0"] if form == "relu_shared" else dev(x0, dt), wgt0=dev(w0, dt), K0=K0, N=N, M=M, flags=0)
+        if form == "two":
+            x1, w1 = _dense_operands(M, K1, N, dt, exact, seed + 10)
+            z, mag = X.two_segment(x0, w0, x1, w1)
+            z0 = z - x1[:, -1:].double() * w1.double()[:, -1]               # the last channel of the second segment zeroed
+            L.update(src1=dev(x1, dt), wgt1=dev(w1, dt), K1=K1)
+        else:
+            z, mag = x0.double() @ w0.double().T, x0.double().abs() @ w0.double().abs().T
+            z0 = z - x0[:, -1:].double() * w0.double()[:, -1]
+        ref, ref0, pre = z, z0, None
+        if form in ("relu", "relu_shared", "final"):
+            bias = _operands((N,), 0, exact, 0, seed + 2, 0.3, small=True)
+            if form == "final":
+                bias[6:] = 0
+            L["bias"] = bias.cuda()
+            ref, ref0, mag = z + bias.double(), z0 + bias.double(), mag + bias.double().abs()
+        if form.startswith("relu"):
+            L["flags"] = hip.EPI_RELU
+            pre, ref, ref0 = ref, F.relu(ref), F.relu(ref0)
+        if form == "add_mask":
+            add = _operands((M, N), dt, exact, 0, seed + 3, small=True)
+            mt = _operands((M, N), dt, True, 0, seed + 4, small=True)
+            keep = (mt > 0).double()
+            ref, ref0, mag = (z + add.double()) * keep, (z0 + add.double()) * keep, (mag + add.double().abs()) * keep
+            L.update(add=dev(add, dt), mask=dev(mt, dt))
+        out_dt = 0 if form == "final" else dt
+        if form == "final":
+            L["flags"] = hip.EPI_OUT_F32
+        L["dst"] = full((M, N), out_dt)
+        layers.append(L)
+        checks.append((L["dst"], ref, ref0, pre, mag, out_dt, K0 + K1 + 2, "%s layer %d (%s)" % (launch, i, form)))
+    nw = "Li16EE" if max(k0 + k1 for k0, k1, _, _ in DENSE_LAUNCHES[launch]) >= 2048 else "Li8EE"
+    with X.ran(("dense_multi_kernel", nw)):
+        hip.DenseMulti([{k: v for k, v in L.items() if k != "x0"} for L in layers], dt).run()
+    torch.cuda.synchronize()
+    for dst, ref, ref0, pre, mag, out_dt, K, what in checks:
+        if exact:
+            X.premise(out_dt, stored=[(what, ref)], mags=[(what, mag)])
+            X.assert_sensitive(ref, ref0, pre, what)
+            X.assert_exact(dst, ref, what)
+        else:
+            _record("dense_multi", X.assert_rounded_once(dst, ref, mag, out_dt, K, what))
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("M", [32, 5])
+def test_dense_wgrad_multi_kernel(M, dt, exact):
+    """hip.DenseWgradMulti: dW = x^T dz (fp32) and the column sums of dz for four layers of the heads' shapes in one launch (a ragged
+    2600 x 1000, the final layer's N = 8); nothing written behind K * N."""
+    hip = _hip()
+    layers, refs = [], []
+    for i, (K, N) in enumerate([(2560, 1024), (1024, 8), (1024, 4096), (2600, 1000)]):
+        seed = 10 * i + M + dt
+        x, dz = _operands((M, K), dt, exact, M, seed), _operands((M, N), dt, exact, M, seed + 1)
+        part, col = full((K * N + 64,), 0), full((N,), 0)
+        layers.append(dict(x=dev(x, dt), dz=dev(dz, dt), part=part, colpart=col, M=M, K=K, N=N))
+        refs.append((x.double().T @ dz.double(), x.double().abs().T @ dz.double().abs(), dz.double().sum(0), dz.double().abs().sum(0)))
+    with X.ran("dense_wgrad_multi_kernel"):
+        hip.DenseWgradMulti(layers, dt).run()
+    torch.cuda.synchronize()
+    for L, (rw, mw, rc, mc) in zip(layers, refs):
+        K, N = L["K"], L["N"]
+        what = "dense wgrad %d x %d" % (K, N)
+        assert bool((L["part"][K * N:] == SENTINEL).all()), "%s: written behind K * N" % what
+        for got, r, m, part in ((L["part"][:K * N].reshape(K, N), rw, mw, "dW"), (L["colpart"], rc, mc, "column sums")):
+            if exact:
+                X.premise(0, stored=[(what, r)], mags=[(what, m)])
+                X.assert_exact(got, r, "%s %s" % (what, part))
+            else:
+                _record("dense_wgrad_multi", X.assert_rounded_once(got, r, m, 0, M, "%s %s" % (what, part)))
+
+
+# ---------------------------------------------------------------- batched weight gradients (conv_wgrad.hip, conv_hwgrad.hip)
+def _wgrad_operands(g, dt, exact, seed):
+    """x [B][H][W][C] and dz [B][OH][OW][N] of a weight gradient over K = B OH OW pixels (exact: sparse integers), and the float64
+    references on the device: dW, its magnitude, the column sums and theirs."""
+    K = g.B * g.OH * g.OW
+    x = _operands((g.B, g.H, g.W, g.C), dt, exact, K, seed)
+    dz = _operands((g.B, g.OH, g.OW, g.N), dt, exact, K, seed + 1)
+    xc, zc = x.cuda().double(), dz.cuda().double()
+    k, s, pad = g.KH, g.SH, (g.PH, g.PW)
+    r = (X.wgrad64(xc, zc, k, s, pad).cpu(), X.wgrad64(xc.abs(), zc.abs(), k, s, pad).cpu(), zc.sum((0, 1, 2)).cpu(), zc.abs().sum((0, 1, 2)).cpu())
+    if exact:
+        X.premise(0, stored=[("dW", r[0]), ("colsum", r[2])], mags=[("dW", r[1]), ("colsum", r[3])])
+    return x, dz, r
+
+
+def _check_partials(ws, splits, g, r, exact, what, K):
+    """float64 sums of a layer's split partials (layout of urso_conv_wgrad_partial) and column-sum partials against the references."""
+    kn = g.KH * g.KW * g.C * g.N
+    stride = kn + _hip().WGRAD_PART_PAD
+    part = ws[:splits * stride].reshape(splits, stride)[:, :kn].double().cpu().sum(0).reshape(g.KH, g.KW, g.C, g.N)
+    col = ws[splits * stride:splits * stride + splits * g.N].reshape(splits, g.N).double().cpu().sum(0)
+    for got, ref, mag, p in ((part, r[0], r[1], "dW"), (col, r[2], r[3], "column sums")):
+        if exact:
+            X.assert_exact(got, ref, "%s %s" % (what, p))
+        else:
+            _record("wgrad_batched", X.assert_rounded_once(got, ref, mag, 0, K, "%s %s" % (what, p)))
+
+
+def _pw(M, C, N):
+    return (1, 1, M, C, 1, M, N, 1, 1, 1, 1, 0, 0)
+
+
+# the layer lists of test_grouped_weight_gradients: pointwise, strided 1x1, strided 3x3 and narrow-row 3x3 layers in one launch, ragged
+# channel counts; the wide lists take wgrad_group_big_kernel under wgrad_big = 1
+WG_LISTS = {
+    "pair": [_pw(4096, 256, 128), _pw(4096, 128, 256)],
+    "ragged_mixed_geometries": [_pw(8200, 1024, 256), _pw(8200, 256, 1024), _pw(4160, 136, 72), _pw(16384, 128, 512),
+                                (4, 65, 81, 128, 33, 41, 136, 3, 3, 2, 2, 1, 1), (4, 64, 80, 256, 32, 40, 128, 1, 1, 2, 2, 0, 0),
+                                (3, 40, 9, 128, 40, 9, 192, 3, 3, 1, 1, 1, 1)],
+    "wide_stage4_stage5_mix": [_pw(40960, 256, 1024)] * 2 + [_pw(10240, 2048, 512), _pw(10240, 512, 2048)],
+    "wide_ragged_mixed_geometries": [_pw(8200, 1024, 264), _pw(4160, 264, 520), (4, 65, 81, 256, 33, 41, 328, 3, 3, 2, 2, 1, 1),
+                                     (4, 64, 80, 512, 32, 40, 256, 1, 1, 2, 2, 0, 0), (3, 40, 9, 128, 40, 9, 256, 3, 3, 1, 1, 1, 1)],
+}
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("name", list(WG_LISTS))
+def test_wgrad_group_kernels(name, dt, exact):
+    """hip.WgradGroup: wgrad_group_kernel (wgrad_big = 0) with wgrad_ring 0 / 4 / 5 and, on the wide list, wgrad_group_big_kernel
+    (wgrad_big = 1): per layer, the float64 sum of its split partials and column-sum partials against float64 x^T dz of the layer's full
+    geometry; workspaces pre-filled with NaN (an unwritten split fails)."""
+    hip = _hip()
+    geoms = [hip.geom(*l) for l in WG_LISTS[name]]
+    ops = [_wgrad_operands(g, dt, exact, 40 + 7 * i + dt) for i, g in enumerate(geoms)]
+    xs, dzs = [dev(o[0], dt) for o in ops], [dev(o[1], dt) for o in ops]
+    wide = name.startswith("wide")
+    variants = [(0, ring, "wgrad_group_kernel") for ring in (0, 4, 5)] + ([(1, 0, "wgrad_group_big_kernel")] if wide else [])
+    for big, ring, sym in variants:
+        with hip.options(wgrad_big=big):
+            grp = hip.WgradGroup(geoms, dt)
+            assert grp.nblocks > 0
+            KN = [g.KH * g.KW * g.C * g.N for g in geoms]
+            wss = [torch.full((s * (kn + hip.WGRAD_PART_PAD) + s * g.N + 64,), float("nan"), device="cuda")
+                   for s, kn, g in zip(grp.splits, KN, geoms)]
+            grp.bind(xs, dzs, wss, "cuda")
+        with hip.options(wgrad_ring=ring), X.ran(sym):
+            grp.run()
+        torch.cuda.synchronize()
+        for i, g in enumerate(geoms):
+            _check_partials(wss[i], grp.splits[i], g, ops[i][2], exact, "%s layer %d (big %d, ring %d)" % (name, i, big, ring), g.B * g.OH * g.OW)
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("shapes", [((4, 32, 40, 256, 256), (4, 32, 40, 256, 256)), ((4, 33, 41, 128, 128), (3, 17, 23, 256, 128)),
+                                    ((8, 64, 80, 128, 128), (8, 32, 40, 256, 256))],
+                         ids=["twins", "ragged_unequal", "stage3_with_stage4"])
+def test_hwgrad2_kernel(shapes, dt, exact):
+    """urso_conv_wgrad_partial2 (hwgrad2_kernel): two 3x3 / s1 / pad-1 weight gradients in one launch, each layer's partials against float64."""
+    hip = _hip()
+    gs = [hip.geom(B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 1) for (B, H, W, C, N) in shapes]
+    sp = hip.conv_wgrad_pair_splits(gs[0], gs[1], dt)
+    assert sp is not None
+    ops = [_wgrad_operands(g, dt, exact, 60 + 5 * i + dt) for i, g in enumerate(gs)]
+    wss = [torch.full((s * (9 * g.C * g.N + hip.WGRAD_PART_PAD) + s * g.N + 64,), float("nan"), device="cuda") for s, g in zip(sp, gs)]
+    with X.ran("hwgrad2_kernel"):
+        hip.conv_wgrad_partial2(gs[0], gs[1], dt, dev(ops[0][0], dt), dev(ops[0][1], dt), wss[0], dev(ops[1][0], dt), dev(ops[1][1], dt), wss[1])
+    torch.cuda.synchronize()
+    for i, g in enumerate(gs):
+        _check_partials(wss[i], sp[i], g, ops[i][2], exact, "hwgrad2 layer %d" % i, g.B * g.H * g.W)
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("shape", [(2, 16, 24, 64, 64, 3), (2, 32, 40, 128, 128, 3), (3, 16, 16, 64, 256, 1), (4, 128, 160, 64, 64, 3)],
+                         ids=["c3x3_64", "c3x3_128", "pointwise_wide", "stage2_rows"])
+def test_wgrad_coarse_grid_dz(shape, dt, exact):
+    """urso_conv_wgrad with dz read on a coarser grid (FH / FW / OSH / OSW: element (2 oy, 2 ox) of a [B][H][W][N] tensor is output pixel
+    (oy, ox) of the stride-2 layer) against float64 x^T dz of the COMPACT gradient; the positions between are never read (sentinel there)."""
+    hip = _hip()
+    B, H, W, Ci, N, k = shape
+    pad = k // 2
+    g = hip.geom(B, H, W, Ci, H // 2, W // 2, N, k, k, 2, 2, pad, pad, FH=H, FW=W, OSH=2, OSW=2)
+    x, compact, r = _wgrad_operands(hip.geom(B, H, W, Ci, H // 2, W // 2, N, k, k, 2, 2, pad, pad), dt, exact, sum(shape) + dt)
+    dense = full((B, H, W, N), dt)
+    dense[:, ::2, ::2] = dev(compact, dt)
+    ws = torch.full((hip.conv_wgrad_ws_bytes(g, dt) // 4 + 64,), float("nan"), device="cuda")
+    dw, cs = full((k, k, Ci, N), 0), full((N,), 0)
+    with X.ran("wgrad"):
+        hip.conv_wgrad(g, dt, dev(x, dt), dense, ws, dw, cs)
+    torch.cuda.synchronize()
+    for got, ref, mag, p in ((dw, r[0], r[1], "dW"), (cs, r[2], r[3], "column sums")):
+        if exact:
+            X.assert_exact(got, ref, "coarse-grid dz " + p)
+        else:
+            _record("wgrad_coarse", X.assert_rounded_once(got, ref, mag, 0, B * (H // 2) * (W // 2), "coarse-grid dz " + p))

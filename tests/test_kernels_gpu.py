@@ -1636,8 +1636,8 @@ def test_dense_heads_in_one_launch(dt, M):
 @pytest.mark.parametrize("shape", [(3, 16, 20, 128, 32, 0), (32, 16, 20, 2048, 32, 0), (2, 20, 30, 256, 32, 0), (2, 9, 11, 64, 32, 1), (2, 4, 4, 512, 32, 0), (2, 16, 20, 64, 24, 0)],
                          ids=["tfsame_small", "cfg2_full", "cfg5_grid", "odd_grid_pad1", "cfg1_r18", "n24"])
 def test_bottleneck_layer_kernels(dt, shape):
-    """conv_bneck.hip through urso_conv_igemm_ex (option bneck: bit 0 = data gradient, default; bit 1 = forward, opt-in): bottleneck_layer (net.py:639-640: 3x3 / stride 2 / SAME, <= 32
-    filters) forward in one launch with the reduction split over the block's waves, and its data gradient by parity class (only the real
+    """conv_bneck.hip through urso_conv_igemm_ex (option bneck: bit 0 = data gradient, bit 1 = forward; default 3, both): bottleneck_layer (net.py:639-640: 3x3 / stride 2 / SAME, <= 32
+    filters) forward in one launch with the reduction split over the block's waves (C % 512 == 0; the general kernel otherwise), and its data gradient by parity class (only the real
     taps).  Forward against the CPU fp32 reference and the general split-K kernel (bneck = 0; other summation order: tolerance); the data
     gradient -- same taps in the same order, zero taps skipped -- BIT FOR BIT against the general dilated kernel, with and without the ReLU
     bit mask of the destination."""
