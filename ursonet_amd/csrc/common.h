@@ -90,11 +90,13 @@ template <> struct Elem<float> {
 };
 template <> struct Elem<__bf16> {
     static constexpr int VE = 8;
+    static constexpr int ONES = 0x3F803F80;         // two packed 1.0: a register of an all-ones MFMA operand (column sums)
     static __device__ __forceinline__ float to_f(__bf16 v) { return (float)v; }
     static __device__ __forceinline__ __bf16 from_f(float v) { return (__bf16)v; }
 };
 template <> struct Elem<_Float16> {
     static constexpr int VE = 8;
+    static constexpr int ONES = 0x3C003C00;
     static __device__ __forceinline__ float to_f(_Float16 v) { return (float)v; }
     static __device__ __forceinline__ _Float16 from_f(float v) { return (_Float16)v; }
 };

@@ -11,7 +11,8 @@
 //             taps in registers: the launch reads 164 KB of dz and writes dx once (42 MB), ReLU bit mask applied in registers.
 // Same operand layouts as urso_conv_igemm_ex (filters [n][ky][kx][c] forward, [c][ky'][kx'][n] flipped for the data gradient, as
 // urso_conv_weight_prep writes them), same tap order, fp32 accumulation, one rounding.
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 
 struct BnfArgs {
     const void* src; const void* wgt; const float* bias; void* dst;
@@ -19,16 +20,6 @@ struct BnfArgs {
     int B, H, W, C, OH, OW, N, PH, PW, M, relu;
     int cq;                  // 512-channel quarters per tap (C / 512)
 };
-
-__device__ __forceinline__ void bn_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    // m0 = wave-uniform LDS destination; lane l lands at m0 + 16 l (conv_pw.hip pw_dma16)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t bn_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void bn_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // forward: grid = ceil(M / 16) blocks of 16 waves; a block = 16 output pixels x 32 filters.  The reduction (9 taps x C channels) is cut into
 // chunks of (one tap, 512 channels): per chunk 32 filter rows and 16 pixel rows of 1 KiB each arrive by LDS-DMA -- one instruction = one
@@ -44,7 +35,7 @@ __global__ __launch_bounds__(1024) void bneck_fwd_kernel(const BnfArgs a) {
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
-    const i32x4_t rs = bn_rsrc(a.src, a.src_bytes), rw = bn_rsrc(a.wgt, a.wgt_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.src_bytes), rw = raw_rsrc(a.wgt, a.wgt_bytes);
     // this wave's copy roles: filter rows `wave` and 16 + `wave`, pixel row `wave` (output pixel m0 + wave)
     const int mw = blockIdx.x * 16 + wave;
     const int ohw = a.OH * a.OW;
@@ -62,9 +53,9 @@ __global__ __launch_bounds__(1024) void bneck_fwd_kernel(const BnfArgs a) {
         const bool pok = mw < a.M && iy >= 0 && ix >= 0 && iy < a.H && ix < a.W;
         const uint32_t psrc = pok ? (uint32_t)(((bw * a.H + iy) * a.W + ix) * a.C + q * 512) * 2u + lsw : URSO_OOB_SHIFT;
         const uint32_t st = lds0 + (uint32_t)(ch % NSTG) * STAGE;
-        bn_dma16(rw, st + (uint32_t)wave * 1024u, wsrc0 == URSO_OOB_SHIFT ? URSO_OOB_SHIFT : wsrc0 + ko);
-        bn_dma16(rw, st + (uint32_t)(16 + wave) * 1024u, wsrc1 == URSO_OOB_SHIFT ? URSO_OOB_SHIFT : wsrc1 + ko);
-        bn_dma16(rs, st + (uint32_t)(32 + wave) * 1024u, psrc);
+        lds_dma16(rw, st + (uint32_t)wave * 1024u, wsrc0 == URSO_OOB_SHIFT ? URSO_OOB_SHIFT : wsrc0 + ko);
+        lds_dma16(rw, st + (uint32_t)(16 + wave) * 1024u, wsrc1 == URSO_OOB_SHIFT ? URSO_OOB_SHIFT : wsrc1 + ko);
+        lds_dma16(rs, st + (uint32_t)(32 + wave) * 1024u, psrc);
     };
     // fragment read offsets inside a stage: k-step `wave` = logical slots 4 wave .. 4 wave + 3; row r's slot s sits at s ^ (r & 15)
     const uint32_t slot = (uint32_t)(((4 * wave + fg) ^ fr) << 4);
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(1024) void bneck_fwd_kernel(const BnfArgs a) {
     issue(0);
     if (nch > 1) issue(1);
     for (int ch = 0; ch < nch; ++ch) {
-        if (ch + 1 < nch) bn_wait_vm<3>(); else bn_wait_vm<0>();     // this wave's copies of chunk ch have landed (chunk ch + 1's may be in flight)
+        if (ch + 1 < nch) wait_vm<3>(); else wait_vm<0>();           // this wave's copies of chunk ch have landed (chunk ch + 1's may be in flight)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // ... every wave's have; and every wave is done reading the stage chunk ch + 2 goes to
         if (ch + 2 < nch) issue(ch + 2);
         const char* sb = smem + (ch % NSTG) * STAGE;
@@ -81,7 +72,7 @@ __global__ __launch_bounds__(1024) void bneck_fwd_kernel(const BnfArgs a) {
         Mma<T>::run(fw0, fp, acc0);                                   // D rows -> filters, columns -> pixels
         Mma<T>::run(fw1, fp, acc1);
     }
-    bn_wait_vm<0>();
+    wait_vm<0>();
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // every stage is free: the partial sums go to stage 0
     f32x4_t (*red)[2][64] = (f32x4_t (*)[2][64])smem;
     red[wave][0][lane] = acc0; red[wave][1][lane] = acc1;

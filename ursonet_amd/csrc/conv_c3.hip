@@ -14,10 +14,9 @@
 //   * LDS rows are 128 B with slot ^ ((row >> 1) & 7): conflict-free for any tap shift (conv_halo.hip derivation);
 //   * the result goes through a 16 KiB LDS tile to row-contiguous 16-byte stores (+ the ReLU mask of the data gradient, loaded with the
 //     same coalesced addresses); 72 KiB of LDS -> two blocks per CU.
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 #include <utility>
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 struct C3Args {
     const void* src; const void* wgt; const float* bias; const void* mask; void* dst;
@@ -30,26 +29,6 @@ constexpr int C3_TH = 4, C3_TW = 32, C3_HW = C3_TW + 2, C3_HROWS = (C3_TH + 2) *
 constexpr int C3_NA = 7;                                                                    // DMA instructions per lane and tile (4 waves x 7 x 8 rows = 224)
 constexpr int C3_ABUF = 224 * 128, C3_OOFF = 2 * C3_ABUF, C3_BOFF = C3_OOFF + C3_TH * C3_TW * 128, C3_LDS = C3_BOFF + 256;   // 2 x 28 KiB + 16 KiB + bias
 
-template <typename T> struct C3Mma;
-template <> struct C3Mma<__bf16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct C3Mma<_Float16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ void c3_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t c3_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void c3_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void c3_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // byte offset of (row, 16-byte slot 2 j + h) in a [rows][128 B] tile with slot ^ ((row >> 1) & 7)
 __device__ __forceinline__ uint32_t c3_rd(int row, int h, int j) {
     const int s = (row >> 1) & 7;
@@ -72,7 +51,7 @@ __global__ __launch_bounds__(256, 2) void c3_kernel(const C3Args a) {
     int tile = xcd * cpx + lb;
     if (tile >= t_end) return;
 
-    const i32x4_t rs = c3_rsrc(a.src, a.bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.bytes);
     const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.dst, a.bytes);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(MASK ? a.mask : a.dst, MASK ? a.bytes : 0u);
 
@@ -96,7 +75,7 @@ __global__ __launch_bounds__(256, 2) void c3_kernel(const C3Args a) {
             const int y = y0 - 1 + hy, x = x0 - 1 + hx;
             const bool ok = hr < C3_HROWS && y >= 0 && y < a.H && x >= 0 && x < a.W;
             const uint32_t off = (uint32_t)(base + (hy * a.W + hx) * 128 + (((lane_d & 7) ^ ((hx >> 1) & 7)) << 4));      // slot swizzle: see rd below
-            c3_dma16(rs, lds0 + buf * C3_ABUF + (wave + 4 * i) * 1024, ok ? off : URSO_OOB_SHIFT);
+            lds_dma16(rs, lds0 + buf * C3_ABUF + (wave + 4 * i) * 1024, ok ? off : URSO_OOB_SHIFT);
         }
     };
 
@@ -125,9 +104,9 @@ __global__ __launch_bounds__(256, 2) void c3_kernel(const C3Args a) {
     bool first = true;
     while (true) {
         const bool has_next = tile + bpx < t_end;
-        if (first) c3_wait_vm<0>(); else c3_wait_vm<NST>();      // this tile's patch (requested one tile ago); younger: that tile's stores
+        if (first) wait_vm<0>(); else wait_vm<NST>();            // this tile's patch (requested one tile ago); younger: that tile's stores
         first = false;
-        c3_barrier();
+        lds_barrier_asm();
         if (has_next) dma_tile(tile + bpx, buf ^ 1);
 
         f32x16_t acc[2];
@@ -164,8 +143,8 @@ __global__ __launch_bounds__(256, 2) void c3_kernel(const C3Args a) {
             if (s + 3 < 48) rd(f[(s + 3) & 3], s + 3);
             __builtin_amdgcn_sched_barrier(0);
             const int hr = s / 12, kx = (s / 4) % 3, j = s & 3;
-            if (hr <= 2) C3Mma<T>::run(wfr[3 * hr + kx][j], f[s & 3], acc[0]);
-            if (hr >= 1) C3Mma<T>::run(wfr[3 * (hr - 1) + kx][j], f[s & 3], acc[1]);
+            if (hr <= 2) Mma32<T>::run(wfr[3 * hr + kx][j], f[s & 3], acc[0]);
+            if (hr >= 1) Mma32<T>::run(wfr[3 * (hr - 1) + kx][j], f[s & 3], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
         }
 
@@ -194,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void c3_kernel(const C3Args a) {
             so[i] = (y < a.H && x < a.W) ? (uint32_t)(((b * a.H + y) * a.W + x) * 128 + (((lane & 7) ^ ((row >> 1) & 7)) << 4)) : URSO_OOB_SHIFT;
             if constexpr (MASK) mv[i] = buf_load16(rmk, so[i]);
         }
-        c3_barrier();
+        lds_barrier_asm();
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
             i32x4_t v = *(const i32x4_t*)(sO + (wave + 4 * i) * 1024 + lane * 16);
@@ -245,7 +224,7 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
     int tile = xcd * cpx + lb;
     if (tile >= t_end) return;
 
-    const i32x4_t rs = c3_rsrc(a.src, a.bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.bytes);
     const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.dst, a.bytes);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(MASK ? a.mask : a.dst, MASK ? a.bytes : 0u);
 
@@ -273,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
             // with 16 virtual rows between the two half rows of the 8 x 16 tile do those 16 lanes see 16 different (parity, swizzle) pairs
             const int sw = (hx >> 1) & 7;                      // on the position inside the halo row (= the virtual-pitch-16 index of the 18-pixel pitch, mod 8)
             const uint32_t off = (uint32_t)(base + (hy * a.W + hx) * 256 + half * 128 + (((lane_d & 7) ^ sw) << 4));
-            if (ii < 54) c3_dma16(rs, lds0 + buf * C3W_PATCH + half * C3_ABUF + rb * 1024, ok ? off : URSO_OOB_SHIFT);
+            if (ii < 54) lds_dma16(rs, lds0 + buf * C3W_PATCH + half * C3_ABUF + rb * 1024, ok ? off : URSO_OOB_SHIFT);
         }
     };
 
@@ -302,9 +281,9 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
     bool first = true;
     while (true) {
         const bool has_next = tile + bpx < t_end;
-        if (first) c3_wait_vm<0>(); else c3_wait_vm<NST>();
+        if (first) wait_vm<0>(); else wait_vm<NST>();
         first = false;
-        c3_barrier();                                          // (1)
+        lds_barrier_asm();                                     // (1)
         if (has_next) dma_tile(tile + bpx, buf ^ 1);
         f32x16_t acc[4];
 #pragma unroll
@@ -337,7 +316,7 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int ky = hr - r;
-                    if (ky >= 0 && ky <= 2) C3Mma<T>::run(wfr[3 * ky + kx][j], f[s & 3], acc[r]);
+                    if (ky >= 0 && ky <= 2) Mma32<T>::run(wfr[3 * ky + kx][j], f[s & 3], acc[r]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -359,7 +338,7 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     const int ky = rp - 2 * m;
-                    if (ky >= 0 && ky <= 2) C3Mma<T>::run(wfr[3 * ky + kx][j], f[s % 3], acc[m]);
+                    if (ky >= 0 && ky <= 2) Mma32<T>::run(wfr[3 * ky + kx][j], f[s % 3], acc[m]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -372,14 +351,14 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
             const uint32_t o = (uint32_t)(w * 8192 + ((rr * 4 + q) * 64 + lane) * 16);
             return (o < (uint32_t)C3W_PATCH) ? sX + o : smem + C3W_EOFF + (o - C3W_PATCH);
         };
-        c3_barrier();                                          // (2) every wave is done reading the patch
+        lds_barrier_asm();                                     // (2) every wave is done reading the patch
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
             const f32x16_t& v = (ch == 0) ? acc[2 + rr] : acc[rr];
 #pragma unroll
             for (int q = 0; q < 4; ++q) *(f32x4_t*)xoff(wave, rr, q) = f32x4_t{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
         }
-        c3_barrier();                                          // (3)
+        lds_barrier_asm();                                     // (3)
         f32x16_t fin[2];
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
@@ -390,7 +369,7 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
                 fin[rr][4 * q] += p.x; fin[rr][4 * q + 1] += p.y; fin[rr][4 * q + 2] += p.z; fin[rr][4 * q + 3] += p.w;
             }
         }
-        c3_barrier();                                          // (4) the exchange area is free: the output tile goes over it
+        lds_barrier_asm();                                     // (4) the exchange area is free: the output tile goes over it
         char* sO = sX;                                         // [128 pixels][256 B], slot ^ (pixel & 15)
         {
             const f32x4_t* bp = (const f32x4_t*)(smem + C3W_BOFF + (32 * fq + 16 * h) * 4);
@@ -420,7 +399,7 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
             so[i] = (y < a.H && x < a.W) ? (uint32_t)(((b * a.H + y) * a.W + x) * 256 + (((p & 15) ^ (px & 15)) << 4)) : URSO_OOB_SHIFT;
             if constexpr (MASK) mv[i] = buf_load16(rmk, so[i]);
         }
-        c3_barrier();                                          // (5)
+        lds_barrier_asm();                                     // (5)
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
             i32x4_t v = *(const i32x4_t*)(sO + (wave + 8 * i) * 1024 + lane * 16);
@@ -503,7 +482,7 @@ __global__ __launch_bounds__(512, 2) void c3v_kernel(const C3Args a) {
     int tile = xcd * cpx + lb;
     if (tile >= t_end) return;
 
-    const i32x4_t rs = c3_rsrc(a.src, a.bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.bytes);
     const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.dst, a.bytes);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(MASK ? a.mask : a.dst, MASK ? a.bytes : 0u);
 
@@ -527,7 +506,7 @@ __global__ __launch_bounds__(512, 2) void c3v_kernel(const C3Args a) {
             const int y = y0 - 1 + hy, x = x0 - 1 + hx;
             const bool ok = ii < 45 && y >= 0 && y < a.H && x >= 0 && x < a.W;
             const uint32_t off = (uint32_t)(base + (hy * a.W + hx) * 256 + (((uint32_t)(lane_d & 15) ^ c3v_swz(hx)) << 4));
-            if (ii < 45) c3_dma16(rs, lds0 + buf * C3V_PATCH + ii * 1024, ok ? off : URSO_OOB_SHIFT);
+            if (ii < 45) lds_dma16(rs, lds0 + buf * C3V_PATCH + ii * 1024, ok ? off : URSO_OOB_SHIFT);
         }
     };
 
@@ -572,8 +551,8 @@ __global__ __launch_bounds__(512, 2) void c3v_kernel(const C3Args a) {
     bool pend = false;
     while (true) {
         const bool has_next = tile + bpx < t_end;
-        c3_wait_vm<0>();                                       // this tile's patch (requested one tile ago) and the previous tile's mask vectors
-        c3_barrier();                                          // every wave's part of the patch has landed; the previous output tile is complete
+        wait_vm<0>();                                          // this tile's patch (requested one tile ago) and the previous tile's mask vectors
+        lds_barrier_asm();                                     // every wave's part of the patch has landed; the previous output tile is complete
         if (has_next) dma_tile(tile + bpx, buf ^ 1);
         if (pend) flush(ob ^ 1);
         f32x4_t acc[8];
@@ -636,8 +615,8 @@ __global__ __launch_bounds__(512, 2) void c3v_kernel(const C3Args a) {
         if (!has_next) break;
         tile += bpx; buf ^= 1; ob ^= 1;
     }
-    if constexpr (MASK) c3_wait_vm<0>();
-    c3_barrier();                                              // the last output tile is complete
+    if constexpr (MASK) wait_vm<0>();
+    lds_barrier_asm();                                         // the last output tile is complete
     flush(ob);
 }
 

@@ -9,10 +9,8 @@
 //     the tg 1 / ct 0 waves also carry the column sums): 5 x 16 accumulator registers, never reset;
 // a block walks its tiles (double-buffered LDS-DMA, one tile ahead) and writes ONE fp32 partial [576][64] (+ [64]) at the end; the
 // partials are summed in a fixed order by the batched split reduction like every other layer's.  88 KiB of LDS, one block per CU.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef short cg_s16x4_t __attribute__((ext_vector_type(4)));
+#include "lds_mfma.h"
+#include "internal.h"
 
 struct C3gArgs {
     const void* x; const void* dz; float* part; float* colpart; size_t part_stride;
@@ -28,54 +26,31 @@ constexpr int CG_ABUF = 224 * 128, CG_ZOFF = CG_ABUF, CG_STAGE = CG_ABUF + CG_TH
 #ifndef CG_SWZ
 #define CG_SWZ(r) ((((r) >> 1) & 1) << 2)
 #endif
-template <typename T> struct CgMma;
-template <> struct CgMma<__bf16> {
-    static constexpr int ONES = 0x3F803F80;
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct CgMma<_Float16> {
-    static constexpr int ONES = 0x3C003C00;
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ i32x2_t cg_tr16(const char* p) {
-    return __builtin_bit_cast(i32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) cg_s16x4_t*)p));
-}
-__device__ __forceinline__ void cg_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t cg_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
 
 // one tile's 8 reduction steps for a wave of tap group TG (taps 5 TG .. 5 TG + 4; tap 9 does not exist: the column sums) -- the taps are
 // compile-time constants here, so every halo-row offset folds into the address arithmetic
 template <typename T, int TG>
 __device__ __forceinline__ void cg_tile(const char* st, f32x16_t (&acc)[5], const uint32_t (&zoff)[2], const uint32_t (&abase)[8], bool csum) {
-    const i32x4_t ones = {CgMma<T>::ONES, CgMma<T>::ONES, CgMma<T>::ONES, CgMma<T>::ONES};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {                           // reduction step: tile row ry = ks >> 1, pixels 16 (ks & 1) .. + 15
         const int ry = ks >> 1, hs = ks & 1;
         const uint32_t zb = (uint32_t)((32 * ry + 16 * hs) * 128);
-        const i32x2_t zl = cg_tr16(st + zoff[0] + zb), zh = cg_tr16(st + zoff[1] + zb);
+        const i32x2_t zl = lds_read_tr16(st + zoff[0] + zb), zh = lds_read_tr16(st + zoff[1] + zb);
         const i32x4_t fz = i32x4_t{zl.x, zl.y, zh.x, zh.y};
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             constexpr int dummy = 0; (void)dummy;
             const int tap = 5 * TG + i;
-            if (tap == 9) { if (csum) CgMma<T>::run(ones, fz, acc[4]); continue; }
+            if (tap == 9) { if (csum) Mma32<T>::run(ones, fz, acc[4]); continue; }
             const int ky = tap / 3, kx = tap - 3 * ky;
             // halo rows of the 4 + 4 pixels this lane addresses: c + pix8 (+ 4) with c = (ry + ky) * 34 + 16 hs + kx a compile-time constant:
             // the swizzle term only depends on c mod 8 (abase[]), the rest is an immediate offset -- no address arithmetic per read
             constexpr int dummy2 = 0; (void)dummy2;
             const int c0 = (ry + ky) * CG_HW + 16 * hs + kx, c1 = c0 + 4;
-            const i32x2_t al = cg_tr16(st + abase[c0 & 7] + c0 * 128);
-            const i32x2_t ah = cg_tr16(st + abase[c1 & 7] + c1 * 128);
-            CgMma<T>::run(i32x4_t{al.x, al.y, ah.x, ah.y}, fz, acc[i]);
+            const i32x2_t al = lds_read_tr16(st + abase[c0 & 7] + c0 * 128);
+            const i32x2_t ah = lds_read_tr16(st + abase[c1 & 7] + c1 * 128);
+            Mma32<T>::run(i32x4_t{al.x, al.y, ah.x, ah.y}, fz, acc[i]);
         }
     }
 }
@@ -94,7 +69,7 @@ __global__ __launch_bounds__(512, 2) void c3g_kernel(const C3gArgs a) {
     const int t_end = min((xcd + 1) * cpx, a.ntiles);
     int tile = xcd * cpx + lb;
 
-    const i32x4_t rx = cg_rsrc(a.x, a.bytes), rz = cg_rsrc(a.dz, a.bytes);
+    const i32x4_t rx = raw_rsrc(a.x, a.bytes), rz = raw_rsrc(a.dz, a.bytes);
 
     // ---- copies of a tile: the halo patch (instruction ii = wave + 8 i covers halo rows 8 ii + (lane >> 3), slot (lane & 7) ^ CG_SWZ(row);
     //      pixels outside the image = out-of-range offsets = zeros) and the dz tile (rows = the tile's 128 pixels in row-major order)
@@ -110,7 +85,7 @@ __global__ __launch_bounds__(512, 2) void c3g_kernel(const C3gArgs a) {
             const int y = y0 - 1 + hy, x = x0 - 1 + hx;
             const bool ok = hr < CG_HROWS && y >= 0 && y < a.H && x >= 0 && x < a.W;
             const uint32_t off = (uint32_t)(((b * a.H + y) * a.W + x) * 128 + (((lane & 7) ^ CG_SWZ(hr)) << 4));
-            if (ii < 26) cg_dma16(rx, sb + ii * 1024, ok ? off : URSO_OOB_SHIFT);
+            if (ii < 26) lds_dma16(rx, sb + ii * 1024, ok ? off : URSO_OOB_SHIFT);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -119,7 +94,7 @@ __global__ __launch_bounds__(512, 2) void c3g_kernel(const C3gArgs a) {
             const int y = y0 + (row >> 5), x = x0 + (row & 31);
             const bool ok = y < a.H && x < a.W;
             const uint32_t off = (uint32_t)(((b * a.H + y) * a.W + x) * 128 + (((lane & 7) ^ CG_SWZ(row)) << 4));
-            cg_dma16(rz, sb + CG_ZOFF + ii * 1024, ok ? off : URSO_OOB_SHIFT);
+            lds_dma16(rz, sb + CG_ZOFF + ii * 1024, ok ? off : URSO_OOB_SHIFT);
         }
     };
 

@@ -12,6 +12,7 @@
 //   * grid = N / 16 blocks: 64-256 CUs busy for the head layers of cfg2.
 // Same operand layouts and k order conventions as urso_conv_igemm (weights [N][K] as urso_conv_weight_prep writes them).
 #include "common.h"
+#include "internal.h"
 
 #ifndef URSO_DENSE_UN
 #define URSO_DENSE_UN 4

@@ -25,9 +25,8 @@
 // every cfg2 layer -- see DESIGN.md section 13.
 // The filter rows are permuted on the DMA source side so that a lane's 16 accumulators are two runs of 8 consecutive output
 // channels: the epilogue (bias, residual, ReLU, mask) stores 16-byte vectors straight from registers.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+#include "lds_mfma.h"
+#include "internal.h"
 
 struct HcArgs {
     const void* src; const void* wgt; const float* bias; const void* add; const void* mask; void* dst;
@@ -48,41 +47,6 @@ struct HcArgs {
     unsigned int* flags;       // [gridDim.x] hand-over flags, zero on entry and on exit
     float* part;               // [gridDim.x][512 threads][64] fp32 partial accumulators
 };
-
-template <typename T> struct Mma32;
-template <> struct Mma32<__bf16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma32<_Float16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ void hc_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    // m0 = wave-uniform LDS destination; lane l lands at m0 + 16 l (conv_pw.hip pw_dma16)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t hc_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void hc_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void hc_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-// byte offset of (row, 16-byte chunk 2*k16 + h) inside a [rows][128 B] tile is  hc_rd(row, h) ^ (k16 << 5)
-__device__ __forceinline__ uint32_t hc_rd(int row, int h) {
-    const int s = (row >> 1) & 7;
-    return (uint32_t)(row * 128 + ((s >> 1) << 5) + ((h ^ (s & 1)) << 4));
-}
-// MFMA row rho of a 32-filter sub-tile <-> filter offset: lane half h then holds filters 8h..8h+7 in accumulators 0..7 and 16+8h.. in 8..15
-__device__ __forceinline__ int hc_perm(int rho) {
-    const int g = rho >> 3, hh = (rho >> 2) & 1, e = rho & 3;
-    return 16 * (g >> 1) + 8 * hh + 4 * (g & 1) + e;
-}
 
 constexpr int HC_BM = 256, HC_BN = 128, HC_BSLOT = HC_BN * 128, HC_AROWS = 424, HC_ABUF = HC_AROWS * 128;
 constexpr int HC_AOFF = 3 * HC_BSLOT, HC_XOFF = HC_AOFF + 2 * HC_ABUF, HC_LDS = 163840, HC_MAXN = (HC_LDS - HC_XOFF) / 4;
@@ -115,7 +79,7 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
     if (g0 >= g1) return;
     const int t_begin = g0 / a.nchunks, c_begin = g0 - t_begin * a.nchunks;
 
-    const i32x4_t rs = hc_rsrc(a.src, a.src_bytes), rw = hc_rsrc(a.wgt, a.wgt_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.src_bytes), rw = raw_rsrc(a.wgt, a.wgt_bytes);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(a.mask ? a.mask : a.dst, a.mask ? a.dst_bytes : 0u);
     const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.dst, a.dst_bytes);
 
@@ -131,7 +95,7 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
     uint32_t boff[2];
     int rb[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) boff[j] = hc_rd(64 * wn + 32 * j + l31, h);
+    for (int j = 0; j < 2; ++j) boff[j] = halo_rd(64 * wn + 32 * j + l31, h);
 #pragma unroll
     for (int i = 0; i < 2; ++i) rb[i] = 64 * wm + 32 * i + l31;
 
@@ -141,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int Rr = 8 * (wave + LW * q) + r8;
-        const int nl = (Rr & ~31) + hc_perm(Rr & 31);
+        const int nl = (Rr & ~31) + halo_perm(Rr & 31);
         bsrc0[q] = (uint32_t)nl * (uint32_t)a.krow + (uint32_t)((c8 ^ ((Rr >> 1) & 7)) << 4);
     }
 
@@ -175,13 +139,13 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
     };
     auto dma_a = [&](int j, int cc, int buf) {                 // static j
         if (wave < LW && 8 * (wave + LW * j) < a.R)
-            hc_dma16(rs, lds0 + AOFF + buf * ABUF + (wave + LW * j) * 1024, arow[j] + (uint32_t)cc * 128u);      // OOB_SHIFT + small stays out of range
+            lds_dma16(rs, lds0 + AOFF + buf * ABUF + (wave + LW * j) * 1024, arow[j] + (uint32_t)cc * 128u);     // OOB_SHIFT + small stays out of range
     };
     auto dma_b = [&](int n0_, int cc, int t, int slot) {       // filter tile (chunk cc, tap t) of the filter block starting at n0_
         const uint32_t koff = (uint32_t)n0_ * (uint32_t)a.krow + (uint32_t)(t * a.C + cc * 64) * 2u;
         if (wave < LW) {
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) hc_dma16(rw, lds0 + slot * BSLOT + (wave + LW * q) * 1024, bsrc0[q] + koff);
+            for (int q = 0; q < NQ; ++q) lds_dma16(rw, lds0 + slot * BSLOT + (wave + LW * q) * 1024, bsrc0[q] + koff);
         }
     };
 
@@ -193,8 +157,8 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
         for (int j = 0; j < NJ; ++j) dma_a(j, c_begin, 0);
         dma_b(n0, c_begin, 0, 0);
         dma_b(n0, c_begin, 1, 1);
-        hc_wait_vm<0>();
-        hc_barrier();                                         // also publishes the bias written above
+        wait_vm<0>();
+        lds_barrier_asm();                                    // also publishes the bias written above
     }
     int buf = 0;
     i32x4_t fw0[2], fp0[2], fw1[2], fp1[2];                  // fragment sets of two consecutive 16-deep k sub-steps
@@ -202,7 +166,7 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) fw[j] = *(const i32x4_t*)(smem + bbase + (boff[j] ^ (uint32_t)(k << 5)));
 #pragma unroll
-        for (int i = 0; i < 2; ++i) fp[i] = *(const i32x4_t*)(smem + abase + (hc_rd(rb[i] + shift, h) ^ (uint32_t)(k << 5)));
+        for (int i = 0; i < 2; ++i) fp[i] = *(const i32x4_t*)(smem + abase + (halo_rd(rb[i] + shift, h) ^ (uint32_t)(k << 5)));
     };
     rd(fw0, fp0, 0, AOFF, 0, 0);                              // step 0, k = 0
 
@@ -256,7 +220,7 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
                 // ---- mid-step: this wave's copies issued one step ago have landed -> barrier -> every wave's have, and every wave has
                 //      finished reading the previous step's ring slot and (at t = 0) the previous chunk's halo buffer
-                if (t == 0 && first_wait_after_epilogue) hc_wait_vm<HC_NST>(); else hc_wait_vm<0>();
+                if (t == 0 && first_wait_after_epilogue) wait_vm<HC_NST>(); else wait_vm<0>();
                 if (!(a.dbg & 64)) hc_sbarrier();
                 if (!(a.dbg & 32)) {   // filter tile two steps ahead -> ring slot (t + 2) % 3; one piece of the next halo tile -> the other halo buffer
                     const int t2 = (t + 2) % 9;
@@ -408,12 +372,7 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
     }
 }
 
-int urso_hconv2_try_launch(const urso_conv_geom* g, int dt, int relu, const void* src, const void* wgt, const float* bias, const void* mask,
-                           void* dst, uint32_t src_bytes, uint32_t wgt_bytes, uint32_t dst_bytes, void* ws, bool has_ws, hipStream_t st);      // conv_halo2.hip
-
 static int hc_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
-int urso_hconv2_pick(const urso_conv_geom* g, bool has_ws);                                                                          // conv_halo2.hip
 
 // Does (g, dt, flags) qualify?  3x3 / stride 1 / pad 1 / undilated, same-size output, C % 128 == 0, N % 128 == 0, halo tile within the LDS
 // budget -- and a tile count that fills the 256 one-block-per-CU slots evenly: every block walks ceil(tiles / blocks) tiles, so e.g. 340

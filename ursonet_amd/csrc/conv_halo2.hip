@@ -29,13 +29,12 @@
 // Results are bit-identical to conv_halo.hip's whole-tile schedule (same MFMA, same k order per output element).
 // Measured (bf16, B = 32, isolated / in the step): stage 4 47.7 / 46-50 us (1.01 PFLOP/s), stage 5 49.0 / 57-59 us (its 4.7 MB filter
 // is cold in the step and a two-slot ring hides one step of latency).
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 #include <type_traits>
 #ifndef URSO_HX2_NS1
 #define URSO_HX2_NS1 4          // filter-ring slots of the NJ = 1 shapes (2: the two-slot protocol of NJ = 2; A/B through URSO_VARIANT_FLAGS)
 #endif
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 struct Hx2Args {
     const void* src; const void* wgt; const float* bias; const void* mask; void* dst;
@@ -52,39 +51,6 @@ struct Hx2Args {
     unsigned long long* clk;   // experiments: per block {shader cycles, 100 MHz ticks} of the run (hconv_dbg bit 11, needs a workspace)
     int dbg;                   // experiments (urso_set_option("hconv_dbg")): bit 0 no epilogue, bit 1 no step loop, bit 5 no copies in the loop, bit 6 no barrier in the loop (timing only)
 };
-
-template <typename T> struct Hx2Mma;
-template <> struct Hx2Mma<__bf16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct Hx2Mma<_Float16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ void hx_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    // m0 = wave-uniform LDS destination; lane l lands at m0 + 16 l (conv_pw.hip pw_dma16)
-    // (readfirstlane: under SGPR pressure hipcc has been seen to keep this wave-uniform value in a VGPR and hand it to the "s" operand as such)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(__builtin_amdgcn_readfirstlane(lds_byte)), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t hx_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void hx_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-// byte offset of (row, 16-byte chunk 2*k16 + h) inside a [rows][128 B] tile is  hx_rd(row, h) ^ (k16 << 5)   (conv_halo.hip hc_rd)
-__device__ __forceinline__ uint32_t hx_rd(int row, int h) {
-    const int s = (row >> 1) & 7;
-    return (uint32_t)(row * 128 + ((s >> 1) << 5) + ((h ^ (s & 1)) << 4));
-}
-// MFMA row rho of a 32-filter sub-tile <-> filter offset: lane half h then holds filters 8h..8h+7 in accumulators 0..7 and 16+8h.. in 8..15
-__device__ __forceinline__ int hx_perm(int rho) {
-    const int g = rho >> 3, hh = (rho >> 2) & 1, e = rho & 3;
-    return 16 * (g >> 1) + 8 * hh + 4 * (g & 1) + e;
-}
 
 constexpr int HX_LDS = 163840;
 // LDS map (fixed, so that every fragment read is a VGPR base + an immediate): halo buffer 0 at 0, halo buffer 1 at HX_ABUF1 (a 16-bit
@@ -123,7 +89,7 @@ __global__ __launch_bounds__(512, 2) void hconv2_kernel(const Hx2Args a) {
     const int t_begin = (int)(((long long)lid * a.ntiles) / G), t_end = (int)(((long long)(lid + 1) * a.ntiles) / G);
     if (t_begin >= t_end || (a.dbg & 1024)) return;
 
-    const i32x4_t rs = hx_rsrc(a.src, a.src_bytes), rw = hx_rsrc(a.wgt, a.wgt_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.src_bytes), rw = raw_rsrc(a.wgt, a.wgt_bytes);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(a.mask ? a.mask : a.dst, a.mask ? a.dst_bytes : 0u);
     const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.dst, a.dst_bytes);
 
@@ -138,16 +104,16 @@ __global__ __launch_bounds__(512, 2) void hconv2_kernel(const Hx2Args a) {
     //      virtual pixel p0 - Vw - 1).  The swizzle depends on (row >> 1) & 7 only, so 32 rows further is +4096 bytes: the MFMA sub-tiles
     //      i, j, the ring slot and halo buffer 0 are immediates of the read, the k sub-step is one v_xor per operand (bits 5-6)
     uint32_t fb, pb[9];
-    fb = HX_FOFF + hx_rd(32 * NJ * wn + l31, h);
+    fb = HX_FOFF + halo_rd(32 * NJ * wn + l31, h);
 #pragma unroll
-    for (int t = 0; t < 9; ++t) pb[t] = hx_rd(32 * MI * wm + l31 + (t / 3) * a.Vw + (t % 3), h);
+    for (int t = 0; t < 9; ++t) pb[t] = halo_rd(32 * MI * wm + l31 + (t / 3) * a.Vw + (t % 3), h);
 
     // ---- filter-tile DMA roles: instruction q covers ring rows 8 (wave + 8 q) + r8
     uint32_t bsrc0[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int Rr = 8 * (wave + 8 * q) + r8;
-        const int nl = (Rr & ~31) + hx_perm(Rr & 31);
+        const int nl = (Rr & ~31) + halo_perm(Rr & 31);
         bsrc0[q] = (uint32_t)nl * (uint32_t)a.krow + (uint32_t)((c8 ^ ((Rr >> 1) & 7)) << 4);
     }
 
@@ -184,12 +150,12 @@ __global__ __launch_bounds__(512, 2) void hconv2_kernel(const Hx2Args a) {
     };
     auto dma_a = [&](int j, int cc, int buf, uint32_t rowoff) {
         if (8 * (wave + 8 * j) < a.R)
-            hx_dma16(rs, lds0 + buf * HX_ABUF1 + (wave + 8 * j) * 1024, rowoff + aswz + (uint32_t)cc * 128u);      // OOB_SHIFT + small stays out of range
+            lds_dma16_sgpr(rs, lds0 + buf * HX_ABUF1 + (wave + 8 * j) * 1024, rowoff + aswz + (uint32_t)cc * 128u);  // OOB_SHIFT + small stays out of range
     };
     auto dma_b = [&](int n0_, int cc, int t, int slot) {       // filter tile (chunk cc, tap t) of the filter block starting at n0_
         const uint32_t koff = (uint32_t)n0_ * (uint32_t)a.krow + (uint32_t)(t * a.C + cc * 64) * 2u;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) hx_dma16(rw, lds0 + HX_FOFF + slot * BSLOT + (wave + 8 * q) * 1024, bsrc0[q] + koff);
+        for (int q = 0; q < NQ; ++q) lds_dma16_sgpr(rw, lds0 + HX_FOFF + slot * BSLOT + (wave + 8 * q) * 1024, bsrc0[q] + koff);
     };
 
     const unsigned long long clk0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
@@ -204,7 +170,7 @@ __global__ __launch_bounds__(512, 2) void hconv2_kernel(const Hx2Args a) {
             if (j < a.JA) dma_a(j, 0, 0, table_entry(0, j));
 #pragma unroll
         for (int t = 0; t < NS; ++t) dma_b(n0, 0, t, t);
-        hx_wait_vm<0>();
+        wait_vm<0>();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // also publishes the bias written above
     }
     i32x4_t fwA[NJ], fpA[MI], fwB[NJ], fpB[MI];               // fragment sets of two consecutive 16-deep k sub-steps
@@ -258,7 +224,7 @@ __global__ __launch_bounds__(512, 2) void hconv2_kernel(const Hx2Args a) {
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) Hx2Mma<T>::run(fw[j], fp[i], acc[i][j]);
+                for (int j = 0; j < NJ; ++j) Mma32<T>::run(fw[j], fp[i], acc[i][j]);
         };
         // A region = the MI + NJ fragment reads of the next k sub-step, then the MI NJ MFMAs of this one (operands read a region ago).  Spreading
         // the reads between the MFMAs (sched_group_barrier: one read behind each MFMA) was measured and lost: 51.6 against 48.6 us on the cfg2

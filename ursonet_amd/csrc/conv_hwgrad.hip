@@ -17,11 +17,9 @@
 //   * double-buffered LDS-DMA one tile ahead, 112 KiB of LDS, one block per CU; logical block ids are XCD-contiguous with the group index
 //     fastest, so the blocks that share a pixel range (all groups of a split) sit behind one L2.
 // Copies per layer: groups x pixels x 256 B x (1 + halo) -- 3.5x fewer than before at stage 4.
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef short hw_s16x4_t __attribute__((ext_vector_type(4)));
 
 struct HwgArgs {
     const void* x; const void* dz; float* part; float* colpart; size_t part_stride;
@@ -36,46 +34,20 @@ constexpr int HW_AROWS = 320, HW_ABUF = HW_AROWS * 128, HW_ZOFF = HW_ABUF, HW_ST
 constexpr int HW_TBL = 6144;                                  // entries of the block's pixel-offset tables (2 x 23 KiB behind the stages)
 #define HW_SWZ(r) ((((r) >> 1) & 1) << 2)                     // conv_c3g.hip: the four rows of a transposing read land on four bank quarters
 
-template <typename T> struct HwMma;
-template <> struct HwMma<__bf16> {
-    static constexpr int ONES = 0x3F803F80;
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct HwMma<_Float16> {
-    static constexpr int ONES = 0x3C003C00;
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ i32x2_t hw_tr16(const char* p) {
-    return __builtin_bit_cast(i32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) hw_s16x4_t*)p));
-}
-__device__ __forceinline__ void hw_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t hw_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    // (readfirstlane: the paired launch selects its argument set per block, and the selects are not always proven wave-uniform)
-    return i32x4_t{__builtin_amdgcn_readfirstlane((int)(uint32_t)a), __builtin_amdgcn_readfirstlane((int)(uint32_t)((a >> 32) & 0xFFFFu)),
-                   __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-}
-
 // one tile's 8 reduction steps (16 pixels each) for a wave of tap group TG; abase[i] = this lane's read base of tap 5 TG + i.  The
 // fragments of step ks + 1 are read (into the other of two named register sets) while step ks multiplies: left to itself hipcc reads two
 // fragments, waits, issues one MFMA -- the LDS latency of every transposing read is then exposed (66 us per layer against 48)
 template <typename T, int TG>
 __device__ __forceinline__ void hw_tile(const char* st, f32x16_t (&acc)[5], const uint32_t (&zoff)[2], const uint32_t (&abase)[5], bool csum) {
-    const i32x4_t ones = {HwMma<T>::ONES, HwMma<T>::ONES, HwMma<T>::ONES, HwMma<T>::ONES};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
     constexpr int NT = (TG == 0) ? 5 : 4;                      // real taps of this group (tap 9 = the column sums: no x fragment)
     i32x4_t fz[2], fa[2][5];
     auto rd = [&](int set, int ks) {
-        const i32x2_t zl = hw_tr16(st + zoff[0] + ks * 16 * 128), zh = hw_tr16(st + zoff[1] + ks * 16 * 128);
+        const i32x2_t zl = lds_read_tr16(st + zoff[0] + ks * 16 * 128), zh = lds_read_tr16(st + zoff[1] + ks * 16 * 128);
         fz[set] = i32x4_t{zl.x, zl.y, zh.x, zh.y};
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            const i32x2_t al = hw_tr16(st + abase[i] + ks * 16 * 128), ah = hw_tr16(st + abase[i] + ks * 16 * 128 + 4 * 128);
+            const i32x2_t al = lds_read_tr16(st + abase[i] + ks * 16 * 128), ah = lds_read_tr16(st + abase[i] + ks * 16 * 128 + 4 * 128);
             fa[set][i] = i32x4_t{al.x, al.y, ah.x, ah.y};
         }
     };
@@ -85,8 +57,8 @@ __device__ __forceinline__ void hw_tile(const char* st, f32x16_t (&acc)[5], cons
         const int cur = ks & 1;
         if (ks < 7) rd(cur ^ 1, ks + 1);
 #pragma unroll
-        for (int i = 0; i < NT; ++i) HwMma<T>::run(fa[cur][i], fz[cur], acc[i]);
-        if (TG == 1 && csum) HwMma<T>::run(ones, fz[cur], acc[4]);
+        for (int i = 0; i < NT; ++i) Mma32<T>::run(fa[cur][i], fz[cur], acc[i]);
+        if (TG == 1 && csum) Mma32<T>::run(ones, fz[cur], acc[4]);
         if (ks < 7) {                                          // (2 + 2 NT) reads of the next step spread behind this step's MFMAs
             __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -121,7 +93,7 @@ __device__ __forceinline__ void hwgrad_body(const HwgArgs& a, const int bid, con
     const int cg = grp / a.Gn, ng = grp - cg * a.Gn;
     const int t0 = (int)(((long long)sp * a.T) / a.S), t1 = (int)(((long long)(sp + 1) * a.T) / a.S);
 
-    const i32x4_t rx = hw_rsrc(a.x, a.x_bytes), rz = hw_rsrc(a.dz, a.dz_bytes);
+    const i32x4_t rx = raw_rsrc_sgpr(a.x, a.x_bytes), rz = raw_rsrc_sgpr(a.dz, a.dz_bytes);
     auto divmod = [](int n, int d, float rcp, int& q, int& r) {
         q = (int)((float)n * rcp);
         r = n - q * d;
@@ -175,9 +147,9 @@ __device__ __forceinline__ void hwgrad_body(const HwgArgs& a, const int bid, con
         const uint32_t sb = lds0 + buf * HW_STAGE;
 #pragma unroll
         for (int i = 0; i < 5; ++i)
-            if (8 * (wave + 8 * i) < a.R) hw_dma16(rx, sb + (wave + 8 * i) * 1024, xo[i]);
+            if (8 * (wave + 8 * i) < a.R) lds_dma16(rx, sb + (wave + 8 * i) * 1024, xo[i]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) hw_dma16(rz, sb + HW_ZOFF + (wave + 8 * i) * 1024, zo[i]);
+        for (int i = 0; i < 2; ++i) lds_dma16(rz, sb + HW_ZOFF + (wave + 8 * i) * 1024, zo[i]);
     };
 
     // transposing fragment reads (conv_c3g.hip): 16-lane group g: (g & 1) = which 16 of the operand's 32 rows, (g >> 1) = which 8 of the 16

@@ -11,6 +11,7 @@
 // of k per row (64 bf16 / 32 fp32), LDS double-buffered, global->register prefetch of the
 // next K-tile while the MFMAs of the current one run, one barrier per K-tile.
 #include "common.h"
+#include "internal.h"
 #include <stdlib.h>
 
 struct IgemmArgs {
@@ -394,31 +395,6 @@ static void plan_splitk(int ntiles, int nkt, int ncu, int& S, int& kps) {
     kps = ceil_div(nkt, S); S = ceil_div(nkt, kps);
 }
 
-int urso_pw_launch(const urso_conv_geom* g, int dt, int conv, int dhs, int dws, int relu,
-                   const void* src, const void* wgt, const float* bias, const void* add, const void* mask, void* dst,
-                   uint32_t src_bytes, uint32_t wgt_bytes, uint32_t dst_bytes, int mask_bits, void* bits_out, int add_src, hipStream_t st);      // conv_pw.hip
-
-bool urso_pair_single_fits(const urso_conv_geom* g, int dt, int flags, const void* add, const void* mask);                         // conv_pair.hip
-int urso_pair_single_launch(const urso_conv_geom* g, int dt, int flags, const void* src, const void* wgt, const float* bias, const void* add,
-                            const void* mask_bits, void* dst, void* bits_out, hipStream_t st);
-bool urso_stem_fits(const urso_conv_geom* g, int dt, int flags, const void* add, const void* mask);                                // conv_stem.hip
-int urso_stem_launch(const urso_conv_geom* g, int dt, int relu, const void* src, const void* wgt, const float* bias, void* dst, hipStream_t st);
-bool urso_c3_fits(const urso_conv_geom* g, int dt, int flags, const void* add);                                                      // conv_c3.hip
-int urso_c3_launch(const urso_conv_geom* g, int dt, int relu, const void* src, const void* wgt, const float* bias, const void* mask,
-                   void* dst, hipStream_t st);
-bool urso_hconv_fits(const urso_conv_geom* g, int dt, int flags, const void* add);                                                   // conv_halo.hip
-int urso_hconv_launch(const urso_conv_geom* g, int dt, int relu, const void* src, const void* wgt, const float* bias, const void* add,
-                      const void* mask, void* dst, uint32_t src_bytes, uint32_t wgt_bytes, uint32_t dst_bytes, void* ws, size_t ws_bytes,
-                      hipStream_t st);
-size_t urso_hconv_ws_bytes();
-bool urso_bneck_fwd_fits(const urso_conv_geom* g, int dt, int flags, const void* add, const void* mask);                                 // conv_bneck.hip
-int urso_bneck_fwd_launch(const urso_conv_geom* g, int dt, int flags, const void* src, const void* wgt, const float* bias, void* dst, hipStream_t st);
-bool urso_bneck_dgrad_fits(const urso_conv_geom* g, int dt, int flags, const void* add, const void* mask);
-int urso_bneck_dgrad_launch(const urso_conv_geom* g, int dt, int flags, const void* dz, const void* wd, const void* mask, void* dst, hipStream_t st);
-bool urso_dense_fits(const urso_conv_geom* g, int dt, int flags, int pointwise, long long M);                                      // conv_dense.hip
-int urso_dense_launch(const urso_conv_geom* g, int dt, int flags, const void* src, const void* wgt, const float* bias, const void* add,
-                      const void* mask, void* dst, uint32_t src_bytes, uint32_t wgt_bytes, uint32_t dst_bytes, hipStream_t st);
-
 static int ilog2_exact(int v) { if (v == 1) return 0; if (v == 2) return 1; if (v == 4) return 2; return -1; }
 
 static int device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
@@ -483,7 +459,6 @@ extern "C" int urso_conv_igemm_halo_ok(const urso_conv_geom* g, int dt, int flag
 
 extern "C" size_t urso_conv_igemm_halo_ws_bytes(void) { return urso_hconv_ws_bytes(); }
 
-int urso_hconv2_pick(const urso_conv_geom* g, bool has_ws);                                                                          // conv_halo2.hip
 extern "C" int urso_conv_igemm_halo2_shape(const urso_conv_geom* g, int dt, int flags, int has_add, int has_ws) {
     if (!g || !urso_hconv_fits(g, dt, flags, has_add ? (const void*)g : nullptr)) return 0;
     return urso_hconv2_pick(g, has_ws != 0);

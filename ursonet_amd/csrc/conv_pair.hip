@@ -21,9 +21,8 @@
 // LDS rows are XOR-swizzled per 16-byte slot (src: slot ^ ((row >> 1) & 7), add/mid: slot ^ (row & 15)) on the DMA source side, so
 // every ds_read_b128 / ds_write_b128 below is conflict-free.  Three LDS barriers per tile; vector-memory waits are hand-counted
 // (conv_pw.hip explains why).
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+#include "lds_mfma.h"
+#include "internal.h"
 
 struct PairArgs {
     const void* src; const void* w1; const float* bias1; const void* add; void* bits; void* mid;
@@ -41,29 +40,6 @@ struct PairArgs {
     // bytes per pixel row of add / mid and of the bit mask in memory, and what one group index adds to each pointer
     uint32_t wide_pitch, bits_pitch, g_w1, g_bias, g_wide, g_bits;
 };
-
-template <typename T> struct PrMma32;
-template <> struct PrMma32<__bf16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct PrMma32<_Float16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ void pr_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    // m0 = wave-uniform LDS destination; lane l lands at m0 + 16 l (conv_pw.hip pw_dma16)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t pr_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void pr_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void pr_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Two shapes of the same kernel (CW = 4 CM; every wave owns 64 of the CW channels in GEMM 1 and 16 of the CM channels in GEMM 2):
 //   stage 2:  CM  64, CW 256, 4 waves, 64-pixel tiles, 2 LDS stages ( 80 KiB): two blocks per CU, inputs one tile ahead;
@@ -120,7 +96,7 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
 
     const uint32_t grp = blockIdx.y, gwide = grp * a.g_wide, gbits = grp * a.g_bits;
     const uint32_t pitch = a.wide_pitch, bpitch = a.bits_pitch;
-    const i32x4_t rs = pr_rsrc(a.src, a.nar_bytes), ra = pr_rsrc((const char*)a.add + gwide, (SPADD ? a.add_bytes : a.wide_bytes) - gwide);
+    const i32x4_t rs = raw_rsrc(a.src, a.nar_bytes), ra = raw_rsrc((const char*)a.add + gwide, (SPADD ? a.add_bytes : a.wide_bytes) - gwide);
     const __amdgpu_buffer_rsrc_t rmid = make_rsrc((char*)a.mid + gwide, a.wide_bytes - gwide), rdst = make_rsrc(a.dst, a.nar_bytes);
     const __amdgpu_buffer_rsrc_t rbit = make_rsrc(a.bits ? (char*)a.bits + gbits : (char*)a.mid, a.bits ? a.bits_bytes - gbits : 0u);
     const __amdgpu_buffer_rsrc_t rmk2 = make_rsrc(MODE == 1 ? a.mask2 : a.dst, MODE == 1 ? a.nar_bytes : 0u);
@@ -144,10 +120,10 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
     auto dma_tile = [&](int t, int buf) {
         const uint32_t nb = (uint32_t)t * (uint32_t)(BM * AROW), wb = (uint32_t)t * (uint32_t)BM * pitch;
 #pragma unroll
-        for (int i = 0; i < NA; ++i) pr_dma16(rs, lds0 + buf * S::ABUF + (wave + NW * i) * 1024, nb + aoff[i]);
+        for (int i = 0; i < NA; ++i) lds_dma16(rs, lds0 + buf * S::ABUF + (wave + NW * i) * 1024, nb + aoff[i]);
         if constexpr (HAS_ADD && !SPADD) {
 #pragma unroll
-            for (int i = 0; i < NR; ++i) pr_dma16(ra, lds0 + S::ROFF + buf * S::RBUF + (wave + NW * i) * 1024, (PAIR_DBG & 4) ? URSO_OOB_SHIFT : wb + rgo[i]);
+            for (int i = 0; i < NR; ++i) lds_dma16(ra, lds0 + S::ROFF + buf * S::RBUF + (wave + NW * i) * 1024, (PAIR_DBG & 4) ? URSO_OOB_SHIFT : wb + rgo[i]);
         }
         if constexpr (SPADD) {
             // row -> pixel (b, y, x) of the dense grid; odd y or x: the gradient is zero there (out-of-range offset = zero fill),
@@ -162,7 +138,7 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
                 int y = (int)((float)rem * a.rcp_w), x = rem - y * a.sp_w;
                 { const bool lo = x < 0, hi = x >= a.sp_w; y += hi ? 1 : (lo ? -1 : 0); x += hi ? -a.sp_w : (lo ? a.sp_w : 0); }
                 const uint32_t off = (uint32_t)((b * hw4 + (y >> 1) * w2 + (x >> 1)) * RROW) + (roff[i] & (uint32_t)(RROW - 1));
-                pr_dma16(ra, lds0 + S::ROFF + buf * S::RBUF + (wave + NW * i) * 1024, ((y | x) & 1) ? URSO_OOB_SHIFT : off);
+                lds_dma16(ra, lds0 + S::ROFF + buf * S::RBUF + (wave + NW * i) * 1024, ((y | x) & 1) ? URSO_OOB_SHIFT : off);
             }
         }
     };
@@ -255,13 +231,13 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
         const bool has_far = tile + D * bpx < t_end;           // tile k + D exists (its inputs are requested in this iteration)
         // ---- (1) this tile's inputs (and its prefetched vectors) have landed.  Younger than them: with D = 2 the inputs of tile k + 1,
         //      and the stores of tile k - 1
-        if constexpr (D == 1) { if (first) pr_wait_vm<0>(); else pr_wait_vm<NST>(); }
+        if constexpr (D == 1) { if (first) wait_vm<0>(); else wait_vm<NST>(); }
         else {
-            if (first) { if (has_next) pr_wait_vm<NDMA>(); else pr_wait_vm<0>(); }
-            else { if (has_next) pr_wait_vm<NST + NDMA>(); else pr_wait_vm<NST>(); }
+            if (first) { if (has_next) wait_vm<NDMA>(); else wait_vm<0>(); }
+            else { if (has_next) wait_vm<NST + NDMA>(); else wait_vm<NST>(); }
         }
         first = false;
-        pr_barrier();
+        lds_barrier_asm();
         i32x2_t cbits[PT1]; i32x4_t cm2[NA];
         if constexpr (MODE == 1) {
 #pragma unroll
@@ -293,7 +269,7 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
 #pragma unroll
             for (int pt = 0; pt < PT1; ++pt)
 #pragma unroll
-                for (int c2 = 0; c2 < C2T; ++c2) PrMma32<T>::run(w1f[c2][j], px[pt], acc[pt][c2]);
+                for (int c2 = 0; c2 < C2T; ++c2) Mma32<T>::run(w1f[c2][j], px[pt], acc[pt][c2]);
             } else { asm volatile("" :: "v"(px[0])); }
         }
         // ---- epilogue 1, in place in the add tile: mid = act(acc + add)
@@ -337,7 +313,7 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
                 else __builtin_amdgcn_raw_buffer_store_b32(pk.x, rbit, bo, 0, 0);
             }
         }
-        pr_barrier();                                           // (2) mid complete in LDS
+        lds_barrier_asm();                                      // (2) mid complete in LDS
         // ---- mid -> HBM, row-contiguous (same slot map as the DMA that brought the add tile in)
         {
             const uint32_t wb = (uint32_t)tile * (uint32_t)BM * pitch;
@@ -398,7 +374,7 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
             __builtin_memcpy(&pk, out, 8);
             *(i32x2_t*)(sO + e2[pt]) = pk;
         }
-        pr_barrier();                                           // (3)
+        lds_barrier_asm();                                      // (3)
         {
             const uint32_t nb = (uint32_t)tile * (uint32_t)(BM * AROW);
 #pragma unroll

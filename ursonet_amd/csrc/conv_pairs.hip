@@ -10,9 +10,7 @@
 // W2: 32), three LDS stages of (src 8 KiB + xin 8 KiB) fed by LDS-DMA two tiles ahead plus ONE 32 KiB `mid` tile (written by epilogue 1,
 // read by GEMM 2 and by the row-contiguous stores): 80 KiB, two blocks per CU.  Swizzles, epilogues and the hand-counted vector-memory
 // waits are those of conv_pair.hip.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+#include "lds_mfma.h"
 
 struct PairsArgs {
     const void* src; const void* xin; const void* w1; const void* ws; const float* bias1; const float* bias_s;
@@ -23,27 +21,6 @@ struct PairsArgs {
 
 constexpr int PS_BM = 64, PS_NW = 4, PS_NBUF = 3;
 constexpr int PS_STAGE = 16384, PS_X = 8192, PS_MID = PS_NBUF * PS_STAGE, PS_LDS = PS_MID + 32768;
-
-template <typename T> struct PsMma32;
-template <> struct PsMma32<__bf16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct PsMma32<_Float16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ void ps_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t ps_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void ps_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void ps_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <typename T, bool EMIT>
 __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
@@ -60,7 +37,7 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
     int tile = xcd * cpx + lb;
     if (tile >= t_end) return;
 
-    const i32x4_t rs = ps_rsrc(a.src, a.nar_bytes), rx = ps_rsrc(a.xin, a.nar_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.nar_bytes), rx = raw_rsrc(a.xin, a.nar_bytes);
     const __amdgpu_buffer_rsrc_t rmid = make_rsrc(a.mid, a.wide_bytes), rdst = make_rsrc(a.dst, a.nar_bytes);
     const __amdgpu_buffer_rsrc_t rbit = make_rsrc(EMIT ? a.bits : a.mid, EMIT ? a.bits_bytes : 0u);
 
@@ -80,9 +57,9 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
     auto dma_tile = [&](int t, int buf) {
         const uint32_t nb = (uint32_t)t * (BM * 128u), sb = lds0 + buf * PS_STAGE;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) ps_dma16(rs, sb + (wave + NW * i) * 1024, nb + aoff[i]);
+        for (int i = 0; i < 2; ++i) lds_dma16(rs, sb + (wave + NW * i) * 1024, nb + aoff[i]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) ps_dma16(rx, sb + PS_X + (wave + NW * i) * 1024, nb + aoff[i]);
+        for (int i = 0; i < 2; ++i) lds_dma16(rx, sb + PS_X + (wave + NW * i) * 1024, nb + aoff[i]);
     };
     constexpr int NDMA = 4, NST = 8 + 2 + (EMIT ? 2 : 0);
 
@@ -136,10 +113,10 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
     char* sR = smem + PS_MID;
     while (true) {
         const bool has_next = tile + bpx < t_end, has_far = tile + 2 * bpx < t_end;
-        if (first) { if (has_next) ps_wait_vm<NDMA>(); else ps_wait_vm<0>(); }
-        else { if (has_next) ps_wait_vm<NST + NDMA>(); else ps_wait_vm<NST>(); }
+        if (first) { if (has_next) wait_vm<NDMA>(); else wait_vm<0>(); }
+        else { if (has_next) wait_vm<NST + NDMA>(); else wait_vm<NST>(); }
         first = false;
-        ps_barrier();                                          // (1) this tile's inputs are in LDS; every wave is done with the previous tile
+        lds_barrier_asm();                                     // (1) this tile's inputs are in LDS; every wave is done with the previous tile
         if (has_far) { int nb_ = buf + 2; if (nb_ >= NBUF) nb_ -= NBUF; dma_tile(tile + 2 * bpx, nb_); }
         char* sA = smem + buf * PS_STAGE;
 
@@ -156,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
             for (int j = 0; j < 8; ++j) {
                 const i32x4_t px = *(const i32x4_t*)(sA + (j < 4 ? 0 : PS_X) + g1rd[pt][0] + ((((uint32_t)(2 * (j & 3) + h)) ^ g1rd[pt][1]) << 4));
 #pragma unroll
-                for (int c2 = 0; c2 < 2; ++c2) PsMma32<T>::run(w1f[c2][j], px, acc[c2]);
+                for (int c2 = 0; c2 < 2; ++c2) Mma32<T>::run(w1f[c2][j], px, acc[c2]);
             }
             uint32_t keep[2] = {0u, 0u};
 #pragma unroll
@@ -184,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
                 __builtin_amdgcn_raw_buffer_store_b64(pk, rbit, bo, 0, 0);
             }
         }
-        ps_barrier();                                          // (2) mid complete in LDS
+        lds_barrier_asm();                                     // (2) mid complete in LDS
         {
             const uint32_t wb = (uint32_t)tile * (BM * 512u);
             i32x4_t v[8];
@@ -216,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
             __builtin_memcpy(&pk, out, 8);
             *(i32x2_t*)(sA + e2[pt]) = pk;                     // the src tile of this stage: every wave is past GEMM 1
         }
-        ps_barrier();                                          // (3)
+        lds_barrier_asm();                                     // (3)
         {
             const uint32_t nb = (uint32_t)tile * (BM * 128u);
 #pragma unroll

@@ -13,10 +13,7 @@
 //   weight gradient (32x32x16 over pixels): wave w owns dW[0..63][32 w .. +31]: both operands read TRANSPOSED from their row-major LDS
 //     tiles with ds_read_b64_tr_b16 (conv_wgrad.hip); 32 + 16 persistent accumulator registers; one fp32 partial per block at the end,
 //     summed over blocks by the same batched split reduction as every other layer.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef short pw_s16x4_t __attribute__((ext_vector_type(4)));
+#include "lds_mfma.h"
 
 struct PairwArgs {
     const void* src; const void* w1; const void* add; const void* bits; void* mid; const void* w2; const void* u; void* dst;
@@ -29,32 +26,6 @@ struct PairwArgs {
 
 constexpr int PW_BM = 64, PW_NW = 8, PW_NBUF = 3;
 constexpr int PW_A = 0, PW_U = 8192, PW_R = 16384, PW_STAGE = 49152, PW_LDS = PW_NBUF * PW_STAGE;
-
-template <typename T> struct PwMma;
-template <> struct PwMma<__bf16> {
-    static constexpr int ONES = 0x3F803F80;
-    static __device__ __forceinline__ void m32(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct PwMma<_Float16> {
-    static constexpr int ONES = 0x3C003C00;
-    static __device__ __forceinline__ void m32(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ i32x2_t pw_tr16(const char* p) {
-    return __builtin_bit_cast(i32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) pw_s16x4_t*)p));
-}
-__device__ __forceinline__ void pw_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t pw_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void pw_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void pw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // SOLO: the data gradient and the weight gradient of ONE 64 -> 256 pointwise layer from a single pass over its output gradient (no
 // GEMM 1: `add` IS the 256-channel gradient dz, u the layer's input): dst = dz W2^T (masked by u > 0 if a.masked), dW += u^T dz.
@@ -74,7 +45,7 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
     int tile = xcd * cpx + lb;
     const bool active = tile < t_end;
 
-    const i32x4_t rs = pw_rsrc(a.src, a.nar_bytes), ru = pw_rsrc(a.u, a.nar_bytes), ra = pw_rsrc(a.add, SPARSE ? a.add_bytes : a.wide_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.nar_bytes), ru = raw_rsrc(a.u, a.nar_bytes), ra = raw_rsrc(a.add, SPARSE ? a.add_bytes : a.wide_bytes);
     const __amdgpu_buffer_rsrc_t rmid = make_rsrc(a.mid, a.wide_bytes), rdst = make_rsrc(a.dst, a.nar_bytes);
     const __amdgpu_buffer_rsrc_t rbit = make_rsrc(a.bits, a.bits_bytes);
 
@@ -98,11 +69,11 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
     }
     auto dma_tile = [&](int t, int buf) {
         const uint32_t nb = (uint32_t)t * (BM * 128u), wb = (uint32_t)t * (BM * 512u), sb = lds0 + buf * PW_STAGE;
-        if constexpr (!SOLO) pw_dma16(rs, sb + PW_A + wave * 1024, nb + noff);
-        pw_dma16(ru, sb + PW_U + wave * 1024, nb + toff);
+        if constexpr (!SOLO) lds_dma16(rs, sb + PW_A + wave * 1024, nb + noff);
+        lds_dma16(ru, sb + PW_U + wave * 1024, nb + toff);
         if constexpr (!SPARSE) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) pw_dma16(ra, sb + PW_R + (wave + NW * i) * 1024, wb + roff[i]);
+            for (int i = 0; i < 4; ++i) lds_dma16(ra, sb + PW_R + (wave + NW * i) * 1024, wb + roff[i]);
         } else {
             const int hw = a.sp_h * a.sp_w, w2 = a.sp_w >> 1, hw4 = (a.sp_h >> 1) * w2;
 #pragma unroll
@@ -114,7 +85,7 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
                 int y = (int)((float)rem * a.rcp_w), x = rem - y * a.sp_w;
                 { const bool lo = x < 0, hi = x >= a.sp_w; y += hi ? 1 : (lo ? -1 : 0); x += hi ? -a.sp_w : (lo ? a.sp_w : 0); }
                 const uint32_t off = (uint32_t)((b * hw4 + (y >> 1) * w2 + (x >> 1)) * 512) + (roff[i] & 511u);
-                pw_dma16(ra, sb + PW_R + (wave + NW * i) * 1024, ((y | x) & 1) ? URSO_OOB_SHIFT : off);
+                lds_dma16(ra, sb + PW_R + (wave + NW * i) * 1024, ((y | x) & 1) ? URSO_OOB_SHIFT : off);
             }
         }
     };
@@ -169,7 +140,7 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
     f32x16_t accw[2], accc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { accw[0][e] = 0.f; accw[1][e] = 0.f; accc[e] = 0.f; }
-    const i32x4_t ones = {PwMma<T>::ONES, PwMma<T>::ONES, PwMma<T>::ONES, PwMma<T>::ONES};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 
     uint32_t pbits[2];
     auto prefetch = [&](int t) {
@@ -187,10 +158,10 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
         while (true) {
             const bool has_next = tile + bpx < t_end, has_far = tile + 2 * bpx < t_end;
             // this tile's inputs and bit masks have landed; younger: the next tile's inputs and the previous tile's stores
-            if (first) { if (has_next) pw_wait_vm<NDMA>(); else pw_wait_vm<0>(); }
-            else { if (has_next) pw_wait_vm<NDMA + NST>(); else pw_wait_vm<NST>(); }
+            if (first) { if (has_next) wait_vm<NDMA>(); else wait_vm<0>(); }
+            else { if (has_next) wait_vm<NDMA + NST>(); else wait_vm<NST>(); }
             first = false;
-            pw_barrier();                                      // (1)
+            lds_barrier_asm();                                 // (1)
             uint32_t cbits[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) { cbits[i] = pbits[i]; asm volatile("" : "+v"(cbits[i])); }
@@ -211,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
 #pragma unroll
                     for (int pt = 0; pt < 2; ++pt) px[pt] = *(const i32x4_t*)(st + PW_A + g1rd[pt][0] + ((((uint32_t)(2 * j + h)) ^ g1rd[pt][1]) << 4));
 #pragma unroll
-                    for (int pt = 0; pt < 2; ++pt) PwMma<T>::m32(w1f[j], px[pt], acc[pt]);
+                    for (int pt = 0; pt < 2; ++pt) Mma32<T>::run(w1f[j], px[pt], acc[pt]);
                 }
 #pragma unroll
                 for (int pt = 0; pt < 2; ++pt) {
@@ -234,7 +205,7 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
                     *(i32x4_t*)(st + (e1[pt] ^ 16u)) = rv[1];
                 }
             }
-            if constexpr (!SOLO) pw_barrier();                 // (2) mid complete in LDS
+            if constexpr (!SOLO) lds_barrier_asm();            // (2) mid complete in LDS
             if constexpr (!SOLO) {   // mid -> HBM, row-contiguous
                 const uint32_t wb = (uint32_t)tile * (BM * 512u);
                 i32x4_t v[4];
@@ -259,16 +230,16 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
                 i32x4_t fu[2], fm;
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
-                    const i32x2_t lo = pw_tr16(st + tu[ct][0] + ks * 16 * 128), hi = pw_tr16(st + tu[ct][1] + ks * 16 * 128);
+                    const i32x2_t lo = lds_read_tr16(st + tu[ct][0] + ks * 16 * 128), hi = lds_read_tr16(st + tu[ct][1] + ks * 16 * 128);
                     fu[ct] = i32x4_t{lo.x, lo.y, hi.x, hi.y};
                 }
                 {
-                    const i32x2_t lo = pw_tr16(st + tm[0] + ks * 16 * 512), hi = pw_tr16(st + tm[1] + ks * 16 * 512);
+                    const i32x2_t lo = lds_read_tr16(st + tm[0] + ks * 16 * 512), hi = lds_read_tr16(st + tm[1] + ks * 16 * 512);
                     fm = i32x4_t{lo.x, lo.y, hi.x, hi.y};
                 }
-                PwMma<T>::m32(fu[0], fm, accw[0]);
-                PwMma<T>::m32(fu[1], fm, accw[1]);
-                PwMma<T>::m32(ones, fm, accc);
+                Mma32<T>::run(fu[0], fm, accw[0]);
+                Mma32<T>::run(fu[1], fm, accw[1]);
+                Mma32<T>::run(ones, fm, accc);
             }
             // ---- epilogue 2 -> the src tile of this stage (every wave is past GEMM 1), then masked row-contiguous stores
 #pragma unroll
@@ -280,7 +251,7 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
                 __builtin_memcpy(&pk, out, 8);
                 *(i32x2_t*)(st + e2[pt]) = pk;
             }
-            pw_barrier();                                      // (3)
+            lds_barrier_asm();                                 // (3)
             {
                 i32x4_t v = *(const i32x4_t*)(st + PW_A + wave * 1024 + lane * 16);
                 const i32x4_t m4 = *(const i32x4_t*)(st + PW_U + moff);

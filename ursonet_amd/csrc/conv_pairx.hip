@@ -17,10 +17,7 @@
 // 0-3 own 16 channels of dst, waves 4-7 16 channels of dP, each for all 64 pixels (ONE 32-VGPR filter set per wave); weight gradients
 // (32x32x16 over pixels, operands read transposed with ds_read_b64_tr_b16): wave w owns columns 32 w .. +31 of dW2c AND of dWs (2 x 32
 // persistent accumulator registers) and of the column sums; one fp32 partial per block and layer, summed by the batched split reduction.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef short px_s16x4_t __attribute__((ext_vector_type(4)));
+#include "lds_mfma.h"
 
 struct PairxArgs {
     const void* src; const void* w1; const void* add; const void* bits; const void* w2; const void* w3; const void* u; const void* p;
@@ -37,31 +34,9 @@ constexpr int PX_S2BASE = 3 * PX_S3, PX_S2 = 16384, PX_U = 0, PX_P = 8192;   // 
 constexpr int PX_DP = PX_S2BASE + 2 * PX_S2, PX_LDS = PX_DP + 8192;
 static_assert(PX_LDS == 163840, "all of the LDS");
 
-template <typename T> struct PxMma;
-template <> struct PxMma<__bf16> {
-    static constexpr int ONES = 0x3F803F80;
-    static __device__ __forceinline__ void m32(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct PxMma<_Float16> {
-    static constexpr int ONES = 0x3C003C00;
-    static __device__ __forceinline__ void m32(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ i32x2_t px_tr16(const char* p) {
-    return __builtin_bit_cast(i32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) px_s16x4_t*)p));
-}
-__device__ __forceinline__ void px_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t px_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// wave-uniform count: the immediate of s_waitcnt has to be a constant
-__device__ __forceinline__ void px_wait_vm(int n) {
+// wait_vm<N>() of lds_mfma.h for a wave-uniform count known only at run time (whether a next / a far tile exists): the immediate of
+// s_waitcnt has to be a constant, so one branch per sum that the two call sites below can form
+__device__ __forceinline__ void wait_vm_uniform(int n) {
     switch (n) {
         case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
         case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
@@ -74,7 +49,6 @@ __device__ __forceinline__ void px_wait_vm(int n) {
         default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
     }
 }
-__device__ __forceinline__ void px_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <typename T>
 __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
@@ -91,7 +65,7 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
     int tile = xcd * cpx + lb;
     const bool active = tile < t_end;
 
-    const i32x4_t rs = px_rsrc(a.src, a.nar_bytes), ru = px_rsrc(a.u, a.nar_bytes), rp = px_rsrc(a.p, a.nar_bytes), ra = px_rsrc(a.add, a.wide_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.nar_bytes), ru = raw_rsrc(a.u, a.nar_bytes), rp = raw_rsrc(a.p, a.nar_bytes), ra = raw_rsrc(a.add, a.wide_bytes);
     const __amdgpu_buffer_rsrc_t rdst = make_rsrc(a.dst, a.nar_bytes), rdp = make_rsrc(a.dp, a.nar_bytes);
     const __amdgpu_buffer_rsrc_t rbit = make_rsrc(a.bits, a.bits_bytes);
 
@@ -114,14 +88,14 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
     }
     auto dma_main = [&](int t, int s3) {                       // 5 instructions
         const uint32_t nb = (uint32_t)t * (BM * 128u), wb = (uint32_t)t * (BM * 512u), sb = lds0 + s3 * PX_S3;
-        px_dma16(rs, sb + PX_A + wave * 1024, nb + noff);
+        lds_dma16(rs, sb + PX_A + wave * 1024, nb + noff);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) px_dma16(ra, sb + PX_R + (wave + NW * i) * 1024, wb + roff[i]);
+        for (int i = 0; i < 4; ++i) lds_dma16(ra, sb + PX_R + (wave + NW * i) * 1024, wb + roff[i]);
     };
     auto dma_side = [&](int t, int s2) {                       // 2 instructions
         const uint32_t nb = (uint32_t)t * (BM * 128u), sb = lds0 + PX_S2BASE + s2 * PX_S2;
-        px_dma16(ru, sb + PX_U + wave * 1024, nb + toff);
-        px_dma16(rp, sb + PX_P + wave * 1024, nb + toff);
+        lds_dma16(ru, sb + PX_U + wave * 1024, nb + toff);
+        lds_dma16(rp, sb + PX_P + wave * 1024, nb + toff);
     };
     constexpr int NMAIN = 5, NSIDE = 2, NPRE = 2, NST = 2;
 
@@ -166,7 +140,7 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
     f32x16_t accw[2], accs[2], accc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { accw[0][e] = 0.f; accw[1][e] = 0.f; accs[0][e] = 0.f; accs[1][e] = 0.f; accc[e] = 0.f; }
-    const i32x4_t ones = {PxMma<T>::ONES, PxMma<T>::ONES, PxMma<T>::ONES, PxMma<T>::ONES};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 
     uint32_t pbits[2];
     auto prefetch = [&](int t) {
@@ -185,8 +159,8 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
         while (true) {
             const bool has_next = tile + bpx < t_end, has_far = tile + 2 * bpx < t_end;
             // ---- (1) bits and main tiles of this tile have landed.  Younger: [main of the next tile], side of this tile, [stores of the previous tile]
-            px_wait_vm((has_next ? NMAIN : 0) + NSIDE + (first ? 0 : NST));
-            px_barrier();
+            wait_vm_uniform((has_next ? NMAIN : 0) + NSIDE + (first ? 0 : NST));
+            lds_barrier_asm();
             uint32_t cbits[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) { cbits[i] = pbits[i]; asm volatile("" : "+v"(cbits[i])); }
@@ -210,7 +184,7 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
 #pragma unroll
                     for (int pt = 0; pt < 2; ++pt) px[pt] = *(const i32x4_t*)(st + g1rd[pt][0] + ((((uint32_t)(2 * j + h)) ^ g1rd[pt][1]) << 4));
 #pragma unroll
-                    for (int pt = 0; pt < 2; ++pt) PxMma<T>::m32(w1f[j], px[pt], acc[pt]);
+                    for (int pt = 0; pt < 2; ++pt) Mma32<T>::run(w1f[j], px[pt], acc[pt]);
                 }
 #pragma unroll
                 for (int pt = 0; pt < 2; ++pt) {
@@ -235,8 +209,8 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
             }
             // ---- (2) mid complete in LDS; the side tiles of this tile have landed.  Younger than them: [the previous tile's stores] and
             //      what this iteration issued
-            px_wait_vm((first ? 0 : NST) + (has_next ? NPRE + NSIDE : 0) + (has_far ? NMAIN : 0));
-            px_barrier();
+            wait_vm_uniform((first ? 0 : NST) + (has_next ? NPRE + NSIDE : 0) + (has_far ? NMAIN : 0));
+            lds_barrier_asm();
             // ---- GEMM 2 (waves 0-3: dst) / GEMM 3 (waves 4-7: dP): 16 channels x 64 pixels, K = 256
             f32x4_t acc2[4];
 #pragma unroll
@@ -255,20 +229,20 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
                 i32x4_t fu[2], fq[2], fm;
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
-                    const i32x2_t lo = px_tr16(sd + PX_U + tn[ct][0] + ks * 16 * 128), hi = px_tr16(sd + PX_U + tn[ct][1] + ks * 16 * 128);
+                    const i32x2_t lo = lds_read_tr16(sd + PX_U + tn[ct][0] + ks * 16 * 128), hi = lds_read_tr16(sd + PX_U + tn[ct][1] + ks * 16 * 128);
                     fu[ct] = i32x4_t{lo.x, lo.y, hi.x, hi.y};
-                    const i32x2_t lo2 = px_tr16(sd + PX_P + tn[ct][0] + ks * 16 * 128), hi2 = px_tr16(sd + PX_P + tn[ct][1] + ks * 16 * 128);
+                    const i32x2_t lo2 = lds_read_tr16(sd + PX_P + tn[ct][0] + ks * 16 * 128), hi2 = lds_read_tr16(sd + PX_P + tn[ct][1] + ks * 16 * 128);
                     fq[ct] = i32x4_t{lo2.x, lo2.y, hi2.x, hi2.y};
                 }
                 {
-                    const i32x2_t lo = px_tr16(st + tm[0] + ks * 16 * 512), hi = px_tr16(st + tm[1] + ks * 16 * 512);
+                    const i32x2_t lo = lds_read_tr16(st + tm[0] + ks * 16 * 512), hi = lds_read_tr16(st + tm[1] + ks * 16 * 512);
                     fm = i32x4_t{lo.x, lo.y, hi.x, hi.y};
                 }
-                PxMma<T>::m32(fu[0], fm, accw[0]);
-                PxMma<T>::m32(fu[1], fm, accw[1]);
-                PxMma<T>::m32(fq[0], fm, accs[0]);
-                PxMma<T>::m32(fq[1], fm, accs[1]);
-                PxMma<T>::m32(ones, fm, accc);
+                Mma32<T>::run(fu[0], fm, accw[0]);
+                Mma32<T>::run(fu[1], fm, accw[1]);
+                Mma32<T>::run(fq[0], fm, accs[0]);
+                Mma32<T>::run(fq[1], fm, accs[1]);
+                Mma32<T>::run(ones, fm, accc);
             }
             // ---- epilogue 2 / 3 -> staging: dst into the G tile of this stage (every wave is past GEMM 1), dP into its own tile
             {
@@ -283,7 +257,7 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
                     *(i32x2_t*)(so + e23 + pt * 2048) = pk;
                 }
             }
-            px_barrier();                                      // (3)
+            lds_barrier_asm();                                 // (3)
             {
                 i32x4_t v = *(const i32x4_t*)(st + PX_A + wave * 1024 + lane * 16);
                 const i32x4_t m4 = *(const i32x4_t*)(sd + PX_U + moff);
@@ -325,8 +299,6 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
         if (a.colpart_s) a.colpart_s[(size_t)blockIdx.x * 256 + 32 * wave + l31] = accc[0];
     }
 }
-
-extern "C" int urso_conv_pair_wgrad_splits(long long M, int dt);
 
 extern "C" int urso_conv_pair_wgrad_entry(long long M, int dt, const void* src_d, const void* w1_d, const void* add_d, const void* bits_d,
                                           const void* w2_d, const void* u_d, void* dst_d, const void* ws_d, const void* xin_d, int mask_by_xin, void* dxin_d,

@@ -12,7 +12,8 @@
 //     after one of those hand-placed waits has already covered it, so the compiler's own (weaker) counts are harmless;
 //   * the residual / mask vectors of tile t+1 are requested slot by slot while the epilogue of tile t consumes the
 //     registers ("rolling" prefetch): their latency hides behind a whole tile instead of one K-tile of MFMAs.
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 
 struct PwArgs {
     const void* src; const void* wgt; const float* bias; const void* add; const void* mask; void* dst;
@@ -25,23 +26,6 @@ struct PwArgs {
     int H, W, KH, KW, SH, SW, PH, PW, DHs, DWs;   // CONV: general source mapping (conv_igemm.hip), Cc % 8 == 0 so a K-tile never straddles taps
     int add_src; uint32_t add_bytes;   // URSO_EPI_ADD_SRCGRID: the residual operand is a [B][H][W][N] tensor read at (oy*SH, ox*SW)
 };
-
-__device__ __forceinline__ void pw_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-#if defined(URSO_DMA_KEEP_M0)
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-#else
-    // m0 is not saved: nothing else in these kernels uses it (DS instructions need no m0 on gfx9+), and hipcc itself sets it
-    // afresh before every LDS-DMA it emits
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-#endif
-}
-__device__ __forceinline__ i32x4_t pw_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void pw_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // MASKK: 0 none, 1 mask_d is a tensor like dst (keep where > 0), 2 mask_d is a ReLU BIT mask (1 byte per 16-byte vector of dst);
 // EMIT: also write such a bit mask of (stored dst > 0) to bits_out (include/ursonet_hip.h, urso_conv_igemm_ex).
@@ -72,7 +56,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
     int tile = xcd * cpx + lb;
     if (tile >= t_end) return;
 
-    const i32x4_t rs = pw_rsrc(a.src, a.src_bytes), rw = pw_rsrc(a.wgt, a.wgt_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.src_bytes), rw = raw_rsrc(a.wgt, a.wgt_bytes);
     const __amdgpu_buffer_rsrc_t rbi = make_rsrc(a.bias ? (const void*)a.bias : a.dst, a.bias ? (uint32_t)a.N * 4u : 0u);
     const __amdgpu_buffer_rsrc_t rad = make_rsrc(a.add ? a.add : a.dst, a.add ? (a.add_src ? a.add_bytes : a.dst_bytes) : 0u);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(a.mask ? a.mask : a.dst, a.mask ? (MASKK == 2 ? a.dst_bytes / 16u : a.dst_bytes) : 0u);
@@ -138,7 +122,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
                 const int tapi = kt * 8 + chA[i];
                 const int ky = tapi >> 2, kx = tapi & 3;                               // KW == 4 (checked on the host)
                 const bool ok = tapi < a.Kc && ((vmask[i] >> (tapi & 31)) & 1u);
-                pw_dma16(rs, la + i * 32 * 128, ok ? base0[i] + (uint32_t)((ky * a.W + kx) * 16) : URSO_OOB_SHIFT);
+                lds_dma16(rs, la + i * 32 * 128, ok ? base0[i] + (uint32_t)((ky * a.W + kx) * 16) : URSO_OOB_SHIFT);
             }
         } else if constexpr (CONV == 1) {
             if (ft_cc == 0) {
@@ -149,7 +133,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
             }
 #pragma unroll
             for (int i = 0; i < RA; ++i)
-                pw_dma16(rs, la + i * 32 * 128, rowbase[i] + (uint32_t)(ft_cc + chA[i]) * 16u);      // OOB_SHIFT + small stays out of range
+                lds_dma16(rs, la + i * 32 * 128, rowbase[i] + (uint32_t)(ft_cc + chA[i]) * 16u);     // OOB_SHIFT + small stays out of range
             ft_cc += 8; if (ft_cc >= a.Cc) { ft_cc = 0; if (++ft_kx == a.KW) { ft_kx = 0; ++ft_ky; } }
         } else {
 #pragma unroll
@@ -157,15 +141,15 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
                 // no select: Cc % 8 == 0 (host-checked) so a K-tile has no tail, and a row m >= M lies beyond the descriptor's
                 // num_records (= M*C*2 bytes), i.e. it is zero-filled by the hardware
                 const int m = m0 + r0 + 32 * i, kc = kt * 8 + chA[i];
-                pw_dma16(rs, la + i * 32 * 128, (uint32_t)m * (uint32_t)a.C * 2u + (uint32_t)kc * 16u);
+                lds_dma16(rs, la + i * 32 * 128, (uint32_t)m * (uint32_t)a.C * 2u + (uint32_t)kc * 16u);
             }
         }
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
             const int n = n0 + nrow[i], kc = kt * 8 + chB[i];
             const uint32_t off = ((uint32_t)n * (uint32_t)a.Kc + (uint32_t)kc) * 16u;
-            if constexpr (CONV == 2) pw_dma16(rw, lb_ + i * 32 * 128, (n < a.N && kc < a.Kc) ? off : URSO_OOB_SHIFT);   // the stem's K = 28 chunks has a tail
-            else pw_dma16(rw, lb_ + i * 32 * 128, off);               // Kc % 8 == 0; a filter row n >= N lies beyond num_records
+            if constexpr (CONV == 2) lds_dma16(rw, lb_ + i * 32 * 128, (n < a.N && kc < a.Kc) ? off : URSO_OOB_SHIFT);  // the stem's K = 28 chunks has a tail
+            else lds_dma16(rw, lb_ + i * 32 * 128, off);              // Kc % 8 == 0; a filter row n >= N lies beyond num_records
         }
     };
 
@@ -210,7 +194,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
         }
     setup_src(tile);
     dma(tile, 0, 0);
-    pw_wait_vm<0>();
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     int cur = 0;
     while (true) {
@@ -304,10 +288,10 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
                         for (int j = 0; j < TN; ++j) Mma<T>::run(fa[j], fb[i], acc[i][j]);
                 }
             }
-            if (!last) { pw_wait_vm<0>(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); cur ^= 1; }
+            if (!last) { wait_vm<0>(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); cur ^= 1; }
         }
         // everything older than the DMAs of the next tile's first K-tile (bias, residual, mask of THIS tile) has landed
-        if (has_next) pw_wait_vm<RA + RB>(); else pw_wait_vm<0>();
+        if (has_next) wait_vm<RA + RB>(); else wait_vm<0>();
         float bv[CH];
 #pragma unroll
         for (int q = 0; q < CH / 4; ++q) { f32x4_t b = __builtin_bit_cast(f32x4_t, rbias[q]); bv[q * 4] = b.x; bv[q * 4 + 1] = b.y; bv[q * 4 + 2] = b.z; bv[q * 4 + 3] = b.w; }
@@ -351,7 +335,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
             }
         }
         if (!has_next) break;
-        pw_wait_vm<NEPI>();                              // the next tile's first K-tile (issued before this epilogue's stores/loads) is in LDS
+        wait_vm<NEPI>();                                 // the next tile's first K-tile (issued before this epilogue's stores/loads) is in LDS
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         cur ^= 1;
@@ -362,9 +346,6 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
 }
 
 static int pw_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-int urso_pwx_try(const urso_conv_geom* g, int dt, int relu, const void* src, const void* wgt, const float* bias, const void* add,
-                 const void* mask, void* dst, uint32_t src_bytes, uint32_t wgt_bytes, uint32_t dst_bytes, int mask_bits, void* bits_out,
-                 hipStream_t st);                              // conv_pwx.hip
 
 // Called by urso_conv_igemm_ex for qualifying geometries (conv_igemm.hip decides); returns URSO_OK after launching.
 int urso_pw_launch(const urso_conv_geom* g, int dt, int conv, int dhs, int dws, int relu,

@@ -20,7 +20,8 @@
 // Same math, weight layout (filter rows permuted on the DMA source side so that a lane owns whole 16-byte output vectors) and epilogue
 // semantics (bias, residual, ReLU, mask tensor / ReLU bit mask, emitted bit mask, scatter destination) as conv_pw.hip; results are
 // bit-identical to it (same MFMA, same k order inside a 64-wide K-tile, same fp32 epilogue).
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 #include <string.h>
 
 struct PxArgs {
@@ -37,16 +38,6 @@ struct PxArgs {
     // instead of written, read back and written again, and rounded once.
     const void* src1; const void* wgt1; uint32_t src1_bytes, wgt1_bytes; int C1, Kc1, nkt0;
 };
-
-__device__ __forceinline__ void px_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    // m0 = wave-uniform LDS destination; lane l lands at m0 + 16 l (conv_pw.hip pw_dma16)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t px_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void px_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // MASKK: 0 none, 1 mask tensor like dst (keep where > 0), 2 ReLU BIT mask (1 byte per 16-byte vector of dst); EMIT: write such a bit mask
 template <typename T, int TMW, int BN, int NST, bool HAS_ADD, int MASKK, bool EMIT, bool SEG2 = false>
@@ -74,8 +65,8 @@ __global__ __launch_bounds__(512, 2) void pwx_kernel(const PxArgs a) {
     const int tile0 = xcd * cpx + lb;
     if (tile0 >= t_end) return;
 
-    const i32x4_t rs = px_rsrc(a.src, a.src_bytes), rw = px_rsrc(a.wgt, a.wgt_bytes);
-    const i32x4_t rbi = px_rsrc(a.bias ? (const void*)a.bias : a.dst, a.bias ? (uint32_t)a.N * 4u : 0u);
+    const i32x4_t rs = raw_rsrc(a.src, a.src_bytes), rw = raw_rsrc(a.wgt, a.wgt_bytes);
+    const i32x4_t rbi = raw_rsrc(a.bias ? (const void*)a.bias : a.dst, a.bias ? (uint32_t)a.N * 4u : 0u);
     const __amdgpu_buffer_rsrc_t rad = make_rsrc(a.add ? a.add : a.dst, a.add ? a.dst_bytes : 0u);
     const __amdgpu_buffer_rsrc_t rmk = make_rsrc(a.mask ? a.mask : a.dst, a.mask ? (MASKK == 2 ? a.dst_bytes / 16u : a.dst_bytes) : 0u);
     const __amdgpu_buffer_rsrc_t rmo = make_rsrc(EMIT ? a.bits_out : a.dst, EMIT ? a.dst_bytes / 16u : 0u);
@@ -131,22 +122,22 @@ __global__ __launch_bounds__(512, 2) void pwx_kernel(const PxArgs a) {
         const uint32_t la = lds0 + (uint32_t)stg * STAGE;
         if (dkt == 0 && wave == 0) {                      // the tile's bias (BN floats) -> table slot dcnt & 3
             const int n0 = (dtile % a.tilesN) * BN;
-            px_dma16(rbi, lds0 + BIAS_OFF + (uint32_t)(dcnt & 3) * 1024u, (dtile < t_end && lane * 4 < BN) ? (uint32_t)(n0 + lane * 4) * 4u : URSO_OOB_SHIFT);
+            lds_dma16(rbi, lds0 + BIAS_OFF + (uint32_t)(dcnt & 3) * 1024u, (dtile < t_end && lane * 4 < BN) ? (uint32_t)(n0 + lane * 4) * 4u : URSO_OOB_SHIFT);
         }
         if (SEG2 && dkt == a.nkt0) { d_a = d_a1; d_b = d_b1; }      // (wave-uniform) entering the second segment: re-base the running offsets
         if (SEG2 && dkt >= a.nkt0) {                       // ... and copy from the other pair of tensors
             // (descriptors formed here from the kernel arguments, and ONE pair of running offsets for both segments: with a second pair
             // incremented in this branch hipcc merged the two `+= 128` into a store through a selected address and kept all four in scratch)
-            const i32x4_t rs1 = px_rsrc(a.src1, a.src1_bytes), rw1 = px_rsrc(a.wgt1, a.wgt1_bytes);
+            const i32x4_t rs1 = raw_rsrc(a.src1, a.src1_bytes), rw1 = raw_rsrc(a.wgt1, a.wgt1_bytes);
 #pragma unroll
-            for (int q = 0; q < RB; ++q) px_dma16(rw1, la + BM * 128 + (uint32_t)(wave + 8 * q) * 1024u, d_b + bsrc1[q]);
+            for (int q = 0; q < RB; ++q) lds_dma16(rw1, la + BM * 128 + (uint32_t)(wave + 8 * q) * 1024u, d_b + bsrc1[q]);
 #pragma unroll
-            for (int q = 0; q < RA; ++q) px_dma16(rs1, la + (uint32_t)ga[q] * 1024u, d_a + asrc1[q]);
+            for (int q = 0; q < RA; ++q) lds_dma16(rs1, la + (uint32_t)ga[q] * 1024u, d_a + asrc1[q]);
         } else {
 #pragma unroll
-        for (int q = 0; q < RB; ++q) px_dma16(rw, la + BM * 128 + (uint32_t)(wave + 8 * q) * 1024u, d_b + bsrc[q]);
+        for (int q = 0; q < RB; ++q) lds_dma16(rw, la + BM * 128 + (uint32_t)(wave + 8 * q) * 1024u, d_b + bsrc[q]);
 #pragma unroll
-        for (int q = 0; q < RA; ++q) px_dma16(rs, la + (uint32_t)ga[q] * 1024u, d_a + asrc[q]);
+        for (int q = 0; q < RA; ++q) lds_dma16(rs, la + (uint32_t)ga[q] * 1024u, d_a + asrc[q]);
         }
         d_a += 128u; d_b += 128u;                         // an OOB base stays out of range: nkt * 128 < 2 GiB
         if (++dkt == a.nkt) { dkt = 0; dtile += bpx; ++dcnt; dma_tile_base(); }
@@ -202,7 +193,7 @@ __global__ __launch_bounds__(512, 2) void pwx_kernel(const PxArgs a) {
     // ---- block prologue: the first NST K-steps of the stream
 #pragma unroll
     for (int p = 0; p < NST; ++p) dma_issue(p);
-    px_wait_vm<(NST - 1) * NDMA>();
+    wait_vm<(NST - 1) * NDMA>();
     __builtin_amdgcn_s_barrier();
 
     i32x4_t fa0[TN], fb0[TM], fa1[TN], fb1[TM];         // fragment sets of the two 32-deep halves of a K-step (a = filters, b = pixels)
@@ -245,7 +236,7 @@ __global__ __launch_bounds__(512, 2) void pwx_kernel(const PxArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             // ---- mid-step: this wave's copies of step s + 1 have landed (the younger ones stay in flight) -> barrier -> every wave's
             //      have, and every wave has finished reading this step's buffer: the copies of step s + NST go there
-            if (kt == 0 && tcnt > 0) px_wait_vm<(NST - 2) * NDMA + NEPI>(); else px_wait_vm<(NST - 2) * NDMA>();
+            if (kt == 0 && tcnt > 0) wait_vm<(NST - 2) * NDMA + NEPI>(); else wait_vm<(NST - 2) * NDMA>();
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             if (!(a.dbg & 1)) dma_issue(stage);
             __builtin_amdgcn_sched_barrier(0);
@@ -324,7 +315,7 @@ __global__ __launch_bounds__(512, 2) void pwx_kernel(const PxArgs a) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) eo_cur[i] = eo_nxt[i];
     }
-    px_wait_vm<0>();                                     // the (out-of-range) copies past the end of the stream must not outlive the block's LDS
+    wait_vm<0>();                                        // the (out-of-range) copies past the end of the stream must not outlive the block's LDS
 }
 
 // ---------------------------------------------------------------- host side

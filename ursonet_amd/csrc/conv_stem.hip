@@ -14,10 +14,9 @@
 //     the row operand) and a patch-row fragment serves every output row it belongs to: 26 ds_read_b128 feed the 56 MFMAs of a tile;
 //   * the wave's filter rows (32 filters x 224) live in 56 VGPRs for the whole kernel;
 //   * result through a 32 KiB LDS tile to row-contiguous 16-byte stores.  57 KiB LDS -> two blocks per CU.
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 struct StemArgs {
     const void* src; const void* wgt; const float* bias; void* dst;
@@ -29,27 +28,6 @@ struct StemArgs {
 constexpr int ST_TH = 8, ST_TW = 32, ST_PROWS = 2 * ST_TH + 5, ST_PPIX = 2 * ST_TW + 8, ST_PROW_B = ST_PPIX * 8;     // 21 rows x 576 B
 constexpr int ST_PIECES = ST_PROWS * (ST_PROW_B / 16);                                                                 // 756 16-byte pieces
 constexpr int ST_ABUF = 12288, ST_OOFF = 2 * ST_ABUF, ST_BOFF = ST_OOFF + ST_TH * ST_TW * 128, ST_LDS = ST_BOFF + 256;
-
-template <typename T> struct StMma;
-template <> struct StMma<__bf16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct StMma<_Float16> {
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ void st_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t st_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <int N> __device__ __forceinline__ void st_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void st_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <typename T>
 __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
@@ -67,7 +45,7 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
     int tile = xcd * cpx + lb;
     if (tile >= t_end) return;
 
-    const i32x4_t rs = st_rsrc(a.src, a.src_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.src_bytes);
     const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.dst, a.dst_bytes);
 
     int lane_d = lane;
@@ -88,7 +66,7 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
             const int r = (p * 1821) >> 16, s = p - 36 * r;             // p / 36 for p < 768
             const int iy = iy0 + r, ix = ix0 + 2 * s;                    // a piece = 2 pixels; ix0 and W are even: fully inside or fully outside
             const bool ok = p < ST_PIECES && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            st_dma16(rs, lds0 + buf * ST_ABUF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * a.H + iy) * a.W + ix) * 8) : URSO_OOB_SHIFT);
+            lds_dma16(rs, lds0 + buf * ST_ABUF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * a.H + iy) * a.W + ix) * 8) : URSO_OOB_SHIFT);
         }
     };
 
@@ -108,9 +86,9 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
     bool first = true;
     while (true) {
         const bool has_next = tile + bpx < t_end;
-        if (first) st_wait_vm<0>(); else st_wait_vm<NST>();
+        if (first) wait_vm<0>(); else wait_vm<NST>();
         first = false;
-        st_barrier();
+        lds_barrier_asm();
         if (has_next) dma_tile(tile + bpx, buf ^ 1);
         const char* sA = smem + buf * ST_ABUF;
 
@@ -143,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ky = rho - 2 * r;
-                if (ky >= 0 && ky <= 6) StMma<T>::run(wfr[2 * ky + half], f[s & 3], acc[r]);
+                if (ky >= 0 && ky <= 6) Mma32<T>::run(wfr[2 * ky + half], f[s & 3], acc[r]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -164,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
         }
         int b, oy0, ox0;
         tile_origin(tile, b, oy0, ox0);
-        st_barrier();
+        lds_barrier_asm();
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
             const int row = 8 * (wave + 4 * i) + (lane >> 3);
@@ -251,17 +229,6 @@ template <> __device__ __forceinline__ uint32_t sp_pack2<_Float16>(float a, floa
     const f2 v = {a, b};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h2));
 }
-template <typename T> struct StMma3;
-template <> struct StMma3<__bf16> {
-    static __device__ __forceinline__ f32x16_t run(const i32x4_t& a, const i32x4_t& b, const f32x16_t& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct StMma3<_Float16> {
-    static __device__ __forceinline__ f32x16_t run(const i32x4_t& a, const i32x4_t& b, const f32x16_t& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
 // the value of the next lane (lane 63: 0)
 __device__ __forceinline__ int sp_next_lane(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, true); }
 __device__ __forceinline__ int sp_max(int a, int b) { return a > b ? a : b; }
@@ -282,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StempArgs a) {
     int tile = xcd * cpx + lb;
     if (tile >= t_end) return;
 
-    const i32x4_t rs = st_rsrc(a.src, a.src_bytes);
+    const i32x4_t rs = raw_rsrc(a.src, a.src_bytes);
     const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.dst, a.dst_bytes);
     const __amdgpu_buffer_rsrc_t rma = make_rsrc(a.am, a.am_bytes);
 
@@ -303,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StempArgs a) {
             const int r = (p * 1821) >> 16, s = p - 36 * r;             // p / 36 for p < 3276
             const int iy = iy0 + r, ix = ix0 + 2 * s;                    // a piece = 2 pixels; ix0 and W are even: fully inside or fully outside
             const bool ok = p < SP_PIECES && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            st_dma16(rs, lds0 + buf * SP_ABUF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * a.H + iy) * a.W + ix) * 8) : URSO_OOB_SHIFT);
+            lds_dma16(rs, lds0 + buf * SP_ABUF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * a.H + iy) * a.W + ix) * 8) : URSO_OOB_SHIFT);
         }
     };
 
@@ -328,9 +295,9 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StempArgs a) {
     bool first = true;
     while (true) {
         const bool has_next = tile + bpx < t_end;
-        if (first) st_wait_vm<0>(); else st_wait_vm<NST>();
+        if (first) wait_vm<0>(); else wait_vm<NST>();
         first = false;
-        st_barrier();
+        lds_barrier_asm();
         if (has_next) dma_tile(tile + bpx, buf ^ 1);
         const char* sA = smem + buf * SP_ABUF;
         int b, ty, tx;
@@ -369,8 +336,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StempArgs a) {
 #pragma unroll
                 for (int r = 0; r < NR; ++r) {
                     const int ky = rho - 2 * r;
-                    if (ky == 0 && half == 0) acc[r] = StMma3<T>::run(wfr[0], f[s & 3], bsel);
-                    else if (ky >= 0 && ky <= 6) acc[r] = StMma3<T>::run(wfr[2 * ky + half], f[s & 3], acc[r]);
+                    if (ky == 0 && half == 0) acc[r] = Mma32<T>::mad(wfr[0], f[s & 3], bsel);
+                    else if (ky >= 0 && ky <= 6) acc[r] = Mma32<T>::mad(wfr[2 * ky + half], f[s & 3], acc[r]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -448,7 +415,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StempArgs a) {
             pool_out(3, P);
         }
         }
-        st_barrier();
+        lds_barrier_asm();
         // ---- the pooled tile -> row-contiguous 16-byte stores: values [8][16 (15 used)][8 chunks], arg-max bytes [8][16][4 chunks]
 #pragma unroll
         for (int i = 0; i < 4; ++i) {

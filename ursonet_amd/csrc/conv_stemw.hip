@@ -22,11 +22,9 @@
 // the windows of two 2 x 2 pixel blocks x 8 channels to their arg-max positions in urso_maxpool3x3s2_bwd's order and rounding -- the dz
 // tile in LDS is bit for bit what that kernel would have written -- and the weight gradient proceeds as above.  The gradient of conv1's
 // output (335 MB at cfg2) is then neither written by the pool's backward pass nor read here, and that launch disappears.
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef short sw_s16x4_t __attribute__((ext_vector_type(4)));
 
 struct StemwArgs {
     const void* x; const void* dz; float* part; float* colpart;
@@ -44,29 +42,6 @@ constexpr int SW_DPOFF = SW_LDS, SW_AMOFF = SW_DPOFF + 12288, SW_LDS_POOLED = SW
 
 // the dz tile is read only by transposing reads: 32-byte-block swizzle that separates the two row pairs of such a read (conv_c3g.hip)
 #define SW_SWZT(r) ((((r) >> 1) & 1) << 2)
-template <typename T> struct SwMma;
-template <> struct SwMma<__bf16> {
-    static constexpr int ONES = 0x3F803F80;
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct SwMma<_Float16> {
-    static constexpr int ONES = 0x3C003C00;
-    static __device__ __forceinline__ void run(const i32x4_t& a, const i32x4_t& b, f32x16_t& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
-__device__ __forceinline__ i32x2_t sw_tr16(const char* p) {
-    return __builtin_bit_cast(i32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) sw_s16x4_t*)p));
-}
-__device__ __forceinline__ void sw_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ i32x4_t sw_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
 
 template <typename T, bool POOLED>
 __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwArgs a) {
@@ -81,8 +56,8 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
     const int cpx = ceil_div(a.ntiles, 8);
     const int t_end = min((xcd + 1) * cpx, a.ntiles);
 
-    const i32x4_t rx = sw_rsrc(a.x, a.x_bytes), rz = sw_rsrc(POOLED ? a.dpool : a.dz, POOLED ? a.dpool_bytes : a.dz_bytes);
-    const i32x4_t ram = sw_rsrc(POOLED ? (const void*)a.am : a.x, POOLED ? a.am_bytes : 0u);
+    const i32x4_t rx = raw_rsrc(a.x, a.x_bytes), rz = raw_rsrc(POOLED ? a.dpool : a.dz, POOLED ? a.dpool_bytes : a.dz_bytes);
+    const i32x4_t ram = raw_rsrc(POOLED ? (const void*)a.am : a.x, POOLED ? a.am_bytes : 0u);
 
     // transposing fragment reads (conv_pairw.hip): a 16-lane group g reads 4 "rows" x 16 elements; lane l15 supplies row l15 >> 2, 8-byte
     // piece l15 & 3 and receives element-column l15 of the 4 rows.  Group g: (g & 1) = which 16 of the operand's 32 rows / columns,
@@ -102,7 +77,7 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-    const i32x4_t ones = {SwMma<T>::ONES, SwMma<T>::ONES, SwMma<T>::ONES, SwMma<T>::ONES};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 
     // ONE tile loop per window-row group ks (the waves of a group never meet the other group's code): with `ks` tested inside the reduction
     // loop hipcc kept acc[3] of the two arms in different registers and copied it back behind EVERY step -- 16 register moves behind an
@@ -122,7 +97,7 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
                 const int r = (p * 1821) >> 16, s = p - 36 * r;
                 const int iy = iy0 + r, ix = ix0 + 2 * s;
                 const bool ok = p < SW_PIECES && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-                sw_dma16(rx, lds0 + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * a.H + iy) * a.W + ix) * 8) : URSO_OOB_SHIFT);
+                lds_dma16(rx, lds0 + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * a.H + iy) * a.W + ix) * 8) : URSO_OOB_SHIFT);
             }
         }
         if constexpr (!POOLED) {
@@ -132,7 +107,7 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
                 const int row = 8 * (wave + 4 * i) + (lane >> 3);
                 const int oy = oy0 + (row >> 5), ox = ox0 + (row & 31);
                 const uint32_t so = (oy < a.OH && ox < a.OW) ? (uint32_t)(((b * a.OH + oy) * a.OW + ox) * 128 + (((lane & 7) ^ SW_SWZT(row)) << 4)) : URSO_OOB_SHIFT;
-                sw_dma16(rz, lds0 + SW_ZOFF + (wave + 4 * i) * 1024, so);
+                lds_dma16(rz, lds0 + SW_ZOFF + (wave + 4 * i) * 1024, so);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -146,7 +121,7 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
                 const int r = (pp * 3856) >> 16, c = pp - 17 * r;                         // pp / 17 for pp < 96
                 const int py = py0 + r, px = px0 + c;
                 const bool ok = pp < SW_PP && py >= 0 && py < PH && px >= 0 && px < PW;
-                sw_dma16(rz, lds0 + SW_DPOFF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * PH + py) * PW + px) * 128 + (p & 7) * 16) : URSO_OOB_SHIFT);
+                lds_dma16(rz, lds0 + SW_DPOFF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * PH + py) * PW + px) * 128 + (p & 7) * 16) : URSO_OOB_SHIFT);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -154,7 +129,7 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
                 const int r = (pp * 3856) >> 16, c = pp - 17 * r;
                 const int py = py0 + r, px = px0 + c;
                 const bool ok = pp < SW_PP && py >= 0 && py < PH && px >= 0 && px < PW;
-                sw_dma16(ram, lds0 + SW_AMOFF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * PH + py) * PW + px) * 64 + (p & 3) * 16) : URSO_OOB_SHIFT);
+                lds_dma16(ram, lds0 + SW_AMOFF + (wave + 4 * i) * 1024, ok ? (uint32_t)(((b * PH + py) * PW + px) * 64 + (p & 3) * 16) : URSO_OOB_SHIFT);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -210,15 +185,15 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
         for (int st = 0; st < 16; ++st) {                      // reduction step: tile row ry = st >> 1, pixels 16 (st & 1) .. + 15
             const int ry = st >> 1, hs = st & 1;
             const uint32_t zb = (uint32_t)((32 * ry + 16 * hs) * 128);
-            const i32x2_t zl = sw_tr16(smem + zoff[0] + zb), zh = sw_tr16(smem + zoff[1] + zb);
+            const i32x2_t zl = lds_read_tr16(smem + zoff[0] + zb), zh = lds_read_tr16(smem + zoff[1] + zb);
             const i32x4_t fz = i32x4_t{zl.x, zl.y, zh.x, zh.y};
             const uint32_t ab = (uint32_t)((2 * ry + KS) * SW_PROW_B + 16 * hs * 16) + aoff;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                if (i == 3 && KS == 1) { SwMma<T>::run(ones, fz, acc[3]); continue; }          // ky = 7 does not exist: the column sums
+                if (i == 3 && KS == 1) { Mma32<T>::run(ones, fz, acc[3]); continue; }          // ky = 7 does not exist: the column sums
                 const uint32_t ap = ab + (uint32_t)(2 * i * SW_PROW_B);                      // window row ky = KS + 2 i
-                const i32x2_t al = sw_tr16(smem + ap), ah = sw_tr16(smem + ap + 64);
-                SwMma<T>::run(i32x4_t{al.x, al.y, ah.x, ah.y}, fz, acc[i]);
+                const i32x2_t al = lds_read_tr16(smem + ap), ah = lds_read_tr16(smem + ap + 64);
+                Mma32<T>::run(i32x4_t{al.x, al.y, ah.x, ah.y}, fz, acc[i]);
             }
         }
         __syncthreads();                                       // every wave is done with the tiles before the next copies land

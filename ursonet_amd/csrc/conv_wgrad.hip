@@ -14,7 +14,8 @@
 // (fp32) per step, double-buffered LDS.  The pixel range is split over gridDim.z blocks that
 // write fp32 partial tiles; a second kernel sums the partials in a fixed order (deterministic,
 // no atomics) and also produces colsum[n] = sum_m dZ[m][n].
-#include "common.h"
+#include "lds_mfma.h"
+#include "internal.h"
 #include <stdlib.h>
 
 struct WgradArgs {
@@ -214,31 +215,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
 // LDS image of a chunk: row p = pixel (256 B), 16-B slot s of the row at position s ^ (2*(p&7)): 32-B channel blocks stay
 // contiguous, the 8 pixel rows a half-wave reads hit 8 disjoint bank groups, the staging writes fill whole rows.
 // colsum comes from the same fragments: one extra MFMA per n-block against an all-ones operand.
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x2_t lds_read_tr16(const char* p) {
-    return __builtin_bit_cast(i32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p));
-}
-// buffer_load_dwordx4 ... lds issued behind the compiler's back: through the builtin, hipcc waits vmcnt(0) before the next
-// LDS read of ANY buffer (it cannot tell the DMA's destination from the buffer being multiplied), which serialises the
-// copy with the MFMAs.  The caller orders it by hand: s_waitcnt vmcnt(0) before the barrier that publishes the buffer.
-__device__ __forceinline__ void lds_dma16(const i32x4_t& rsrc, uint32_t lds_byte, uint32_t voff) {
-#if defined(URSO_DMA_KEEP_M0)
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-#else
-    // m0 is not saved: nothing else in these kernels uses it (DS instructions need no m0 on gfx9+), and hipcc itself sets it
-    // afresh before every LDS-DMA it emits
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" :: "v"(voff), "s"(lds_byte), "s"(rsrc) : "memory");
-#endif
-}
-__device__ __forceinline__ i32x4_t raw_rsrc(const void* p, uint32_t bytes) {
-    const uint64_t a = (uint64_t)p;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-template <typename T> struct OnesFrag;
-template <> struct OnesFrag<__bf16> { static constexpr int W = 0x3F803F80; };
-template <> struct OnesFrag<_Float16> { static constexpr int W = 0x3C003C00; };
 
 // The block's work: tile `wid % tiles` of split `wid / tiles` of the layer described by `a` (called by the per-layer kernel and by
 // the grouped one below, which takes `a` from a device table).
@@ -343,7 +319,7 @@ __device__ __forceinline__ void wgrad_tr_body(const WgradArgs& a, const int wid,
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
     const bool do_col = (kt == 0) && (wk == 0) && a.colpart;
-    const i32x4_t ones = {OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 
     const int nsteps = (m_end > m_begin) ? ceil_div(m_end - m_begin, RM) : 0;
     if (nsteps > 0) dma(0);
@@ -538,7 +514,7 @@ __device__ __forceinline__ void wgrad_ring_body(const WgradArgs& a, const int wi
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
     const bool do_col = (kt == 0) && (wk == 0) && a.colpart;
-    const i32x4_t ones = {OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 
     constexpr int NDMA = 2 * ITEMS;                        // copies per thread and step
     const int nsteps = (m_end > m_begin) ? ceil_div(m_end - m_begin, RM) : 0;
@@ -689,7 +665,7 @@ __device__ __forceinline__ void wgrad_big_body(const WgradArgs& a, const int wid
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const bool do_col = (kt == 0) && (wk == 0) && a.colpart;
-    const i32x4_t ones = {OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 
     constexpr int NDMA = 4;
     const int nsteps = (m_end > m_begin) ? ceil_div(m_end - m_begin, RM) : 0;
@@ -919,7 +895,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tr64_kernel(const WgradArgs a) {
         for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     accc[0] = accc[1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const bool do_col = (kt == 0) && (wk == 0) && a.colpart;
-    const i32x4_t ones = {OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W, OnesFrag<T>::W};
+    const i32x4_t ones = {Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES, Elem<T>::ONES};
 
     const int nsteps = (m_end > m_begin) ? ceil_div(m_end - m_begin, RM) : 0;
     if (nsteps > 0) dma(0);
@@ -1038,18 +1014,6 @@ void urso_reduce_partials_batch_launch(const urso_param_desc* descs_d, const int
 
 struct WgradPlan { int VE, RM, Cc, Kc, K, M, ktiles, ntiles, splits, m_per_split, narrow; size_t part_elems, col_elems; };
 
-// conv_c3g.hip: the 64-channel 3x3 layers keep the whole gradient in registers (one partial per block)
-bool urso_c3g_fits(const urso_conv_geom* g, int dt);
-int urso_c3g_splits(const urso_conv_geom* g);
-int urso_c3g_launch(const urso_conv_geom* g, int dt, const void* x, const void* dz, float* part, float* colpart, size_t part_stride, hipStream_t st);
-// conv_hwgrad.hip: the same scheme for the 3x3 layers with >= 128 channels, one (64-channel, 64-filter) group of the gradient per block
-bool urso_hwg_fits(const urso_conv_geom* g, int dt);
-int urso_hwg_splits(const urso_conv_geom* g);
-int urso_hwg_launch(const urso_conv_geom* g, int dt, const void* x, const void* dz, float* part, float* colpart, size_t part_stride, hipStream_t st);
-bool urso_hwg_pair_splits(const urso_conv_geom* g0, const urso_conv_geom* g1, int dt, int* s0, int* s1);
-int urso_hwg_launch2(const urso_conv_geom* g0, const urso_conv_geom* g1, int dt, const void* x0, const void* dz0, float* part0, float* colpart0,
-                     const void* x1, const void* dz1, float* part1, float* colpart1, hipStream_t st);
-
 static int plan_wgrad(const urso_conv_geom* g, int dt, WgradPlan& p) {
     const int es = (int)dt_size(dt);
     p.VE = 16 / es; p.RM = 128 / es;
@@ -1083,12 +1047,6 @@ static int plan_wgrad(const urso_conv_geom* g, int dt, WgradPlan& p) {
     p.col_elems = (size_t)splits * g->N;
     return URSO_OK;
 }
-
-// conv_stemw.hip: the packed 7x7 stem has a kernel of its own (one partial per block)
-bool urso_stemw_fits(const urso_conv_geom* g, int dt);
-int urso_stemw_splits(const urso_conv_geom* g, bool pooled);
-int urso_stemw_launch(const urso_conv_geom* g, int dt, const void* x, const void* dz, const void* dpool, const uint8_t* am,
-                      float* part, float* colpart, size_t part_stride, hipStream_t st);
 
 extern "C" size_t urso_conv_wgrad_ws_bytes(const urso_conv_geom* g, int dt) {
     WgradPlan p;

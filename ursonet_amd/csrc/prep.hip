@@ -2,6 +2,7 @@
 // molding.  HBM-bound helper kernels on weight-sized tensors; see include/ursonet_hip.h for the
 // math and the net.py lines each one replaces.
 #include "common.h"
+#include "internal.h"
 
 template <typename T> __device__ __forceinline__ void store_elem(void* p, size_t i, float v) { ((T*)p)[i] = Elem<T>::from_f(v); }
 
@@ -449,7 +450,6 @@ static int param_grad_finalize_impl(int K, int N, int ldn, const float* dw_raw_d
 // ------------------------------------------------------------------ batched parameter-side phases
 // One launch covers many layers: every block looks its layer up in a (layer, local block) map built on the host by
 // urso_param_batch_plan.  Same arithmetic, in the same order, as the per-layer entry points above.
-void urso_reduce_partials_batch_launch(const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, hipStream_t st);   // conv_wgrad.hip
 
 static int batch_layer_blocks(int phase, const urso_param_desc& d) {
     switch (phase) {
