@@ -402,7 +402,8 @@ int urso_param_batch_run(int phase, int dt, const urso_param_desc* descs_d, cons
 /* The finalisation phases with the global norm folded in (keras clipnorm, net.py:980-981): block b of the launch ALSO writes the sum of squares
  * of the gradient values it stored to sqpart_d[b] (fixed order inside the block), so that sum over all slots = |g|^2 without reading the
  * gradient buffer back: urso_sqnorm_final adds the slots in index order into out_d[0] (what urso_sqnorm leaves there, up to fp32 summation
- * order).  urso_param_grad_finalize_sq: the per-layer form (the stem), urso_param_grad_finalize_sq_slots(K, N) slots.  Only valid when every
+ * order).  urso_param_grad_finalize_sq: the per-layer form (the stem), urso_param_grad_finalize_sq_slots(K, N) slots; a layer with neither
+ * bias nor BN launches no channel pass, and the entry point clears its ceil(N / 256) channel slots to 0 instead.  Only valid when every
  * gradient slice is written by these launches and nothing (an all-reduce) changes the buffer afterwards. */
 int urso_param_batch_run_sq(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, float* sqpart_d, void* stream);
 int urso_param_grad_finalize_sq_slots(int K, int N);

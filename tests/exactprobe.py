@@ -13,6 +13,9 @@ Two ways to compare a kernel with a float64 reference of the same operation, bot
 int_operands() / int_plan() make the integer data; ran() asserts which kernel a call actually launched.  The references of the
 packed stem (stem_taps, stem_conv64), of the max-pool's gradient routing (pool_route), of weight gradients (wgrad64) and of
 two-segment reductions (two_segment) live here too, each with a CPU test that it rejects the fault it is there to expose.
+
+The second half holds the float64 references and counted bounds of the step's tail (losses, global norm, optimizers, gradient
+finalisation, batch-statistics BatchNorm) that tests/test_step_tail_exact_gpu.py compares the kernels with.
 """
 import contextlib
 import math
@@ -282,3 +285,510 @@ def two_segment(x0, w0, x1, w1):
     """(x0 w0^T + x1 w1^T, |x0| |w0|^T + |x1| |w1|^T) in float64: ONE reduction of K0 + K1 terms, rounded once when stored."""
     d = lambda t: t.to(torch.float64)
     return d(x0) @ d(w0).T + d(x1) @ d(w1).T, d(x0).abs() @ d(w0).abs().T + d(x1).abs() @ d(w1).abs().T
+
+
+# =====================================================================================================================
+# The tail of a training step: losses, global norm, optimizers, gradient finalisation, batch-statistics BatchNorm.
+# Every reference mirrors the operation's DEFINITION in float64 (not the kernel's loop order); every bound is counted
+# from the operation: half an ulp of the storage type at the reference + U = 2^-24 times the magnitude of each fp32
+# intermediate times the number of roundings on its path (FMA contraction only lowers it).  Differences of larger
+# numbers are charged with the SUM of the magnitudes of their terms.  Each docstring states its count.
+U32 = 2.0 ** -24
+EXP_FLOOR = 2.0 ** -120             # absolute floor for fp32 denormals the exp unit may flush
+
+
+def d64(t):
+    return t.detach().to("cpu").to(torch.float64) if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t), dtype=torch.float64)
+
+
+def f32v(x):
+    """The float32 value of a Python scalar, as float64 (what a `float` argument of the C ABI carries)."""
+    return float(np.float32(x))
+
+
+def store_bound(ref64, err64, dt):
+    """err + half an ulp of the storage type at (|ref| + err): the value is rounded ONCE when stored."""
+    return 0.5 * ulp(ref64.abs() + err64, dt) + err64
+
+
+def assert_within(got, ref64, bound64, what="output"):
+    """Elementwise |got - ref| <= bound over the WHOLE extent (no masking); returns the largest ratio to the bound
+    (0 / 0 counts as 0: an element whose bound is 0 must be exact)."""
+    got = _host64(got).reshape(ref64.shape)
+    ref64, bound64 = ref64.to(torch.float64), bound64.to(torch.float64)
+    assert got.shape == ref64.shape == bound64.shape, "%s: shapes %s %s %s" % (what, tuple(got.shape), tuple(ref64.shape), tuple(bound64.shape))
+    assert bool(torch.isfinite(got).all()), "%s: non-finite values" % what
+    err = (got - ref64).abs()
+    bad = err > bound64
+    if bool(bad.any()):
+        raise AssertionError(_report(what, bad, got, ref64, bound64))
+    return float(torch.where(err > 0, err / bound64.clamp_min(1e-300), torch.zeros_like(err)).max()) if err.numel() else 0.0
+
+
+def violations(got, ref64, bound64):
+    """Share of elements outside the bound (the CPU rejection tests count it)."""
+    got = _host64(got).reshape(ref64.shape)
+    bad = ((got - ref64).abs() > bound64) | ~torch.isfinite(got)
+    return float(bad.sum()) / max(bad.numel(), 1)
+
+
+def pairwise_sum32(t, dim=-1):
+    """fp32 sum by halving (a tree of depth ceil(log2 n)): the summation of the simulated kernels."""
+    t = t.to(torch.float32).movedim(dim, -1)
+    while t.shape[-1] > 1:
+        if t.shape[-1] & 1:
+            t = torch.cat([t, torch.zeros_like(t[..., :1])], -1)
+        t = t[..., 0::2] + t[..., 1::2]
+    return t[..., 0]
+
+
+# ---- sums of nonnegative terms
+def tree_sum_bound(ref64, depth):
+    """A sum of nonnegative fp32 terms through an addition tree whose longest chain has `depth` roundings (the product that
+    makes a term counts as one): relative depth U / (1 - depth U)."""
+    return ref64.abs() * (depth * U32 / (1.0 - depth * U32))
+
+
+def block_sum_depth(nthreads=256):
+    """wave_sum (6 xor-shuffle additions over 64 lanes) + the serial addition of the block's waves."""
+    return 6 + nthreads // 64
+
+
+def sqnorm_depth(n):
+    """urso_sqnorm (pool_loss_optim.hip): 1024 x 256 threads sweep float4s: square 1 + 3 additions inside the float4 + one
+    addition to the thread's sum per sweep (ceil(n / 4 / 262144)) + 2 for the ragged tail (square, addition; block 0) +
+    block sum 10; the final pass adds 1024 parts: 4 per thread + block sum 10."""
+    sweeps = max(-(-(n // 4) // (1024 * 256)), 1)
+    return 1 + 3 + sweeps + 2 + block_sum_depth() + 4 + block_sum_depth()
+
+
+def sqnorm_final_depth(nparts):
+    """urso_sqnorm_final: ceil(nparts / 256) additions per thread + block sum 10."""
+    return -(-nparts // 256) + block_sum_depth()
+
+
+# ---- softmax cross-entropy with soft labels (TF: dz = (softmax - p) weight / B; row loss lse sum(p) - sum(p z))
+def xent_inputs(B, K, psum, seed=0):
+    """(logits, labels) float32 [B][K] of the loss probes: post-ReLU logits (about half exactly 0) in the engine's range; soft
+    labels that sum to `psum`; row 0 all zero; row 1 (if B > 1) with one logit of 80 (every other term underflows); the last
+    row's maximum is its last element."""
+    g = torch.Generator().manual_seed(1000 * int(seed) + K + B)
+    z = torch.relu(torch.randn(B, K, generator=g) * 2)
+    z[0] = 0
+    if B > 1:
+        z[1, K // 3] = 80.0
+    z[B - 1, K - 1] = z[B - 1].max() + 1.5
+    p = torch.softmax(torch.randn(B, K, generator=g) * 4, 1) * psum
+    return z.contiguous(), p.to(torch.float32).contiguous()
+
+
+def softmax_sum_depth(K):
+    """Longest chain of additions of a row sum in urso_softmax_xent_fwd_bwd: K <= 4096: 4 per thread + 6 (wave) + 16 waves;
+    K <= 16384: 16 + 6 + 16; larger: ceil(K / 256) per thread + block sum 10."""
+    if K <= 4096:
+        return 4 + 6 + 16
+    if K <= 16384:
+        return 16 + 6 + 16
+    return -(-K // 256) + block_sum_depth()
+
+
+def softmax_xent64(z, p, weight, relu_mask, B=None):
+    """-> (loss, row_loss [B], dz [B][K]) in float64.  The scale weight / B is the fp32 quotient the entry point passes on."""
+    z, p = d64(z), d64(p)
+    B = z.shape[0] if B is None else B
+    gs = float(np.float32(weight) / np.float32(B))
+    lse = torch.logsumexp(z, 1)
+    row = lse * p.sum(1) - (p * z).sum(1)
+    dz = (torch.softmax(z, 1) - p) * gs
+    if relu_mask:
+        dz = torch.where(z > 0, dz, torch.zeros_like(dz))
+    return row.sum() * gs, row, dz
+
+
+def softmax_xent_bounds(z, p, weight, relu_mask, dt):
+    """-> (bound of loss, of row_loss, of dz) for fp32 arithmetic with the exp unit, D = softmax_sum_depth(K).
+    term e = exp(x), x = z - max <= 0:        (|x| + 4) U e + 2^-120   (x rounded 1, x log2e 1 + the constant, exp2 1 ulp = 2)
+    sum S:                                    sum of the terms' errors + D U S
+    softmax = e (1 / S):                      err_e / S + softmax (err_S / S + 2 U)            (reciprocal 1, product 1)
+    dz = (softmax - p) gs:                    gs err_softmax + 3 U gs (softmax + |p|)          (difference 1, product 1, gs itself 1)
+    row = lse sp - spz, lse = max + log S:    |sp| (err_S / S + 2 U |log S| + U |lse|)  (logf 1 ulp = 2, addition 1)
+                                              + |lse| (D + 1) U sum|p| + (D + 2) U sum|p z| + U (|lse sp| + |spz|)
+    loss = gs sum(row):                       gs (sum of the rows' errors + (ceil(B / 256) + 10 + 2) U sum|row|)
+    dz is stored in `dt` (half an ulp on top), the losses in fp32."""
+    z, p = d64(z), d64(p)
+    B, K = z.shape
+    D = softmax_sum_depth(K)
+    gs = float(np.float32(weight) / np.float32(B))
+    m = z.max(1, keepdim=True).values
+    x = z - m
+    e = torch.exp(x)
+    S = e.sum(1, keepdim=True)
+    err_e = (x.abs() + 4) * U32 * e + EXP_FLOOR
+    err_S = err_e.sum(1, keepdim=True) + D * U32 * S
+    soft = e / S
+    err_soft = err_e / S + soft * (err_S / S + 2 * U32)
+    err_dz = gs * err_soft + 3 * U32 * gs * (soft + p.abs())
+    if relu_mask:
+        err_dz = torch.where(z > 0, err_dz, torch.zeros_like(err_dz))
+    _, row, dz = softmax_xent64(z, p, weight, relu_mask)
+    logS, sp, spz = torch.log(S[:, 0]), p.sum(1), (p * z).sum(1)
+    lse = m[:, 0] + logS
+    sabs, spzabs = p.abs().sum(1), (p * z).abs().sum(1)
+    err_row = (sp.abs() * (err_S[:, 0] / S[:, 0] + 2 * U32 * logS.abs() + U32 * lse.abs())
+               + lse.abs() * (D + 1) * U32 * sabs + (D + 2) * U32 * spzabs + U32 * ((lse * sp).abs() + spz.abs()))
+    err_loss = gs * (err_row.sum() + (-(-B // 256) + block_sum_depth() + 2) * U32 * row.abs().sum())
+    return store_bound(row.sum() * gs, err_loss, 0), store_bound(row, err_row, 0), store_bound(dz, err_dz, dt)
+
+
+def softmax_xent32(z, p, weight, relu_mask, dt, exp2=True):
+    """Plain fp32 restatement (the simulated kernel): exp as exp2(x * 1.442695), pairwise fp32 sums, gradient rounded once."""
+    z, p = z.to(torch.float32), p.to(torch.float32)
+    B = z.shape[0]
+    gs = torch.tensor(np.float32(weight) / np.float32(B))
+    m = z.max(1, keepdim=True).values
+    x = z - m
+    e = torch.exp2(x * torch.tensor(1.442695, dtype=torch.float32)) if exp2 else torch.exp(x)
+    S = pairwise_sum32(e)[:, None]
+    dz = (e * (1.0 / S) - p) * gs
+    if relu_mask:
+        dz = torch.where(z > 0, dz, torch.zeros_like(dz))
+    row = (m[:, 0] + torch.log(S[:, 0])) * pairwise_sum32(p) - pairwise_sum32(p * z)
+    return pairwise_sum32(row) * gs, row, dz.to(tdtype(dt))
+
+
+# ---- the regression losses on [B][D] heads stored with row stride ld (columns D.. of the gradient are exactly 0)
+def _pad_cols(g, ld):
+    return F.pad(g, (0, ld - g.shape[1]))
+
+
+def rel_l2_64(gt, pred, weight, gscale=1.0):
+    """||gt - pred||_F / ||gt||_F over the batch: -> (loss, dpred [B][ld], (sd, sg)); pred is [B][ld], its columns D.. are ignored.
+    The gradient is -weight gscale (gt - pred) / (nd ng)."""
+    gt, pred = d64(gt), d64(pred)
+    D, ld, w = gt.shape[1], pred.shape[1], f32v(weight)
+    e = gt - pred[:, :D]
+    sd, sg = (e * e).sum(), (gt * gt).sum()
+    nd, ng = sd.sqrt(), sg.sqrt()
+    return w * nd / ng, _pad_cols(-w * f32v(gscale) / (nd * ng) * e, ld), torch.stack([sd, sg])
+
+
+def rel_l2_bounds(gt, pred, weight, dt, gscale=1.0):
+    """S = ceil(B D / 256) + 10 (+ 3: difference 1, square 1, first addition) roundings on each squared norm, relative.
+    loss = w nd / ng: half of each norm's error ((S + 3) U in all) + 2 square roots + product + quotient = (S + 7) U.
+    gradient c (gt - pred), c = -w gscale / (nd ng): (S + 3) + 2 + product 1 + quotient 1 + gscale 1, difference 1,
+    product 1 = (S + 10) U relative, + half an ulp of `dt`.  -> (loss, gradient, norms)."""
+    loss, g, norms = rel_l2_64(gt, pred, weight, gscale)
+    S = -(-gt.numel() // 256) + block_sum_depth()
+    return (store_bound(loss, (S + 7) * U32 * loss.abs(), 0), store_bound(g, (S + 10) * U32 * g.abs(), dt),
+            store_bound(norms, tree_sum_bound(norms, S + 3), 0))
+
+
+def mse64(gt, pred, weight):
+    """weight mean((pred - gt)^2) -> (loss, dpred [B][ld] = 2 weight (pred - gt) / (B D))."""
+    gt, pred = d64(gt), d64(pred)
+    B, D = gt.shape
+    e = pred[:, :D] - gt
+    w = f32v(weight)
+    return w * (e * e).sum() / (B * D), _pad_cols(2 * w / (B * D) * e, pred.shape[1])
+
+
+def mse_bounds(gt, pred, weight, dt):
+    """gradient: quotient in c 1, difference 1, product 1 = 3 U relative + half an ulp of `dt`;
+    loss: S = ceil(B ld / 256) + 10 additions + 3 (difference, square, first addition) + product 1 + quotient 1 = (S + 5) U."""
+    loss, g = mse64(gt, pred, weight)
+    S = -(-pred.numel() // 256) + block_sum_depth()
+    return store_bound(loss, (S + 5) * U32 * loss.abs(), 0), store_bound(g, 3 * U32 * g.abs(), dt)
+
+
+ABSDOT_CLAMP = float(np.float32(1e-12))
+
+
+def absdot64(gt, x, weight, normalize, clamp_branch=True):
+    """q = x / sqrt(max(|x|^2, 1e-12)) (normalize) or x; loss = weight mean(1 - |gt . q|); dq = -sign(dot) gt weight / B with
+    sign(0) = 0; dx = rinv (dq - q (q . dq)), and rinv dq on a clamped row (|x|^2 <= 1e-12: q = x rinv has no norm
+    constraint).  gt None: the inference form, only q.  -> (q [B][D], loss, dx [B][ld], dot [B], magnitude of dx's terms)."""
+    x = d64(x)
+    B, ld = x.shape
+    D = gt.shape[1] if gt is not None else None
+    if D is None:
+        raise ValueError("pass D through absdot_q64 for the inference form")
+    xv = x[:, :D]
+    ss = (xv * xv).sum(1, keepdim=True)
+    clamped = ~(ss > ABSDOT_CLAMP)
+    rinv = torch.rsqrt(ss.clamp_min(ABSDOT_CLAMP)) if normalize else torch.ones_like(ss)
+    q = xv * rinv
+    gt = d64(gt)
+    w = f32v(weight)
+    dot = (gt * q).sum(1, keepdim=True)
+    dq = -torch.sign(dot) * gt * (w / B)
+    qdq = (q * dq).sum(1, keepdim=True)
+    proj = q * qdq
+    if normalize and clamp_branch:
+        proj = torch.where(clamped, torch.zeros_like(proj), proj)
+    dx = rinv * (dq - proj) if normalize else dq
+    mag = rinv * (dq.abs() + (proj != 0) * q.abs() * (q * dq).abs().sum(1, keepdim=True)) if normalize else dq.abs()
+    return q, w * (1 - dot.abs()).mean(), _pad_cols(dx, ld), dot[:, 0], _pad_cols(mag, ld)
+
+
+def absdot_q64(x, D, normalize):
+    """The inference form (gt = None): q alone."""
+    xv = d64(x)[:, :D]
+    ss = (xv * xv).sum(1, keepdim=True)
+    return xv * (torch.rsqrt(ss.clamp_min(ABSDOT_CLAMP)) if normalize else 1.0)
+
+
+def absdot_bounds(gt, x, weight, normalize, dt):
+    """R = D + 4 roundings on q = x rinv, relative (|x|^2: D + 1 roundings, halved by the root; rsqrt 1 ulp = 2; product 1);
+    0 without normalisation (q = x, dx = dq).
+    dot = sum gt q: (R + D + 1) U sum|gt q|.     loss: w (mean of the dots' errors + (ceil(B / 256) + 10 + 3) U mean|1 - |dot||).
+    dx = rinv (dq - q qdq): on the sum of the magnitudes rinv (|dq| + |q| sum|q dq|):
+      c = -sign w / B 1, dq 1, rinv R, q R, qdq R + D + 1, difference 1, two products 2  ->  (3 R + D + 6) U;  dq alone: 2 U.
+    -> (q, loss, dx) bounds; dx stored in `dt`."""
+    q, loss, dx, dot, mag = absdot64(gt, x, weight, normalize)
+    B, D = q.shape
+    R = D + 4 if normalize else 0
+    gtq = (d64(gt) * q).abs().sum(1)
+    err_dot = (R + D + 1) * U32 * gtq
+    w = f32v(weight)
+    err_loss = w * (err_dot.mean() + (-(-B // 256) + block_sum_depth() + 3) * U32 * (1 - dot.abs()).abs().mean())
+    err_dx = ((3 * R + D + 6) if normalize else 2) * U32 * mag
+    return store_bound(q, R * U32 * q.abs(), 0), store_bound(loss, err_loss, 0), store_bound(dx, err_dx, dt)
+
+
+# ---- optimizers.  normsq is an ARGUMENT: the GPU tests pass the value the device wrote (checked on its own)
+def sgd_data(n, case, seed=0):
+    """(w, g, v, lr, mom, clip) of the SGD probes, float32; the median of |step g| / |mom v| is >= 0.1 in every case (a wrong
+    step size shows in v), and the gradient norm is a factor 2 away from clip.  case: 'unclipped', 'clipped', 'noclip'
+    (clip = 0 with a large gradient), 'mom0'."""
+    g_ = torch.Generator().manual_seed(int(seed) + n)
+    w = torch.randn(n, generator=g_)
+    v = torch.randn(n, generator=g_) * 0.01
+    g = torch.randn(n, generator=g_) * (10.0 if case == "noclip" else 0.1)
+    norm = float(g.double().pow(2).sum().sqrt())
+    clip = {"unclipped": 2.0 * norm, "clipped": 0.5 * norm, "noclip": 0.0, "mom0": 2.0 * norm}[case]
+    return w, g, v, 0.05, (0.0 if case == "mom0" else 0.9), float(np.float32(clip))
+
+
+def clip_factor64(normsq, clip):
+    norm = math.sqrt(float(normsq))
+    clip = f32v(clip)
+    return clip / norm if (clip > 0 and norm >= clip) else 1.0
+
+
+def sgd64(w, g, v, lr, mom, clip, normsq):
+    """keras SGD(momentum, clipnorm) with the global norm: step = lr c, c = clip / norm if clip > 0 and norm >= clip else 1;
+    v' = mom v - step g; w' = w + v'.  -> (w', v', bound of w', bound of v', median |step g| / |mom v|).
+    Roundings: step: square root 1, quotient 1, product 1 = 3; v': mom v 1, step g 3 + 1, difference 1 on the sum of the
+    magnitudes -> U (2 |mom v| + 5 |step g|); w': the error of v' + U (|w| + |v'|); both stored in fp32."""
+    w, g, v = d64(w), d64(g), d64(v)
+    step, mom = f32v(lr) * clip_factor64(normsq, clip), f32v(mom)
+    a, b = mom * v, step * g
+    v2 = a - b
+    w2 = w + v2
+    err_v = U32 * (2 * a.abs() + 5 * b.abs())
+    err_w = err_v + U32 * (w.abs() + v2.abs())
+    ratio = float((b.abs() / a.abs().clamp_min(1e-300)).median()) if mom != 0 else float("inf")
+    return w2, v2, store_bound(w2, err_w, 0), store_bound(v2, err_v, 0), ratio
+
+
+def sgd32(w, g, v, lr, mom, clip, normsq, lr_factor=1.0, keep_from=None, keep_to=None):
+    """fp32 restatement (the simulated kernel); lr_factor plants a wrong learning rate, [keep_from, keep_to) is left
+    un-updated (a dropped tail or grid sweep)."""
+    f = np.float32
+    norm = np.sqrt(f(normsq))
+    c = f(clip) / norm if (f(clip) > 0 and norm >= f(clip)) else f(1)
+    step = torch.tensor(f(f(lr) * f(lr_factor)) * c)
+    v2 = v * torch.tensor(f(mom)) - g * step
+    w2 = w + v2
+    if keep_from is not None:
+        v2[keep_from:keep_to] = v[keep_from:keep_to]
+        w2[keep_from:keep_to] = w[keep_from:keep_to]
+    return w2, v2
+
+
+# Adam's lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) goes through powf, whose error is amplified by the cancellation in 1 - b2^t
+# (b2 = 0.999): not derivable from rounding counts.  MEASURED: the float32 NumPy restatement adam_lr_t32() against float64 on
+# the probes' hyper-parameters (lr 1e-3, b1 0.9, b2 0.999, t = 1, 2, 3) is off by at most 3.42e-6 relative
+# (tests/test_exactprobe_cpu.py::test_adam_lr_t_measured recomputes it); allowed: 4 x that.
+ADAM_LRT_MEASURED = 3.42e-6
+ADAM_LRT_REL = 4 * ADAM_LRT_MEASURED
+
+
+def adam_lr_t32(lr, b1, b2, t):
+    f = np.float32
+    return f(lr) * (np.sqrt(f(1) - np.power(f(b2), f(t), dtype=f)) / (f(1) - np.power(f(b1), f(t), dtype=f)))
+
+
+def adam_lr_t64(lr, b1, b2, t):
+    lr, b1, b2 = f32v(lr), f32v(b1), f32v(b2)
+    return lr * math.sqrt(1 - b2 ** t) / (1 - b1 ** t)
+
+
+def adam64(w, g, m, v, vhat, hyper, normsq, v_from_unclipped=False):
+    """Keras 2 Adam(amsgrad=True, clipnorm): hyper = (lr, b1, b2, eps, clip, t AFTER the tick, 1 - b1, 1 - b2) as the device holds
+    them (fp32 values).  gc = g c; m' = b1 m + c1 gc; v' = b2 v + c2 gc^2; vhat' = max(vhat, v'); w' = w - lr_t m' / (sqrt(vhat') + eps).
+    -> dict name -> (reference, bound).  Roundings: c: square root 1 + quotient 1, gc: + 1 = 3 (0 when not clipped -- kept);
+    m': U (2 |b1 m| + 5 |c1 gc|);  v': U (2 |b2 v| + 9 |c2 gc^2|) (gc^2: 6 + 1, product 1, addition 1);  vhat': that of v';
+    update u = lr_t m' / (sqrt(vhat') + eps): relative ADAM_LRT_REL (measured, see above) + err_m / |m'| + err_vhat / (2 vhat')
+    + 4 U (root, addition, product, quotient);  w': err_u + U (|w| + |u|)."""
+    w, g, m, v, vhat = d64(w), d64(g), d64(m), d64(v), d64(vhat)
+    lr, b1, b2, eps, clip, t, c1, c2 = [float(h) for h in d64(hyper)[:8]]
+    gc = g * clip_factor64(normsq, clip)
+    gv = g if v_from_unclipped else gc
+    a, b = b1 * m, c1 * gc
+    m2 = a + b
+    p, q = b2 * v, c2 * gv * gv
+    v2 = p + q
+    vh2 = torch.maximum(vhat, v2)
+    den = vh2.sqrt() + eps
+    u = adam_lr_t64(lr, b1, b2, t) * m2 / den
+    w2 = w - u
+    err_m = U32 * (2 * a.abs() + 5 * b.abs())
+    err_v = U32 * (2 * p.abs() + 9 * q.abs())
+    err_u = u.abs() * (ADAM_LRT_REL + 4 * U32) + adam_lr_t64(lr, b1, b2, t) * (err_m / den + m2.abs() * err_v / (2 * vh2.sqrt().clamp_min(1e-300) * den * den))
+    err_w = err_u + U32 * (w.abs() + u.abs())
+    return {"w": (w2, store_bound(w2, err_w, 0)), "m": (m2, store_bound(m2, err_m, 0)),
+            "v": (v2, store_bound(v2, err_v, 0)), "vhat": (vh2, store_bound(vh2, err_v, 0))}
+
+
+def adam32(w, g, m, v, vhat, hyper, normsq, v_from_unclipped=False):
+    """fp32 restatement of the update (the simulated kernel)."""
+    f = np.float32
+    lr, b1, b2, eps, clip, t, c1, c2 = [f(h) for h in hyper[:8].tolist()]
+    norm = np.sqrt(f(normsq))
+    c = torch.tensor(clip / norm if (clip > 0 and norm >= clip) else f(1))
+    gc = g * c
+    gv = g if v_from_unclipped else gc
+    m2 = torch.tensor(b1) * m + torch.tensor(c1) * gc
+    v2 = torch.tensor(b2) * v + torch.tensor(c2) * (gv * gv)
+    vh2 = torch.maximum(vhat, v2)
+    w2 = w - torch.tensor(adam_lr_t32(lr, b1, b2, t)) * m2 / (vh2.sqrt() + torch.tensor(eps))
+    return w2, m2, v2, vh2
+
+
+# ---- parameter-gradient finalisation of a conv / dense layer with its frozen BatchNorm folded in
+def finalize64(dw_raw, colsum, W, b, gamma, mean, var, eps, wd, gamma_term=True):
+    """Closed form; s = gamma / sqrt(var + eps) (1 without BN), dw_raw [K][N] (the padded columns already dropped):
+      gW = s dw_raw + 2 wd / (K N) W;  gb = s colsum + 2 wd / N b;
+      ggamma = (sum_k W dw_raw + (b - mean) colsum) / sqrt(var + eps);  gbeta = colsum.
+    b / gamma None: absent.  -> dict name -> (reference, magnitude of the terms).  (tests/test_exactprobe_cpu.py proves it
+    equal to float64 autograd through conv -> frozen BatchNorm + the L2 term.)"""
+    dw, cs, W = d64(dw_raw), d64(colsum), d64(W)
+    K, N = W.shape
+    eps, wd = f32v(eps), f32v(wd)
+    rstd = torch.rsqrt(d64(var) + eps) if gamma is not None else None
+    s = d64(gamma) * rstd if gamma is not None else torch.ones(N, dtype=torch.float64)
+    regc, regb = 2 * wd / (float(K) * float(N)), 2 * wd / float(N)
+    out = {"gw": (s * dw + regc * W, (s * dw).abs() + (regc * W).abs())}
+    if b is not None:
+        out["gb"] = (s * cs + regb * d64(b), (s * cs).abs() + (regb * d64(b)).abs())
+    if gamma is not None:
+        bm = (d64(b) if b is not None else 0.0) - d64(mean)
+        extra = bm * cs if gamma_term else torch.zeros_like(cs)
+        out["ggamma"] = (rstd * ((W * dw).sum(0) + extra), rstd * ((W * dw).abs().sum(0) + (bm * cs).abs()))
+        out["gbeta"] = (cs.clone(), cs.abs())
+    return out
+
+
+def finalize_bounds(ref, K, N, ldn, ks):
+    """Roundings (ks = row slabs of the launch, kb = ceil(K / ks) rows each; vector body when (N | ldn) % 4 == 0):
+      gW, gb: s = gamma rsqrt(var + eps): addition 1, rsqrt 1 ulp = 2, product 1 = 4; s d 1; the L2 factor 2, its product 1;
+              sum 1  ->  6 U on |s d| + |reg W|.
+      ggamma: the dot sum_k W d: product 1 + ceil(kb / 16) additions per row lane + 15 lanes (vector) or ceil(kb / 4) + 3
+              (scalar), + the slabs: ceil(ks / 4) + 2; (b - mean) colsum: 2; sum 1; rstd 3, product 1
+              ->  (dot depth + 6) U on rstd (sum|W d| + |(b - mean) colsum|).
+      gbeta = colsum: exact.        All stored in fp32.  -> dict name -> bound."""
+    kb = -(-K // ks)
+    ddot = 1 + ((-(-kb // 16) + 15) if ((N | ldn) & 3) == 0 else (-(-kb // 4) + 3)) + -(-ks // 4) + 2
+    cnt = {"gw": 6, "gb": 6, "ggamma": ddot + 6, "gbeta": 0}
+    return {k: store_bound(r, cnt[k] * U32 * mag, 0) if cnt[k] else torch.zeros_like(r) for k, (r, mag) in ref.items()}
+
+
+def finalize_sq_depth(K, N, ldn, ks, nslots):
+    """Sum of squares through the _sq slots and urso_sqnorm_final: a block's slot: square 1 + 3 inside a float4 + ceil(kb / 16)
+    additions per thread (vector; scalar: 1 + ceil(kb / 4)) + block sum 10; the channel block: 3 squares' sum + block sum;
+    then sqnorm_final_depth(nslots)."""
+    kb = -(-K // ks)
+    per = (4 + -(-kb // 16)) if ((N | ldn) & 3) == 0 else (1 + -(-kb // 4))
+    return per + block_sum_depth() + sqnorm_final_depth(nslots)
+
+
+def finalize32(dw_raw, colsum, W, b, gamma, mean, var, eps, wd, gamma_term=True):
+    """fp32 restatement (the simulated kernel), pairwise column dots."""
+    f = torch.float32
+    K, N = W.shape
+    rstd = torch.rsqrt(var + torch.tensor(eps, dtype=f)) if gamma is not None else None
+    s = gamma * rstd if gamma is not None else torch.ones(N)
+    regc = torch.tensor(np.float32(2.0) * np.float32(wd) / (np.float32(K) * np.float32(N)))
+    regb = torch.tensor(np.float32(2.0) * np.float32(wd) / np.float32(N))
+    out = {"gw": s * dw_raw + regc * W}
+    if b is not None:
+        out["gb"] = s * colsum + regb * b
+    if gamma is not None:
+        bm = (b if b is not None else torch.zeros(N)) - mean
+        out["ggamma"] = rstd * (pairwise_sum32(W * dw_raw, 0) + (bm * colsum if gamma_term else 0.0))
+        out["gbeta"] = colsum.clone()
+    return out
+
+
+# ---- batch-statistics BatchNorm over [M][N]
+def bn_stats64(z, mmean, mvar, momentum, eps, corrected=True):
+    """mean, biased variance (clamped at 0), and Keras' moving statistics: mmean' = mmean mom + mean (1 - mom);
+    mvar' = mvar mom + var M / (M - (1 + eps)) (1 - mom).  -> dict name -> (reference, bound).
+    The kernel sums in float64 (M terms: M 2^-53 on the sums' magnitudes, var = E[z^2] - mean^2 charged with both terms), rounds
+    mean / var to fp32 once; the moving updates run in fp32 on those rounded values: (1 - mom) 1, two products 2, sum 1 ->
+    U (2 |old mom| + 3 |new (1 - mom)|) + the rounding of the batch value (1 - mom) / 2 ulp."""
+    z = d64(z)
+    M = z.shape[0]
+    mom, eps = f32v(momentum), f32v(eps)
+    D = M * 2.0 ** -53
+    mean = z.mean(0)
+    ez2 = (z * z).mean(0)
+    var = (ez2 - mean * mean).clamp_min(0)
+    err_mean, err_var = D * z.abs().mean(0), 3 * D * (ez2 + mean * mean)
+    out = {"mean": (mean, store_bound(mean, err_mean, 0)), "var": (var, store_bound(var, err_var, 0))}
+    corr = M / (M - (1 + eps)) if corrected else 1.0
+    for name, old, new, e_new in (("mmean", d64(mmean), mean, err_mean), ("mvar", d64(mvar), var * corr, err_var * corr)):
+        a, b = old * mom, new * (1 - mom)
+        e_new = store_bound(new, e_new + 2.0 ** -52 * new.abs(), 0)             # the batch value itself is rounded to fp32
+        out[name] = (a + b, store_bound(a + b, U32 * (2 * a.abs() + 3 * b.abs()) + (1 - mom) * e_new, 0))
+    return out
+
+
+def bn_apply64(z, mean, var, gamma, beta, eps, res, relu, dt, scale_channel=None):
+    """y = relu?(gamma (z - mean) rstd + beta + res) with the mean / var the device holds (fp32 values) -> (y, bound).
+    s = gamma rsqrt(var + eps): 4 roundings (addition, rsqrt 1 ulp = 2, product); z - mean 1; product 1; + beta 1; + res 1:
+    U (8 |(z - mean) s| + 2 |beta| + |res|), + half an ulp of `dt`."""
+    z = d64(z)
+    s = d64(gamma) * torch.rsqrt(d64(var) + f32v(eps))
+    t = (z - d64(mean)) * s
+    y = t + d64(beta)
+    err = U32 * (8 * t.abs() + 2 * d64(beta).abs())
+    if res is not None:
+        y = y + d64(res)
+        err = err + U32 * d64(res).abs()
+    if relu:
+        y = y.clamp_min(0)
+    return y, store_bound(y, err, dt)
+
+
+def bn_backward64(g, z, mean, var, gamma, eps, dt, dbeta=None, dgamma=None):
+    """dbeta = sum g; dgamma = sum g xhat, xhat = (z - mean) rstd; dz = gamma rstd (g - dbeta / M - xhat dgamma / M), with the
+    device's mean / var and -- for dz -- the device's dbeta / dgamma when given.  -> dict name -> (reference, bound).
+    dbeta: float64 sums, rounded once.  dgamma: each term g xhat in fp32: difference 1, rstd 3, product 1, product 1 = 6 U on
+    sum|g xhat|, rounded once.  dz on gamma rstd (|g| + |dbeta / M| + |xhat dgamma / M|): k = gamma rstd 4 + its product 1;
+    dbeta / M 2 (1 / M, product); xhat 5, dgamma 1, 1 / M 2; two differences 2  ->  14 U, + half an ulp of `dt`."""
+    g, z = d64(g), d64(z)
+    M = z.shape[0]
+    rstd = torch.rsqrt(d64(var) + f32v(eps))
+    xh = (z - d64(mean)) * rstd
+    db, dg = g.sum(0), (g * xh).sum(0)
+    D = M * 2.0 ** -53
+    out = {"dbeta": (db, store_bound(db, D * g.abs().sum(0), 0)),
+           "dgamma": (dg, store_bound(dg, (6 * U32 + D) * (g * xh).abs().sum(0), 0))}
+    db_, dg_ = (d64(dbeta) if dbeta is not None else db), (d64(dgamma) if dgamma is not None else dg)
+    k = d64(gamma) * rstd
+    dz = k * (g - db_ / M - xh * dg_ / M)
+    mag = k.abs() * (g.abs() + (db_ / M).abs() + (xh * dg_ / M).abs())
+    out["dz"] = (dz, store_bound(dz, 14 * U32 * mag, dt))
+    return out

@@ -401,3 +401,308 @@ def test_wgrad64_is_the_filter_gradient_of_a_strided_padded_conv():
         y = F.conv2d(F.pad(x.permute(0, 3, 1, 2), (pad[1], pr, pad[0], pb)), w.permute(3, 2, 0, 1), stride=s).permute(0, 2, 3, 1)
         (y * dz).sum().backward()
         assert float((X.wgrad64(x, dz, k, s, pad) - w.grad).abs().max()) < 1e-12
+
+
+# =====================================================================================================================
+# The step-tail references and bounds (losses, norm, optimizers, finalisation, batch-statistics BatchNorm): each accepts a plain
+# fp32 restatement of the operation and rejects the planted faults below (>= 1 % of elements outside the bound; the dropped tail
+# and the dropped sweep need one).
+XENT_K = [1, 63, 64, 65, 257, 512, 4095, 4096, 4097, 13824, 16383, 16384, 16385, 32768]
+
+
+def flush16(v, t):
+    """16-bit store that flushes subnormal results to zero."""
+    r = rne(v, t)
+    return torch.where(r.abs() < 2.0 ** X._EMIN[t], torch.zeros_like(r), r)
+
+
+def test_xent_restatement_inside_bound_on_every_probe_input():
+    """exp as exp2(x * 1.442695) + pairwise fp32 sums stays inside softmax_xent_bounds on every input of the GPU probe; the largest
+    ratios (printed) is recorded in the pull request."""
+    worst = {"loss": 0.0, "row": 0.0, "dz fp32": 0.0, "dz bf16": 0.0, "dz fp16": 0.0}
+    for K in XENT_K:
+        for Bn in (1, 32):
+            for psum in (1.0, 0.6):
+                z, p = X.xent_inputs(Bn, K, psum)
+                for relu in (0, 1):
+                    if relu and K >= 63:
+                        assert float((z == 0).sum()) / z.numel() >= 0.01
+                    for dt in (0, 1, 2):
+                        ref = X.softmax_xent64(z, p, 1.0, relu)
+                        bnd = X.softmax_xent_bounds(z, p, 1.0, relu, dt)
+                        got = X.softmax_xent32(z, p, 1.0, relu, dt)
+                        for name, g, r, b in zip(("loss", "row", "dz " + ("fp32", "bf16", "fp16")[dt]), got, ref, bnd):
+                            worst[name] = max(worst[name], X.assert_within(g, r, b, "%s K=%d B=%d" % (name, K, Bn)))
+                    if K >= 63 and not relu:
+                        assert float((ref[2] != 0).sum()) / ref[2].numel() >= 0.25
+    print("softmax_xent restatement, largest ratio to the bound:", worst)
+    assert max(worst.values()) <= 1.0
+
+
+@pytest.mark.parametrize("dt", [1, 2])
+def test_xent_faults_rejected(dt):
+    t = X.tdtype(dt)
+    Bn, K = 32, 13824
+    z, p = X.xent_inputs(Bn, K, 0.6)
+    for relu in (0, 1):
+        _, _, ref = X.softmax_xent64(z, p, 1.0, relu)
+        bnd = X.softmax_xent_bounds(z, p, 1.0, relu, dt)[2]
+        f32 = X.softmax_xent32(z, p, 1.0, relu, 0)[2].double()
+        assert X.violations(rne(f32, t), ref, bnd) == 0
+        # softmax * sum(p) - p (the gradient of the row loss with softmax scaled by the labels' mass)
+        soft = torch.softmax(z.double(), 1)
+        wrong = (soft * 0.6 - p.double()) / Bn
+        if relu:
+            wrong = wrong * (z > 0)
+        assert X.violations(rne(wrong, t), ref, bnd) >= 0.01
+        assert X.violations(trunc(f32, t), ref, bnd) >= 0.01                       # truncating store
+        if dt == 2:
+            assert X.violations(flush16(f32, t), ref, bnd) >= 0.01                 # subnormals flushed
+            assert X.violations(rne(rne(f32, torch.bfloat16), t), ref, bnd) >= 0.01   # rounded to bf16, then to fp16
+    # ReLU mask taken as z >= 0: the exact zeros (half of the logits) keep their gradient
+    _, _, ref = X.softmax_xent64(z, p, 1.0, 1)
+    bnd = X.softmax_xent_bounds(z, p, 1.0, 1, dt)[2]
+    unmasked = X.softmax_xent32(z, p, 1.0, 0, dt)[2]
+    assert X.violations(unmasked, ref, bnd) >= 0.01
+    # the row loss with the labels' mass dropped (lse - sum p z)
+    _, row, _ = X.softmax_xent64(z, p, 1.0, 0)
+    wrong_row = torch.logsumexp(z.double(), 1) - (p.double() * z.double()).sum(1)
+    assert X.violations(wrong_row.float(), row, X.softmax_xent_bounds(z, p, 1.0, 0, dt)[1]) >= 0.5
+
+
+def test_fp16_subnormal_share_of_the_benchmark_softmax_gradient():
+    """At B = 32, K = 24^3 nearly every nonzero fp16 gradient is subnormal (the numbers of the issue)."""
+    z, p = X.xent_inputs(32, 13824, 1.0)
+    _, _, ref = X.softmax_xent64(z, p, 1.0, 0)
+    nz = ref != 0
+    sub = nz & (ref.abs() < 2.0 ** -14)
+    assert float(sub.sum()) / float(nz.sum()) > 0.9
+    assert float((rne(ref, torch.float16)[nz] == 0).sum()) / float(nz.sum()) < 0.05
+
+
+def _head(Bn, D, ld, seed, tiny=0):
+    g = torch.Generator().manual_seed(seed)
+    gt = torch.randn(Bn, D, generator=g)
+    x = torch.randn(Bn, ld, generator=g)
+    for i in range(tiny):
+        x[3 * i + 1] *= 1e-7                          # |x|^2 <= 1e-12: the clamp branch, with a nonzero dot
+    return gt, x
+
+
+@pytest.mark.parametrize("dt", [0, 1, 2])
+def test_regression_losses_accept_fp32_and_reject_faults(dt):
+    t = X.tdtype(dt)
+    for Bn, D in ((1, 3), (5, 3), (32, 4), (300, 3)):
+        gt, x = _head(Bn, D, 8, Bn + D)
+        f = lambda v: v.float()
+        # rel_l2 / mse restated in fp32
+        e = gt - x[:, :D]
+        nd, ng = X.pairwise_sum32((e * e).reshape(-1)).sqrt(), X.pairwise_sum32((gt * gt).reshape(-1)).sqrt()
+        loss, g, _ = X.rel_l2_64(gt, x, 0.7)
+        bl, bg, _ = X.rel_l2_bounds(gt, x, 0.7, dt)
+        got = F.pad(f(torch.tensor(-0.7)) / (nd * ng) * e, (0, 8 - D)).to(t)
+        assert X.violations(got, g, bg) == 0 and X.violations(f(torch.tensor(0.7)) * nd / ng, loss, bl) == 0
+        assert float((g[:, :D] != 0).sum()) / g[:, :D].numel() >= 0.25
+        if dt and Bn == 300:                          # a truncating 16-bit store
+            assert X.violations(trunc(F.pad(f(torch.tensor(-0.7)) / (nd * ng) * e, (0, 8 - D)).double(), t), g, bg) >= 0.01
+        loss, g = X.mse64(gt, x, 0.7)
+        bl, bg = X.mse_bounds(gt, x, 0.7, dt)
+        e = x[:, :D] - gt
+        got = F.pad(torch.tensor(2 * 0.7, dtype=torch.float32) / (Bn * D) * e, (0, 8 - D)).to(t)
+        assert X.violations(got, g, bg) == 0
+        assert X.violations(torch.tensor(0.7, dtype=torch.float32) * X.pairwise_sum32((e * e).reshape(-1)) / (Bn * D), loss, bl) == 0
+        assert X.violations((got.double() * 1.01).to(t), g, bg) >= 0.25 * D / 8
+
+
+@pytest.mark.parametrize("normalize", [0, 1])
+def test_absdot_reference_and_clamp_branch(normalize):
+    Bn, D, ld = 300, 4, 8
+    gt, x = _head(Bn, D, ld, 7, tiny=10)
+    gt[0], x[0] = 0, 0
+    gt[0, 0], x[0, 1] = 1, 1                          # dot == 0 exactly: zero gradient, loss term 1
+    x[2] = 0                                          # a row of zeros
+    q, loss, dx, dot, _ = X.absdot64(gt, x, 0.9, normalize)
+    assert float(dot[0]) == 0 and float(dx[0].abs().sum()) == 0 and float(dx[2].abs().sum()) == 0
+    assert float((dx[:, D:] != 0).sum()) == 0
+    # against autograd of the definition (rows away from the clamp)
+    xr = x.double().clone().requires_grad_(True)
+    xv = xr[:, :D]
+    qq = xv * torch.rsqrt((xv * xv).sum(1, keepdim=True).clamp_min(X.ABSDOT_CLAMP)) if normalize else xv
+    (X.f32v(0.9) * (1 - (gt.double() * qq).sum(1).abs()).mean()).backward()
+    big = (x[:, :D].double() ** 2).sum(1) > 1e-6
+    assert float((xr.grad[big] - dx[big]).abs().max()) <= 1e-12 * float(dx.abs().max())
+    for dt in (0, 1, 2):
+        bq, bl, bdx = X.absdot_bounds(gt, x, 0.9, normalize, dt)
+        # fp32 restatement
+        xv = x[:, :D]
+        ss = (xv * xv).sum(1, keepdim=True)
+        rinv = torch.rsqrt(ss.clamp_min(1e-12)) if normalize else torch.ones_like(ss)
+        q32 = xv * rinv
+        d32 = (gt * q32).sum(1, keepdim=True)
+        dq = -torch.sign(d32) * torch.tensor(np.float32(0.9) / np.float32(Bn)) * gt
+        proj = q32 * (q32 * dq).sum(1, keepdim=True)
+        good = rinv * (dq - torch.where(ss > 1e-12, proj, torch.zeros_like(proj))) if normalize else dq
+        assert X.violations(q32, q, bq) == 0
+        assert X.violations(F.pad(good, (0, ld - D)).to(X.tdtype(dt)), dx, bdx) == 0
+        assert X.violations(torch.tensor(np.float32(0.9)) * (1 - d32.abs()).mean(), loss, bl) == 0
+        if normalize:                                 # without the clamp branch: the 10 tiny rows are wrong (10 x 4 of 300 x 8 values)
+            nocl = rinv * (dq - proj)
+            assert X.violations(F.pad(nocl, (0, ld - D)).to(X.tdtype(dt)), dx, bdx) >= 0.01
+
+
+import numpy as np  # noqa: E402
+
+
+def test_adam_lr_t_measured():
+    """The measured error behind ADAM_LRT_REL (4 x the largest deviation of the float32 restatement of lr_t)."""
+    worst = max(abs(float(X.adam_lr_t32(1e-3, 0.9, 0.999, t)) - X.adam_lr_t64(1e-3, 0.9, 0.999, t)) / X.adam_lr_t64(1e-3, 0.9, 0.999, t)
+                for t in (1, 2, 3))
+    assert worst <= X.ADAM_LRT_MEASURED and X.ADAM_LRT_REL == 4 * X.ADAM_LRT_MEASURED and worst >= 0.5 * X.ADAM_LRT_MEASURED
+
+
+@pytest.mark.parametrize("case", ["unclipped", "clipped", "noclip", "mom0"])
+def test_sgd_reference_accepts_fp32_and_rejects_faults(case):
+    n = 1_000_003
+    w, g, v, lr, mom, clip = X.sgd_data(n, case)
+    nsq = float(X.pairwise_sum32(g * g))
+    assert abs(nsq - float((g.double() ** 2).sum())) <= float(X.tree_sum_bound((g.double() ** 2).sum(), 21))
+    w64, v64, bw, bv, ratio = X.sgd64(w, g, v, lr, mom, clip, nsq)
+    assert ratio >= 0.1, ratio                                              # a wrong step shows in v
+    norm = nsq ** 0.5
+    assert clip == 0 or abs(norm - clip) > 0.01 * clip
+    w32, v32 = X.sgd32(w, g, v, lr, mom, clip, nsq)
+    assert X.violations(w32, w64, bw) == 0 and X.violations(v32, v64, bv) == 0
+    assert float((v64 != 0).sum()) / n >= 0.25
+    wf, vf = X.sgd32(w, g, v, lr, mom, clip, nsq, lr_factor=1.01)           # lr wrong by 1 %
+    assert X.violations(vf, v64, bv) >= 0.01 and X.violations(wf, w64, bw) >= 0.01
+    wf, vf = X.sgd32(w, g, v, lr, mom, clip, nsq, keep_from=n - n % 4, keep_to=n)      # the last n % 4 elements not updated
+    assert X.violations(vf, v64, bv) > 0 and X.violations(wf, w64, bw) > 0
+    wf, vf = X.sgd32(w, g, v, lr, mom, clip, nsq, keep_from=n // 2, keep_to=n)         # elements past the first sweep not updated
+    assert X.violations(vf, v64, bv) > 0.4 and X.violations(wf, w64, bw) > 0.4
+
+
+def test_adam_reference_accepts_fp32_and_rejects_faults():
+    n = 10007
+    g_ = torch.Generator().manual_seed(3)
+    w = torch.randn(n, generator=g_)
+    m, v, vh = torch.zeros(n), torch.zeros(n), torch.zeros(n)
+    f = np.float32
+    for t in (1, 2, 3):
+        hyper = torch.tensor([1e-3, 0.9, 0.999, 1e-7, 5.0, float(t), float(f(1) - f(0.9)), float(f(1) - f(0.999))], dtype=torch.float32)
+        g = torch.randn(n, generator=g_) * (3.0 if t == 2 else 0.01)        # step 2 is clipped
+        nsq = float(X.pairwise_sum32(g * g))
+        assert (nsq ** 0.5 >= 5.0) == (t == 2)
+        ref = X.adam64(w, g, m, v, vh, hyper, nsq)
+        got = X.adam32(w, g, m, v, vh, hyper, nsq)
+        for name, val in zip(("w", "m", "v", "vhat"), got):
+            assert X.violations(val, *ref[name]) == 0, (t, name)
+        if t == 2:                                                          # v updated from the unclipped gradient
+            bad = X.adam32(w, g, m, v, vh, hyper, nsq, v_from_unclipped=True)
+            assert X.violations(bad[2], *ref["v"]) >= 0.01 and X.violations(bad[0], *ref["w"]) >= 0.01
+            h2 = hyper.clone(); h2[0] *= 1.01                               # lr wrong by 1 %, clipped step
+            assert X.violations(X.adam32(w, g, m, v, vh, h2, nsq)[0], *ref["w"]) >= 0.01
+        w, m, v, vh = got
+
+
+@pytest.mark.parametrize("bias,bn", [(True, True), (False, True), (True, False), (False, False)])
+def test_finalize_closed_form_equals_autograd(bias, bn, monkeypatch):
+    """finalize64 == float64 autograd through oracle.graph_ref.conv2d + frozen batchnorm + the L2 term (1e-12 relative); eps is the
+    fp32 value the entry point receives, in both."""
+    from oracle import graph_ref as G
+    monkeypatch.setattr(G, "BN_EPS", X.f32v(G.BN_EPS))
+    torch.manual_seed(11)
+    Bn, Hh, Ww, Ci, Nn = 2, 6, 5, 8, 12
+    d = torch.float64
+    x = torch.randn(Bn, Ci, Hh, Ww, dtype=d)
+    P = {"kernel": torch.randn(3, 3, Ci, Nn, dtype=d).requires_grad_(True)}
+    if bias:
+        P["bias"] = torch.randn(Nn, dtype=d).requires_grad_(True)
+    Q = {"gamma": (torch.rand(Nn, dtype=d) + 0.5).requires_grad_(True), "beta": torch.randn(Nn, dtype=d).requires_grad_(True),
+         "moving_mean": torch.randn(Nn, dtype=d), "moving_variance": torch.rand(Nn, dtype=d) + 0.5}
+    zc = G.conv2d(x, P, 1, "same")
+    z = G.batchnorm(zc, Q, False) if bn else zc
+    dz = torch.randn_like(z)
+    wd = X.f32v(1e-2)
+    reg = wd * (P["kernel"] ** 2).sum() / P["kernel"].numel() + (wd * (P["bias"] ** 2).sum() / Nn if bias else 0.0)
+    ((z * dz).sum() + reg).backward()
+    xp = F.pad(x, (1, 1, 1, 1))
+    dw_raw = torch.stack([torch.stack([torch.einsum("bchw,bnhw->cn", xp[:, :, ky:ky + Hh, kx:kx + Ww], dz) for kx in range(3)]) for ky in range(3)])
+    K = 9 * Ci
+    ref = X.finalize64(dw_raw.reshape(K, Nn), dz.sum(dim=(0, 2, 3)), P["kernel"].detach().reshape(K, Nn), P["bias"].detach() if bias else None,
+                       Q["gamma"].detach() if bn else None, Q["moving_mean"], Q["moving_variance"], X.f32v(G.BN_EPS), 1e-2)
+    want = {"gw": P["kernel"].grad.reshape(K, Nn)}
+    if bias:
+        want["gb"] = P["bias"].grad
+    if bn:
+        want["ggamma"], want["gbeta"] = Q["gamma"].grad, Q["beta"].grad
+    assert set(ref) == set(want)
+    for k_, wv in want.items():
+        assert float((ref[k_][0] - wv).abs().max()) <= 1e-12 * float(wv.abs().max()), k_
+
+
+@pytest.mark.parametrize("KNl", [(144, 24, 24), (2048, 3, 8), (4608, 512, 512)])
+def test_finalize_bounds_accept_fp32_and_reject_missing_term(KNl):
+    K, Nn, ldn = KNl
+    torch.manual_seed(K + Nn)
+    dw, cs, Wt = torch.randn(K, Nn), torch.randn(Nn) * 5, torch.randn(K, Nn) / K ** 0.5
+    b, gamma, mean, var = torch.randn(Nn), torch.rand(Nn) + 0.5, torch.randn(Nn), torch.rand(Nn) + 0.5
+    ks = max(min(-(-512 // -(-Nn // 64)), 32, max(K // 128, 1)), 1)
+    ref = X.finalize64(dw, cs, Wt, b, gamma, mean, var, 1e-3, 1e-2)
+    bnd = X.finalize_bounds(ref, K, Nn, ldn, ks)
+    got = X.finalize32(dw, cs, Wt, b, gamma, mean, var, 1e-3, 1e-2)
+    for k_ in ref:
+        assert X.violations(got[k_], ref[k_][0], bnd[k_]) == 0, k_
+        assert float((ref[k_][0] != 0).sum()) / ref[k_][0].numel() >= 0.25
+    bad = X.finalize32(dw, cs, Wt, b, gamma, mean, var, 1e-3, 1e-2, gamma_term=False)      # ggamma without (b - mean) colsum
+    assert X.violations(bad["ggamma"], ref["ggamma"][0], bnd["ggamma"]) >= 0.9
+    # a helper broken the same way is caught by the correct restatement
+    broken = X.finalize64(dw, cs, Wt, b, gamma, mean, var, 1e-3, 1e-2, gamma_term=False)
+    assert X.violations(got["ggamma"], broken["ggamma"][0], bnd["ggamma"]) >= 0.9
+
+
+def _bn_case(M, Nn, dt, seed=0):
+    g = torch.Generator().manual_seed(seed + M + Nn)
+    t = X.tdtype(dt)
+    z = torch.randn(M, Nn, generator=g) * 2 + torch.randn(Nn, generator=g)
+    z[:, 0] = 0.75                                                          # a constant channel: the variance clamps at 0
+    z[:, 1] = torch.randn(M, generator=g) + 1000.0                          # mean 1000, unit spread
+    return (z.to(t), torch.randn(M, Nn, generator=g).to(t), torch.rand(Nn, generator=g) + 0.5, torch.randn(Nn, generator=g),
+            torch.randn(Nn, generator=g), torch.rand(Nn, generator=g) + 0.5, torch.randn(M, Nn, generator=g).to(t))
+
+
+@pytest.mark.parametrize("dt", [0, 1, 2])
+def test_bn_references_accept_fp32_and_reject_faults(dt):
+    M, Nn, eps, mom = 2048, 16, 1e-3, 0.99
+    t = X.tdtype(dt)
+    z, res, gamma, beta, mm, mv, gy = _bn_case(M, Nn, dt)
+    zf = z.float()
+    st = X.bn_stats64(z, mm, mv, mom, eps)
+    mean32, var32 = zf.double().mean(0).float(), zf.double().var(0, unbiased=False).float()
+    assert X.violations(mean32, *st["mean"]) == 0 and X.violations(var32, *st["var"]) == 0
+    f = torch.float32
+    momt, one = torch.tensor(mom, dtype=f), torch.tensor(1.0, dtype=f)
+    corr = M / (M - (1 + X.f32v(eps)))
+    assert X.violations(mm * momt + mean32 * (one - momt), *st["mmean"]) == 0
+    assert X.violations(mv * momt + (zf.double().var(0, unbiased=False) * corr).float() * (one - momt), *st["mvar"]) == 0
+    # the moving variance without the M / (M - (1 + eps)) factor: all but the constant channel
+    assert X.violations(mv * momt + var32 * (one - momt), *st["mvar"]) >= 0.9
+    rstd = torch.rsqrt(var32 + torch.tensor(eps, dtype=f))
+    for relu in (0, 1):
+        y64, by = X.bn_apply64(z, mean32, var32, gamma, beta, eps, res, relu, dt)
+        y32 = (zf - mean32) * (gamma * rstd) + beta + res.float()
+        y32 = torch.relu(y32) if relu else y32
+        assert X.violations(y32.to(t), y64, by) == 0
+        assert float((y64 != 0).sum()) / y64.numel() >= 0.25
+        bad = y32.clone(); bad[:, 5] *= 1.005                               # one channel scaled by 1.005
+        assert X.violations(bad.to(t), y64, by) >= (0.01 if not relu else 0.005)
+        assert X.violations(trunc(y32, t), y64, by) >= (0.01 if dt else 0)
+    g = gy.float()
+    xh = (zf - mean32) * rstd
+    db32, dg32 = g.double().sum(0).float(), (g * xh).double().sum(0).float()
+    bw = X.bn_backward64(gy, z, mean32, var32, gamma, eps, dt, db32, dg32)
+    assert X.violations(db32, *bw["dbeta"]) == 0 and X.violations(dg32, *bw["dgamma"]) == 0
+    invM = torch.tensor(1.0 / M, dtype=f)
+    dz32 = (gamma * rstd) * (g - db32 * invM - xh * dg32 * invM)
+    assert X.violations(dz32.to(t), *bw["dz"]) == 0
+    bad = dz32.clone(); bad[:, 5] *= 1.005
+    assert X.violations(bad.to(t), *bw["dz"]) >= 0.01

@@ -636,7 +636,8 @@ def test_regression_losses():
 
 @pytest.mark.parametrize("gscale", [0.01, 30.0])
 def test_sgd_momentum_global_clipnorm(gscale):
-    """keras SGD(momentum, clipnorm) with the GLOBAL norm [A10] vs oracle.sgd_step."""
+    """keras SGD(momentum, clipnorm) with the GLOBAL norm [A10] vs oracle.sgd_step.  (Normwise gates: a wrong step size can pass them in
+    the unclipped case; tests/test_step_tail_exact_gpu.py::test_sgd_momentum_clip_elementwise checks v and w element by element.)"""
     from oracle import graph_ref as G
     hip = _hip()
     torch.manual_seed(1)

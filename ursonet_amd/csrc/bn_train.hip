@@ -251,7 +251,9 @@ static int bn_check(const char* who, int M, int N, int dt) {
 static int bn_col_groups(int N, int dt) { const int VE = 16 / (int)dt_size(dt); return ceil_div(N / VE, BN_RED_CG); }
 // row slabs of a reduction launch: BN_RED_BLOCKS blocks over the column groups, and at least one unrolled pass of rows per thread
 static int bn_red_blocks(int M, int N, int dt) {
-    const int VE = 16 / (int)dt_size(dt), nv = N / VE, cg = nv < BN_RED_CG ? nv : BN_RED_CG, rpp = 256 / cg;
+    const int VE = 16 / (int)dt_size(dt), nv = N / VE;
+    if (nv < 1) return 1;                                 // N below one vector of this type (urso_bn_ws_bytes sizes for both widths; the launches refuse it)
+    const int cg = nv < BN_RED_CG ? nv : BN_RED_CG, rpp = 256 / cg;
     int nb = BN_RED_BLOCKS / bn_col_groups(N, dt);
     const int cap = M / (rpp * BN_RED_UNROLL);
     if (nb > cap) nb = cap;
