@@ -682,6 +682,26 @@ int urso_sim2real_op(int B, int H, int W, const uint8_t* src_d, uint8_t* dst_d, 
 int urso_pad_images_u8(int B, int H, int W, int C, int OH, int OW, int top, int left, const uint8_t* src_d, uint8_t* dst_d, void* stream);
 
 /*
+ * utils.resize_image (utils.py:398-511; modes square / pad64) of a uint8 batch [B,H,W,C] of one frame size on the device: every frame is
+ * rescaled to NH x NW with the arithmetic of skimage.transform.resize(order=1, mode='constant', preserve_range=True) -- Gaussian
+ * anti-aliasing of each SHRINKING axis (rows first, then columns; zero boundary), then bilinear interpolation with zeros outside -- and
+ * written at (top, left) of dst [B,OH,OW,C], zeros elsewhere.  The result has the BYTES of ursonet_amd/utils.py::resize_image: the
+ * same IEEE float64 multiplies and adds in the same order, no fused multiply-add.  The host computes everything else and passes it as
+ * device tables (ursonet_amd/utils.py::resize_tables):
+ *   ky_d / kx_d   fp64 [2 ry + 1] / [2 rx + 1] normalised Gaussian taps of the row / column pass; NULL = that axis does not shrink and is
+ *                 not smoothed (its radius is then ignored).  acc = 0; acc += k[i] * src[p - r + i] in tap order.
+ *   y0_d, fy_d    int32 / fp64 [NH]: floor(ys) and ys - floor(ys) of ys = (j + 0.5) H / NH - 0.5; x0_d, fx_d [NW] likewise.
+ *   trunc_passes  1: every smoothing pass is stored back truncated to uint8 (scikit-image <= 0.18 on integer frames, URSO_RESIZE_COMPAT
+ *                 = 0.18, the default); 0: intermediates stay fp64 (scikit-image >= 0.19).
+ * out = trunc((v00 (1-fx) + v01 fx)(1-fy) + (v10 (1-fx) + v11 fx) fy), a neighbour outside the frame contributing 0.  URSO_EINVAL: null
+ * pointer, non-positive size, window outside the output, radius < 1 with a tap table, src == dst, or a shrink so strong that one output
+ * pixel's source patch exceeds 64 KiB of LDS.  With NH x NW = H x W and no taps this is urso_pad_images_u8.
+ */
+int urso_resize_images_u8(int B, int H, int W, int C, int NH, int NW, int OH, int OW, int top, int left,
+                          const double* ky_d, int ry, const double* kx_d, int rx, const int32_t* y0_d, const double* fy_d,
+                          const int32_t* x0_d, const double* fx_d, int trunc_passes, const uint8_t* src_d, uint8_t* dst_d, void* stream);
+
+/*
  * Opt-in launch profiler: when enabled every urso_* launch is bracketed by HIP events on
  * its stream.  urso_prof_collect() synchronises and returns per-record milliseconds.
  */

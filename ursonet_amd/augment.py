@@ -11,6 +11,7 @@ re-encode run as HIP kernels (urso_warp_perspective, urso_encode_ori) on whole b
 in HBM; the 3x3 / quaternion algebra per sample stays on the host in float64.
 """
 import math
+import threading
 
 import numpy as np
 
@@ -227,3 +228,60 @@ def sim2real_batch(images, draw=None, rng=np.random):
         hip.sim2real_op(B, H, W, a, b, torch.as_tensor(ops).cuda(), torch.as_tensor(par).cuda(), seed_d, drop_d, stride)
         a, b = b, a
     return a
+
+
+# --------------------------------------------------------------------------- resize / pad (utils.py:398-511)
+_RESIZE_TABLES = {}                          # (h, w, nh, nw, device) -> device tables of utils.resize_tables: a feeder asks for the same geometry every batch
+_RESIZE_TABLES_LOCK = threading.Lock()       # feeder producer threads and the main thread (detect) share the cache
+_RESIZE_TABLES_MAX = 64
+
+
+def _resize_device_tables(h, w, nh, nw, device):
+    import torch
+    from . import utils
+    key = (h, w, nh, nw, str(device))
+    with _RESIZE_TABLES_LOCK:
+        if key in _RESIZE_TABLES:
+            _RESIZE_TABLES[key] = _RESIZE_TABLES.pop(key)      # most recently used last
+            return _RESIZE_TABLES[key]
+        t = utils.resize_tables(h, w, nh, nw)
+        up = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a)).to(device)
+        if len(_RESIZE_TABLES) >= _RESIZE_TABLES_MAX:
+            # the least recently used entry goes; a kernel launched on some thread's stream may still read its tables, so they are freed
+            # only after the device has drained (rare: one or two geometries per run is the normal case)
+            torch.cuda.synchronize(device)
+            _RESIZE_TABLES.pop(next(iter(_RESIZE_TABLES)))
+        _RESIZE_TABLES[key] = {"ky": up(t["taps"][0]), "kx": up(t["taps"][1]), "ry": 0 if t["taps"][0] is None else len(t["taps"][0]) // 2,
+                               "rx": 0 if t["taps"][1] is None else len(t["taps"][1]) // 2,
+                               "y0": up(t["y0"]), "fy": up(t["fy"]), "x0": up(t["x0"]), "fx": up(t["fx"])}
+        return _RESIZE_TABLES[key]
+
+
+def resize_images(images, min_dim=None, max_dim=None, min_scale=None, mode="square", out=None):
+    """utils.resize_image for a uint8 batch [B,H,W,C] of one frame size (array or device tensor), on the GPU and with the host function's
+    BYTES (urso_resize_images_u8; scale 1: urso_pad_images_u8): -> (uint8 CUDA tensor [B,OH,OW,C], window, scale, padding), the last three
+    as utils.resize_image returns them for one frame.  Modes 'square' and 'pad64'; 'none', 'crop' (which draws from `random`) and
+    non-uint8 input raise ValueError -- callers keep the host path for those.  `out`: a uint8 CUDA tensor of the result's shape to write into."""
+    from . import utils
+    if mode not in ("square", "pad64"):
+        raise ValueError("resize_images: mode %r stays on the host (utils.resize_image)" % (mode,))
+    dtype, shape = getattr(images, "dtype", None), tuple(getattr(images, "shape", ()))
+    if str(dtype).replace("torch.", "") != "uint8" or len(shape) != 4:
+        raise ValueError("resize_images: uint8 [B,H,W,C] frames expected, not %s %s" % (dtype, shape))
+    import torch
+    from . import hip
+    B, H, W, C = shape
+    scale, (nh, nw), pads, window = utils.resize_geometry(H, W, min_dim, max_dim, min_scale, mode)
+    padding = [pads[0], pads[1], (0, 0)]
+    OH, OW = nh + sum(pads[0]), nw + sum(pads[1])
+    x = torch.as_tensor(images).cuda().contiguous()
+    if out is None:
+        out = torch.empty((B, OH, OW, C), dtype=torch.uint8, device=x.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (B, OH, OW, C) and out.is_contiguous()
+    if scale == 1:
+        hip.pad_images_u8(B, H, W, C, OH, OW, window[0], window[1], x, out)
+    else:
+        t = _resize_device_tables(H, W, nh, nw, x.device)
+        hip.resize_images_u8(B, H, W, C, nh, nw, OH, OW, window[0], window[1], t["ky"], t["ry"], t["kx"], t["rx"], t["y0"], t["fy"], t["x0"],
+                             t["fx"], 1 if utils._resize_compat() == "0.18" else 0, x, out)
+    return out, window, scale, padding

@@ -54,6 +54,9 @@ class Config(object):
     LOSS_WEIGHTS = {"loc_loss": 1., "ori_loss": 1., "k2_loss": 1., "k3_loss": 1.}
     TRAIN_BN = False
     GRADIENT_CLIP_NORM = 5.0
+    # Not a reference field: True = uint8 RGB frames of one size are rescaled and padded on the GPU (augment.resize_images, byte-exact to
+    # utils.resize_image) by the feeders, detect() and evaluate(); False = the host path (utils.resize_image), call for call as before.
+    DEVICE_RESIZE = False
 
     def update(self):
         """Derived fields (config.py:151-166)."""

@@ -6,10 +6,16 @@ images through a queue.  At ~2,800 images/s per GPU that design cannot keep up (
 PCIe alone is 2.3 ms of an 11.4 ms step).  Here:
   * workers (threads: image decode / synthesis and NumPy release the GIL) only produce the RAW sample -- uint8 frame + pose;
   * everything per-pixel runs batched on the GPU: sim2real stages, camera / in-plane rotation warps (one urso_warp_perspective for
-    the minibatch) and target re-encoding (urso_encode_ori); resize / zero padding stay on the host (finish_sample:
-    utils.resize_image); mean subtraction + cast are the engine's first kernel (urso_mold_images reads uint8);
+    the minibatch) and target re-encoding (urso_encode_ori); mean subtraction + cast are the engine's first kernel (urso_mold_images
+    reads uint8);
+  * resize / zero padding (utils.resize_image) run where Config.DEVICE_RESIZE says.  False (default): on the host, frame by frame in the
+    producer thread (finish_sample) -- float64 NumPy over the native frame, ~0.3 s per 960 x 1280 frame, by far the slowest stage as soon
+    as a frame is really rescaled.  True: a batch of uint8 RGB frames of one size (modes square / pad64) goes up RAW from pinned memory, is
+    augmented where it lies and finished by urso_resize_images_u8 (augment.resize_images: the host function's bytes); the augmented frames
+    are no longer copied back.  Mixed sizes, other dtypes, 'crop' / 'none' and the molded generator format keep the host path;
   * uint8 frames go host -> device from PINNED memory on a side stream into a double buffer while the previous step computes:
-    31 MB instead of 126 MB per step, off the critical path.
+    31 MB instead of 126 MB per step, off the critical path (DEVICE_RESIZE: the raw frames, 118 MB for 32 URSO frames, on the
+    producer's own stream; the finished batch reaches the double buffer by a device-to-device copy).
 `data_generator` keeps the reference's signature and yield format on top of the same pieces.
 """
 import logging
@@ -52,19 +58,26 @@ def load_sample(dataset, config, image_id):
 def _hip_section():
     """The lock that keeps this thread out of HIP while another thread captures a hipGraph (hip.capture_lock; Engine.capture holds it).  Taken
     around the batched augmentation launches with their device-to-host copies and around pin_memory only: disk loads, the CPU draws and the
-    resize / padding of a batch run unlocked, so a capture waits for a kernel's worth of work, not for a batch's preparation."""
+    host resize / padding of a batch run unlocked, so a capture waits for a kernel's worth of work, not for a batch's preparation.  With
+    Config.DEVICE_RESIZE (RawUploader) the host copy of the raw frames into the reused pinned buffer runs unlocked as well; the lock is held
+    while the batch's upload, augmentation and resize kernels are ENQUEUED (asynchronous launches plus the host algebra of the warps), not
+    while they run."""
     from . import hip
     return hip.capture_lock
 
 
-def augment_samples(samples, dataset, config):
+def augment_samples(samples, dataset, config, frames=None):
     """The augmentation third (net.py:390-438) for a LIST of samples, in place.  NumPy's GLOBAL generator is consumed exactly as the
     reference consumes it, sample by sample: the sim2real dice (net.py:395), then that sample's rotation dice (net.py:415) and angles
     (utils.py:33 / :62) -- the imgaug stage parameters come from a separate generator, as imgaug's do, and only for the samples the dice
     select.  The samples themselves are loaded ahead of the draws and the pixel work is batched (one sim2real pass set and one warp
-    launch for all samples of the list that need it), which changes no draw.  Images come back as uint8 arrays."""
+    launch for all samples of the list that need it), which changes no draw.  Images come back as uint8 arrays.
+
+    frames (DEVICE_RESIZE): a uint8 device tensor [n,H,W,3] that holds the samples' frames, all of one size.  The pixel work then reads and
+    writes device memory only -- same draws, same kernels, no copy back -- the samples' `image` fields are left alone, and the tensor of
+    the augmented frames is RETURNED instead of the list."""
     if not samples:
-        return samples
+        return samples if frames is None else frames
     from . import augment
     rot = bool(config.ROT_AUG or config.ROT_IMAGE_AUG)
     if rot:
@@ -94,9 +107,13 @@ def augment_samples(samples, dataset, config):
                       "par": np.concatenate([draws[i]["par"] for i in g]), "seeds": np.concatenate([draws[i]["seeds"] for i in g]),
                       "masks": [draws[i]["masks"][0] for i in g]}
             with _hip_section():
-                out = augment.sim2real_batch(np.stack([samples[i].image for i in g]), draw=merged).cpu().numpy()
-            for k, i in enumerate(g):
-                samples[i].image = out[k]
+                if frames is not None:
+                    frames = augment.sim2real_batch(frames, draw=merged)
+                else:
+                    out = augment.sim2real_batch(np.stack([samples[i].image for i in g]), draw=merged).cpu().numpy()
+            if frames is None:
+                for k, i in enumerate(g):
+                    samples[i].image = out[k]
         ids = [i for i in g if i in warp_ids]
         if ids:
             quats = []
@@ -105,20 +122,80 @@ def augment_samples(samples, dataset, config):
                     samples[i].ori = dataset.load_quaternion(samples[i].image_id)   # classification targets are re-encoded from the rotated pose
                 quats.append(samples[i].ori)
             with _hip_section():
-                warped, t_new, q_new = augment.rotate_cam_batch(np.stack([samples[i].image for i in ids]), np.stack([samples[i].loc for i in ids]),
+                if frames is not None:
+                    import torch
+                    sel = torch.as_tensor(ids, dtype=torch.int64, device=frames.device)
+                    src = frames.index_select(0, sel)
+                else:
+                    src = np.stack([samples[i].image for i in ids])
+                warped, t_new, q_new = augment.rotate_cam_batch(src, np.stack([samples[i].loc for i in ids]),
                                                                 np.stack(quats), dataset.camera.K, pyr[ids])
-                warped = warped.cpu().numpy()
+                if frames is not None:
+                    frames.index_copy_(0, sel, warped)
+                else:
+                    warped = warped.cpu().numpy()
                 enc = None
                 if not (config.REGRESS_ORI or config.REGRESS_KEYPOINTS):
                     enc = augment.encode_orientations(q_new, dataset.ori_histogram_map, dataset.ori_output_mask, config.BETA).cpu().numpy()
             for k, i in enumerate(ids):
                 s = samples[i]
-                s.image, s.loc, s.ori = warped[k], t_new[k], q_new[k]
+                s.loc, s.ori = t_new[k], q_new[k]
+                if frames is None:
+                    s.image = warped[k]
                 if config.REGRESS_KEYPOINTS:
                     s.k1, s.k2 = augment.encode_as_keypoints(s.ori, s.loc)      # net.py:424, 433
                 elif enc is not None:
                     s.ori = enc[k]
-    return samples
+    return samples if frames is None else frames
+
+
+def device_resize_applies(images, config):
+    """Config.DEVICE_RESIZE and a batch augment.resize_images takes: uint8 RGB frames of one size, mode square / pad64."""
+    if not getattr(config, "DEVICE_RESIZE", False) or config.IMAGE_RESIZE_MODE not in ("square", "pad64") or len(images) == 0:
+        return False
+    shape = getattr(images[0], "shape", None)
+    return all(getattr(im, "dtype", None) == np.uint8 and im.ndim == 3 and im.shape[-1] == 3 and im.shape == shape for im in images)
+
+
+class RawUploader(object):
+    """DEVICE_RESIZE: a list of same-size uint8 frames [H,W,3] -> one host copy into a REUSED pinned buffer (two of them, alternating: a
+    buffer is refilled only after the upload that last read it has run) -> `device` on this object's own stream -> `augment_fn` on the device
+    tensor -> augment.resize_images.  Returns (uint8 CUDA tensor [B,OH,OW,3], window, scale, an event recorded behind that work, bytes of
+    one pinned buffer).  The host copy runs outside hip.capture_lock; the lock is held where HIP is entered (no call while another thread
+    captures a hipGraph): allocation, waiting for a buffer, and enqueueing the batch's copies and kernels."""
+
+    def __init__(self, device=None):
+        self.device, self.stream, self.k = device, None, 0
+        self.slots = [None, None]                              # [pinned tensor, event behind its last upload]
+
+    def __call__(self, frames, config, augment_fn=None):
+        import torch
+        from . import augment
+        shape = (len(frames),) + tuple(frames[0].shape)
+        i = self.k & 1
+        self.k += 1
+        slot = self.slots[i]
+        with _hip_section():
+            if self.stream is None:
+                self.stream = torch.cuda.Stream(device=self.device)
+            if slot is None or tuple(slot[0].shape) != shape:
+                slot = self.slots[i] = [torch.empty(shape, dtype=torch.uint8).pin_memory(), None]
+            elif slot[1] is not None:
+                slot[1].synchronize()
+        host = slot[0].numpy()
+        for b, f in enumerate(frames):
+            host[b] = f
+        with _hip_section(), torch.cuda.stream(self.stream):
+            dev = slot[0].to(self.stream.device, non_blocking=True)
+            slot[1] = torch.cuda.Event()
+            slot[1].record()
+            if augment_fn is not None:
+                dev = augment_fn(dev)
+            out, window, scale, _padding = augment.resize_images(dev, min_dim=config.IMAGE_MIN_DIM, max_dim=config.IMAGE_MAX_DIM,
+                                                                 min_scale=config.IMAGE_MIN_SCALE, mode=config.IMAGE_RESIZE_MODE)
+            ready = torch.cuda.Event()
+            ready.record()
+        return out, window, scale, ready, slot[0].numel()
 
 
 def finish_sample(sample, config):
@@ -134,10 +211,13 @@ def finish_sample(sample, config):
 class BatchAssembler(object):
     """Pre-allocated per-field arrays of one minibatch; `images` is uint8 (device path) or the molded float type (reference format)."""
 
-    def __init__(self, config, batch_size, image_shape, meta_len, image_dtype):
+    def __init__(self, config, batch_size, image_shape, meta_len, image_dtype, host_images=True):
         ft = np.float16 if config.F16 else np.float32
         self.config, self.n = config, batch_size
-        self.images = np.zeros((batch_size,) + tuple(image_shape), dtype=image_dtype)
+        # DEVICE_RESIZE (host_images=False): the finished frames never visit the host -- `device_images` is the uint8 CUDA tensor, `ready` the
+        # event recorded behind the kernels that write it, `raw_pinned_bytes` the pinned memory the raw frames went up from
+        self.images = np.zeros((batch_size,) + tuple(image_shape), dtype=image_dtype) if host_images else None
+        self.device_images, self.ready, self.raw_pinned_bytes = None, None, 0
         self.meta = np.zeros((batch_size, meta_len), dtype=np.float64)
         self.loc = np.zeros((batch_size, 3 if config.REGRESS_LOC else config.LOC_BINS_PER_DIM ** 3), dtype=ft)
         if config.REGRESS_KEYPOINTS:
@@ -148,7 +228,8 @@ class BatchAssembler(object):
             self.ori = np.zeros((batch_size, width), dtype=ft)
 
     def put(self, b, image, meta, sample):
-        self.images[b] = image
+        if self.images is not None:
+            self.images[b] = image
         self.meta[b] = meta
         self.loc[b] = sample.loc
         if self.ori is None:
@@ -166,7 +247,7 @@ class BatchAssembler(object):
 DP_SHUFFLE_SEED = 1234
 
 
-def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, world=1):
+def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, world=1, device=None):
     """Endless iterator of BatchAssembler objects.  molded=True: images are mean-subtracted floats (the reference's generator
     format); False: uint8 frames for the device path.  Up to 5 failing samples are logged and skipped, the 6th re-raises
     (net.py:553-559).  workers > 0 loads the raw samples of a batch with that many threads.
@@ -175,7 +256,9 @@ def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, wor
     RandomState(DP_SHUFFLE_SEED), identical on all ranks, instead of NumPy's global one -- and keeps samples [rank * batch_size,
     (rank + 1) * batch_size) of every global batch of world * batch_size: the ranks' shards are disjoint and together they are the batch a
     single process with GPU_COUNT = world would have drawn.  The global RNG (augmentation draws) is seeded with DP_SHUFFLE_SEED + rank so
-    that the ranks do not apply identical warps to their different samples.  world == 1 is the reference's generator, draw for draw."""
+    that the ranks do not apply identical warps to their different samples.  world == 1 is the reference's generator, draw for draw.
+
+    device: the card Config.DEVICE_RESIZE uploads the raw frames to and resizes them on (None: the calling thread's current device)."""
     from .net import mold_image
     ids = np.copy(dataset.image_ids)
     cursor, errors = -1, 0
@@ -188,6 +271,7 @@ def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, wor
         from concurrent.futures import ThreadPoolExecutor
         pool = ThreadPoolExecutor(max_workers=workers)
     ft = np.float16 if config.F16 else np.float32
+    uploader = RawUploader(device)                              # DEVICE_RESIZE: pinned buffers + the producer's own stream (upload, augmentation, resize)
 
     def safe_load(image_id):
         try:
@@ -220,6 +304,17 @@ def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, wor
                     chosen.append(s)
         for _ in range((world - 1 - rank) * batch_size if world > 1 else 0):     # ... and to the ranks behind it
             advance()
+        if not molded and device_resize_applies([s.image for s in chosen], config):
+            shape = chosen[0].image.shape
+            out, window, scale, ready, nbytes = uploader([s.image for s in chosen], config,
+                                                         lambda dev: augment_samples(chosen, dataset, config, frames=dev))
+            metas = [compose_image_meta(s.image_id, shape, tuple(out.shape[1:]), window, scale) for s in chosen]
+            asm = BatchAssembler(config, batch_size, tuple(out.shape[1:]), len(metas[0]), np.uint8, host_images=False)
+            asm.device_images, asm.ready, asm.raw_pinned_bytes = out, ready, nbytes
+            for b, s in enumerate(chosen):
+                asm.put(b, None, metas[b], s)
+            yield asm
+            continue
         augment_samples(chosen, dataset, config)
         asm = None
         for b, s in enumerate(chosen):
@@ -247,7 +342,7 @@ class DeviceFeeder(object):
         self.consumed = [None, None]                           # recorded on the compute stream once a slot's batch has been copied out of it
         self.k = 0
         self.pinned_bytes = 0
-        gen = batches(dataset, config, shuffle, engine.B, molded=False, workers=workers, rank=rank, world=world)
+        gen = batches(dataset, config, shuffle, engine.B, molded=False, workers=workers, rank=rank, world=world, device=engine.device)
 
         def produce():
             from . import hip
@@ -256,10 +351,12 @@ class DeviceFeeder(object):
                     # the generator takes hip.capture_lock itself around its HIP sections (augment_samples: the batched augmentation kernels and
                     # their device-to-host copies); here only hipHostMalloc in pin_memory needs it -- not while the consumer thread captures a hipGraph
                     asm = next(gen)
-                    arrays = [np.ascontiguousarray(a) for a in ([asm.images, asm.loc] + ([asm.k1, asm.k2] if asm.ori is None else [asm.ori]))]
+                    on_device = asm.device_images is not None  # DEVICE_RESIZE: the frames are finished and stay where they are
+                    arrays = [np.ascontiguousarray(a) for a in (([] if on_device else [asm.images]) + [asm.loc] +
+                                                                ([asm.k1, asm.k2] if asm.ori is None else [asm.ori]))]
                     with hip.capture_lock:
                         host = [torch.from_numpy(a).pin_memory() for a in arrays]
-                    self.q.put(host)
+                    self.q.put((([asm.device_images] if on_device else []) + host, asm.ready, asm.raw_pinned_bytes))
             except BaseException as e:                         # surfaced by next_into
                 self.err = e
                 self.q.put(None)
@@ -269,20 +366,26 @@ class DeviceFeeder(object):
 
     def _upload(self):
         torch = self.torch
-        host = self.q.get()
-        if host is None:
+        item = self.q.get()
+        if item is None:
             raise self.err
+        host, ready, raw_pinned = item
         slot = self.k & 1
         with torch.cuda.stream(self.side):
             if self.consumed[slot] is not None:
                 self.side.wait_event(self.consumed[slot])      # the engine's copy out of this slot (two batches ago) must have run first
+            if ready is not None:
+                self.side.wait_event(ready)                    # DEVICE_RESIZE: the producer's resize kernel writes host[0] on its own stream
             if self.stage[slot] is None:
                 self.stage[slot] = [torch.empty(h.shape, dtype=h.dtype, device=self.eng.device) for h in host]
             for d, h in zip(self.stage[slot], host):
                 d.copy_(h, non_blocking=True)
+                if h.is_cuda:
+                    h.record_stream(self.side)                 # allocated on the producer's stream, read here
             self.events[slot].record(self.side)
         self._pending = (slot, host)                           # keep the pinned tensors alive until the copy has been consumed
-        self.pinned_bytes = sum(h.numel() * h.element_size() for h in host)
+        # pinned memory of one ring entry: the targets, and the frames as they went up (finished, or RAW with DEVICE_RESIZE)
+        self.pinned_bytes = sum(h.numel() * h.element_size() for h in host if not h.is_cuda) + int(raw_pinned)
 
     def next_into(self):
         """Engine inputs <- the uploaded batch; immediately starts uploading the following one."""
@@ -331,7 +434,8 @@ class EvalBatch(object):
 
 class EvalFeeder(object):
     """Finite, ordered, augmentation-free input of evaluate(): walks dataset.image_ids once in order (eval_batch_plan).  Loader
-    threads load every image with load_sample / finish_sample (host resize / pad, no augmentation: ROT_AUG, ROT_IMAGE_AUG and
+    threads load every image with load_sample / finish_sample (host resize / pad -- with Config.DEVICE_RESIZE the producer instead uploads
+    each batch of same-size uint8 RGB frames raw and finishes it with augment.resize_images; no augmentation: ROT_AUG, ROT_IMAGE_AUG and
     SIM2REAL_AUG are ignored, and the encoded targets are the dataset's stored ones); a producer thread assembles each batch in
     pinned memory (under hip.capture_lock, as DeviceFeeder does); iterating uploads batch k+1 on a side stream into the other half
     of a double buffer while batch k is used.  A batch's staging slot is reused only after the work the consumer put on the current
@@ -349,6 +453,7 @@ class EvalFeeder(object):
         self.events = [torch.cuda.Event(), torch.cuda.Event()]
         self.consumed = [None, None]
         self.k = 0
+        uploader = RawUploader(self.eng.device)                # DEVICE_RESIZE: pinned buffers + the producer's own stream (raw upload, resize)
         pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
 
         def load(image_id):
@@ -357,10 +462,12 @@ class EvalFeeder(object):
             q = np.asarray(dataset.load_quaternion(image_id), dtype=np.float64)
             el = np.asarray(dataset.load_location_encoded(image_id), dtype=np.float32) if enc_loc else None
             eo = np.asarray(dataset.load_orientation_encoded(image_id), dtype=np.float32) if enc_ori else None
+            kind = "float"                                      # not uint8 RGB: molded on the host, as detect does for such frames
             if getattr(image, "dtype", None) == np.uint8 and image.ndim == 3 and image.shape[-1] == 3:
-                image = finish_sample(Sample(image_id, image, None, None), config)[0]
-                return True, image, loc, q, el, eo
-            return False, image, loc, q, el, eo
+                kind = "raw"                                    # DEVICE_RESIZE: finished per batch by the producer
+                if not device_resize_applies([image], config):
+                    kind, image = "u8", finish_sample(Sample(image_id, image, None, None), config)[0]
+            return kind, image, loc, q, el, eo
 
         def produce():
             from . import hip
@@ -372,16 +479,23 @@ class EvalFeeder(object):
                     rows = [got[i] for i in slots]
                     if self.loc_dtype is None:
                         self.loc_dtype = rows[0][2].dtype
-                    if all(r[0] for r in rows):
-                        images = np.stack([r[1] for r in rows])
-                    else:                                       # not uint8 RGB: molded on the host, as detect does for such frames
-                        images = model.mold_inputs([r[1] for r in rows])[0].astype(np.float32)
-                    arrays = [images, np.stack([r[2] for r in rows]).astype(np.float64), np.stack([r[3] for r in rows])]
-                    arrays += [np.stack([r[k] for r in rows]) if rows[0][k] is not None else None for k in (4, 5)]
-                    arrays = [None if a is None else np.ascontiguousarray(a) for a in arrays]
+                    frames, ready = {i: r[1] for i, r in got.items()}, None
+                    if all(r[0] == "raw" for r in rows) and device_resize_applies([r[1] for r in rows], config):
+                        images, _w, _s, ready, _n = uploader([r[1] for r in rows], config)      # uint8 CUDA tensor, finished
+                    else:
+                        for i, r in got.items():                # DEVICE_RESIZE with mixed frame sizes: the host path for this batch
+                            if r[0] == "raw":
+                                frames[i] = finish_sample(Sample(i, r[1], None, None), config)[0]
+                        if any(r[0] == "float" for r in rows):
+                            images = model.mold_inputs([frames[i] for i in slots])[0].astype(np.float32)
+                        else:
+                            images = np.stack([frames[i] for i in slots])
+                    targets = [np.stack([r[2] for r in rows]).astype(np.float64), np.stack([r[3] for r in rows])]
+                    targets += [np.stack([r[k] for r in rows]) if rows[0][k] is not None else None for k in (4, 5)]
                     with hip.capture_lock:
-                        host = [None if a is None else torch.from_numpy(a).pin_memory() for a in arrays]
-                    self.q.put((row0, n, host))
+                        pin = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
+                        host = [images if ready is not None else pin(images)] + [pin(t) for t in targets]
+                    self.q.put((row0, n, host, ready))
                 self.q.put(None)
             except BaseException as e:                         # surfaced by the consumer
                 self.err = e
@@ -400,11 +514,13 @@ class EvalFeeder(object):
                 raise self.err
             self._pending = None
             return False
-        row0, n, host = item
+        row0, n, host, ready = item
         slot = self.k & 1
         with torch.cuda.stream(self.side):
             if self.consumed[slot] is not None:
                 self.side.wait_event(self.consumed[slot])      # the work that read this slot two batches ago must have run first
+            if ready is not None:
+                self.side.wait_event(ready)                    # DEVICE_RESIZE: host[0] is written by the producer's resize kernel
             st = self.stage[slot]
             if st is None or any((d is None) != (h is None) or (h is not None and (d.shape != h.shape or d.dtype != h.dtype))
                                  for d, h in zip(st, host)):
@@ -412,6 +528,8 @@ class EvalFeeder(object):
             for d, h in zip(st, host):
                 if h is not None:
                     d.copy_(h, non_blocking=True)
+                    if h.is_cuda:
+                        h.record_stream(self.side)
             self.events[slot].record(self.side)
         self._pending = (slot, row0, n, host)                  # the pinned tensors stay alive until their copy has been waited for
         self.k += 1

@@ -189,6 +189,7 @@ _SIGS = {
     "urso_rgb_to_grey3": (_i, [_i, _i, _i, _vp, _vp, _vp]),
     "urso_sim2real_op": (_i, [_i, _i, _i, _vp, _vp, _vp, _fp, _vp, _vp, _i, _vp]),
     "urso_pad_images_u8": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "urso_resize_images_u8": (_i, [_i] * 10 + [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "urso_conv_winograd_ws_bytes": (_sz, [_gp, _i]),
     "urso_conv_winograd_fwd": (_i, [_gp, _i, _i, _vp, _vp, _fp, _vp, _vp, _sz, _vp]),
     "urso_prof_enable": (_i, [_i]),
@@ -795,6 +796,15 @@ def sim2real_op(B, H, W, src, dst, op, par, seed, drop, drop_stride, stream=None
 def pad_images_u8(B, H, W, Cc, OH, OW, top, left, src, dst, stream=None):
     assert src.dtype == torch.uint8 and dst.dtype == torch.uint8
     _chk(_lib.urso_pad_images_u8(B, H, W, Cc, OH, OW, int(top), int(left), ptr(src), ptr(dst), stream_ptr(stream)), "urso_pad_images_u8")
+
+
+def resize_images_u8(B, H, W, Cc, NH, NW, OH, OW, top, left, ky, ry, kx, rx, y0, fy, x0, fx, trunc_passes, src, dst, stream=None):
+    """urso_resize_images_u8: utils.resize_image of a uint8 batch [B,H,W,C] -> [B,OH,OW,C], byte-exact; the tables are device tensors built from
+    utils.resize_tables (ky / kx None where the axis does not shrink)."""
+    assert src.dtype == torch.uint8 and dst.dtype == torch.uint8 and y0.dtype == torch.int32 and x0.dtype == torch.int32
+    assert all(t is None or t.dtype == torch.float64 for t in (ky, kx, fy, fx))
+    _chk(_lib.urso_resize_images_u8(B, H, W, Cc, NH, NW, OH, OW, int(top), int(left), ptr(ky), int(ry), ptr(kx), int(rx), ptr(y0), ptr(fy), ptr(x0),
+                                    ptr(fx), int(trunc_passes), ptr(src), ptr(dst), stream_ptr(stream)), "urso_resize_images_u8")
 
 
 def prof_enable(on):

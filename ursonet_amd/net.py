@@ -432,15 +432,23 @@ class UrsoNet(object):
 
     def detect(self, images, verbose=0):
         """net.py:1207-1259: one dict of RAW network outputs per image -- {'loc', 'ori'}, or {'loc', 'k1', 'k2'} in keypoint mode
-        (the reference's key names for the three keypoint heads).  uint8 frames take the device path: they are padded on the host,
-        uploaded as uint8 and mean-subtracted by the first kernel; anything else goes through mold_inputs / predict."""
+        (the reference's key names for the three keypoint heads).  uint8 frames take the device path: they are resized / padded on the host
+        (Config.DEVICE_RESIZE and frames of one size: uploaded raw and resized there, same bytes), uploaded as uint8 and mean-subtracted by
+        the first kernel; anything else goes through mold_inputs / predict."""
         assert self.mode == "inference", "Create model in inference mode."
         assert len(images) == self.config.BATCH_SIZE, "len(images) must be equal to BATCH_SIZE"
         if verbose:
             log("Processing {} images".format(len(images)))
             for image in images:
                 log("image", image)
-        if all(getattr(im, "dtype", None) == np.uint8 and im.ndim == 3 and im.shape[-1] == 3 for im in images):
+        from .feeder import device_resize_applies
+        if device_resize_applies(images, self.config):        # DEVICE_RESIZE: the raw frames go up once and are resized / padded there
+            from . import augment
+            frames = augment.resize_images(np.stack(images), min_dim=self.config.IMAGE_MIN_DIM, max_dim=self.config.IMAGE_MAX_DIM,
+                                           min_scale=self.config.IMAGE_MIN_SCALE, mode=self.config.IMAGE_RESIZE_MODE)[0]
+            self._engine.load_batch_u8(frames)
+            outs = self._outputs_after_forward()
+        elif all(getattr(im, "dtype", None) == np.uint8 and im.ndim == 3 and im.shape[-1] == 3 for im in images):
             frames = [f for f, _, _ in self._resized(images)]
             assert all(f.shape == frames[0].shape for f in frames), \
                 "After resizing, all images must have the same size. Check IMAGE_RESIZE_MODE and image sizes."
