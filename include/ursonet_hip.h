@@ -644,6 +644,40 @@ typedef struct urso_pose_eval_args {
 int urso_pose_eval(const urso_pose_eval_args* args, void* stream);
 
 /*
+ * Decode of one batch of head outputs WITHOUT ground truth (pose_estimator.py:217-318, test_and_submit), batched on the GPU:
+ * one workgroup per valid row b < n writes row row0 + b of the fp64 table [rows][URSO_DEC_COLS]; rows past n are not touched.
+ * loc / ori / ori2 / loc_map, loc_mode / ori_mode (URSO_EVAL_LOC_* / URSO_EVAL_ORI_*) and the row strides are those of
+ * urso_pose_eval, and LOC_EST / Q_EST are the same bits urso_pose_eval writes for the same inputs (shared device routines).
+ * Confidence columns, fp64 from the fp32 inputs, NaN where the head does not define them:
+ *   LOC_PEAK    URSO_EVAL_LOC_CLASS: the largest probability of softmax(loc[b, 0:loc_bins]).
+ *   ORI_PEAK    _SOFT with ori_logits (fp32, rows ori_logits_ld floats apart, ori_bins = ori_map_rows = rows of the bin map):
+ *               the largest probability of softmax(ori_logits[b, 0:ori_bins]).
+ *   ORI_LAMBDA  _SOFT with ori_scatter (urso_quat_wavg_decode's a_d, fp32 [B][16]): q^T A q / q^T q for q = ori[b, 0:4], the
+ *               largest eigenvalue of A = sum_i w_i q_i q_i^T at the decoded q: 1 for a point mass, 1/4 for a uniform spread.
+ * The remaining columns are 0.  A NaN input gives NaN outputs.  No workspace, no allocation, no host synchronisation; n = 0
+ * launches nothing.  Bad arguments return URSO_EINVAL before any launch: a null struct, null loc / ori / table, B <= 0, n outside
+ * [0, B], row0 < 0, an unknown mode, loc_bins != loc_map_rows, ori_bins != ori_map_rows with ori_logits, a row stride below the
+ * row width, ori2 missing in keypoint mode, loc_map missing in _LOC_CLASS, ori_logits / ori_scatter outside _SOFT.
+ */
+enum { URSO_DEC_LOC_EST = 0, URSO_DEC_Q_EST = 3, URSO_DEC_LOC_PEAK = 7, URSO_DEC_ORI_PEAK = 8, URSO_DEC_ORI_LAMBDA = 9, URSO_DEC_COLS = 12 };
+typedef struct urso_pose_decode_args {
+    int32_t B, n;                    /* rows of the batch buffers, valid rows (0 <= n <= B) */
+    int64_t row0;                    /* table row of batch row 0 */
+    int32_t loc_mode, ori_mode;
+    int32_t loc_ld, ori_ld;          /* floats between rows of loc / ori / ori2 */
+    int32_t loc_bins, loc_map_rows, ori_bins, ori_map_rows;
+    int32_t ori_logits_ld, pad0;     /* floats between rows of ori_logits */
+    const float* loc;
+    const float* ori;
+    const float* ori2;               /* k2 in keypoint mode, else NULL */
+    const double* loc_map;
+    const float* ori_logits;         /* optional, _SOFT only */
+    const float* ori_scatter;        /* optional, _SOFT only */
+    double* table;
+} urso_pose_decode_args;
+int urso_pose_decode(const urso_pose_decode_args* args, void* stream);
+
+/*
  * Rotation augmentation on the GPU ("next" scope row f-1; reference: utils.rotate_cam / rotate_image utils.py:30-86 called
  * from load_image_gt net.py:415-438, and utils.encode_ori_fast utils.py:319-346 for the re-encoded target).
  *   urso_warp_perspective: OpenCV warpPerspective arithmetic on uint8 images [B,H,W,C], constant-0 border.  M [B][9]

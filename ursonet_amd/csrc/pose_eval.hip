@@ -6,6 +6,9 @@
 // Bin reductions (location first moment, encoded targets) are accumulated in fp64: per-thread partials, 64-lane shuffles, one
 // LDS exchange across the 4 waves, in a fixed order.  The soft-argmax orientation is NOT recomputed here: the caller passes
 // urso_quat_wavg_decode's output, so q_est is that entry point's result bit for bit.
+//
+// urso_pose_decode is the same decode without a ground truth (predict / submit): it shares the device routines below with
+// urso_pose_eval, so both write the same loc_est / q_est bits, and adds the peak probabilities of the classification heads.
 #include "common.h"
 #include <math.h>
 
@@ -126,32 +129,72 @@ __device__ __forceinline__ double ev_angle(const double (&a)[4], const double* b
     return 2 * acos(d);
 }
 
+// Block-wide maximum of row[0:K] (fmaxf: a NaN logit is dropped here and comes back through the exp sum).  All threads must call it.
+__device__ __forceinline__ float ev_block_max(const float* row, int K, float* redf) {
+    float mx = -INFINITY;
+    for (int i = threadIdx.x; i < K; i += ET) mx = fmaxf(mx, row[i]);
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) redf[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = -INFINITY;
+    for (int i = 0; i < EW; ++i) mx = fmaxf(mx, redf[i]);
+    return mx;
+}
+
+// loc_est = softmax(lrow[0:K]) @ loc_map in fp64 (:380-383); returns sum_i exp(lrow[i] - max), whose reciprocal is the largest
+// softmax probability.  `red` holds EW * 4 doubles, `res` 4, `redf` EW floats.  All threads must call it.
+__device__ __forceinline__ double ev_loc_softmax(const float* lrow, int K, const double* loc_map, double* red, double* res, float* redf,
+                                                 double (&loc_est)[3]) {
+    const float mx = ev_block_max(lrow, K, redf);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < K; i += ET) {
+        const double e = exp((double)lrow[i] - (double)mx);
+        acc[0] += e; acc[1] += e * loc_map[3 * i]; acc[2] += e * loc_map[3 * i + 1]; acc[3] += e * loc_map[3 * i + 2];
+    }
+    ev_block_sum<4>(acc, red, res);
+    for (int c = 0; c < 3; ++c) loc_est[c] = res[1 + c] / res[0];
+    return res[0];
+}
+
+// The orientation estimate [x, y, z, w] of one row for every ori_mode (include/ursonet_hip.h); one thread.
+__device__ __forceinline__ void ev_decode_ori(int ori_mode, const float* orow, const float* k2, const double (&loc_est)[3], double (&q)[4]) {
+    switch (ori_mode) {
+        case URSO_EVAL_ORI_EULER: {
+            double R[3][3];
+            ev_euler_to_so3(orow[0], orow[1], orow[2], R);
+            ev_so3_to_quat(R, q);
+            break;
+        }
+        case URSO_EVAL_ORI_ANGLE_AXIS: {                                   // :397-403
+            const double v[3] = {orow[0], orow[1], orow[2]};
+            const double th = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+            const double s = sin(th / 2);
+            for (int c = 0; c < 3; ++c) q[c] = (th < 1e-6 ? 0.0 : v[c] / th) * s;
+            q[3] = cos(th / 2);
+            break;
+        }
+        case URSO_EVAL_ORI_KEYPOINTS: {
+            const double k1d[3] = {orow[0], orow[1], orow[2]}, k2d[3] = {k2[0], k2[1], k2[2]};
+            ev_keypoints_quat(k1d, k2d, loc_est, q);
+            break;
+        }
+        default:                                                            // quaternion (q_out) or the soft-argmax decode
+            for (int c = 0; c < 4; ++c) q[c] = orow[c];
+    }
+}
+
 __global__ void __launch_bounds__(ET) pose_eval_kernel(urso_pose_eval_args a) {
     __shared__ double red[EW * 10];
     __shared__ double res[10];
     __shared__ float redf[EW];
     const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const float* lrow = a.loc + (size_t)b * a.loc_ld;
 
     // location: softmax(logits) @ histogram_3D_map (:380-383), and the encoded target's first moment (:386-387, no softmax)
     double loc_est[3], loc_dec[3] = {NAN, NAN, NAN};
     if (a.loc_mode == URSO_EVAL_LOC_CLASS) {
         const int K = a.loc_bins;
-        float mx = -INFINITY;
-        for (int i = threadIdx.x; i < K; i += ET) mx = fmaxf(mx, lrow[i]);
-        mx = wave_max(mx);
-        if (lane == 0) redf[w] = mx;
-        __syncthreads();
-        mx = -INFINITY;
-        for (int i = 0; i < EW; ++i) mx = fmaxf(mx, redf[i]);
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int i = threadIdx.x; i < K; i += ET) {
-            const double e = exp((double)lrow[i] - (double)mx);
-            acc[0] += e; acc[1] += e * a.loc_map[3 * i]; acc[2] += e * a.loc_map[3 * i + 1]; acc[3] += e * a.loc_map[3 * i + 2];
-        }
-        ev_block_sum<4>(acc, red, res);
-        for (int c = 0; c < 3; ++c) loc_est[c] = res[1 + c] / res[0];
+        ev_loc_softmax(lrow, K, a.loc_map, red, res, redf, loc_est);
         if (a.enc_loc) {
             const float* p = a.enc_loc + (size_t)b * K;
             double m[3] = {0.0, 0.0, 0.0};
@@ -194,32 +237,8 @@ __global__ void __launch_bounds__(ET) pose_eval_kernel(urso_pose_eval_args a) {
     if (threadIdx.x != 0) return;
 
     // orientation
-    const float* orow = a.ori + (size_t)b * a.ori_ld;
     double q[4];
-    switch (a.ori_mode) {
-        case URSO_EVAL_ORI_EULER: {
-            double R[3][3];
-            ev_euler_to_so3(orow[0], orow[1], orow[2], R);
-            ev_so3_to_quat(R, q);
-            break;
-        }
-        case URSO_EVAL_ORI_ANGLE_AXIS: {                                   // :397-403
-            const double v[3] = {orow[0], orow[1], orow[2]};
-            const double th = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            const double s = sin(th / 2);
-            for (int c = 0; c < 3; ++c) q[c] = (th < 1e-6 ? 0.0 : v[c] / th) * s;
-            q[3] = cos(th / 2);
-            break;
-        }
-        case URSO_EVAL_ORI_KEYPOINTS: {
-            const float* k2 = a.ori2 + (size_t)b * a.ori_ld;
-            const double k1d[3] = {orow[0], orow[1], orow[2]}, k2d[3] = {k2[0], k2[1], k2[2]};
-            ev_keypoints_quat(k1d, k2d, loc_est, q);
-            break;
-        }
-        default:                                                            // quaternion (q_out) or the soft-argmax decode
-            for (int c = 0; c < 4; ++c) q[c] = orow[c];
-    }
+    ev_decode_ori(a.ori_mode, a.ori + (size_t)b * a.ori_ld, a.ori2 ? a.ori2 + (size_t)b * a.ori_ld : nullptr, loc_est, q);
     const double* lg = a.loc_gt + (size_t)b * 3;
     const double* qg = a.q_gt + (size_t)b * 4;
     double* row = a.table + (size_t)(a.row0 + b) * URSO_EVAL_COLS;
@@ -297,5 +316,89 @@ extern "C" int urso_pose_eval(const urso_pose_eval_args* a, void* stream) {
     const double bins = (a->loc_mode == URSO_EVAL_LOC_CLASS ? a->loc_bins * (a->enc_loc ? 32.0 : 28.0) : 12.0) + (a->enc_ori ? a->ori_bins * 20.0 : 0.0);
     ProfScope ps(st, URSO_K_DECODE, 0, (double)a->n * (bins + 56 + URSO_EVAL_COLS * 8));
     URSO_KLAUNCH(pose_eval_kernel, dim3(a->n), dim3(ET), 0, st, *a);
+    return urso_check_launch(fn);
+}
+
+// Decode without ground truth: the estimates of pose_eval_kernel (the same device routines, so the same bits) and how
+// concentrated the classification heads' PMFs are.
+__global__ void __launch_bounds__(ET) pose_decode_kernel(urso_pose_decode_args a) {
+    __shared__ double red[EW * 4];
+    __shared__ double res[4];
+    __shared__ float redf[EW];
+    const int b = blockIdx.x;
+    const float* lrow = a.loc + (size_t)b * a.loc_ld;
+
+    double loc_est[3], loc_peak = NAN, ori_peak = NAN;
+    if (a.loc_mode == URSO_EVAL_LOC_CLASS) {
+        loc_peak = 1.0 / ev_loc_softmax(lrow, a.loc_bins, a.loc_map, red, res, redf, loc_est);
+    } else {
+        for (int c = 0; c < 3; ++c) loc_est[c] = lrow[c];
+    }
+    if (a.ori_logits) {                                                     // max softmax probability = 1 / sum exp(z - max)
+        const float* z = a.ori_logits + (size_t)b * a.ori_logits_ld;
+        const float mx = ev_block_max(z, a.ori_bins, redf);
+        double acc[1] = {0.0};
+        for (int i = threadIdx.x; i < a.ori_bins; i += ET) acc[0] += exp((double)z[i] - (double)mx);
+        ev_block_sum<1>(acc, red, res);
+        ori_peak = 1.0 / res[0];
+    }
+    if (threadIdx.x != 0) return;
+
+    const float* orow = a.ori + (size_t)b * a.ori_ld;
+    double q[4];
+    ev_decode_ori(a.ori_mode, orow, a.ori2 ? a.ori2 + (size_t)b * a.ori_ld : nullptr, loc_est, q);
+    double lambda = NAN;
+    if (a.ori_scatter) {                                                    // Rayleigh quotient of the decode's A at its q
+        const float* A = a.ori_scatter + (size_t)b * 16;
+        double num = 0.0, den = 0.0;
+        for (int i = 0; i < 4; ++i) {
+            double r = 0.0;
+            for (int j = 0; j < 4; ++j) r += (double)A[i * 4 + j] * q[j];
+            num += q[i] * r; den += q[i] * q[i];
+        }
+        lambda = num / den;
+    }
+    double* row = a.table + (size_t)(a.row0 + b) * URSO_DEC_COLS;
+    for (int c = 0; c < 3; ++c) row[URSO_DEC_LOC_EST + c] = loc_est[c];
+    for (int c = 0; c < 4; ++c) row[URSO_DEC_Q_EST + c] = q[c];
+    row[URSO_DEC_LOC_PEAK] = loc_peak;
+    row[URSO_DEC_ORI_PEAK] = ori_peak;
+    row[URSO_DEC_ORI_LAMBDA] = lambda;
+    for (int c = URSO_DEC_ORI_LAMBDA + 1; c < URSO_DEC_COLS; ++c) row[c] = 0.0;
+}
+
+extern "C" int urso_pose_decode(const urso_pose_decode_args* a, void* stream) {
+    const char* fn = "urso_pose_decode";
+    if (!a) { urso_set_error("%s: null argument struct", fn); return URSO_EINVAL; }
+    if (!a->loc || !a->ori || !a->table) { urso_set_error("%s: null pointer (loc, ori, table)", fn); return URSO_EINVAL; }
+    if (a->B <= 0 || a->n < 0 || a->n > a->B) { urso_set_error("%s: need 0 <= n <= B and B > 0 (B=%d, n=%d)", fn, a->B, a->n); return URSO_EINVAL; }
+    if (a->row0 < 0) { urso_set_error("%s: row0 must be >= 0 (got %lld)", fn, (long long)a->row0); return URSO_EINVAL; }
+    if (a->loc_mode != URSO_EVAL_LOC_REGRESS && a->loc_mode != URSO_EVAL_LOC_CLASS) { urso_set_error("%s: unknown loc_mode %d", fn, a->loc_mode); return URSO_EINVAL; }
+    if (a->ori_mode < URSO_EVAL_ORI_QUAT || a->ori_mode > URSO_EVAL_ORI_KEYPOINTS) { urso_set_error("%s: unknown ori_mode %d", fn, a->ori_mode); return URSO_EINVAL; }
+    const int soft = a->ori_mode == URSO_EVAL_ORI_SOFT, kp = a->ori_mode == URSO_EVAL_ORI_KEYPOINTS;
+    const int ow = (a->ori_mode == URSO_EVAL_ORI_QUAT || soft) ? 4 : 3;
+    if (a->ori_ld < ow) { urso_set_error("%s: ori_ld %d < %d values per row", fn, a->ori_ld, ow); return URSO_EINVAL; }
+    if (kp && !a->ori2) { urso_set_error("%s: keypoint mode needs ori2 (k2)", fn); return URSO_EINVAL; }
+    if (kp && a->loc_mode != URSO_EVAL_LOC_REGRESS) { urso_set_error("%s: keypoint mode needs a regressed location", fn); return URSO_EINVAL; }
+    if (a->loc_mode == URSO_EVAL_LOC_CLASS) {
+        if (!a->loc_map || a->loc_bins <= 0 || a->loc_bins != a->loc_map_rows) {
+            urso_set_error("%s: location classification needs loc_map with loc_bins rows (loc_bins=%d, loc_map_rows=%d)", fn, a->loc_bins, a->loc_map_rows);
+            return URSO_EINVAL;
+        }
+        if (a->loc_ld < a->loc_bins) { urso_set_error("%s: loc_ld %d < loc_bins %d", fn, a->loc_ld, a->loc_bins); return URSO_EINVAL; }
+    } else if (a->loc_ld < 3) { urso_set_error("%s: loc_ld %d < 3", fn, a->loc_ld); return URSO_EINVAL; }
+    if ((a->ori_logits || a->ori_scatter) && !soft) { urso_set_error("%s: ori_logits and ori_scatter are defined for soft classification only", fn); return URSO_EINVAL; }
+    if (a->ori_logits) {
+        if (a->ori_bins <= 0 || a->ori_bins != a->ori_map_rows) {
+            urso_set_error("%s: ori_logits needs ori_bins equal to the rows of the bin map (ori_bins=%d, ori_map_rows=%d)", fn, a->ori_bins, a->ori_map_rows);
+            return URSO_EINVAL;
+        }
+        if (a->ori_logits_ld < a->ori_bins) { urso_set_error("%s: ori_logits_ld %d < ori_bins %d", fn, a->ori_logits_ld, a->ori_bins); return URSO_EINVAL; }
+    }
+    if (a->n == 0) return URSO_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const double bins = (a->loc_mode == URSO_EVAL_LOC_CLASS ? a->loc_bins * 28.0 : 12.0) + (a->ori_logits ? a->ori_bins * 4.0 : 0.0);
+    ProfScope ps(st, URSO_K_DECODE, 0, (double)a->n * (bins + 16 + (a->ori_scatter ? 64 : 0) + URSO_DEC_COLS * 8));
+    URSO_KLAUNCH(pose_decode_kernel, dim3(a->n), dim3(ET), 0, st, *a);
     return urso_check_launch(fn);
 }

@@ -86,12 +86,12 @@ def head_modes(config):
                       "angle_axis": hip.EVAL_ORI_ANGLE_AXIS}[config.ORIENTATION_PARAM]
 
 
-def _check(model, dataset, multimodal):
+def _check(model, dataset, multimodal, who="evaluate"):
     assert model.mode == "inference", "Create model in inference mode."
     cfg = model.config
     soft = not (cfg.REGRESS_ORI or cfg.REGRESS_KEYPOINTS)
     if multimodal and not soft:
-        raise ValueError("evaluate(multimodal=True) needs the soft-classification orientation head (REGRESS_ORI = False)")
+        raise ValueError("%s(multimodal=True) needs the soft-classification orientation head (REGRESS_ORI = False)" % who)
     if not cfg.REGRESS_LOC and getattr(dataset, "histogram_3D_map", None) is None:
         raise ValueError("location classification (REGRESS_LOC = False) needs dataset.histogram_3D_map, the bin map the location "
                          "head was trained on")

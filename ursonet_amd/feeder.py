@@ -423,7 +423,7 @@ def eval_batch_plan(image_ids, batch_size):
 
 class EvalBatch(object):
     """One uploaded evaluation batch: table rows [row0, row0 + n), device tensors `images` (uint8 frames, or molded float32 where the
-    dataset's frames are not uint8 RGB), `loc_gt` fp64 [B,3], `q_gt` fp64 [B,4] and, where a classification head needs them, the
+    dataset's frames are not uint8 RGB), `loc_gt` fp64 [B,3], `q_gt` fp64 [B,4] (None from a label-free feeder) and, where a classification head needs them, the
     stored encoded targets `enc_loc` / `enc_ori` fp32 [B,K] (else None)."""
     __slots__ = ("row0", "n", "images", "loc_gt", "q_gt", "enc_loc", "enc_ori")
 
@@ -439,11 +439,14 @@ class EvalFeeder(object):
     SIM2REAL_AUG are ignored, and the encoded targets are the dataset's stored ones); a producer thread assembles each batch in
     pinned memory (under hip.capture_lock, as DeviceFeeder does); iterating uploads batch k+1 on a side stream into the other half
     of a double buffer while batch k is used.  A batch's staging slot is reused only after the work the consumer put on the current
-    stream while holding it (the forward pass and the scoring kernels) has run.  `loc_dtype` is the dtype of the dataset's locations."""
+    stream while holding it (the forward pass and the scoring kernels) has run.  `loc_dtype` is the dtype of the dataset's locations.
+    With labels=False (predict(): datasets without ground truth) no label loader of the dataset is called, only load_image, and the
+    batches' `loc_gt` / `q_gt` are None; everything else is the same code."""
 
-    def __init__(self, model, dataset, config, enc_loc=False, enc_ori=False, workers=4, depth=3):
+    def __init__(self, model, dataset, config, enc_loc=False, enc_ori=False, workers=4, depth=3, labels=True):
         import torch
         from concurrent.futures import ThreadPoolExecutor
+        assert labels or not (enc_loc or enc_ori), "the encoded targets are labels"
         self.torch, self.eng = torch, model._engine
         self.plan = eval_batch_plan(dataset.image_ids, self.eng.B)
         self.q = queue.Queue(maxsize=depth)
@@ -458,8 +461,8 @@ class EvalFeeder(object):
 
         def load(image_id):
             image = dataset.load_image(image_id)
-            loc = np.asarray(dataset.load_location(image_id))
-            q = np.asarray(dataset.load_quaternion(image_id), dtype=np.float64)
+            loc = np.asarray(dataset.load_location(image_id)) if labels else None
+            q = np.asarray(dataset.load_quaternion(image_id), dtype=np.float64) if labels else None
             el = np.asarray(dataset.load_location_encoded(image_id), dtype=np.float32) if enc_loc else None
             eo = np.asarray(dataset.load_orientation_encoded(image_id), dtype=np.float32) if enc_ori else None
             kind = "float"                                      # not uint8 RGB: molded on the host, as detect does for such frames
@@ -477,7 +480,7 @@ class EvalFeeder(object):
                         return
                     got = dict(zip(slots[:n], pool.map(load, slots[:n])))
                     rows = [got[i] for i in slots]
-                    if self.loc_dtype is None:
+                    if self.loc_dtype is None and labels:
                         self.loc_dtype = rows[0][2].dtype
                     frames, ready = {i: r[1] for i, r in got.items()}, None
                     if all(r[0] == "raw" for r in rows) and device_resize_applies([r[1] for r in rows], config):
@@ -490,7 +493,7 @@ class EvalFeeder(object):
                             images = model.mold_inputs([frames[i] for i in slots])[0].astype(np.float32)
                         else:
                             images = np.stack([frames[i] for i in slots])
-                    targets = [np.stack([r[2] for r in rows]).astype(np.float64), np.stack([r[3] for r in rows])]
+                    targets = [np.stack([r[2] for r in rows]).astype(np.float64), np.stack([r[3] for r in rows])] if labels else [None, None]
                     targets += [np.stack([r[k] for r in rows]) if rows[0][k] is not None else None for k in (4, 5)]
                     with hip.capture_lock:
                         pin = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).pin_memory()

@@ -91,6 +91,18 @@ EVAL_LOC_EST, EVAL_Q_EST, EVAL_LOC_ERR, EVAL_ORI_ERR, EVAL_ESA, EVAL_DIST = 0, 3
 EVAL_LOC_ENC_ERR, EVAL_ORI_ENC_ERR, EVAL_ORI_ERR_SOFT, EVAL_MODE, EVAL_COLS = 11, 12, 13, 14, 16
 
 
+class PoseDecodeArgs(C.Structure):
+    """urso_pose_decode_args (include/ursonet_hip.h): one batch of urso_pose_decode."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] +
+                [(n, C.c_int32) for n in ("loc_mode", "ori_mode", "loc_ld", "ori_ld", "loc_bins", "loc_map_rows", "ori_bins", "ori_map_rows",
+                                          "ori_logits_ld", "pad0")] +
+                [(n, C.c_void_p) for n in ("loc", "ori", "ori2", "loc_map", "ori_logits", "ori_scatter", "table")])
+
+
+# urso_pose_decode table columns (include/ursonet_hip.h); the modes are urso_pose_eval's
+DEC_LOC_EST, DEC_Q_EST, DEC_LOC_PEAK, DEC_ORI_PEAK, DEC_ORI_LAMBDA, DEC_COLS = 0, 3, 7, 8, 9, 12
+
+
 class DenseWgradLayer(C.Structure):
     """urso_dense_wgrad_layer (include/ursonet_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("x", "dz", "part", "colpart")] + [(n, C.c_int32) for n in ("M", "K", "N")]
@@ -158,6 +170,7 @@ _SIGS = {
     "urso_quat_wavg_decode": (_i, [_i, _i, _fp, _fp, _fp, _fp, _vp]),
     "urso_quat_gmm_fit": (_i, [_i, _i, _fp, _i, _fp, _f, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp]),
     "urso_pose_eval": (_i, [C.POINTER(PoseEvalArgs), _vp]),
+    "urso_pose_decode": (_i, [C.POINTER(PoseDecodeArgs), _vp]),
     "urso_warp_perspective": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "urso_encode_ori": (_i, [_i, _i, _vp, _fp, _vp, C.c_double, _fp, _vp]),
     "urso_encode_loc": (_i, [_i, _i, _vp, _vp, C.c_double, _fp, _vp]),
@@ -674,6 +687,26 @@ def pose_eval(B, n, row0, loc_mode, ori_mode, loc, ori, loc_gt, q_gt, table, ori
     a.gmm_mean, a.gmm_nmodes = ptr(gmm_mean), ptr(gmm_nmodes)
     a.gmm_modes = 0 if gmm_mean is None else gmm_mean.shape[1]
     _chk(_lib.urso_pose_eval(C.byref(a), stream_ptr(stream)), "urso_pose_eval")
+
+
+def pose_decode(B, n, row0, loc_mode, ori_mode, loc, ori, table, ori2=None, loc_map=None, ori_logits=None, ori_map_rows=0, ori_scatter=None,
+                stream=None):
+    """urso_pose_decode on one batch (no ground truth): loc / ori / ori2 / ori_logits are fp32 device tensors with contiguous rows,
+    ori_scatter is urso_quat_wavg_decode's a_d [B, 16], ori_map_rows the rows of the bin map the logits index; table is fp64
+    [rows, DEC_COLS]."""
+    a = PoseDecodeArgs()
+    a.B, a.n, a.row0, a.loc_mode, a.ori_mode = int(B), int(n), int(row0), int(loc_mode), int(ori_mode)
+    a.loc, a.loc_ld = _rows(loc)
+    a.ori, a.ori_ld = _rows(ori)
+    a.ori2 = _rows(ori2)[0]
+    a.loc_map = ptr(loc_map)
+    a.loc_map_rows = 0 if loc_map is None else loc_map.shape[0]
+    a.loc_bins = loc.shape[1] if loc_mode == EVAL_LOC_CLASS else 0
+    a.ori_logits, a.ori_logits_ld = _rows(ori_logits)
+    a.ori_bins = 0 if ori_logits is None else ori_logits.shape[1]
+    a.ori_map_rows = int(ori_map_rows)
+    a.ori_scatter, a.table = ptr(ori_scatter), ptr(table)
+    _chk(_lib.urso_pose_decode(C.byref(a), stream_ptr(stream)), "urso_pose_decode")
 
 
 def warp_perspective(B, H, W, Cc, interp, src, m, dst, stream=None):
