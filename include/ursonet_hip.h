@@ -501,7 +501,11 @@ int urso_stem_conv_pool(const urso_conv_geom* g, int dt, const void* x_d, const 
  * in bit 4, whether the window maximum is <= 0.
  * bwd: dx[b,iy,ix,c] = sum over windows whose arg-max is (iy,ix) of dy; with relu_mask=1 windows
  * whose maximum is <= 0 contribute nothing (the ReLU in front of the pool, net.py:173) -- read from bit 4 of the arg-max byte:
- * y_d is not read (kept in the signature; may be NULL). */
+ * y_d is not read (kept in the signature; may be NULL).
+ * Both reject (URSO_EINVAL, "too large for 32-bit indexing") a tensor whose B * H/2 * W/2 * C/VE (VE = elements per 16 bytes) reaches 2^31 - 1;
+ * fwd also one whose count padded to its 4 x 8 output-pixel tiles, B * ceil(H/8) * ceil(W/16) * 32 * C/VE -- what its kernel iterates,
+ * up to 32x the former on small maps -- does (it used to wrap there: B = 2^22, H = W = 2, C = 256 in a 16-bit type launched a loop of 0
+ * iterations and returned URSO_OK with nothing written). */
 int urso_maxpool3x3s2_fwd(int B, int H, int W, int C, int dt, const void* x_d, void* y_d,
                           uint8_t* argmax_d, void* stream);
 int urso_maxpool3x3s2_bwd(int B, int H, int W, int C, int dt, const void* y_d, const void* dy_d,

@@ -277,12 +277,13 @@ def invert3x3(M):
     return adj * (1.0 / det)
 
 
-def warp_perspective(image, M, inverse_map=False, interp="linear"):
+def warp_perspective(image, M, inverse_map=False, interp="linear", rows=None):
     """cv2.warpPerspective(image, M, (W, H), flags=interp | (WARP_INVERSE_MAP if inverse_map)) for uint8 images,
     constant-0 border.  Per destination pixel (Python loop over pixels: the checker, small images only).
       nearest: src(cvRound(X/W), cvRound(Y/W));
       linear : coordinates quantised to 1/32 pixel (cvRound(32 X/W)), taps weighted by the 15-bit table
-               w = round((1-ax/32)(1-ay/32) 2^15) ..., result (sum + 2^14) >> 15; taps outside the image read 0."""
+               w = round((1-ax/32)(1-ay/32) 2^15) ..., result (sum + 2^14) >> 15; taps outside the image read 0.
+    rows: evaluate these destination rows only (the others stay 0): a sample of a full-size frame in affordable time."""
     image = np.asarray(image)
     assert image.dtype == np.uint8
     H, W = image.shape[:2]
@@ -296,7 +297,7 @@ def warp_perspective(image, M, inverse_map=False, interp="linear"):
             return image[yy, xx].astype(np.int64)
         return np.zeros(image.shape[2:], dtype=np.int64)
 
-    for y in range(H):
+    for y in (range(H) if rows is None else rows):
         for x in range(W):
             X = Mi[0, 0] * x + Mi[0, 1] * y + Mi[0, 2]
             Y = Mi[1, 0] * x + Mi[1, 1] * y + Mi[1, 2]

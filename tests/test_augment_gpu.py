@@ -209,10 +209,19 @@ def test_sim2real_stages_against_numpy_restatement():
                     torch.as_tensor(masks.astype(np.uint8)).cuda(), 15)
     torch.cuda.synchronize()
     o = out.cpu().numpy(); gi = g.cpu().numpy()
+    import inputref as R
     for b in range(B):
         ref = _s2r_ref(gi[b], int(codes[b]), par[b], masks[b].reshape(3, 5))
+        if codes[b] == 1:
+            # blur: equal to the float64 reference, except by one level where that lies within the derived delta of a .5 tie (fp32 summation);
+            # a uniform one-level offset no longer passes (tests/test_inputref_cpu.py::test_uniform_one_level_offset_is_no_longer_accepted)
+            ref64, un = R.sim2real_stage(gi[b], 1, par[b])
+            delta = R.delta_blur(par[b, 0])
+            R.assert_equal_off_ties(o[b], ref64, un, delta, 4 * delta, "blur sigma %g" % par[b, 0])
+            assert np.abs(ref.astype(int) - ref64.astype(int)).max() <= 1
+            continue
         d = np.abs(o[b].astype(int) - ref.astype(int)).max()
-        assert d <= (1 if codes[b] == 1 else 0), (b, int(codes[b]), d)       # blur: fp32 summation order may move a .5 tie by one level
+        assert d == 0, (b, int(codes[b]), d)
     # noise
     flat = torch.full((2, 64, 64, 3), 128, dtype=torch.uint8, device="cuda"); outn = torch.empty_like(flat)
     hip.sim2real_op(2, 64, 64, flat, outn, torch.zeros(2, dtype=torch.int32, device="cuda"),

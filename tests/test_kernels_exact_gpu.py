@@ -489,6 +489,21 @@ def test_maxpool_ties_and_relu_mask(shape, dt, exact):
     """Post-ReLU-like integers with many positive ties and zero windows: values, arg-max bytes (first maximum wins, bit 4 =
     window maximum <= 0) and the backward pass (sum of <= 4 window gradients per pixel, nothing through a window whose maximum
     is <= 0)."""
+    _maxpool_case(shape, dt, exact)
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+def test_maxpool_grid_stride(exact):
+    """The same probe at (16, 256, 320, 64) in bf16: 2.6 M channel vectors against 8192 x 256 threads, so that both kernels' stride loops and
+    the (b, tile, pixel, vector) decomposition of a large index run.  pool_loss_optim.hip, pool_blocks(): `size_t b = (total + 255) / 256;
+    return (int)(b > 8192 ? 8192 : ...)` with total = B * H/2 * W/2 * C/VE, and the kernels' `i += gridDim.x * blockDim.x`."""
+    B, H, W, C = shape = (16, 256, 320, 64)
+    total = B * (H // 2) * (W // 2) * (C // 8)
+    assert -(-total // (min((total + 255) // 256, 8192) * 256)) >= 2
+    _maxpool_case(shape, 1, exact)
+
+
+def _maxpool_case(shape, dt, exact):
     hip = _hip()
     B, H, W, C = shape
     OH, OW = H // 2, W // 2
@@ -549,10 +564,15 @@ def test_rows_subsample_expand_scatter(shape):
     assert torch.equal(sc.cpu(), want), "rows_scatter2: %d bytes wrong (odd pixels must stay untouched)" % int((sc.cpu() != want).sum())
 
 
-@pytest.mark.parametrize("geo", [(2, 5, 7, 3, 8, 12, 1, 2), (1, 30, 17, 3, 64, 64, 17, 0), (3, 16, 16, 1, 16, 16, 0, 0)])
+@pytest.mark.parametrize("geo", [(2, 5, 7, 3, 8, 12, 1, 2), (1, 30, 17, 3, 64, 64, 17, 0), (3, 16, 16, 1, 16, 16, 0, 0),
+                                 (8, 480, 640, 3, 512, 640, 16, 0), (2, 1200, 1920, 1, 1920, 1920, 360, 0)])
 def test_pad_images_u8(geo):
     hip = _hip()
     B, H, W, Cc, OH, OW, top, left = geo
+    # augment.hip, urso_pad_images_u8: `int bx = (int)((n + 255) / 256); if (bx > 2048) bx = 2048;` with n = OH * OW * C bytes per image, and
+    # place_kernel's `i += (size_t)gridDim.x * blockDim.x`: the two frame-sized cases walk the stride loop twice and eight times
+    n = OH * OW * Cc
+    assert (-(-n // (min((n + 255) // 256, 2048) * 256)) >= 2) == (H >= 480)
     src = X.rand_bits(B * H * W * Cc, 3).reshape(B, H, W, Cc)
     dst = torch.full((B, OH, OW, Cc), 0xA5, dtype=torch.uint8, device="cuda")
     hip.pad_images_u8(B, H, W, Cc, OH, OW, top, left, src.cuda(), dst)

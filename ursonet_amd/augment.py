@@ -201,10 +201,11 @@ def sim2real_draw(n, height, width, rng=np.random, prng=None):
     return {"apply": apply, "order": order, "par": par, "seeds": seeds, "masks": masks}
 
 
-def sim2real_batch(images, draw=None, rng=np.random):
+def sim2real_batch(images, draw=None, rng=np.random, trace=None):
     """net.py:390-406 for a uint8 batch [B,H,W,3] (array or device tensor): grey conversion, then for the samples whose dice say
     so the five imgaug stages in their drawn order -- five passes of urso_sim2real_op over the batch, ping-ponging two HBM
-    buffers.  Returns a uint8 CUDA tensor."""
+    buffers.  Returns a uint8 CUDA tensor.  trace (tests only): a list that receives a copy of the grey batch and of the batch after each
+    of the five launches."""
     import torch
     from . import hip
     x = torch.as_tensor(images)
@@ -214,6 +215,8 @@ def sim2real_batch(images, draw=None, rng=np.random):
     d = draw if draw is not None else sim2real_draw(B, H, W, rng)
     a, b = torch.empty_like(x), torch.empty_like(x)
     hip.rgb_to_grey3(B, H, W, x, a)
+    if trace is not None:
+        trace.append(a.clone())
     if not d["apply"].any():
         return a
     stride = max(m.size for m in d["masks"])
@@ -227,6 +230,8 @@ def sim2real_batch(images, draw=None, rng=np.random):
         par = np.stack([d["par"][i, d["order"][i, slot]] for i in range(B)]).astype(np.float32)
         hip.sim2real_op(B, H, W, a, b, torch.as_tensor(ops).cuda(), torch.as_tensor(par).cuda(), seed_d, drop_d, stride)
         a, b = b, a
+        if trace is not None:
+            trace.append(a.clone())
     return a
 
 

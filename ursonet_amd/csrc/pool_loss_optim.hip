@@ -114,7 +114,9 @@ extern "C" int urso_maxpool3x3s2_fwd(int B, int H, int W, int C, int dt, const v
     if (!x_d || !y_d || B <= 0 || (H & 1) || (W & 1) || C % VE) { urso_set_error("urso_maxpool3x3s2_fwd: bad argument (H,W even; C multiple of %d)", VE); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / VE);
-    if (total >= 0x7FFFFFFFull) { urso_set_error("urso_maxpool3x3s2_fwd: tensor too large for 32-bit indexing"); return URSO_EINVAL; }
+    // the kernel walks the TILE-PADDED count (4 x 8 output-pixel tiles: up to 32x `total` on small maps) in a uint32_t
+    const size_t padded = (size_t)B * ((H / 2 + 3) >> 2) * ((W / 2 + 7) >> 3) * 32u * (size_t)(C / VE);
+    if (total >= 0x7FFFFFFFull || padded >= 0x7FFFFFFFull) { urso_set_error("urso_maxpool3x3s2_fwd: tensor too large for 32-bit indexing"); return URSO_EINVAL; }
     ProfScope ps(st, URSO_K_POOL, 0, (double)B * H * W * C * dt_size(dt) * 1.25 + (double)B * H * W * C / 4);
     if (dt == URSO_F32) URSO_KLAUNCH((maxpool_fwd_kernel<float>), dim3(pool_blocks(total)), dim3(256), 0, st, B, H, W, C, (const float*)x_d, (float*)y_d, argmax_d);
     else if (dt == URSO_BF16) URSO_KLAUNCH((maxpool_fwd_kernel<__bf16>), dim3(pool_blocks(total)), dim3(256), 0, st, B, H, W, C, (const __bf16*)x_d, (__bf16*)y_d, argmax_d);
