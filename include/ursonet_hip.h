@@ -740,6 +740,26 @@ int urso_resize_images_u8(int B, int H, int W, int C, int NH, int NW, int OH, in
                           const int32_t* x0_d, const double* fx_d, int trunc_passes, const uint8_t* src_d, uint8_t* dst_d, void* stream);
 
 /*
+ * Device-resident cache of RAW uint8 RGB frames (ursonet_amd/frame_cache.py, Config.DEVICE_CACHE_GB): pure byte movement.  A frame is a
+ * flat array of HW pixels; a batch is uint8 [B][HW][3].  A GREY frame (R == G == B at every pixel) is stored as one plane of HW bytes,
+ * any other frame as its 3 HW bytes.  The address tables hold absolute device addresses (uint64 [B]) and are built by the Python cache
+ * object alone, from its own slab tensors; any alignment works, 16-byte aligned addresses with HW a multiple of 16 take the all-vector
+ * path.  kind_d is uint8 [B]: 0 grey plane, 1 RGB, anything else = skip the slot (no memory of it is read or written).
+ *   urso_frames_grey_flags_u8  flags_d[b] = 1 iff every pixel of frame b of src_d has R == G == B, else 0 (integer reduction, the same
+ *                              result in any launch order; flags_d may sit at any address and only its B bytes are written).
+ *   urso_frames_put_u8         frame b of src_d -> dst_addr_d[b]: kind 0 stores channel 0 (HW bytes), kind 1 all 3 HW bytes.
+ *   urso_frames_gather_u8      slot b of dst_d <- src_addr_d[b]: kind 0 expands a grey plane (every byte three times), kind 1 copies
+ *                              3 HW bytes.  Several slots may name the same source; a source may be a cache slot or a frame of a
+ *                              freshly uploaded batch.  A source must not overlap dst_d.
+ * URSO_EINVAL before any launch: a negative size, a null pointer or table, B > 65535 or 3 HW >= 2^31.  B = 0 or HW = 0 launches nothing
+ * (urso_frames_grey_flags_u8 with HW = 0: every flag 1).  The launch profiler books all three under URSO_K_MOLD with the byte count of
+ * an all-RGB batch (6 HW per slot), an upper bound: the kinds are device data.
+ */
+int urso_frames_grey_flags_u8(int B, int HW, const uint8_t* src_d, uint8_t* flags_d, void* stream);
+int urso_frames_put_u8(int B, int HW, const uint8_t* src_d, const uint64_t* dst_addr_d, const uint8_t* kind_d, void* stream);
+int urso_frames_gather_u8(int B, int HW, const uint64_t* src_addr_d, const uint8_t* kind_d, uint8_t* dst_d, void* stream);
+
+/*
  * Opt-in launch profiler: when enabled every urso_* launch is bracketed by HIP events on
  * its stream.  urso_prof_collect() synchronises and returns per-record milliseconds.
  */

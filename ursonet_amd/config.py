@@ -57,6 +57,12 @@ class Config(object):
     # Not a reference field: True = uint8 RGB frames of one size are rescaled and padded on the GPU (augment.resize_images, byte-exact to
     # utils.resize_image) by the feeders, detect() and evaluate(); False = the host path (utils.resize_image), call for call as before.
     DEVICE_RESIZE = False
+    # Not a reference field: > 0 = budget in GiB of a device-resident cache of RAW frames (ursonet_amd/frame_cache.py).  Every frame that
+    # takes the DEVICE_RESIZE path is decoded and uploaded once and served from HBM from the second epoch on; needs DEVICE_RESIZE = True
+    # (ValueError otherwise) and a dataset whose load_image(i) always returns the same frame.  The budget is spent in whole slabs of 1 GiB,
+    # each holding either grey frames (one plane) or RGB frames: give a dataset that has both at least 2.  The budget is PER FEEDER:
+    # UrsoNet.train owns a training and a validation feeder, so up to 2 x DEVICE_CACHE_GB of HBM per rank.  0 = off: nothing changes.
+    DEVICE_CACHE_GB = 0
 
     def update(self):
         """Derived fields (config.py:151-166)."""

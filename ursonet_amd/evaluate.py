@@ -102,11 +102,13 @@ def _check(model, dataset, multimodal, who="evaluate"):
     return soft
 
 
-def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None):
+def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None):
     """pose_estimator.evaluate(model, dataset): prints the reference's four summary lines (verbose > 0), writes ori_err.csv,
     loc_err.csv and dists_err.csv into out_dir and returns an EvalResult.  multimodal=True (soft classification only) fits up to
     three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 / 12, 5 iterations, nr_max_modes 4) and
-    takes mode 0 if it is the only one or closer to the truth than mode 1, else mode 1 (the commented block of :410-426)."""
+    takes mode 0 if it is the only one or closer to the truth than mode 1, else mode 1 (the commented block of :410-426).
+    cache: a frame_cache.FrameCache of the caller's (Config.DEVICE_RESIZE only) that keeps this dataset's raw frames on the device, so
+    that the next call with it -- the next checkpoint, say -- loads no image again; the table is the same with and without it."""
     soft = _check(model, dataset, multimodal)
     import torch
     from . import hip
@@ -130,7 +132,7 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
             var = (cfg.BETA / cfg.ORI_BINS_PER_DIM) ** 2 / 12                      # :333-334
     if workers is None:
         workers = int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1)))
-    feed = EvalFeeder(model, dataset, cfg, enc_loc=loc_enc, enc_ori=soft, workers=workers)
+    feed = EvalFeeder(model, dataset, cfg, enc_loc=loc_enc, enc_ori=soft, workers=workers, cache=cache)
     try:
         for bt in feed:
             if bt.images.dtype == torch.uint8:

@@ -39,9 +39,10 @@ class Sample(object):
         self.image_id, self.image, self.loc, self.ori, self.k1, self.k2 = image_id, image, loc, ori, k1, k2
 
 
-def load_sample(dataset, config, image_id):
-    """The host-only first third of load_image_gt (net.py:367-388): frame and targets, no augmentation, no resize."""
-    image = dataset.load_image(image_id)
+def load_sample(dataset, config, image_id, with_image=True):
+    """The host-only first third of load_image_gt (net.py:367-388): frame and targets, no augmentation, no resize.
+    with_image=False (Config.DEVICE_CACHE_GB: the frame is resident on the device) skips dataset.load_image; `image` is then None."""
+    image = dataset.load_image(image_id) if with_image else None
     loc = dataset.load_location(image_id) if config.REGRESS_LOC else dataset.load_location_encoded(image_id)
     k1 = k2 = None
     if config.REGRESS_KEYPOINTS:
@@ -75,7 +76,8 @@ def augment_samples(samples, dataset, config, frames=None):
 
     frames (DEVICE_RESIZE): a uint8 device tensor [n,H,W,3] that holds the samples' frames, all of one size.  The pixel work then reads and
     writes device memory only -- same draws, same kernels, no copy back -- the samples' `image` fields are left alone, and the tensor of
-    the augmented frames is RETURNED instead of the list."""
+    the augmented frames is RETURNED instead of the list.  The frame size is the tensor's: the samples need not carry an image
+    (Config.DEVICE_CACHE_GB: frames served from the device cache were never loaded)."""
     if not samples:
         return samples if frames is None else frames
     from . import augment
@@ -84,14 +86,17 @@ def augment_samples(samples, dataset, config, frames=None):
         assert config.REGRESS_LOC
         assert config.ORIENTATION_PARAM == 'quaternion'
     n = len(samples)
-    h, w = samples[0].image.shape[:2]
-    same_size = all(s.image.shape == samples[0].image.shape for s in samples)
+    if frames is not None:
+        shapes, same_size = [tuple(frames.shape[1:])] * n, True
+    else:
+        shapes = [s.image.shape for s in samples]
+        same_size = all(sh == shapes[0] for sh in shapes)
     draws, pyr, warp_ids = None, np.zeros((n, 3)), []
     if config.SIM2REAL_AUG:
         draws = []
     for i, s in enumerate(samples):
         if config.SIM2REAL_AUG:
-            draws.append(augment.sim2real_draw(1, s.image.shape[0], s.image.shape[1], prng=augment._PIPELINE_RNG))
+            draws.append(augment.sim2real_draw(1, shapes[i][0], shapes[i][1], prng=augment._PIPELINE_RNG))
         if rot:
             dice = np.random.rand(1)
             if config.ROT_AUG and dice > 0.5:
@@ -157,20 +162,50 @@ def device_resize_applies(images, config):
     return all(getattr(im, "dtype", None) == np.uint8 and im.ndim == 3 and im.shape[-1] == 3 and im.shape == shape for im in images)
 
 
+def _device_resize_mode(config):
+    return bool(getattr(config, "DEVICE_RESIZE", False)) and config.IMAGE_RESIZE_MODE in ("square", "pad64")
+
+
+def check_cache_config(config):
+    """Config.DEVICE_CACHE_GB caches the RAW frames Config.DEVICE_RESIZE uploads: without that path there is nothing to cache."""
+    if float(getattr(config, "DEVICE_CACHE_GB", 0) or 0) > 0 and not getattr(config, "DEVICE_RESIZE", False):
+        raise ValueError("Config.DEVICE_CACHE_GB = %r needs Config.DEVICE_RESIZE = True: the device cache holds the raw frames that "
+                         "DEVICE_RESIZE uploads and resizes on the GPU" % (config.DEVICE_CACHE_GB,))
+
+
+def cache_split(chosen, dataset, config, cache):
+    """Config.DEVICE_CACHE_GB, one batch of samples of which those the cache holds carry no image: the samples whose frames have to go
+    up (the misses) when the batch can be assembled on the device -- the misses are uint8 RGB frames of the cache's size, modes
+    square / pad64 -- else None: the batch keeps the host path, and batches() first loads the images that were skipped."""
+    missed = [s for s in chosen if s.image is not None]
+    images = [s.image for s in missed]
+    if _device_resize_mode(config) and (not missed or (device_resize_applies(images, config) and cache.accepts(images[0].shape))):
+        return missed
+    return None
+
+
 class RawUploader(object):
     """DEVICE_RESIZE: a list of same-size uint8 frames [H,W,3] -> one host copy into a REUSED pinned buffer (two of them, alternating: a
     buffer is refilled only after the upload that last read it has run) -> `device` on this object's own stream -> `augment_fn` on the device
     tensor -> augment.resize_images.  Returns (uint8 CUDA tensor [B,OH,OW,3], window, scale, an event recorded behind that work, bytes of
     one pinned buffer).  The host copy runs outside hip.capture_lock; the lock is held where HIP is entered (no call while another thread
-    captures a hipGraph): allocation, waiting for a buffer, and enqueueing the batch's copies and kernels."""
+    captures a hipGraph): allocation, waiting for a buffer, and enqueueing the batch's copies and kernels.
+
+    cache (Config.DEVICE_CACHE_GB, frame_cache.FrameCache): `frames` are then only the frames of `staged_ids`, the images of the batch
+    `ids` that the cache does not hold.  Only they are pinned and uploaded (none: no pinned buffer is touched); the batch tensor is
+    FrameCache.assemble's -- resident frames and the fresh upload gathered by one kernel, the new frames stored on the way -- and the
+    augmentation and the resize run on it as on an uploaded batch.  The pinned buffers keep the capacity of a whole batch; the byte
+    count returned is that of the frames this batch really put into pinned memory."""
 
     def __init__(self, device=None):
         self.device, self.stream, self.k = device, None, 0
         self.slots = [None, None]                              # [pinned tensor, event behind its last upload]
 
-    def __call__(self, frames, config, augment_fn=None):
+    def __call__(self, frames, config, augment_fn=None, cache=None, ids=None, staged_ids=None):
         import torch
         from . import augment
+        if cache is not None:
+            return self._cached(frames, config, augment_fn, cache, ids, staged_ids)
         shape = (len(frames),) + tuple(frames[0].shape)
         i = self.k & 1
         self.k += 1
@@ -196,6 +231,45 @@ class RawUploader(object):
             ready = torch.cuda.Event()
             ready.record()
         return out, window, scale, ready, slot[0].numel()
+
+    def _cached(self, frames, config, augment_fn, cache, ids, staged_ids):
+        import torch
+        from . import augment
+        M = len(frames)
+        assert M == len(staged_ids)
+        slot = None
+        if M:
+            cap = (len(ids),) + tuple(frames[0].shape)         # a whole batch: the number of misses changes from batch to batch
+            i = self.k & 1
+            self.k += 1
+            slot = self.slots[i]
+        with _hip_section():
+            if self.stream is None:
+                self.stream = torch.cuda.Stream(device=self.device)
+            if M:
+                if slot is None or tuple(slot[0].shape[1:]) != cap[1:] or slot[0].shape[0] < M:
+                    slot = self.slots[i] = [torch.empty(cap, dtype=torch.uint8).pin_memory(), None]
+                elif slot[1] is not None:
+                    slot[1].synchronize()
+        if M:
+            host = slot[0].numpy()
+            for b, f in enumerate(frames):
+                host[b] = f
+        with _hip_section(), torch.cuda.stream(self.stream):
+            staged, nbytes = None, 0
+            if M:
+                staged = slot[0][:M].to(self.stream.device, non_blocking=True)
+                slot[1] = torch.cuda.Event()
+                slot[1].record()
+                nbytes = staged.numel()
+            dev = cache.assemble(ids, staged, staged_ids)
+            if augment_fn is not None:
+                dev = augment_fn(dev)
+            out, window, scale, _padding = augment.resize_images(dev, min_dim=config.IMAGE_MIN_DIM, max_dim=config.IMAGE_MAX_DIM,
+                                                                 min_scale=config.IMAGE_MIN_SCALE, mode=config.IMAGE_RESIZE_MODE)
+            ready = torch.cuda.Event()
+            ready.record()
+        return out, window, scale, ready, nbytes
 
 
 def finish_sample(sample, config):
@@ -247,7 +321,7 @@ class BatchAssembler(object):
 DP_SHUFFLE_SEED = 1234
 
 
-def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, world=1, device=None):
+def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, world=1, device=None, cache=None):
     """Endless iterator of BatchAssembler objects.  molded=True: images are mean-subtracted floats (the reference's generator
     format); False: uint8 frames for the device path.  Up to 5 failing samples are logged and skipped, the 6th re-raises
     (net.py:553-559).  workers > 0 loads the raw samples of a batch with that many threads.
@@ -258,8 +332,15 @@ def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, wor
     single process with GPU_COUNT = world would have drawn.  The global RNG (augmentation draws) is seeded with DP_SHUFFLE_SEED + rank so
     that the ranks do not apply identical warps to their different samples.  world == 1 is the reference's generator, draw for draw.
 
-    device: the card Config.DEVICE_RESIZE uploads the raw frames to and resizes them on (None: the calling thread's current device)."""
+    device: the card Config.DEVICE_RESIZE uploads the raw frames to and resizes them on (None: the calling thread's current device).
+
+    cache (frame_cache.FrameCache, molded=False only; DeviceFeeder makes one when Config.DEVICE_CACHE_GB > 0): the order, the draws and the
+    label lookups are unchanged, but dataset.load_image is called only for the images the cache does not hold, only those are pinned and
+    uploaded, and the batch is assembled on the device (RawUploader).  Batches DEVICE_RESIZE does not take keep the host path, uncached."""
     from .net import mold_image
+    check_cache_config(config)
+    if molded:
+        cache = None
     ids = np.copy(dataset.image_ids)
     cursor, errors = -1, 0
     order_rng = None
@@ -273,9 +354,9 @@ def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, wor
     ft = np.float16 if config.F16 else np.float32
     uploader = RawUploader(device)                              # DEVICE_RESIZE: pinned buffers + the producer's own stream (upload, augmentation, resize)
 
-    def safe_load(image_id):
+    def safe_load(image_id, whole=False):
         try:
-            return load_sample(dataset, config, image_id)
+            return load_sample(dataset, config, image_id, with_image=whole or cache is None or not cache.has(image_id))
         except (GeneratorExit, KeyboardInterrupt):
             raise
         except Exception:
@@ -291,23 +372,49 @@ def batches(dataset, config, shuffle, batch_size, molded, workers=0, rank=0, wor
         chosen = []
         for _ in range(rank * batch_size if world > 1 else 0):      # the samples of this global batch that belong to the ranks before this one
             advance()
-        while len(chosen) < batch_size:
-            want = batch_size - len(chosen)
-            todo = [advance() for _ in range(want)]
-            loaded = list(pool.map(safe_load, todo)) if pool is not None else [safe_load(i) for i in todo]
-            for s in loaded:
+        missed = None
+        while True:
+            while len(chosen) < batch_size:
+                want = batch_size - len(chosen)
+                todo = [advance() for _ in range(want)]
+                loaded = list(pool.map(safe_load, todo)) if pool is not None else [safe_load(i) for i in todo]
+                for s in loaded:
+                    if s is None:
+                        errors += 1
+                        if errors > 5:
+                            raise RuntimeError("more than 5 samples failed to load (net.py:553-559)")
+                    else:
+                        chosen.append(s)
+            if cache is None:
+                break
+            missed = cache_split(chosen, dataset, config, cache)
+            skipped = [k for k, s in enumerate(chosen) if s.image is None]
+            if missed is not None or not skipped:
+                break
+            # the host path for this batch (mixed sizes ...): the frames the cache made us skip are loaded after all, by the same loader --
+            # in the pool, a failure logged, counted and the sample replaced by the next one, like any other
+            todo = [chosen[k].image_id for k in skipped]
+            whole = lambda i: safe_load(i, True)
+            loaded = list(pool.map(whole, todo)) if pool is not None else [whole(i) for i in todo]
+            for k, s in zip(skipped, loaded):
+                chosen[k] = s
                 if s is None:
                     errors += 1
                     if errors > 5:
                         raise RuntimeError("more than 5 samples failed to load (net.py:553-559)")
-                else:
-                    chosen.append(s)
+            chosen = [s for s in chosen if s is not None]
         for _ in range((world - 1 - rank) * batch_size if world > 1 else 0):     # ... and to the ranks behind it
             advance()
-        if not molded and device_resize_applies([s.image for s in chosen], config):
-            shape = chosen[0].image.shape
-            out, window, scale, ready, nbytes = uploader([s.image for s in chosen], config,
-                                                         lambda dev: augment_samples(chosen, dataset, config, frames=dev))
+        if missed is not None or (not molded and device_resize_applies([s.image for s in chosen], config)):
+            if missed is not None:
+                out, window, scale, ready, nbytes = uploader([s.image for s in missed], config,
+                                                             lambda dev: augment_samples(chosen, dataset, config, frames=dev), cache=cache,
+                                                             ids=[s.image_id for s in chosen], staged_ids=[s.image_id for s in missed])
+                shape = cache.frame_shape
+            else:
+                shape = chosen[0].image.shape
+                out, window, scale, ready, nbytes = uploader([s.image for s in chosen], config,
+                                                             lambda dev: augment_samples(chosen, dataset, config, frames=dev))
             metas = [compose_image_meta(s.image_id, shape, tuple(out.shape[1:]), window, scale) for s in chosen]
             asm = BatchAssembler(config, batch_size, tuple(out.shape[1:]), len(metas[0]), np.uint8, host_images=False)
             asm.device_images, asm.ready, asm.raw_pinned_bytes = out, ready, nbytes
@@ -331,7 +438,9 @@ class DeviceFeeder(object):
     engine's input buffers hold the next batch (device-to-device copy ordered after the upload by an event)."""
 
     def __init__(self, engine, dataset, config, shuffle=True, workers=4, depth=3, rank=0, world=1):
+        check_cache_config(config)
         import torch
+        from .frame_cache import FrameCache
         self.eng, self.torch = engine, torch
         self.q = queue.Queue(maxsize=depth)
         self.stop = False
@@ -342,7 +451,9 @@ class DeviceFeeder(object):
         self.consumed = [None, None]                           # recorded on the compute stream once a slot's batch has been copied out of it
         self.k = 0
         self.pinned_bytes = 0
-        gen = batches(dataset, config, shuffle, engine.B, molded=False, workers=workers, rank=rank, world=world, device=engine.device)
+        self.cache = FrameCache.from_config(config, engine.device)      # Config.DEVICE_CACHE_GB: this feeder's own, in this rank's HBM
+        gen = batches(dataset, config, shuffle, engine.B, molded=False, workers=workers, rank=rank, world=world, device=engine.device,
+                      cache=self.cache)
 
         def produce():
             from . import hip
@@ -441,12 +552,19 @@ class EvalFeeder(object):
     of a double buffer while batch k is used.  A batch's staging slot is reused only after the work the consumer put on the current
     stream while holding it (the forward pass and the scoring kernels) has run.  `loc_dtype` is the dtype of the dataset's locations.
     With labels=False (predict(): datasets without ground truth) no label loader of the dataset is called, only load_image, and the
-    batches' `loc_gt` / `q_gt` are None; everything else is the same code."""
+    batches' `loc_gt` / `q_gt` are None; everything else is the same code.
+    cache (frame_cache.FrameCache, the caller's: it outlives this feeder): images it holds are not loaded again -- load_image is called for
+    the others only, they alone are pinned and uploaded, and the cache keeps them -- so a caller that evaluates one dataset repeatedly
+    (once per checkpoint) with the same cache pays the decode once.  Needs Config.DEVICE_RESIZE; batches that path does not take (other
+    dtypes, mixed sizes, 'crop') stay on the host path, uncached."""
 
-    def __init__(self, model, dataset, config, enc_loc=False, enc_ori=False, workers=4, depth=3, labels=True):
+    def __init__(self, model, dataset, config, enc_loc=False, enc_ori=False, workers=4, depth=3, labels=True, cache=None):
         import torch
         from concurrent.futures import ThreadPoolExecutor
         assert labels or not (enc_loc or enc_ori), "the encoded targets are labels"
+        check_cache_config(config)
+        if cache is not None and not getattr(config, "DEVICE_RESIZE", False):
+            raise ValueError("a frame cache (Config.DEVICE_CACHE_GB) needs Config.DEVICE_RESIZE = True")
         self.torch, self.eng = torch, model._engine
         self.plan = eval_batch_plan(dataset.image_ids, self.eng.B)
         self.q = queue.Queue(maxsize=depth)
@@ -459,14 +577,17 @@ class EvalFeeder(object):
         uploader = RawUploader(self.eng.device)                # DEVICE_RESIZE: pinned buffers + the producer's own stream (raw upload, resize)
         pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
 
-        def load(image_id):
-            image = dataset.load_image(image_id)
+        def load(image_id, use_cache=True):
+            held = use_cache and cache is not None and cache.has(image_id)
+            image = None if held else dataset.load_image(image_id)
             loc = np.asarray(dataset.load_location(image_id)) if labels else None
             q = np.asarray(dataset.load_quaternion(image_id), dtype=np.float64) if labels else None
             el = np.asarray(dataset.load_location_encoded(image_id), dtype=np.float32) if enc_loc else None
             eo = np.asarray(dataset.load_orientation_encoded(image_id), dtype=np.float32) if enc_ori else None
             kind = "float"                                      # not uint8 RGB: molded on the host, as detect does for such frames
-            if getattr(image, "dtype", None) == np.uint8 and image.ndim == 3 and image.shape[-1] == 3:
+            if held:
+                kind = "cached"                                 # resident on the device: gathered per batch by the producer
+            elif getattr(image, "dtype", None) == np.uint8 and image.ndim == 3 and image.shape[-1] == 3:
                 kind = "raw"                                    # DEVICE_RESIZE: finished per batch by the producer
                 if not device_resize_applies([image], config):
                     kind, image = "u8", finish_sample(Sample(image_id, image, None, None), config)[0]
@@ -479,11 +600,22 @@ class EvalFeeder(object):
                     if self.stop:
                         return
                     got = dict(zip(slots[:n], pool.map(load, slots[:n])))
+                    cached_ok = False
+                    if cache is not None:
+                        raw_ids = [i for i in got if got[i][0] == "raw"]
+                        raws = [got[i][1] for i in raw_ids]
+                        cached_ok = (all(r[0] in ("raw", "cached") for r in got.values()) and _device_resize_mode(config) and
+                                     (not raws or (device_resize_applies(raws, config) and cache.accepts(raws[0].shape))))
+                        if not cached_ok:                       # the host path for this batch: its resident frames are loaded after all
+                            again = [i for i, r in got.items() if r[0] == "cached"]
+                            got.update(zip(again, pool.map(lambda i: load(i, False), again)))
                     rows = [got[i] for i in slots]
                     if self.loc_dtype is None and labels:
                         self.loc_dtype = rows[0][2].dtype
                     frames, ready = {i: r[1] for i, r in got.items()}, None
-                    if all(r[0] == "raw" for r in rows) and device_resize_applies([r[1] for r in rows], config):
+                    if cached_ok:                               # only the misses go up; one gather builds the batch, tail repeats included
+                        images, _w, _s, ready, _n = uploader(raws, config, cache=cache, ids=list(slots), staged_ids=raw_ids)
+                    elif all(r[0] == "raw" for r in rows) and device_resize_applies([r[1] for r in rows], config):
                         images, _w, _s, ready, _n = uploader([r[1] for r in rows], config)      # uint8 CUDA tensor, finished
                     else:
                         for i, r in got.items():                # DEVICE_RESIZE with mixed frame sizes: the host path for this batch

@@ -203,6 +203,9 @@ _SIGS = {
     "urso_sim2real_op": (_i, [_i, _i, _i, _vp, _vp, _vp, _fp, _vp, _vp, _i, _vp]),
     "urso_pad_images_u8": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "urso_resize_images_u8": (_i, [_i] * 10 + [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "urso_frames_grey_flags_u8": (_i, [_i, _i, _vp, _vp, _vp]),
+    "urso_frames_put_u8": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "urso_frames_gather_u8": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "urso_conv_winograd_ws_bytes": (_sz, [_gp, _i]),
     "urso_conv_winograd_fwd": (_i, [_gp, _i, _i, _vp, _vp, _fp, _vp, _vp, _sz, _vp]),
     "urso_prof_enable": (_i, [_i]),
@@ -838,6 +841,27 @@ def resize_images_u8(B, H, W, Cc, NH, NW, OH, OW, top, left, ky, ry, kx, rx, y0,
     assert all(t is None or t.dtype == torch.float64 for t in (ky, kx, fy, fx))
     _chk(_lib.urso_resize_images_u8(B, H, W, Cc, NH, NW, OH, OW, int(top), int(left), ptr(ky), int(ry), ptr(kx), int(rx), ptr(y0), ptr(fy), ptr(x0),
                                     ptr(fx), int(trunc_passes), ptr(src), ptr(dst), stream_ptr(stream)), "urso_resize_images_u8")
+
+
+def frames_grey_flags_u8(B, HW, src, flags, stream=None):
+    """urso_frames_grey_flags_u8: flags[b] (uint8 [B]) = 1 iff frame b of the uint8 batch src [B,HW,3] has R == G == B at every pixel."""
+    assert src.dtype == torch.uint8 and flags.dtype == torch.uint8 and src.numel() >= B * HW * 3 and flags.numel() >= B
+    _chk(_lib.urso_frames_grey_flags_u8(int(B), int(HW), ptr(src), ptr(flags), stream_ptr(stream)), "urso_frames_grey_flags_u8")
+
+
+def frames_put_u8(B, HW, src, dst_addr, kind, stream=None):
+    """urso_frames_put_u8: frame b of src [B,HW,3] -> device address dst_addr[b] (int64 tensor [B] holding the uint64 addresses); kind
+    (uint8 [B]) 0 = channel 0 only, 1 = all three, 2 = skip.  The addresses are ursonet_amd.frame_cache.FrameCache's, nobody else's."""
+    assert src.dtype == torch.uint8 and src.numel() >= B * HW * 3
+    assert dst_addr.dtype == torch.int64 and dst_addr.numel() >= B and kind.dtype == torch.uint8 and kind.numel() >= B
+    _chk(_lib.urso_frames_put_u8(int(B), int(HW), ptr(src), ptr(dst_addr), ptr(kind), stream_ptr(stream)), "urso_frames_put_u8")
+
+
+def frames_gather_u8(B, HW, src_addr, kind, dst, stream=None):
+    """urso_frames_gather_u8: slot b of dst [B,HW,3] <- device address src_addr[b]; kind 0 = grey plane expanded to RGB, 1 = copy, 2 = skip."""
+    assert dst.dtype == torch.uint8 and dst.numel() >= B * HW * 3
+    assert src_addr.dtype == torch.int64 and src_addr.numel() >= B and kind.dtype == torch.uint8 and kind.numel() >= B
+    _chk(_lib.urso_frames_gather_u8(int(B), int(HW), ptr(src_addr), ptr(kind), ptr(dst), stream_ptr(stream)), "urso_frames_gather_u8")
 
 
 def prof_enable(on):

@@ -38,11 +38,12 @@ class PredictResult(object):
         self.modes, self.mode_priors, self.n_modes = gmm if gmm is not None else (None, None, None)
 
 
-def predict(model, dataset, multimodal=False, workers=None):
+def predict(model, dataset, multimodal=False, workers=None, cache=None):
     """Pose estimates of every image of `dataset` -> PredictResult.  The dataset needs image_ids, load_image, image_info and, for
     the classification heads, histogram_3D_map / ori_histogram_map; no label loader is called.  multimodal=True (soft
     classification only) also fits up to three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 /
-    12, 5 iterations, nr_max_modes 4) and returns them; without a truth to pick a mode by, q_est stays the soft-argmax estimate."""
+    12, 5 iterations, nr_max_modes 4) and returns them; without a truth to pick a mode by, q_est stays the soft-argmax estimate.  cache: as in evaluate() -- a
+    frame_cache.FrameCache of the caller's that keeps the raw frames on the device between calls (Config.DEVICE_RESIZE only)."""
     soft = _check(model, dataset, multimodal, "predict")
     import torch
     from . import hip
@@ -67,7 +68,7 @@ def predict(model, dataset, multimodal=False, workers=None):
             var = (cfg.BETA / cfg.ORI_BINS_PER_DIM) ** 2 / 12
     if workers is None:
         workers = int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1)))
-    feed = EvalFeeder(model, dataset, cfg, workers=workers, labels=False)
+    feed = EvalFeeder(model, dataset, cfg, workers=workers, labels=False, cache=cache)
     try:
         for bt in feed:
             if bt.images.dtype == torch.uint8:
