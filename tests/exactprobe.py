@@ -12,7 +12,9 @@ Two ways to compare a kernel with a float64 reference of the same operation, bot
 
 int_operands() / int_plan() make the integer data; ran() asserts which kernel a call actually launched.  The references of the
 packed stem (stem_taps, stem_conv64), of the max-pool's gradient routing (pool_route), of weight gradients (wgrad64) and of
-two-segment reductions (two_segment) live here too, each with a CPU test that it rejects the fault it is there to expose.
+two-segment reductions (two_segment) live here too, each with a CPU test that it rejects the fault it is there to expose; so do
+those of the launches around a stage's first block (pair_shortcut64, pair_entry64), the tile partition of the pair launches
+(tiles_per_block), the pixel map of the compact / sampled forms (pixel_map_f32) and the Winograd operands (winograd_uv).
 
 The second half holds the float64 references and counted bounds of the step's tail (losses, global norm, optimizers, gradient
 finalisation, batch-statistics BatchNorm) that tests/test_step_tail_exact_gpu.py compares the kernels with.
@@ -285,6 +287,112 @@ def two_segment(x0, w0, x1, w1):
     """(x0 w0^T + x1 w1^T, |x0| |w0|^T + |x1| |w1|^T) in float64: ONE reduction of K0 + K1 terms, rounded once when stored."""
     d = lambda t: t.to(torch.float64)
     return d(x0) @ d(w0).T + d(x1) @ d(w1).T, d(x0).abs() @ d(w0).abs().T + d(x1).abs() @ d(w1).abs().T
+
+
+# ---- the launches around a stage's first block and its end (conv_pairs.hip, conv_pairx.hip, the sampled / compact forms of conv_pair.hip)
+def tiles_per_block(ntiles, nblocks):
+    """Tiles each block of a pair launch walks, by blockIdx.x (the kernels' own partition): XCD x = blockIdx.x & 7 owns tiles
+    [x cpx, min((x + 1) cpx, ntiles)), cpx = ceil(ntiles / 8); its nblocks / 8 blocks stride through that segment."""
+    assert nblocks >= 8 and nblocks % 8 == 0
+    bpx, cpx = nblocks // 8, -(-ntiles // 8)
+    out = []
+    for blk in range(nblocks):
+        x, lb = blk & 7, blk >> 3
+        first, end = x * cpx + lb, min((x + 1) * cpx, ntiles)
+        out.append(0 if first >= end else -(-(end - first) // bpx))
+    assert sum(out) == ntiles
+    return out
+
+
+def pair_grid_blocks(ntiles, grid_cap):
+    """Blocks of a stage-2 pair launch of `ntiles` tiles under option grid_cap (0: none), as long as the device's CU cap does not
+    bind (ntiles <= 8 x the CUs / 8): 8 x min(ceil(ntiles / 8), ceil(grid_cap / 8))."""
+    bpx = -(-ntiles // 8)
+    if grid_cap > 0:
+        bpx = min(bpx, -(-grid_cap // 8))
+    return 8 * max(bpx, 1)
+
+
+def pixel_map_f32(p, H, W):
+    """NumPy float32 restatement of the index arithmetic by which the compact-add loads and the sampled store locate pixel p of a
+    [B][H][W] grid (conv_pair.hip, conv_pairw.hip): b = int(f32(p) * f32(1 / (H W))), one +-1 correction, the same for (y, x).
+    p: int32 array.  -> (b, y, x) int32 arrays."""
+    f = np.float32
+    p = np.asarray(p, dtype=np.int32)
+    hw = np.int32(H * W)
+    w = np.int32(W)
+    rcp_hw, rcp_w = f(1.0) / f(H * W), f(1.0) / f(W)
+    b = (p.astype(f) * rcp_hw).astype(np.int32)
+    rem = p - b * hw
+    lo, hi = rem < 0, rem >= hw
+    b = b + hi.astype(np.int32) - lo.astype(np.int32)
+    rem = rem - np.where(hi, hw, 0).astype(np.int32) + np.where(lo, hw, 0).astype(np.int32)
+    y = (rem.astype(f) * rcp_w).astype(np.int32)
+    x = rem - y * w
+    lo, hi = x < 0, x >= w
+    y = y + hi.astype(np.int32) - lo.astype(np.int32)
+    x = x - np.where(hi, w, 0).astype(np.int32) + np.where(lo, w, 0).astype(np.int32)
+    return b, y, x
+
+
+def compact_to_dense(compact, H, W):
+    """[B][H/2][W/2][C] -> [B][H][W][C] with the compact rows at even (y, x) and explicit zeros elsewhere."""
+    B, _, _, C = compact.shape
+    dense = torch.zeros(B, H, W, C, dtype=compact.dtype)
+    dense[:, ::2, ::2] = compact
+    return dense
+
+
+def pair_shortcut64(src, w1, b1, xin, ws, bs):
+    """Pre-activation of the forward pair with the projection shortcut inside, src W1^T + xin Ws^T + (b1 + bs), and its magnitude:
+    ONE reduction of 128 terms + the two biases.  float64 [M][256] each."""
+    z, mag = two_segment(src, w1, xin, ws)
+    d = lambda t: t.to(torch.float64)
+    return z + d(b1) + d(bs), mag + d(b1).abs() + d(bs).abs()
+
+
+def pair_entry64(mid, w2, w3, u, p, mask_p):
+    """The five products of the backward pair of the stage-entry block from ITS mid [M][256] (float64, as the kernel holds it in LDS):
+    dst = (mid W2^T) (u > 0), dP = mid W3^T [(P > 0)], dW2c = u^T mid, dWs = P^T mid, colsum = 1^T mid.
+    -> dict name -> (reference, magnitude)."""
+    d = lambda t: t.to(torch.float64)
+    mid, w2, w3, u, p = d(mid), d(w2), d(w3), d(u), d(p)
+    ku = (u > 0).to(torch.float64)
+    kp = (p > 0).to(torch.float64) if mask_p else torch.ones_like(p)
+    am = mid.abs()
+    return {"dst": ((mid @ w2.T) * ku, (am @ w2.abs().T) * ku),
+            "dP": ((mid @ w3.T) * kp, (am @ w3.abs().T) * kp),
+            "dW2c": (u.T @ mid, u.abs().T @ am),
+            "dWs": (p.T @ mid, p.abs().T @ am),
+            "colsum": (mid.sum(0), am.sum(0))}
+
+
+_WG = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64)        # G: filter transform
+_WBT = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=torch.float64)  # B^T: input transform
+_WAT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float64)                              # A^T: output transform
+
+
+def winograd_uv(g, d):
+    """float64 operands of the Winograd F(2x2, 3x3) evaluation of a 3x3 / stride-1 / pad-1 conv: U = G g G^T [4][4][C][N] of the
+    filter g [3][3][C][N], V = B^T d B [B][TH][TW][4][4][C] of the 4x4 patches (stride 2, zero padding) of the input d [B][H][W][C]."""
+    g, d = g.to(torch.float64), d.to(torch.float64)
+    U = torch.einsum("ir,rscn,js->ijcn", _WG, g, _WG)
+    B, H, W, C = d.shape
+    TH, TW = (H + 1) // 2, (W + 1) // 2
+    dp = F.pad(d.permute(0, 3, 1, 2), (1, 2 * TW + 1 - W, 1, 2 * TH + 1 - H))             # rows / columns -1 .. 2 T
+    pat = dp.unfold(2, 4, 2).unfold(3, 4, 2)                                               # [B][C][TH][TW][4][4]
+    V = torch.einsum("ir,bcyxrs,js->byxijc", _WBT, pat, _WBT)
+    return U, V
+
+
+def winograd_out(U, V, H, W, magnitude=False):
+    """A^T (sum_c U V) A of winograd_uv's operands, cropped to [B][H][W][N]: equals the direct conv (proved on the CPU).
+    magnitude: the same sums of |U| |V| through |A| -- a bound of every fp32 partial sum of the evaluation."""
+    At = _WAT.abs() if magnitude else _WAT
+    Mf = torch.einsum("byxijc,ijcn->byxijn", V.abs() if magnitude else V, U.abs() if magnitude else U)
+    Y = torch.einsum("ri,byxijn,sj->byrxsn", At, Mf, At)
+    B, TH, _, TW, _, N = Y.shape
+    return Y.reshape(B, 2 * TH, 2 * TW, N)[:, :H, :W]
 
 
 # =====================================================================================================================

@@ -706,3 +706,276 @@ def test_bn_references_accept_fp32_and_reject_faults(dt):
     assert X.violations(dz32.to(t), *bw["dz"]) == 0
     bad = dz32.clone(); bad[:, 5] *= 1.005
     assert X.violations(bad.to(t), *bw["dz"]) >= 0.01
+
+
+# =====================================================================================================================
+# The launches around a stage's first block and its end: the pixel map of the compact / sampled forms, the tile partition,
+# and simulated kernels of urso_conv_pair_shortcut, urso_conv_pair_wgrad_entry, urso_conv_pointwise_sampled and the
+# Winograd evaluation -- the clean simulation passes the GPU probes' checks, each planted defect is rejected.
+import numpy as np
+
+
+def _assert_pixel_map(H, W, p):
+    b, y, x = X.pixel_map_f32(p, H, W)
+    p64 = np.asarray(p, dtype=np.int64)
+    wb, rem = np.divmod(p64, H * W)
+    wy, wx = np.divmod(rem, W)
+    bad = (b != wb) | (y != wy) | (x != wx)
+    assert not bad.any(), "H %d W %d: pixel %d maps to (%d, %d, %d), divmod gives (%d, %d, %d)" % (
+        (H, W, int(p64[bad][0])) + tuple(int(v[bad][0]) for v in (b, y, x, wb, wy, wx)))
+
+
+def test_pixel_map_equals_divmod_for_every_small_even_image():
+    """(int)((float)p * rcp) + one correction, as conv_pair.hip and conv_pairw.hip locate a pixel: every even H, W in 2 .. 162 and every
+    p of four images."""
+    for H in range(2, 163, 2):
+        for W in range(2, 163, 2):
+            _assert_pixel_map(H, W, np.arange(4 * H * W, dtype=np.int32))
+
+
+@pytest.mark.parametrize("H,W", [(128, 160), (64, 80), (32, 40), (256, 320), (6, 40), (10, 6), (10, 22), (2, 2)])
+def test_pixel_map_equals_divmod_up_to_the_largest_tensor(H, W):
+    """p up to 2^22 (the entry points accept M * 512 bytes < 2 GiB): within +-2 of every multiple of W and of H W, and 10^5 random pixels."""
+    top = 2 ** 22
+    near = lambda step: (np.arange(0, top + 1, step, dtype=np.int64)[:, None] + np.arange(-2, 3)).reshape(-1)
+    rng = np.random.RandomState(H + W)
+    p = np.concatenate([near(W), near(H * W), rng.randint(0, top, 100000), [0, top - 1]])
+    p = np.unique(p[(p >= 0) & (p < top)]).astype(np.int32)
+    _assert_pixel_map(H, W, p)
+
+
+def test_pixel_map_check_rejects_a_map_without_the_correction():
+    """The same arithmetic without the +-1 step is wrong already at the first pixel of the second 10 x 22 image (f32(1 / 220) rounds down):
+    the correction is needed, and the comparison with divmod can fail."""
+    H, W = 10, 22
+    p = np.arange(4 * H * W, dtype=np.int32)
+    b = (p.astype(np.float32) * (np.float32(1.0) / np.float32(H * W))).astype(np.int32)
+    assert b[H * W] == 0 and (b != p // (H * W)).any()
+    _assert_pixel_map(H, W, p)
+
+
+def test_tiles_per_block_of_the_pair_probes():
+    """The table of tests/test_kernels_exact_gpu.py (PAIR_TILES): one block per XCD under grid_cap = 8."""
+    want = {1: [1] + [0] * 7, 9: [2, 2, 2, 2, 1, 0, 0, 0], 19: [3] * 6 + [1, 0], 29: [4] * 7 + [1], 45: [6] * 7 + [3]}
+    for n, counts in want.items():
+        assert X.pair_grid_blocks(n, 8) == 8 and X.tiles_per_block(n, 8) == counts
+    assert X.pair_grid_blocks(45, 0) == 48 and X.pair_grid_blocks(45, 16) == 16 and X.pair_grid_blocks(3, 0) == 8
+    u = X.tiles_per_block(45, 48)                       # blockIdx.x = 8 lb + xcd: XCD 7 owns 3 tiles, its blocks lb = 3 .. 5 none
+    assert sum(u) == 45 and [u[8 * lb + 7] for lb in range(6)] == [1, 1, 1, 0, 0, 0]
+    assert X.tiles_per_block(45, 16) == [3] * 7 + [2] + [3] * 7 + [1]
+    d = X.compact_to_dense(torch.arange(2 * 2 * 3 * 1, dtype=torch.float32).reshape(2, 2, 3, 1) + 1, 4, 6)
+    assert float(d.sum()) == 78 and float(d[:, 1::2].abs().sum()) == 0 and float(d[:, :, 1::2].abs().sum()) == 0 and float(d[1, 2, 4, 0]) == 12
+
+
+# ---- urso_conv_pair_shortcut
+PM, PC, PC4 = 4 * 64, 64, 256                 # four 64-pixel tiles
+
+
+def shortcut_case(t, exact, seed=21):
+    if exact:
+        a, d = X.int_plan(2 * PC, t, share=48)
+        src, xin = X.int_operands((PM, PC), t, a, d, seed), X.int_operands((PM, PC), t, a, d, seed + 1)
+        w1 = X.fill_last_channel(X.int_operands((PC4, PC), t, a, d, seed + 2), seed + 8)
+        ws = X.fill_last_channel(X.int_operands((PC4, PC), t, a, d, seed + 3), seed + 9)
+        b1, bs, b2 = X.int_operands((PC4,), t, 3, 0.8, seed + 4), X.int_operands((PC4,), t, 3, 0.8, seed + 5), X.int_operands((PC,), t, 3, 0.8, seed + 6)
+        mid = F.relu(X.pair_shortcut64(src, w1, b1, xin, ws, bs)[0])
+        dn = min(0.7, (256 / 12.0) ** 2 / (PC4 * float((mid ** 2).mean()) * 2.5))
+        w2 = X.fill_last_channel(X.int_operands((PC, PC4), t, 2, dn, seed + 7), seed + 10)
+    else:
+        g = torch.Generator().manual_seed(seed)
+        r = lambda *s: torch.randn(*s, generator=g)
+        src, xin = r(PM, PC).to(t).float(), r(PM, PC).to(t).float()
+        w1, ws = (r(PC4, PC) / (2 * PC) ** 0.5).to(t).float(), (r(PC4, PC) / (2 * PC) ** 0.5).to(t).float()
+        w2 = (r(PC, PC4) / (2 * PC ** 0.5)).to(t).float()
+        b1, bs, b2 = r(PC4) * 0.3, r(PC4) * 0.3, r(PC) * 0.3
+    return dict(src=src, xin=xin, w1=w1, ws=ws, w2=w2, b1=b1, bs=bs, b2=b2)
+
+
+def simulated_shortcut(kind, t, o):
+    """fp32 accumulation, one rounding per stored tensor -- or one of the faults."""
+    f = lambda a: a.float()
+    src, xin, w1, ws = o["src"], o["xin"], o["w1"], o["ws"]
+    if kind == "segments_swapped":
+        src, xin = xin, src
+    bsum = f(o["b1"]) + (0 if kind == "bias_s_dropped" else f(o["bs"]))
+    if kind == "shortcut_rounded_first":                 # the two-launch path: the shortcut conv's output is stored, then added
+        sc = rne(f(xin) @ f(ws).T + f(o["bs"]), t)
+        mid = rne(F.relu((f(src) @ f(w1).T + f(o["b1"])).double() + sc), t)
+    else:
+        mid = rne(F.relu(f(src) @ f(w1).T + f(xin) @ f(ws).T + bsum), t)
+    dst = rne(F.relu(mid.float() @ f(o["w2"]).T + f(o["b2"])), t)
+    if kind == "dst_tile_from_previous_tile":            # a ring slot reused too early
+        dst = dst.clone()
+        dst[128:192] = dst[64:128]
+    return mid, dst
+
+
+def check_shortcut(mid, dst, t, o, exact):
+    """The comparisons of test_conv_pair_shortcut (tests/test_kernels_exact_gpu.py)."""
+    pre1, mag1 = X.pair_shortcut64(o["src"], o["w1"], o["b1"], o["xin"], o["ws"], o["bs"])
+    if exact:
+        X.premise(t, stored=[("mid", F.relu(pre1))], mags=[("mid", mag1)])
+        X.assert_exact(mid, F.relu(pre1), "mid")
+    else:
+        X.assert_rounded_once(mid, F.relu(pre1), mag1, t, 2 * PC + 2, "mid")
+    pre2 = mid @ o["w2"].double().T + o["b2"].double()
+    mag2 = mid.abs() @ o["w2"].double().abs().T + o["b2"].double().abs()
+    if exact:
+        X.premise(t, stored=[("dst", F.relu(pre2))], mags=[("dst", mag2)])
+        X.assert_exact(dst, F.relu(pre2), "dst")
+    else:
+        X.assert_rounded_once(dst, F.relu(pre2), mag2, t, PC4 + 1, "dst")
+
+
+SHORTCUT_FAULTS = ["bias_s_dropped", "segments_swapped", "shortcut_rounded_first", "dst_tile_from_previous_tile"]
+
+
+@pytest.mark.parametrize("exact", [True, False], ids=["exact", "rounded_once"])
+@pytest.mark.parametrize("t", DTS, ids=["bf16", "fp16"])
+def test_shortcut_pair_simulation(t, exact):
+    o = shortcut_case(t, exact)
+    check_shortcut(*simulated_shortcut("correct", t, o), t, o, exact)
+    for kind in SHORTCUT_FAULTS:
+        if exact and kind == "shortcut_rounded_first":   # integers are exact at every rounding point: the real-valued probe's job
+            continue
+        with pytest.raises(AssertionError, match="elements wrong"):
+            check_shortcut(*simulated_shortcut(kind, t, o), t, o, exact)
+
+
+# ---- urso_conv_pair_wgrad_entry
+def entry_case(t, exact, seed=31):
+    if exact:
+        a, d = X.int_plan(PC, t, share=48)
+        src, w1 = X.int_operands((PM, PC), t, a, d, seed), X.int_operands((PC4, PC), t, a, d, seed + 1)
+        add = X.int_operands((PM, PC4), t, 3, 0.8, seed + 2)
+        u, p = X.int_operands((PM, PC), t, 3, 0.9, seed + 3), X.int_operands((PM, PC), t, 3, 0.9, seed + 4)
+    else:
+        g = torch.Generator().manual_seed(seed)
+        r = lambda *s: torch.randn(*s, generator=g)
+        src, w1, add = r(PM, PC).to(t).float(), (r(PC4, PC) / PC ** 0.5).to(t).float(), r(PM, PC4).to(t).float()
+        u, p = (r(PM, PC) * (torch.rand(PM, PC, generator=g) < 0.9)).to(t).float(), (r(PM, PC) * (torch.rand(PM, PC, generator=g) < 0.9)).to(t).float()
+    keep = ((X.rand_bits(PM * PC4 // 8, seed + 5).to(torch.int32).reshape(-1, 1) >> torch.arange(8, dtype=torch.int32)) & 1).reshape(PM, PC4).double()
+    mid_ref = (src.double() @ w1.double().T + add.double()) * keep
+    mag1 = (src.double().abs() @ w1.double().abs().T + add.double().abs()) * keep
+    if exact:
+        dn = min(0.7, (256 / 12.0) ** 2 / (PC4 * float((mid_ref ** 2).mean()) * 2.5))
+        w2 = X.fill_last_channel(X.int_operands((PC, PC4), t, 2, dn, seed + 6), seed + 7)
+        w3 = X.fill_last_channel(X.int_operands((PC, PC4), t, 2, dn, seed + 8), seed + 9)
+    else:
+        w2, w3 = (r(PC, PC4) / (2 * PC ** 0.5)).to(t).float(), (r(PC, PC4) / (2 * PC ** 0.5)).to(t).float()
+    return dict(src=src, w1=w1, add=add, u=u, p=p, keep=keep, w2=w2, w3=w3, mid_ref=mid_ref, mag1=mag1)
+
+
+def simulated_entry(kind, t, o, mask_p=1):
+    """mid rounded once into the LDS tile; dst / dP rounded once; fp32 partial sums per 64-pixel tile, summed in float64."""
+    f = lambda a: a.float()
+    mid = rne((f(o["src"]) @ f(o["w1"]).T + f(o["add"])).double() * o["keep"], t)
+    w2, w3 = (o["w3"], o["w2"]) if kind == "w2_w3_exchanged" else (o["w2"], o["w3"])
+    ku = (o["u"] > 0).double()
+    kp = (o["p"] > 0).double() if (mask_p and kind != "dP_mask_ignored") else 1.0
+    out = {"dst": rne((mid.float() @ f(w2).T).double() * ku, t), "dP": rne((mid.float() @ f(w3).T).double() * kp, t)}
+    tiles = range(PM // 64)
+    tsum = lambda a, skip=None: sum((f(a[64 * i:64 * i + 64]).T @ mid[64 * i:64 * i + 64].float()).double() for i in tiles if i != skip)
+    out["dW2c"] = tsum(o["u"])
+    out["dWs"] = tsum(o["p"], skip=2 if kind == "dWs_misses_a_tile" else None)
+    out["colsum"] = sum(mid[64 * i:64 * i + 64].float().sum(0).double() for i in tiles)
+    out["colsum (shortcut)"] = out["colsum"].clone()     # "copied from the first layer's": the same values by definition
+    return mid, out
+
+
+def check_entry(mid, got, t, o, exact, mask_p=1):
+    """The comparisons of test_conv_pair_wgrad_entry: exact against the products of the exact mid; rounded once against the products of the
+    STORED mid (itself within the rounded-once bound of the float64 mid)."""
+    if exact:
+        m = o["mid_ref"]
+        X.premise(t, stored=[("mid", m)], mags=[("mid", o["mag1"])])
+    else:
+        X.assert_rounded_once(mid, o["mid_ref"], o["mag1"], t, PC + 1, "mid")
+        m = mid
+    ref = X.pair_entry64(m, o["w2"], o["w3"], o["u"], o["p"], mask_p)
+    ref["colsum (shortcut)"] = ref["colsum"]
+    for k in ("dst", "dP", "dW2c", "dWs", "colsum", "colsum (shortcut)"):
+        st = t if k in ("dst", "dP") else torch.float32
+        if exact:
+            X.premise(st, stored=[(k, ref[k][0])], mags=[(k, ref[k][1])])
+            X.assert_exact(got[k], ref[k][0], k)
+        else:
+            X.assert_rounded_once(got[k], ref[k][0], ref[k][1], st, PC4 if k in ("dst", "dP") else PM, k)
+
+
+@pytest.mark.parametrize("exact", [True, False], ids=["exact", "rounded_once"])
+@pytest.mark.parametrize("t", DTS, ids=["bf16", "fp16"])
+def test_entry_pair_simulation(t, exact):
+    o = entry_case(t, exact)
+    for mask_p in (1, 0):
+        check_entry(*simulated_entry("correct", t, o, mask_p), t, o, exact, mask_p)
+    for kind in ("w2_w3_exchanged", "dP_mask_ignored", "dWs_misses_a_tile"):
+        with pytest.raises(AssertionError, match="elements wrong"):
+            check_entry(*simulated_entry(kind, t, o), t, o, exact)
+
+
+def test_entry_pair_probe_cannot_tell_the_two_column_sums_apart():
+    """A kernel that wrote the second layer's column sums as a COPY of the first layer's is a correct kernel: both layers' dz is the same mid
+    (conv_pairx.hip stores one accumulator twice), so the references are the same tensor.  The probe covers each buffer's values, block
+    slices and NaN pre-fill -- not which accumulator fed it; nothing else could, and nothing needs to."""
+    o = entry_case(torch.bfloat16, True)
+    mid, got = simulated_entry("correct", torch.bfloat16, o)
+    ref = X.pair_entry64(o["mid_ref"], o["w2"], o["w3"], o["u"], o["p"], 1)
+    assert torch.equal(got["colsum (shortcut)"], got["colsum"]) and torch.equal(ref["colsum"][0], o["mid_ref"].sum(0))
+    check_entry(mid, got, torch.bfloat16, o, True)
+    got["colsum (shortcut)"] = got["colsum"] * 0        # ... while a buffer that was never accumulated is rejected
+    with pytest.raises(AssertionError, match="elements wrong"):
+        check_entry(mid, got, torch.bfloat16, o, True)
+
+
+# ---- urso_conv_pointwise_sampled
+@pytest.mark.parametrize("exact", [True, False], ids=["exact", "rounded_once"])
+@pytest.mark.parametrize("t", DTS, ids=["bf16", "fp16"])
+def test_sampled_copy_simulation(t, exact):
+    """dst_sampled must be dst[:, ::2, ::2] bit for bit: the copy taken at odd columns, or one image's rows shifted by one, is rejected (on
+    integer and on real data: it is a comparison of stored values)."""
+    Bq, Hq, Wq, c, N = 4, 6, 10, 64, 256
+    if exact:
+        a, d = X.int_plan(c, t)
+        x, w = X.int_operands((Bq * Hq * Wq, c), t, a, d, 41), X.int_operands((N, c), t, a, d, 42)
+    else:
+        g = torch.Generator().manual_seed(43)
+        x, w = torch.randn(Bq * Hq * Wq, c, generator=g).to(t).float(), (torch.randn(N, c, generator=g) / 8).to(t).float()
+    z = x.double() @ w.double().T
+    dst = rne(F.relu(x @ w.T), t).reshape(Bq, Hq, Wq, N)
+    if exact:
+        X.premise(t, stored=[("dst", F.relu(z))], mags=[("dst", x.double().abs() @ w.double().abs().T)])
+        X.assert_exact(dst.reshape(-1, N), F.relu(z), "dst")
+    else:
+        X.assert_rounded_once(dst.reshape(-1, N), F.relu(z), x.double().abs() @ w.double().abs().T, t, c + 1, "dst")
+    good = dst[:, ::2, ::2].clone()
+    X.assert_exact(good, dst[:, ::2, ::2], "dst_sampled")
+    shifted = good.clone()
+    shifted[2] = dst[2, 1::2, ::2]
+    for bad in (dst[:, ::2, 1::2], shifted):
+        with pytest.raises(AssertionError, match="elements wrong"):
+            X.assert_exact(bad, dst[:, ::2, ::2], "dst_sampled")
+
+
+# ---- Winograd F(2x2, 3x3)
+@pytest.mark.parametrize("shape", [(2, 9, 15, 16, 8), (1, 4, 6, 8, 8), (3, 17, 23, 24, 16)])
+def test_winograd_operands_and_evaluation(shape):
+    """winograd_uv / winograd_out evaluate the 3x3 / stride-1 / pad-1 conv exactly on integers with |v| <= 2 (odd sizes: the last tiles'
+    second row / column is dropped), U is a multiple of 1/4 with |U| <= 4.5 and V an integer with |V| <= 8 -- representable in bf16 and
+    f16 -- and a filter transform that forgets a factor 1/2 is rejected."""
+    Bq, Hq, Wq, c, N = shape
+    x, w = X.int_operands((Bq, Hq, Wq, c), None, 2, 0.6, 51), X.int_operands((3, 3, c, N), None, 2, 0.6, 52)
+    ref = conv64(x, w)
+    U, V = X.winograd_uv(w, x)
+    assert torch.equal(4 * U, (4 * U).round()) and float(U.abs().max()) <= 4.5
+    assert torch.equal(V, V.round()) and float(V.abs().max()) <= 8
+    for t in DTS:
+        X.premise(t, stored=[("U", U), ("V", V)])
+    X.assert_exact(X.winograd_out(U, V, Hq, Wq), ref, "winograd")
+    assert bool((X.winograd_out(U, V, Hq, Wq, magnitude=True) >= ref.abs()).all())
+    Ubad = U.clone()
+    Ubad[1] *= 2
+    with pytest.raises(AssertionError, match="elements wrong"):
+        X.assert_exact(X.winograd_out(Ubad, V, Hq, Wq), ref, "winograd")
+    worst = X.winograd_uv(torch.full((3, 3, 1, 1), 2.0), torch.tensor([2.0, -2.0]).repeat(4, 2).reshape(1, 4, 4, 1) * torch.tensor([1.0, 1, -1, -1]).reshape(1, 4, 1, 1))
+    assert float(worst[0].abs().max()) == 4.5 and float(worst[1].abs().max()) <= 8

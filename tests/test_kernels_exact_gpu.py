@@ -12,8 +12,10 @@ Families: the generic implicit GEMM, pointwise, halo, register-filter and big-ti
 max-pool, the weight-gradient variants, the fused pointwise pairs and the two-segment pointwise launch; the stem (weight
 pack with a BatchNorm fold, unpooled, fused with ReLU + max-pool, weight gradient from dz and from the pool's gradient);
 bottleneck_layer's forward and parity-class data gradient; the Dense heads in one launch (forward and weight gradients);
-the batched weight gradients (grouped layers, two 3x3 layers in one launch, dz on a coarser grid).  The references of the
-larger layers are float64 on the device."""
+the batched weight gradients (grouped layers, two 3x3 layers in one launch, dz on a coarser grid); the launches around a stage's
+first block and its end (forward pair with the projection shortcut inside, backward pair of the stage-entry block, the stage-closing
+layer with its sampled second output, the compact add operand of the backward pairs) at every tiles-per-block count of their input
+rings; the Winograd evaluation on integers.  The references of the larger layers are float64 on the device."""
 import math
 
 import pytest
@@ -649,8 +651,29 @@ def test_conv_pair(shape, c, dt, exact):
     (mode 1: mid = (src W1^T + add) * bits; dst = (mid W2^T) * (act > 0)).  mid and dst are both stored tensors, each rounded
     once (include/ursonet_hip.h: 'one rounding per stored tensor'): dst's reference is computed from the STORED mid -- the same
     rounding point StorageRounding models, every conv output being stored."""
+    _conv_pair_case(PAIR_SHAPES[shape], c, dt, exact, compact=False)
+
+
+# (B, H, W, grid_cap) of the compact-add probes: 64- / 32-pixel tiles straddle image rows (W = 40, 6) and images (H W = 240, 60: no
+# multiple of a tile, the second smaller than one); (2, 24, 40) is PAIR_SHAPES["small"]'s image
+COMPACT_GEOS = [(4, 6, 40, 0), (16, 10, 6, 8), (2, 24, 40, 0)]
+COMPACT_IDS = ["%dx%dx%d" % g[:3] for g in COMPACT_GEOS]
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("c", [64, 128], ids=["stage2", "stage3"])
+@pytest.mark.parametrize("geo", COMPACT_GEOS, ids=COMPACT_IDS)
+def test_conv_pair_compact_add(geo, c, dt, exact):
+    """urso_conv_pair mode 1 with `add` given as the COMPACT [B][H/2][W/2][4c] gradient (add_hw = (H, W)): the same probe, against the
+    float64 reference of the dense tensor with explicit zeros at the odd rows / columns (conv_pair.hip: the pixel map of the SPARSE
+    loads; tests/test_exactprobe_cpu.py proves its arithmetic against divmod)."""
+    _conv_pair_case(geo, c, dt, exact, compact=True)
+
+
+def _conv_pair_case(geo, c, dt, exact, compact):
     hip = _hip()
-    B, H, W, cap = PAIR_SHAPES[shape]
+    B, H, W, cap = geo
     M, c4 = B * H * W, 4 * c
     seed = M + c + 11 * dt
     if exact:
@@ -658,13 +681,18 @@ def test_conv_pair(shape, c, dt, exact):
         src, w1 = X.int_operands((M, c), dt, a, d, seed), X.int_operands((c4, c), dt, a, d, seed + 1)
     else:
         src, w1 = _operands((M, c), dt, False, c, seed), _operands((c4, c), dt, False, c, seed + 1, c ** -0.5)
-    add = _operands((M, c4), dt, exact, 0, seed + 2, small=True)
+    if compact:                                                             # the kernel's operand; the reference adds the dense tensor
+        add_k = _operands((B, H // 2, W // 2, c4), dt, exact, 0, seed + 2, small=True)
+        add = X.compact_to_dense(add_k, H, W).reshape(M, c4)
+        assert float((add != 0).float().mean()) > 0.1
+    else:
+        add = add_k = _operands((M, c4), dt, exact, 0, seed + 2, small=True)
     act = _operands((M, c), dt, exact, 0, seed + 3, small=True, density=0.9)
     b1 = _operands((c4,), 0, exact, 0, seed + 4, 0.3, small=True)
     b2 = _operands((c,), 0, exact, 0, seed + 5, 0.3, small=True)
     gbits = X.rand_bits(M * c4 // 8, seed + 6)
     keep1 = _unpack_bits(gbits, M, c4).double()
-    for mode in (0, 1):
+    for mode in ((1,) if compact else (0, 1)):                              # the forward form has no compact operand
         if mode == 0:
             pre1, mag1 = _mm(src, w1) + b1.double() + add.double(), _mm(src.abs(), w1.abs()) + b1.double().abs() + add.double().abs()
             pre1_0 = pre1 - src[:, -1:].double() * w1.double()[:, -1]
@@ -677,8 +705,9 @@ def test_conv_pair(shape, c, dt, exact):
         mid = full((M, c4), dt); dst = full((M, c), dt)
         bits = torch.full((M * c4 // 8,), 0xAA, dtype=torch.uint8, device="cuda") if mode == 0 else gbits.cuda()
         with hip.options(grid_cap=cap), X.ran("pair_kernel"):
-            hip.conv_pair(M, c, dt, mode, dev(src, dt), dev(w1, dt), b1.cuda() if mode == 0 else None, dev(add, dt), bits, mid,
-                          dev(w2, dt), b2.cuda() if mode == 0 else None, dev(act, dt) if mode == 1 else None, dst)
+            hip.conv_pair(M, c, dt, mode, dev(src, dt), dev(w1, dt), b1.cuda() if mode == 0 else None, dev(add_k, dt), bits, mid,
+                          dev(w2, dt), b2.cuda() if mode == 0 else None, dev(act, dt) if mode == 1 else None, dst,
+                          add_hw=(H, W) if compact else None)
         torch.cuda.synchronize()
         what = "mode %d" % mode
         if exact:
@@ -714,8 +743,21 @@ def test_conv_pair(shape, c, dt, exact):
 def test_conv_pair_wgrad_and_dgrad_wgrad_pw(shape, dt, exact):
     """urso_conv_pair_wgrad (stage-2 backward pair + the block-closing layer's weight gradient u^T mid from the STORED mid, fp32 split
     partials) and urso_conv_dgrad_wgrad_pw (dx = dz Wd^T masked by x > 0, and the partials of x^T dz): partials summed in float64."""
+    _conv_pair_wgrad_case(PAIR_SHAPES[shape], dt, exact, compact=False)
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("geo", COMPACT_GEOS, ids=COMPACT_IDS)
+def test_conv_pair_wgrad_compact_add(geo, dt, exact):
+    """urso_conv_pair_wgrad with the COMPACT add operand (conv_pairw.hip's copy of the pixel map) against the float64 reference of the
+    dense tensor with explicit zeros: mid, dst, the summed partials of u^T mid and the column sums."""
+    _conv_pair_wgrad_case(geo, dt, exact, compact=True)
+
+
+def _conv_pair_wgrad_case(geo, dt, exact, compact):
     hip = _hip()
-    B, H, W, cap = PAIR_SHAPES[shape]
+    B, H, W, cap = geo
     M, c, c4 = B * H * W, 64, 256
     seed = M + 3 * dt + 1
     if exact:
@@ -723,7 +765,12 @@ def test_conv_pair_wgrad_and_dgrad_wgrad_pw(shape, dt, exact):
         src, w1 = X.int_operands((M, c), dt, a, d, seed), X.int_operands((c4, c), dt, a, d, seed + 1)
     else:
         src, w1 = _operands((M, c), dt, False, c, seed), _operands((c4, c), dt, False, c, seed + 1, c ** -0.5)
-    add = _operands((M, c4), dt, exact, 0, seed + 2, small=True)
+    if compact:
+        add_k = _operands((B, H // 2, W // 2, c4), dt, exact, 0, seed + 2, small=True)
+        add = X.compact_to_dense(add_k, H, W).reshape(M, c4)
+        assert float((add != 0).float().mean()) > 0.1
+    else:
+        add = add_k = _operands((M, c4), dt, exact, 0, seed + 2, small=True)
     u = _operands((M, c), dt, exact, 0, seed + 3, small=True, density=0.9)
     gbits = X.rand_bits(M * c4 // 8, seed + 4)
     keep1 = _unpack_bits(gbits, M, c4).double()
@@ -738,8 +785,8 @@ def test_conv_pair_wgrad_and_dgrad_wgrad_pw(shape, dt, exact):
         colpart = torch.full((splits * c4,), float("nan"), device="cuda")
         mid, dst = full((M, c4), dt), full((M, c), dt)
         with X.ran("pairw_kernel"):
-            hip.conv_pair_wgrad(M, dt, dev(src, dt), dev(w1, dt), dev(add, dt), gbits.cuda(), mid, dev(w2, dt), dev(u, dt), dst,
-                                part, colpart, stride)
+            hip.conv_pair_wgrad(M, dt, dev(src, dt), dev(w1, dt), dev(add_k, dt), gbits.cuda(), mid, dev(w2, dt), dev(u, dt), dst,
+                                part, colpart, stride, add_hw=(H, W) if compact else None)
         torch.cuda.synchronize()
     m = mid.double().cpu()
     ka = (u > 0).double()
@@ -759,6 +806,8 @@ def test_conv_pair_wgrad_and_dgrad_wgrad_pw(shape, dt, exact):
         _record("pair", X.assert_rounded_once(dst, dst_ref, mag2, dt, c4, "conv_pair_wgrad dst"))
         _record("pair_wgrad", X.assert_rounded_once(dw, dw_ref, dw_mag, 0, M, "conv_pair_wgrad dW"))
         _record("pair_wgrad", X.assert_rounded_once(cs, cs_ref, cs_mag, 0, M, "conv_pair_wgrad colsum"))
+    if compact:                                                             # the single-layer form has no add operand
+        return
     # single-layer form: dz = the stored mid, x = u, Wd = w2 [64][256]
     dx = full((M, c), dt)
     part.fill_(float("nan")); colpart.fill_(float("nan"))
@@ -774,6 +823,286 @@ def test_conv_pair_wgrad_and_dgrad_wgrad_pw(shape, dt, exact):
         _record("pair", X.assert_rounded_once(dx, dst_ref, mag2, dt, c4, "conv_dgrad_wgrad_pw dx"))
         _record("pair_wgrad", X.assert_rounded_once(dw, dw_ref, dw_mag, 0, M, "conv_dgrad_wgrad_pw dW"))
         _record("pair_wgrad", X.assert_rounded_once(cs, cs_ref, cs_mag, 0, M, "conv_dgrad_wgrad_pw colsum"))
+
+
+# ---------------------------------------------------------------- the launches around a stage's first block (conv_pairs.hip, conv_pairx.hip)
+# M = 64 ntiles under grid_cap = 8 is one block per XCD, XCD x owning tiles [x cpx, min((x + 1) cpx, ntiles)): per block
+#   1: 1, then seven blocks without a tile      9: 2 2 2 2 1 0 0 0      19: 3 x 6, 1, 0      29: 4 x 7, 1      45: 6 x 7, 3
+# and uncapped (45 tiles on 48 blocks) one tile or none -- every has_next / has_far pattern of the 3-stage and 2-stage input rings:
+# the first tile with and without a next one, the steady state, the last two tiles of a drain.
+PAIR_TILES = [(1, 8), (9, 8), (19, 8), (29, 8), (45, 8), (45, 0)]
+PAIR_TILE_IDS = ["tiles%d_cap%d" % t for t in PAIR_TILES]
+
+
+def _entry_tile_counts(ntiles, cap, dt):
+    """Tiles per block of urso_conv_pair_wgrad_entry's launch: its grid is urso_conv_pair_wgrad_splits blocks."""
+    hip = _hip()
+    with hip.options(grid_cap=cap):
+        splits = hip.conv_pair_wgrad_splits(64 * ntiles, dt)
+    return X.tiles_per_block(ntiles, splits)
+
+
+def test_pair_tile_shapes_reach_every_pipeline_phase():
+    """The tile counts per block that PAIR_TILES reaches under the launch policies as they are now: {0, 1, 2, 3, 4, >= 6} for both
+    kernels.  A change of the policy that shrinks this fails here instead of silently losing a prologue / steady / drain combination."""
+    for name, counts in (("pairs_kernel", [X.tiles_per_block(n, X.pair_grid_blocks(n, cap)) for n, cap in PAIR_TILES]),
+                         ("pairx_kernel", [_entry_tile_counts(n, cap, 1) for n, cap in PAIR_TILES])):
+        seen = set(sum(counts, []))
+        assert {0, 1, 2, 3, 4} <= seen and max(seen) >= 6, "%s: tiles per block reached %s" % (name, sorted(seen))
+    assert _entry_tile_counts(9, 8, 1) == [2, 2, 2, 2, 1, 0, 0, 0] and _entry_tile_counts(45, 8, 2) == [6] * 7 + [3]
+    assert X.pair_grid_blocks(45, 0) == 48 and sorted(set(X.tiles_per_block(45, 48))) == [0, 1]
+
+
+def _differs(a, b):
+    return float((a != b).sum()) / a.numel()
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("tiles", PAIR_TILES, ids=PAIR_TILE_IDS)
+def test_conv_pair_shortcut(tiles, dt, exact):
+    """urso_conv_pair_shortcut (pairs_kernel): mid = relu(src W1^T + xin Ws^T + (b1 + bs)) stored and rounded once -- ONE reduction of 128
+    terms, the two biases added to each other in fp32 first (K = 128 + 2) -- and dst = relu(mid W2^T + b2) from the STORED mid (K = 256 + 1);
+    with and without the emitted bit mask (bit for bit the same mid / dst; bits = stored mid > 0); a guard tile behind every output."""
+    hip = _hip()
+    ntiles, cap = tiles
+    M, c, c4, G = 64 * ntiles, 64, 256, 64
+    seed = 5 * M + 17 * dt + 3
+    if exact:
+        a, d = X.int_plan(2 * c, dt, share=48)
+        src, xin = X.int_operands((M, c), dt, a, d, seed), X.int_operands((M, c), dt, a, d, seed + 1)
+        w1 = X.fill_last_channel(X.int_operands((c4, c), dt, a, d, seed + 2), seed + 20)
+        ws = X.fill_last_channel(X.int_operands((c4, c), dt, a, d, seed + 3), seed + 21)
+    else:
+        src, xin = _operands((M, c), dt, False, c, seed), _operands((M, c), dt, False, c, seed + 1)
+        w1, ws = _operands((c4, c), dt, False, c, seed + 2, (2 * c) ** -0.5), _operands((c4, c), dt, False, c, seed + 3, (2 * c) ** -0.5)
+    b1 = _operands((c4,), 0, exact, 0, seed + 4, 0.3, small=True)
+    bs = _operands((c4,), 0, exact, 0, seed + 5, 0.3, small=True)
+    b2 = _operands((c,), 0, exact, 0, seed + 6, 0.3, small=True)
+    pre1, mag1 = X.pair_shortcut64(src, w1, b1, xin, ws, bs)
+    mid_ref = F.relu(pre1)
+    w2 = _second_operand(mid_ref, c4, dt, exact, seed + 7, (c, 1 / (2 * c ** 0.5)))
+    outs = []
+    with hip.options(grid_cap=cap), X.ran("pairs_kernel"):
+        for emit in (True, False):
+            mid, dst = full((M + G, c4), dt), full((M + G, c), dt)
+            bits = torch.full(((M + G) * c4 // 8,), 0xAA, dtype=torch.uint8, device="cuda") if emit else None
+            hip.conv_pair_shortcut(M, dt, dev(src, dt), dev(w1, dt), b1.cuda(), dev(xin, dt), dev(ws, dt), bs.cuda(), bits, mid,
+                                   dev(w2, dt), b2.cuda(), dst)
+            outs.append((mid, dst, bits))
+    torch.cuda.synchronize()
+    (mid, dst, bits), (mid_nb, dst_nb, _) = outs
+    for name, t, v in (("mid", mid, SENTINEL), ("dst", dst, SENTINEL), ("mid (no bits)", mid_nb, SENTINEL), ("dst (no bits)", dst_nb, SENTINEL)):
+        assert bool((t[M:].float() == v).all()), "%s: the guard tile behind the output was written" % name
+    assert bool((bits[M * c4 // 8:] == 0xAA).all()), "bits: the guard tile behind the mask was written"
+    assert torch.equal(mid, mid_nb) and torch.equal(dst, dst_nb), "the variant without a bit mask stores other values"
+    mid, dst, bits = mid[:M], dst[:M], bits[:M * c4 // 8]
+    if exact:
+        X.premise(dt, stored=[("mid", mid_ref)], mags=[("mid", mag1)])
+        X.assert_sensitive(mid_ref, F.relu(pre1 - src[:, -1:].double() * w1.double()[:, -1]), pre1, "mid (last channel of src)")
+        X.assert_sensitive(mid_ref, F.relu(pre1 - xin[:, -1:].double() * ws.double()[:, -1]), pre1, "mid (last channel of xin)")
+        assert _differs(F.relu(pre1 - bs.double()), mid_ref) >= 0.01, "dropping bias_s would not show"
+        assert _differs(F.relu(X.pair_shortcut64(xin, w1, b1, src, ws, bs)[0]), mid_ref) >= 0.01, "swapping the segments would not show"
+        X.assert_exact(mid, mid_ref, "mid")
+    else:
+        _record("pair_shortcut", X.assert_rounded_once(mid, mid_ref, mag1, dt, 2 * c + 2, "mid"))
+    m = mid.double().cpu()                                                  # the second layer reads the stored mid
+    pre2, mag2 = _mm(m, w2) + b2.double(), _mm(m.abs(), w2.abs()) + b2.double().abs()
+    if exact:
+        X.premise(dt, stored=[("dst", F.relu(pre2))], mags=[("dst", mag2)])
+        X.assert_sensitive(F.relu(pre2), F.relu(pre2 - m[:, -1:] * w2.double()[:, -1]), pre2, "dst")
+        X.assert_exact(dst, F.relu(pre2), "dst")
+    else:
+        _record("pair_shortcut", X.assert_rounded_once(dst, F.relu(pre2), mag2, dt, c4 + 1, "dst"))
+    assert torch.equal(_unpack_bits(bits, M, c4), (mid.cpu().float() > 0).to(torch.int32)), "emitted bits differ from (stored mid > 0)"
+
+
+def _relu_like(shape, dt, exact, seed):
+    """A post-ReLU-like mask operand with exact zeros AND negatives (so that `> 0` is not `!= 0`): small integers of density 0.9, or real
+    values of which a tenth are 0."""
+    if exact:
+        return X.int_operands(shape, dt, 3, 0.9, seed)
+    g = torch.Generator().manual_seed(seed)
+    t = torch.randn(tuple(shape), generator=g).to(X.tdtype(dt)).float()
+    return t * (torch.rand(tuple(shape), generator=g) < 0.9)
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("mask_by_xin", [1, 0], ids=["dP_masked", "dP_unmasked"])
+@pytest.mark.parametrize("tiles", PAIR_TILES, ids=PAIR_TILE_IDS)
+def test_conv_pair_wgrad_entry(tiles, mask_by_xin, dt, exact):
+    """urso_conv_pair_wgrad_entry (pairx_kernel), names as in conv_pairx.hip: mid = (G W1^T + dXb) bits never leaves LDS; stored are
+    dst = (mid W2^T)(u > 0), dP = mid W3^T [(P > 0)], and per block the fp32 partials of dW2c = u^T mid, dWs = P^T mid and of the column
+    sums (twice), summed here in float64.  Exact mode: the reference mid is exact and representable, so everything is bit for bit.
+    Rounded once: mid is what urso_conv_pair_wgrad STORES for the same operands (itself probed against float64 here); the entry kernel's
+    outputs are bounded against float64 products of that stored mid -- K = 256 for dst / dP, K = M for the partial sums -- as dst is
+    referenced from the stored mid everywhere in this file.  Blocks without a tile must write zero partials."""
+    hip = _hip()
+    ntiles, cap = tiles
+    M, c, c4 = 64 * ntiles, 64, 256
+    seed = 7 * M + 13 * dt + 5
+    if exact:
+        a, d = X.int_plan(c, dt, share=48)
+        src, w1 = X.int_operands((M, c), dt, a, d, seed), X.int_operands((c4, c), dt, a, d, seed + 1)
+    else:
+        src, w1 = _operands((M, c), dt, False, c, seed), _operands((c4, c), dt, False, c, seed + 1, c ** -0.5)
+    add = _operands((M, c4), dt, exact, 0, seed + 2, small=True)
+    u, P = _relu_like((M, c), dt, exact, seed + 3), _relu_like((M, c), dt, exact, seed + 4)
+    gbits = X.rand_bits(M * c4 // 8, seed + 5)
+    keep1 = _unpack_bits(gbits, M, c4).double()
+    mid_ref = (_mm(src, w1) + add.double()) * keep1
+    mag1 = (_mm(src.abs(), w1.abs()) + add.double().abs()) * keep1
+    w2 = _second_operand(mid_ref, c4, dt, exact, seed + 6, (c, 1 / (2 * c ** 0.5)))
+    w3 = _second_operand(mid_ref, c4, dt, exact, seed + 16, (c, 1 / (2 * c ** 0.5)))
+    dsrc, dw1, dadd, dbits, dw2, dw3, du, dP = (dev(src, dt), dev(w1, dt), dev(add, dt), gbits.cuda(), dev(w2, dt), dev(w3, dt), dev(u, dt),
+                                                dev(P, dt))
+    with hip.options(grid_cap=cap):
+        splits = hip.conv_pair_wgrad_splits(M, dt)
+        counts = X.tiles_per_block(ntiles, splits)
+        stride = c * c4 + hip.WGRAD_PART_PAD
+        nan = lambda n: torch.full((n,), float("nan"), device="cuda")
+        part, colpart, part_s, colpart_s = nan(splits * stride), nan(splits * c4), nan(splits * stride), nan(splits * c4)
+        dst, dxin = full((M, c), dt), full((M, c), dt)
+        with X.ran("pairx_kernel"):
+            hip.conv_pair_wgrad_entry(M, dt, dsrc, dw1, dadd, dbits, dw2, du, dst, dw3, dP, mask_by_xin, dxin, part, colpart, part_s,
+                                      colpart_s, stride)
+        torch.cuda.synchronize()
+        if exact:
+            m = mid_ref
+        else:
+            mid, dst0 = full((M, c4), dt), full((M, c), dt)
+            part0, colpart0 = nan(splits * stride), nan(splits * c4)
+            with X.ran("pairw_kernel"):
+                hip.conv_pair_wgrad(M, dt, dsrc, dw1, dadd, dbits, mid, dw2, du, dst0, part0, colpart0, stride)
+            torch.cuda.synchronize()
+            _record("pair_entry", X.assert_rounded_once(mid, mid_ref, mag1, dt, c + 1, "the stored mid of urso_conv_pair_wgrad"))
+            m = mid.double().cpu()
+    ref = X.pair_entry64(m, w2, w3, u, P, mask_by_xin)
+    parts = {"dW2c": part, "dWs": part_s}
+    cols = {"colsum": colpart, "colsum (shortcut)": colpart_s}
+    got = {"dst": dst, "dP": dxin}
+    for name, t in parts.items():
+        t = t.reshape(splits, stride)[:, :c * c4].double().cpu()
+        assert bool(torch.isfinite(t).all()), "%s: a split partial was not written" % name
+        for blk, n in enumerate(counts):
+            assert n > 0 or not bool(t[blk].any()), "%s: block %d owns no tile, its partial is not zero" % (name, blk)
+        got[name] = t.sum(0).reshape(c, c4)
+    for name, t in cols.items():
+        t = t.reshape(splits, c4).double().cpu()
+        assert bool(torch.isfinite(t).all()), "%s: a split partial was not written" % name
+        for blk, n in enumerate(counts):
+            assert n > 0 or not bool(t[blk].any()), "%s: block %d owns no tile, its partial is not zero" % (name, blk)
+        got[name] = t.sum(0)
+    ref["colsum (shortcut)"] = ref["colsum"]
+    if exact:
+        X.premise(dt, stored=[("mid", mid_ref), ("dst", ref["dst"][0]), ("dP", ref["dP"][0])],
+                  mags=[("mid", mag1), ("dst", ref["dst"][1]), ("dP", ref["dP"][1])])
+        X.premise(0, stored=[(k, ref[k][0]) for k in ("dW2c", "dWs", "colsum")], mags=[(k, ref[k][1]) for k in ("dW2c", "dWs", "colsum")])
+        X.assert_sensitive(mid_ref, (_mm(src, w1) + add.double() - src[:, -1:].double() * w1.double()[:, -1]) * keep1, None, "mid")
+        swapped = X.pair_entry64(m, w3, w2, P, u, mask_by_xin)                   # W2 <-> W3 and u <-> P: every reference changes
+        for k in ("dst", "dP", "dW2c", "dWs"):
+            assert _differs(swapped[k][0], ref[k][0]) >= 0.01, "%s: exchanging W2 / W3 and u / P would not show" % k
+        if mask_by_xin:
+            assert _differs(X.pair_entry64(m, w2, w3, u, P, 0)["dP"][0], ref["dP"][0]) >= 0.01, "ignoring the dP mask would not show"
+        for k in ("dst", "dP", "dW2c", "dWs", "colsum", "colsum (shortcut)"):
+            X.assert_exact(got[k], ref[k][0], "conv_pair_wgrad_entry " + k)
+    else:
+        for k in ("dst", "dP"):
+            _record("pair_entry", X.assert_rounded_once(got[k], ref[k][0], ref[k][1], dt, c4, "conv_pair_wgrad_entry " + k))
+        for k in ("dW2c", "dWs", "colsum", "colsum (shortcut)"):
+            _record("pair_entry", X.assert_rounded_once(got[k], ref[k][0], ref[k][1], 0, M, "conv_pair_wgrad_entry " + k))
+
+
+# ---------------------------------------------------------------- the stage-closing layer with its sampled second output (conv_pair.hip)
+# (add, relu, emitted bits, grid_cap)
+SAMPLED_FORMS = {"add_relu_bits": (True, True, True, 0), "add_relu_bits_capped": (True, True, True, 8), "relu_bits": (False, True, True, 0),
+                 "add_relu": (True, True, False, 0), "add": (True, False, False, 0)}
+# tiles of 64 / 32 pixels straddle image rows and images: H W = 240 is no multiple of either, 60 is smaller than a 64-pixel tile
+SAMPLED_GEOS = [(8, 6, 40), (16, 10, 6)]
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("form", list(SAMPLED_FORMS))
+@pytest.mark.parametrize("geo", SAMPLED_GEOS, ids=["%dx%dx%d" % g for g in SAMPLED_GEOS])
+@pytest.mark.parametrize("c", [64, 128, 256], ids=["stage2", "stage3", "stage4"])
+def test_pointwise_sampled(c, geo, form, dt, exact):
+    """urso_conv_pointwise_sampled (pair_kernel, single-layer form with the sampled copy): dst = act(src W^T + bias [+ add]) rounded once
+    (K = c + 2, c + 1 without add), dst_sampled bit for bit dst[:, ::2, ::2] (the store's pixel map), bits = (stored dst > 0), a guard
+    tile behind dst_sampled untouched."""
+    hip = _hip()
+    B, H, W = geo
+    has_add, relu, emit, cap = SAMPLED_FORMS[form]
+    N = 4 * c if c < 256 else 1024
+    M, MS, G = B * H * W, B * (H // 2) * (W // 2), 64
+    seed = c + M + 3 * dt + 7 * list(SAMPLED_FORMS).index(form)
+    x = _operands((M, c), dt, exact, c, seed)
+    w = _operands((N, c), dt, exact, c, seed + 1, c ** -0.5)
+    bias = _operands((N,), 0, exact, 0, seed + 2, 0.2, small=True)
+    add = _operands((M, N), dt, exact, 0, seed + 3, small=True) if has_add else None
+    z, mag = _mm(x, w) + bias.double(), _mm(x.abs(), w.abs()) + bias.double().abs()
+    if has_add:
+        z, mag = z + add.double(), mag + add.double().abs()
+    z0 = z - x[:, -1:].double() * w.double()[:, -1]                         # the last input channel zeroed
+    ref, ref0 = (F.relu(z), F.relu(z0)) if relu else (z, z0)
+    flags = (hip.EPI_RELU if relu else 0) | (hip.EPI_EMIT_BITS if emit else 0)
+    g = hip.geom(B, H, W, c, H, W, N, 1, 1)
+    dst, smp = full((B, H, W, N), dt), full((MS + G, N), dt)
+    bits = torch.full((M * N // 8,), 0x55, dtype=torch.uint8, device="cuda") if emit else None
+    with hip.options(grid_cap=cap):
+        assert hip.conv_pointwise_sampled_ok(g, dt, flags, has_add)
+        with X.ran("pair_kernel"):
+            hip.conv_pointwise_sampled(g, dt, flags, dev(x, dt), dev(w, dt), bias.cuda(), dev(add, dt) if has_add else None, dst, bits, smp)
+    torch.cuda.synchronize()
+    assert bool((smp[MS:].float() == SENTINEL).all()), "the guard tile behind dst_sampled was written"
+    smp = smp[:MS].reshape(B, H // 2, W // 2, N)
+    if exact:
+        X.premise(dt, stored=[("dst", ref)], mags=[("dst", mag)])
+        X.assert_sensitive(ref, ref0, z if relu else None, "dst")
+        X.assert_exact(dst.reshape(M, N), ref, "dst")
+        X.assert_exact(smp, ref.reshape(B, H, W, N)[:, ::2, ::2], "dst_sampled")
+    else:
+        _record("pointwise_sampled", X.assert_rounded_once(dst.reshape(M, N), ref, mag, dt, c + (2 if has_add else 1), "dst"))
+    want = dst[:, ::2, ::2]
+    if not torch.equal(smp, want):
+        X.assert_exact(smp, want.double().cpu(), "dst_sampled against dst[:, ::2, ::2]")
+    if emit:
+        assert torch.equal(_unpack_bits(bits, M, N), (dst.reshape(M, N).cpu().float() > 0).to(torch.int32)), "emitted bits differ from (stored dst > 0)"
+
+
+# ---------------------------------------------------------------- Winograd F(2x2, 3x3), exact mode only (conv_winograd.hip)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("shape", [(2, 9, 15, 64, 64), (3, 17, 23, 128, 72)], ids=["c64", "odd_sizes_ragged_N"])
+def test_winograd_exact(shape, dt):
+    """urso_conv_winograd_fwd on integer operands with |v| <= 2: U = G g G^T is then a multiple of 1/4 with |U| <= 4.5 and V = B^T d B an
+    integer with |V| <= 8 -- both exact in bf16 and f16 (premise proves it on the float64 transforms) -- and every fp32 sum is exact, so
+    the output must equal the direct float64 conv BIT FOR BIT.  No rounded-once mode: on real data the transformed operands are rounded by
+    design (tests/test_kernels_gpu.py keeps the normwise test)."""
+    hip = _hip()
+    B, H, W, C, N = shape
+    seed = C + N + H + dt
+    amax, d = X.int_plan(9 * C, dt)
+    assert amax <= 2
+    x, w = X.int_operands((B, H, W, C), dt, amax, d, seed), X.int_operands((3, 3, C, N), dt, amax, d, seed + 1)
+    bias = X.int_operands((N,), None, 3, 0.8, seed + 2)
+    pre = _conv64(x.double(), w.double(), 1, (1, 1), H, W) + bias.double()
+    x0 = x.double().clone(); x0[..., -1] = 0
+    pre0 = _conv64(x0, w.double(), 1, (1, 1), H, W) + bias.double()
+    U, V = X.winograd_uv(w, x)
+    assert float(U.abs().max()) <= 4.5 and float(V.abs().max()) <= 8
+    X.assert_exact(X.winograd_out(U, V, H, W) + bias.double(), pre, "the float64 Winograd evaluation")
+    mag = X.winograd_out(U, V, H, W, magnitude=True) + bias.double().abs()
+    X.premise(dt, stored=[("U", U), ("V", V), ("y", F.relu(pre))], mags=[("y", mag)])
+    X.assert_sensitive(F.relu(pre), F.relu(pre0), pre, "winograd")
+    wf, _, biasf = prep_weights(w, dt, bias)
+    g = hip.geom(B, H, W, C, H, W, N, 3, 3, 1, 1, 1, 1)
+    ws = torch.full((hip.conv_winograd_ws_bytes(g, dt) // 4 + 16,), float("nan"), dtype=torch.float32, device="cuda")
+    y = full((B, H, W, N), dt)
+    with X.ran("wino_filter_kernel"):
+        hip.conv_winograd_fwd(g, dt, hip.EPI_RELU, dev(x, dt), wf, biasf, y, ws)
+    torch.cuda.synchronize()
+    X.assert_exact(y, F.relu(pre), "winograd forward")
 
 
 # ---------------------------------------------------------------- two reduction segments (urso_conv_pointwise2, conv_pwx.hip SEG2)
