@@ -760,6 +760,43 @@ int urso_frames_put_u8(int B, int HW, const uint8_t* src_d, const uint64_t* dst_
 int urso_frames_gather_u8(int B, int HW, const uint64_t* src_addr_d, const uint8_t* kind_d, uint8_t* dst_d, void* stream);
 
 /*
+ * The video path (pose_estimator.detect_video, pose_estimator.py:606-745; ursonet_amd/video.py) around the network.
+ *
+ * Frame prep of pose_estimator.py:641-645 for a uint8 RGB batch src_d [B,H,W,3] in one pass: crop `top` / `bottom` rows and `left` /
+ * `right` columns away, surround what is left by `pad` zero pixels on all four sides, and replace all three channels of every pixel by
+ * its grey value.  dst_d is [B, H - top - bottom + 2 pad, W - left - right + 2 pad, 3].  The grey value has the BYTES of the NumPy statement
+ * `image[:,:,0] = w0*R + w1*G + w2*B` on a uint8 image: (w0 R + w1 G) + w2 B in IEEE float64, each multiply and each add rounded on its
+ * own (no fused multiply-add), converted to uint8 by truncation.  With the reference's weights (0.21, 0.72, 0.07) white maps to 254.
+ * Weights that take the value outside [0, 256) leave that byte unspecified, as the NumPy conversion does.  URSO_EINVAL before any
+ * launch: a null pointer, src == dst, a non-positive size, B > 65535, a negative crop or pad, a crop that leaves no pixel, an input or
+ * output frame of 2 GiB or more.
+ */
+int urso_video_prep_u8(int B, int H, int W, int top, int bottom, int left, int right, int pad, double w0, double w1, double w2,
+                       const uint8_t* src_d, uint8_t* dst_d, void* stream);
+
+/*
+ * Exact rasteriser: draws up to URSO_DRAW_MAX_PRIMS primitives per frame onto a uint8 batch img_d [B,H,W,3], in place.  A primitive is a
+ * row of URSO_DRAW_PRIM_INTS int32: [kind, x0, y0, x1, y1, r, cR, cG, cB]; frame b owns rows [b][0 .. counts[b]) of prims [B][16][9].
+ * Later primitives overwrite earlier ones; pixels no primitive covers are not written.  With (x, y) a pixel (its centre):
+ *   URSO_DRAW_SEGMENT  thickness t = r: painted iff 4 d^2 <= t^2, d^2 the squared distance to the closed segment a = (x0, y0), b = (x1, y1).
+ *                      Integers only: D = b - a, w = p - a, s = w.D; s <= 0: 4 |w|^2 <= t^2; s >= |D|^2: 4 |p - b|^2 <= t^2; else
+ *                      4 (|w|^2 |D|^2 - s^2) <= t^2 |D|^2.  A zero-length segment is a disc of diameter t.
+ *   URSO_DRAW_DISC     painted iff (x - x0)^2 + (y - y0)^2 <= r^2 (x1, y1 unused).
+ * The rule is evaluated in int64 and its result is defined to the byte.  The primitives are given twice, as urso_wgrad_group_run takes
+ * its items: prims_host / counts_host (host memory) are validated here, prims_d / counts_d (the same bytes on the device) are what
+ * the kernel reads.  URSO_EINVAL before any launch: a null pointer, a non-positive size, B > 65535, H or W above URSO_DRAW_COORD_MAX, a
+ * count outside 0 .. URSO_DRAW_MAX_PRIMS, an unknown kind, |x0|, |y0|, |x1|, |y1| or r above URSO_DRAW_COORD_MAX (this keeps every
+ * product below 2^62), a negative r, a colour outside 0 .. 255.  All counts 0: nothing is launched.
+ */
+#define URSO_DRAW_SEGMENT 0
+#define URSO_DRAW_DISC 1
+#define URSO_DRAW_MAX_PRIMS 16
+#define URSO_DRAW_PRIM_INTS 9
+#define URSO_DRAW_COORD_MAX 16384
+int urso_draw_prims_u8(int B, int H, int W, const int32_t* prims_host, const int32_t* counts_host, const int32_t* prims_d,
+                       const int32_t* counts_d, uint8_t* img_d, void* stream);
+
+/*
  * Opt-in launch profiler: when enabled every urso_* launch is bracketed by HIP events on
  * its stream.  urso_prof_collect() synchronises and returns per-record milliseconds.
  */

@@ -290,3 +290,61 @@ def resize_images(images, min_dim=None, max_dim=None, min_scale=None, mode="squa
         hip.resize_images_u8(B, H, W, C, nh, nw, OH, OW, window[0], window[1], t["ky"], t["ry"], t["kx"], t["rx"], t["y0"], t["fy"], t["x0"],
                              t["fx"], 1 if utils._resize_compat() == "0.18" else 0, x, out)
     return out, window, scale, padding
+
+
+# --------------------------------------------------------------------------- video path (pose_estimator.py:606-745; ursonet_amd/video.py)
+def video_prep(frames, prep, out=None):
+    """video.VideoPrep.host for a uint8 batch [B,H,W,3] of one frame size (array or device tensor), on the GPU and with the host function's
+    BYTES (urso_video_prep_u8: crop + zero pad + grey mix in one pass) -> uint8 CUDA tensor [B,OH,OW,3], (OH, OW) = prep.out_shape(H, W).
+    `out`: a uint8 CUDA tensor of the result's shape to write into."""
+    dtype, shape = getattr(frames, "dtype", None), tuple(getattr(frames, "shape", ()))
+    if str(dtype).replace("torch.", "") != "uint8" or len(shape) != 4 or shape[-1] != 3:
+        raise ValueError("video_prep: uint8 [B,H,W,3] frames expected, not %s %s" % (dtype, shape))
+    import torch
+    from . import hip
+    B, H, W, _ = shape
+    OH, OW = prep.out_shape(H, W)
+    x = torch.as_tensor(frames).cuda().contiguous()
+    if out is None or tuple(out.shape) != (B, OH, OW, 3):
+        out = torch.empty((B, OH, OW, 3), dtype=torch.uint8, device=x.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    hip.video_prep_u8(B, H, W, prep.crop, prep.pad, prep.grey, x, out)
+    return out
+
+
+def draw_prims(frames, prims, counts=None):
+    """Draws primitives onto a contiguous uint8 CUDA batch [B,H,W,3] IN PLACE (urso_draw_prims_u8: exact integer segments and discs; rows
+    [kind, x0, y0, x1, y1, r, cR, cG, cB], later rows on top).  prims: an int array [B, P <= 16, 9] with counts [B] (rows at and behind a
+    frame's count are ignored), or, with counts None, a list of B arrays [n_b <= 16, 9].  Unknown kinds, more than 16 primitives and
+    coordinates beyond +-16,384 raise hip.UrsoHipError: drop such primitives first (video.pose_axes_prims does).  Returns `frames`."""
+    import torch
+    from . import hip
+    assert torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3 and \
+        frames.is_contiguous(), "draw_prims draws in place: a contiguous uint8 CUDA tensor [B,H,W,3] expected"
+    B, H, W, _ = frames.shape
+    host = np.zeros((B, hip.DRAW_MAX_PRIMS, hip.DRAW_PRIM_INTS), dtype=np.int32)
+    if counts is None:
+        if len(prims) != B:
+            raise ValueError("draw_prims: %d primitive lists for %d frames" % (len(prims), B))
+        rows = [np.asarray(p, dtype=np.int64).reshape(-1, hip.DRAW_PRIM_INTS) for p in prims]
+        cnt = np.array([len(r) for r in rows], dtype=np.int64)
+    else:
+        arr = np.asarray(prims, dtype=np.int64)
+        if arr.ndim != 3 or arr.shape[0] != B or arr.shape[2] != hip.DRAW_PRIM_INTS:
+            raise ValueError("draw_prims: prims [B, P, 9] expected, not %s" % (arr.shape,))
+        cnt = np.asarray(counts, dtype=np.int64).reshape(-1)
+        if cnt.shape != (B,):
+            raise ValueError("draw_prims: counts [B] expected")
+        rows = [arr[b, :max(0, min(int(cnt[b]), arr.shape[1]))] for b in range(B)]
+        if np.any(cnt > arr.shape[1]):
+            raise ValueError("draw_prims: a count exceeds the %d rows given" % arr.shape[1])
+    if np.any(cnt > hip.DRAW_MAX_PRIMS) or np.any(cnt < 0):
+        raise hip.UrsoHipError("urso_draw_prims_u8: a frame has %d primitives (0 .. %d)" % (int(cnt.max() if cnt.max() > hip.DRAW_MAX_PRIMS else cnt.min()),
+                                                                                          hip.DRAW_MAX_PRIMS))
+    for b, r in enumerate(rows):
+        if np.any(np.abs(r) > 2 ** 31 - 1):
+            raise hip.UrsoHipError("urso_draw_prims_u8: frame %d: a value outside int32" % b)
+        host[b, :len(r)] = r
+    cnt32 = np.ascontiguousarray(cnt, dtype=np.int32)
+    hip.draw_prims_u8(B, H, W, host, cnt32, torch.as_tensor(host).to(frames.device), torch.as_tensor(cnt32).to(frames.device), frames)
+    return frames

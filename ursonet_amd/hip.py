@@ -206,6 +206,8 @@ _SIGS = {
     "urso_frames_grey_flags_u8": (_i, [_i, _i, _vp, _vp, _vp]),
     "urso_frames_put_u8": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "urso_frames_gather_u8": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "urso_video_prep_u8": (_i, [_i] * 8 + [C.c_double] * 3 + [_vp, _vp, _vp]),
+    "urso_draw_prims_u8": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "urso_conv_winograd_ws_bytes": (_sz, [_gp, _i]),
     "urso_conv_winograd_fwd": (_i, [_gp, _i, _i, _vp, _vp, _fp, _vp, _vp, _sz, _vp]),
     "urso_prof_enable": (_i, [_i]),
@@ -862,6 +864,30 @@ def frames_gather_u8(B, HW, src_addr, kind, dst, stream=None):
     assert dst.dtype == torch.uint8 and dst.numel() >= B * HW * 3
     assert src_addr.dtype == torch.int64 and src_addr.numel() >= B and kind.dtype == torch.uint8 and kind.numel() >= B
     _chk(_lib.urso_frames_gather_u8(int(B), int(HW), ptr(src_addr), ptr(kind), ptr(dst), stream_ptr(stream)), "urso_frames_gather_u8")
+
+
+DRAW_SEGMENT, DRAW_DISC, DRAW_MAX_PRIMS, DRAW_PRIM_INTS, DRAW_COORD_MAX = 0, 1, 16, 9, 16384       # include/ursonet_hip.h
+
+
+def video_prep_u8(B, H, W, crop, pad, grey, src, dst, stream=None):
+    """urso_video_prep_u8: crop (top, bottom, left, right) + zero pad + grey mix (three float64 weights) of a uint8 batch [B,H,W,3] ->
+    dst [B, H - top - bottom + 2 pad, W - left - right + 2 pad, 3], with the bytes of ursonet_amd.video.VideoPrep.host."""
+    assert src.dtype == torch.uint8 and dst.dtype == torch.uint8
+    top, bottom, left, right = (int(v) for v in crop)
+    w0, w1, w2 = (float(v) for v in grey)
+    _chk(_lib.urso_video_prep_u8(int(B), int(H), int(W), top, bottom, left, right, int(pad), w0, w1, w2, ptr(src), ptr(dst), stream_ptr(stream)),
+         "urso_video_prep_u8")
+
+
+def draw_prims_u8(B, H, W, prims_host, counts_host, prims, counts, img, stream=None):
+    """urso_draw_prims_u8: prims_host int32 ndarray [B,16,9] and counts_host int32 ndarray [B] (C-contiguous) are validated on the host,
+    prims / counts are their device copies, img the uint8 batch [B,H,W,3] drawn onto in place."""
+    assert prims_host.dtype == "int32" and counts_host.dtype == "int32" and prims_host.flags.c_contiguous and counts_host.flags.c_contiguous
+    assert prims_host.shape == (B, DRAW_MAX_PRIMS, DRAW_PRIM_INTS) and counts_host.shape == (B,)
+    assert prims.dtype == torch.int32 and counts.dtype == torch.int32 and img.dtype == torch.uint8
+    assert prims.numel() == prims_host.size and counts.numel() == B and img.numel() == B * H * W * 3
+    _chk(_lib.urso_draw_prims_u8(int(B), int(H), int(W), prims_host.ctypes.data, counts_host.ctypes.data, ptr(prims), ptr(counts), ptr(img),
+                                 stream_ptr(stream)), "urso_draw_prims_u8")
 
 
 def prof_enable(on):
