@@ -50,22 +50,32 @@ int         urso_abi_version(void);           /* bumped on any signature or data
 /*
  * Kernel-policy options (process-wide, explicit; defaults in parentheses).  They select between kernels / tile shapes
  * that compute the same result, so that variants can be compared inside one process and tests can force rarely-taken
- * code paths on small shapes.  Unknown names return URSO_EINVAL.
+ * code paths on small shapes.  Unknown names return URSO_EINVAL.  One row per option of URSO_OPTION_TABLE (ursonet_amd/csrc/common.h).
  *   pw_kernel (3)     DMA-staged conv kernel coverage: 0 off, 1 pointwise layers, 2 + whole-tap convs, 3 + the stem
  *   pw_small (5)      narrow-tile policy of that kernel (0 never, 1 always, 2 short-K, 3 multi-tap, 5 measured default)
- *   igemm_shortk (0)  general kernel: narrow tile for layers with at most this many K-tiles
  *   wgrad_narrow (1)  128x64 weight-gradient tile for layers with <= 64 filters
  *   wgrad_blocks (512) resident-block target of the weight-gradient pixel split
  *   wgrad_pipe (1)    scheduler-interleaved fragment reads in the 16-bit weight-gradient kernel
+ *   wgrad_big (1)     grouped weight gradients of layers with >= 256 channels and filters on 256 x 256 tiles
+ *   wgrad_ring (0)    grouped weight gradients of the other layers: 0 = 64-pixel double buffer, 4 / 5 = stages of the 32-pixel ring
  *   grid_cap (0)      > 0: upper bound on the block count of the persistent conv kernels (tests: makes every block
  *                     walk several tiles, i.e. exercises the cross-tile prefetch path, on small shapes)
  *   hconv (1)         8-wave halo-tile kernel (conv_halo.hip) for 3x3 stride-1 layers with >= 128 channels and filters:
  *                     0 never, 1 where its tile count fills the chip evenly (measured policy), 2 wherever it applies
  *   hconv_dbg (0)     kernel-development switches of that kernel; leave 0
+ *   hconv2 (1)        whole tiles of a per-layer shape without hand-over (conv_halo2.hip) for the same layers: 0 off, 1 where its cost
+ *                     model beats conv_halo.hip's schedule, 2 whenever a shape fits
+ *   hconv2_shape (0)  10 * MI + NJ: force its tile shape 128 MI x 64 NJ (tests, probes); 0 = by the cost model
+ *   hconv_streamk (1) conv_halo.hip may hand accumulators of cut tiles over between blocks (needs every block resident: a data-parallel
+ *                     host switches it off while collectives run beside the step)
+ *   hwgrad (1)        halo-run weight gradient (conv_hwgrad.hip) of the 3x3 layers with >= 128 channels: 0 off, 1 on; 3 / 5 / 7: timing
+ *                     switches of tools/hwgrad_probe.py
  *   c3 (1)            register-resident-filter kernels (conv_c3.hip) for 3x3 stride-1 layers: 64 channels / filters always, 128 / 128
  *                     where the 4 x 32 tiles cover the image to >= 88 % (else the halo kernel); 2: only the 64-channel form, 3: both always
+ *   c3v (1)           128-channel 3x3 layers on 8 x 16 tiles: 1 = 16 filters per wave over the whole reduction (c3v_kernel), 0 = c3w_kernel
  *   stem (1)          conv_stem.hip for the packed 7x7 / stride-2 stem (0: the DMA kernel's one-copy-per-tap form)
  *   stem_pool (1)     urso_stem_conv_pool available (0: callers run urso_conv_igemm + urso_maxpool3x3s2_fwd)
+ *   mold_scalar (0)   1: urso_mold_images keeps the one-pixel-per-thread form for uint8 frames (A/B, tests; default: 8 pixels per thread)
  *   cus (0)           > 0: the CUs the persistent conv grids, the weight-gradient split and their workspaces are planned for (whole XCD
  *                     rows of 8; 0 = all of the device's).  A data-parallel host sets it to (CUs - what the collective's resident
  *                     workgroups hold) BEFORE it plans a step, so that a CU held by RCCL never gives a statically partitioned tile
@@ -80,6 +90,12 @@ int         urso_abi_version(void);           /* bumped on any signature or data
  *                     itself never fuses behind the caller's back); 1 also lets the stage-2 backward pair accumulate the block-closing
  *                     layer's weight gradient (urso_conv_pair_wgrad) and the first stage-2 forward pair take the projection shortcut in
  *                     (urso_conv_pair_shortcut); 2: without the weight-gradient fold; 3: plain pairs only
+ *   pair_single (3)   urso_conv_pair takes the single c -> 4c layers of stage 4 (bit 0) / stage 5 (bit 1); cleared bits leave them to
+ *                     conv_pwx.hip
+ *   pwx (1)           8-wave 160-row-tile pointwise GEMM (conv_pwx.hip): 0 off, 1 the reduction-heavy layers (K >= 512), 2 every
+ *                     supported layer
+ *   pwx_bn (0)        128 / 256: force its tile width (tests); 0 = by tile-count rounding
+ *   pwx_dbg (0)       kernel-development switches of that kernel (1 no copies after the prologue, 2 no MFMAs, 4 no epilogue); leave 0
  */
 int urso_set_option(const char* name, int value);
 int urso_get_option(const char* name, int* value);

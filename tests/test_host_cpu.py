@@ -458,6 +458,53 @@ def test_policy_options_are_explicit_and_never_read_the_environment():
         assert "getenv" not in open(os.path.join(csrc, f), errors="replace").read(), f
 
 
+def _option_table():
+    """(name, default) rows of URSO_OPTION_TABLE in ursonet_amd/csrc/common.h."""
+    src = open(os.path.join(ROOT, "ursonet_amd", "csrc", "common.h")).read()
+    m = re.search(r"#define URSO_OPTION_TABLE\(X\)((?:.*\\\n)*.*\n)", src)
+    assert m, "URSO_OPTION_TABLE not found in common.h"
+    rows = [(n, int(d)) for n, d in re.findall(r"\bX\((\w+),\s*(-?\d+)\)", m.group(1))]
+    assert len(rows) == len(re.findall(r"^\s*X\(", m.group(1), re.M)), "a table row did not parse"
+    return rows
+
+
+def test_option_table_library_and_header_agree():
+    """The one option table (csrc/common.h) is what the library knows (urso_get_option gives every row's default) and what the comment
+    block above urso_set_option in include/ursonet_hip.h documents, default included; the dropped igemm_shortk is refused."""
+    import ursonet_amd.hip as hip
+    rows = _option_table()
+    assert len(rows) >= 27 and len(set(n for n, _ in rows)) == len(rows)
+    header = open(os.path.join(ROOT, "include", "ursonet_hip.h")).read()
+    block = header[header.index("Kernel-policy options"):header.index("int urso_set_option(")]
+    documented = dict((n, int(d)) for n, d in re.findall(r"^ \*   (\w+) \((-?\d+)\)", block, re.M))
+    for name, default in rows:
+        assert hip.get_option(name) == default, name
+        assert documented.get(name) == default, (name, documented.get(name))
+    assert sorted(documented) == sorted(n for n, _ in rows)
+    with pytest.raises(hip.UrsoHipError):
+        hip.get_option("igemm_shortk")
+    with pytest.raises(hip.UrsoHipError):
+        hip.set_option("igemm_shortk", 1)
+
+
+def test_urso_opt_environment_variables_all_apply_and_unknown_ones_fail():
+    """ursonet_amd/hip.py applies every URSO_OPT_<NAME> at import (options are process-wide: fresh child processes) and refuses to
+    import with one the library does not know, naming the variable."""
+    import subprocess
+    import sys
+    base = dict((k, v) for k, v in os.environ.items() if not k.startswith("URSO_OPT_"))
+
+    def child(code, **extra):
+        return subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(base, **extra), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                              universal_newlines=True, timeout=300)
+
+    r = child("import ursonet_amd.hip as hip; print(hip.get_option('pwx'), hip.get_option('mold_scalar'))", URSO_OPT_PWX="2", URSO_OPT_MOLD_SCALAR="1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == ["2", "1"], r.stdout
+    r = child("import ursonet_amd.hip", URSO_OPT_NO_SUCH="1")
+    assert r.returncode != 0 and "URSO_OPT_NO_SUCH" in r.stderr, (r.returncode, r.stderr[-2000:])
+
+
 def test_cabi_argument_validation_without_gpu():
     import ursonet_amd.hip as hip
     g = hip.geom(2, 8, 8, 12, 8, 8, 16, 3, 3, 1, 1, 1, 1)                 # C=12 is not a 16-byte multiple in bf16

@@ -15,38 +15,41 @@ typedef __attribute__((ext_vector_type(2))) int i32x2_t;
 void urso_set_error(const char* fmt, ...);
 int  urso_check_launch(const char* what);
 
-// Explicit kernel-policy options (runtime.hip; include/ursonet_hip.h urso_set_option).  Defaults are compiled in; nothing
+// Explicit kernel-policy options (include/ursonet_hip.h urso_set_option): one row per option -- name, compiled-in default, what it selects.
+// UrsoOptions below and opt_slot() in runtime.hip are generated from this table; the header's comment block lists the same rows.  Nothing
 // reads the process environment.
+#define URSO_OPTION_TABLE(X) \
+    X(pw_kernel, 3)        /* conv_pw.hip coverage: 0 off, 1 pointwise, 2 + whole-tap convs, 3 + stem */ \
+    X(pw_small, 5)         /* narrow-tile policy of conv_pw.hip */ \
+    X(wgrad_narrow, 1)     /* 128x64 weight-gradient tile for N <= 64 */ \
+    X(wgrad_blocks, 512)   /* resident-block target of the weight-gradient split */ \
+    X(wgrad_pipe, 1)       /* scheduler-interleaved fragment reads in wgrad_tr_kernel */ \
+    X(wgrad_big, 1)        /* grouped weight gradients of layers with >= 256 channels and filters on 256 x 256 tiles (wgrad_group_big_kernel) */ \
+    X(wgrad_ring, 0)       /* grouped weight gradients (wgrad_group_kernel): 0 = 64-pixel double buffer, 4 / 5 = stages of the 32-pixel ring */ \
+    X(grid_cap, 0)         /* > 0: cap the block count of the persistent conv kernels (tests: forces the multi-tile stream on small shapes) */ \
+    X(hconv, 1)            /* conv_halo.hip (8-wave halo-tile kernel) for qualifying 3x3 layers */ \
+    X(pair, 1)             /* conv_pair.hip: fused pointwise pairs of stages 2-3 (read by the host plan, ursonet_amd/engine.py) */ \
+    X(pair_single, 3)      /* conv_pair.hip takes the single c -> 4c layers of stage 4 (bit 0) / stage 5 (bit 1); cleared bits leave them to conv_pwx.hip */ \
+    X(c3, 1)               /* conv_c3.hip (register-resident 3x3 filter) for 64-channel / 64-filter 3x3 layers */ \
+    X(c3v, 1)              /* 128-channel 3x3 layers on 8 x 16 tiles: 1 c3v_kernel (16 filters per wave over the whole reduction, no exchange), 0 c3w_kernel */ \
+    X(stem, 1)             /* conv_stem.hip (im2col on the LDS read side) for the packed 7x7 stem */ \
+    X(stem_pool, 1)        /* conv1 + ReLU + max-pool in one kernel (urso_stem_conv_pool); 0: the engine runs the two kernels */ \
+    X(cus, 0)              /* > 0: CUs the persistent grids and the weight-gradient split may fill (rounded down to whole XCD rows of 8); ursonet_amd/dp.py leaves the rest to the collective's resident workgroups.  0 = all of the device's */ \
+    X(hconv2, 1)           /* conv_halo2.hip (whole tiles of a per-layer shape, no hand-over): 0 off, 1 where its cost model beats conv_halo.hip's schedule, 2 whenever a shape fits */ \
+    X(hconv2_shape, 0)     /* 10 * MI + NJ: force its tile shape 128 MI x 64 NJ (tests, probes); 0 = by the cost model */ \
+    X(hconv_streamk, 1)    /* conv_halo.hip may hand accumulators of cut tiles over between blocks (needs every block resident: ursonet_amd/dp.py switches it off while collectives run beside the step) */ \
+    X(hconv_dbg, 0)        /* kernel-development switches of conv_halo.hip (0 in production) */ \
+    X(hwgrad, 1)           /* conv_hwgrad.hip: halo-run weight gradient of the 3x3 layers with >= 128 channels (gradient groups in registers); 0 off, 1 on; 3 / 5 / 7: timing switches (tools/hwgrad_probe.py) */ \
+    X(dense, 1)            /* conv_dense.hip: skinny GEMM (<= 32 rows) for the Dense heads and their data gradients */ \
+    X(pwx, 1)              /* conv_pwx.hip (8-wave 160-row-tile pointwise GEMM): 0 off, 1 the reduction-heavy layers (K >= 512), 2 every supported layer */ \
+    X(pwx_dbg, 0)          /* kernel-development switches of conv_pwx.hip (0 in production): 1 no copies after the prologue, 2 no MFMAs, 4 no epilogue */ \
+    X(pwx_bn, 0)           /* 128 / 256: force its tile width (tests); 0 = by tile-count rounding */ \
+    X(mold_scalar, 0)      /* 1: urso_mold_images keeps the one-pixel-per-thread form for uint8 frames (A/B, tests; default: 8 pixels per thread, round 6) */ \
+    X(bneck, 3)            /* conv_bneck.hip, bottleneck_layer (3x3 / stride 2, <= 32 filters): bit 0 its data gradient by parity class (no zero taps), bit 1 its forward pass in one launch (LDS-staged, no split-K workspace) */
 struct UrsoOptions {
-    int pw_kernel = 3;       // conv_pw.hip coverage: 0 off, 1 pointwise, 2 + whole-tap convs, 3 + stem
-    int pw_small = 5;        // narrow-tile policy of conv_pw.hip
-    int igemm_shortk = 0;    // conv_igemm.hip: narrow tile for K-tiles <= this
-    int wgrad_narrow = 1;    // 128x64 weight-gradient tile for N <= 64
-    int wgrad_blocks = 512;  // resident-block target of the weight-gradient split
-    int wgrad_pipe = 1;      // scheduler-interleaved fragment reads in wgrad_tr_kernel
-    int wgrad_big = 1;       // grouped weight gradients of layers with >= 256 channels and filters on 256 x 256 tiles (wgrad_group_big_kernel)
-    int wgrad_ring = 0;      // grouped weight gradients (wgrad_group_kernel): 0 = 64-pixel double buffer, 4 / 5 = stages of the 32-pixel ring
-    int grid_cap = 0;        // > 0: cap the block count of the persistent conv kernels (tests: forces the multi-tile stream on small shapes)
-    int hconv = 1;           // conv_halo.hip (8-wave halo-tile kernel) for qualifying 3x3 layers
-    int pair = 1;            // conv_pair.hip: fused pointwise pairs of stages 2-3 (read by the host plan, ursonet_amd/engine.py)
-    int pair_single = 3;     // conv_pair.hip takes the single c -> 4c layers of stage 4 (bit 0) / stage 5 (bit 1); cleared bits leave them to conv_pwx.hip
-    int c3 = 1;              // conv_c3.hip (register-resident 3x3 filter) for 64-channel / 64-filter 3x3 layers
-    int c3v = 1;             // 128-channel 3x3 layers on 8 x 16 tiles: 1 c3v_kernel (16 filters per wave over the whole reduction, no exchange), 0 c3w_kernel
-    int stem = 1;            // conv_stem.hip (im2col on the LDS read side) for the packed 7x7 stem
-    int stem_pool = 1;       // conv1 + ReLU + max-pool in one kernel (urso_stem_conv_pool); 0: the engine runs the two kernels
-    int cus = 0;             // > 0: CUs the persistent grids and the weight-gradient split may fill (rounded down to whole XCD rows of 8);
-                             // ursonet_amd/dp.py leaves the rest to the collective's resident workgroups.  0 = all of the device's
-    int hconv2 = 1;          // conv_halo2.hip (whole tiles of a per-layer shape, no hand-over): 0 off, 1 where its cost model beats conv_halo.hip's schedule, 2 whenever a shape fits
-    int hconv2_shape = 0;    // 10 * MI + NJ: force its tile shape 128 MI x 64 NJ (tests, probes); 0 = by the cost model
-    int hconv_streamk = 1;   // conv_halo.hip may hand accumulators of cut tiles over between blocks (needs every block resident: ursonet_amd/dp.py switches it off while collectives run beside the step)
-    int hconv_dbg = 0;       // kernel-development switches of conv_halo.hip (0 in production)
-    int hwgrad = 1;          // conv_hwgrad.hip: halo-run weight gradient of the 3x3 layers with >= 128 channels (gradient groups in registers); 0 off, 1 on; 3 / 5 / 7: timing switches (tools/hwgrad_probe.py)
-    int dense = 1;           // conv_dense.hip: skinny GEMM (<= 32 rows) for the Dense heads and their data gradients
-    int pwx = 1;             // conv_pwx.hip (8-wave 160-row-tile pointwise GEMM): 0 off, 1 the reduction-heavy layers (K >= 512), 2 every supported layer
-    int pwx_dbg = 0;         // kernel-development switches of conv_pwx.hip (0 in production): 1 no copies after the prologue, 2 no MFMAs, 4 no epilogue
-    int pwx_bn = 0;          // 128 / 256: force its tile width (tests); 0 = by tile-count rounding
-    int mold_scalar = 0;     // 1: urso_mold_images keeps the one-pixel-per-thread form for uint8 frames (A/B, tests; default: 8 pixels per thread, round 6)
-    int bneck = 3;           // conv_bneck.hip, bottleneck_layer (3x3 / stride 2, <= 32 filters): bit 0 its data gradient by parity class (no zero taps), bit 1 its forward pass in one launch (LDS-staged, no split-K workspace)
+#define URSO_OPT_FIELD(name, dflt) int name = dflt;
+    URSO_OPTION_TABLE(URSO_OPT_FIELD)
+#undef URSO_OPT_FIELD
 };
 extern UrsoOptions g_urso_opt;
 int urso_device_cus();      // CUs of the current device (runtime.hip)
@@ -183,4 +186,28 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     int q = nblk / NX, r = nblk % NX;
     int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + idx;
+}
+
+// ---------------------------------------------------------------- persistent tile streams
+// The contract between the launcher of a persistent conv kernel and the kernel: the grid's x extent is 8 * bpx blocks, all resident.  Block
+// b belongs to XCD b & 7 (the hardware deals consecutive block ids round the 8 XCDs) and is block b >> 3 of that XCD's bpx.  XCD x owns the
+// contiguous tiles [x * cpx, min((x + 1) * cpx, ntiles)), cpx = ceil(ntiles / 8), so that neighbouring tiles meet in one L2, and each of
+// its blocks walks them with stride bpx.  (conv_halo.hip / conv_halo2.hip launch the same grid but deal every block one contiguous run.)
+//
+// Host half: the grid's x extent for `ntiles` tiles at `blocks_per_cu` resident blocks per CU, shared among `groups` (gridDim.y).  The
+// clamp of the cap to one block per XCD is a no-op unless groups > blocks_per_cu: urso_usable_cus() never returns less than 8.
+static inline int urso_persistent_grid(int ntiles, int blocks_per_cu, int groups = 1) {
+    int bpx = ceil_div(ntiles, 8), cap = blocks_per_cu * urso_usable_cus() / (8 * groups);
+    if (cap < 1) cap = 1;
+    if (bpx > cap) bpx = cap;
+    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
+    return 8 * bpx;
+}
+// Device half: the calling block's first tile, the end of its XCD's range (tile >= t_end: nothing to do) and the stride it walks with.
+struct UrsoTileStream { int tile, t_end, bpx; };
+__device__ __forceinline__ UrsoTileStream urso_tile_stream(int ntiles) {
+    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
+    const int cpx = ceil_div(ntiles, 8);
+    const int t_end = min((xcd + 1) * cpx, ntiles);
+    return { xcd * cpx + lb, t_end, bpx };
 }

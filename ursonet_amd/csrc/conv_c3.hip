@@ -45,10 +45,9 @@ __global__ __launch_bounds__(256, 2) void c3_kernel(const C3Args a) {
     int l31 = lane & 31;
     const int h = lane >> 5;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.bytes);
@@ -218,10 +217,9 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
     int l31 = lane & 31;
     const int h = lane >> 5;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.bytes);
@@ -476,10 +474,9 @@ __global__ __launch_bounds__(512, 2) void c3v_kernel(const C3Args a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.bytes);
@@ -620,8 +617,6 @@ __global__ __launch_bounds__(512, 2) void c3v_kernel(const C3Args a) {
     flush(ob);
 }
 
-static int c3_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 // 128-channel form: percentage of the tiles' pixels that lie inside the image, for the 4 x 32 (tw = 32) or 8 x 16 (tw = 16) geometry
 static int c3w_util(int H, int W, int tw) {
     const int th = 128 / tw;
@@ -653,11 +648,7 @@ int urso_c3_launch(const urso_conv_geom* g, int dt, int relu, const void* src, c
     const bool wide = g->C == 128;
     const int tw = wide ? c3w_best_tw(g->H, g->W) : C3_TW, th = 128 / tw;
     a.tiles_x = ceil_div(g->W, tw); a.tiles_y = ceil_div(g->H, th); a.ntiles = g->B * a.tiles_y * a.tiles_x;
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = (wide ? 1 : 2) * c3_device_cus() / 8;
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(wide ? 512 : 256);
+    const dim3 grid(urso_persistent_grid(a.ntiles, wide ? 1 : 2)), blk(wide ? 512 : 256);
     if (wide) {
 #define URSO_C3W(TT, TWV) do { if (mask) URSO_KLAUNCH((c3w_kernel<TT, true, TWV>), grid, blk, 0, st, a); \
                                else URSO_KLAUNCH((c3w_kernel<TT, false, TWV>), grid, blk, 0, st, a); } while (0)

@@ -64,10 +64,9 @@ __global__ __launch_bounds__(512, 2) void c3g_kernel(const C3gArgs a) {
     const int ct = wave & 1, nt = (wave >> 1) & 1, tg = wave >> 2;
     const int l31 = lane & 31, h = lane >> 5, l15 = lane & 15, g = lane >> 4;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
 
     const i32x4_t rx = raw_rsrc(a.x, a.bytes), rz = raw_rsrc(a.dz, a.bytes);
 
@@ -146,8 +145,6 @@ __global__ __launch_bounds__(512, 2) void c3g_kernel(const C3gArgs a) {
     }
 }
 
-static int cg_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 // 3x3 / stride 1 / pad 1, 64 channels, 64 filters, dense dz, 16-bit (option "c3")
 bool urso_c3g_fits(const urso_conv_geom* g, int dt) {
     if (!g_urso_opt.c3 || (dt != URSO_BF16 && dt != URSO_F16)) return false;
@@ -157,11 +154,7 @@ bool urso_c3g_fits(const urso_conv_geom* g, int dt) {
 }
 int urso_c3g_splits(const urso_conv_geom* g) {
     const int ntiles = g->B * ceil_div(g->H, CG_TH) * ceil_div(g->W, CG_TW);
-    int bpx = ceil_div(ntiles, 8);
-    const int cap = cg_device_cus() / 8;
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    return 8 * bpx;
+    return urso_persistent_grid(ntiles, 1);
 }
 int urso_c3g_launch(const urso_conv_geom* g, int dt, const void* x, const void* dz, float* part, float* colpart, size_t part_stride, hipStream_t st) {
     C3gArgs a;

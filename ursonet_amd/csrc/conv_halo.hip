@@ -372,8 +372,6 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
     }
 }
 
-static int hc_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 // Does (g, dt, flags) qualify?  3x3 / stride 1 / pad 1 / undilated, same-size output, C % 128 == 0, N % 128 == 0, halo tile within the LDS
 // budget -- and a tile count that fills the 256 one-block-per-CU slots evenly: every block walks ceil(tiles / blocks) tiles, so e.g. 340
 // tiles cost as much as 512.  hconv = 1 (default) takes the layer only when that rounding loses < 35 % (measured on cfg2: stage 3 659
@@ -389,7 +387,7 @@ bool urso_hconv_fits(const urso_conv_geom* g, int dt, int flags, const void* add
     if ((size_t)g->B * (g->H + 1) * (g->W + 1) >= (1u << 24)) return false;
     if (urso_hconv2_pick(g, true)) return true;               // conv_halo2.hip has a tile shape that fills the chip in whole rounds
     if (g_urso_opt.hconv == 1) {
-        const int ntiles = ceil_div(g->B * (g->H + 1) * (g->W + 1), HC_BM) * (g->N / HC_BN), ncu = hc_device_cus();
+        const int ntiles = ceil_div(g->B * (g->H + 1) * (g->W + 1), HC_BM) * (g->N / HC_BN), ncu = urso_usable_cus();
         const int blocks = ntiles < ncu ? ntiles : ncu, rounds = ceil_div(ntiles, blocks);
         if (ntiles * 20 < blocks * rounds * 13 && !(ntiles <= ncu && ntiles * 3 >= ncu * 2)) return false;   // < 65 % of the slots busy
     }
@@ -419,11 +417,7 @@ int urso_hconv_launch(const urso_conv_geom* g, int dt, int relu, const void* src
     a.krow = 9 * g->C * 2;
     a.rcp_vw = 1.0f / (float)a.Vw; a.rcp_vh = 1.0f / (float)a.Vh;
     a.relu = relu; a.dbg = g_urso_opt.hconv_dbg;
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = hc_device_cus() / 8;                   // 160 KiB of LDS: one block per CU; each block walks a contiguous run of tiles
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    dim3 grid(8 * bpx); const dim3 blk(512);
+    dim3 grid(urso_persistent_grid(a.ntiles, 1)); const dim3 blk(512);      // 160 KiB of LDS: one block per CU; each block walks a contiguous run of tiles
     // stream-K needs every block resident (a finishing block waits for the pieces of the runs that follow it): one block per CU, never
     // more blocks than CUs (and than flags); it is used where it shortens the longest run: ceil(tiles x chunks / blocks) chunk units
     // against ceil(tiles / blocks) whole tiles (cfg2: stage 4 6 vs 8, stage 5 6 vs 8, stage 3 6 vs 6 -> whole tiles)
@@ -431,13 +425,13 @@ int urso_hconv_launch(const urso_conv_geom* g, int dt, int relu, const void* src
     // fewer tiles than CUs (stage 5 of cfg2: 180; every stage-4/5 layer at batch 16): whole tiles would leave CUs idle for the whole
     // launch -- with the hand-over workspace the (tile, chunk) units are dealt to ALL CUs instead (cfg2 stage 5: 6 units per block
     // instead of 8, measured 62 -> 50 us per layer)
-    if (ws && ws_bytes >= urso_hconv_ws_bytes() && !(a.dbg & 4) && g_urso_opt.hconv_streamk && g_urso_opt.grid_cap <= 0 && G < hc_device_cus()) {
-        int G2 = hc_device_cus(); const int units = a.ntiles * a.nchunks;
+    if (ws && ws_bytes >= urso_hconv_ws_bytes() && !(a.dbg & 4) && g_urso_opt.hconv_streamk && g_urso_opt.grid_cap <= 0 && G < urso_usable_cus()) {
+        int G2 = urso_usable_cus(); const int units = a.ntiles * a.nchunks;
         if (G2 > units) G2 = units;
         G2 = G2 / 8 * 8;
         if (G2 > G && G2 <= 1024 && ceil_div(units, G2) < ceil_div(a.ntiles, G) * a.nchunks) { G = G2; grid = dim3(G2); }
     }
-    const bool can = ws && ws_bytes >= urso_hconv_ws_bytes() && G <= hc_device_cus() && G <= 1024 && !(a.dbg & 4) && g_urso_opt.hconv_streamk;
+    const bool can = ws && ws_bytes >= urso_hconv_ws_bytes() && G <= urso_usable_cus() && G <= 1024 && !(a.dbg & 4) && g_urso_opt.hconv_streamk;
     const bool streamk = can && ((a.dbg & 8) || ceil_div(a.ntiles * a.nchunks, G) < ceil_div(a.ntiles, G) * a.nchunks);      // hconv_dbg bit 3: whenever a workspace is given (tests)
     a.flags = streamk ? (unsigned int*)ws : nullptr;
     a.part = streamk ? (float*)((char*)ws + 4096) : nullptr;

@@ -444,7 +444,6 @@ int urso_hconv2_try_launch(const urso_conv_geom* g, int dt, int relu, const void
                            void* dst, uint32_t src_bytes, uint32_t wgt_bytes, uint32_t dst_bytes, void* ws, bool has_ws, hipStream_t st) {
     const int shape = urso_hconv2_pick(g, has_ws);
     if (!shape) return 0;
-    const int ncu = urso_usable_cus();
     const int mi = shape / 10, nj = shape % 10;
     Hx2Args a;
     a.src = src; a.wgt = wgt; a.bias = bias; a.mask = mask; a.dst = dst;
@@ -458,11 +457,7 @@ int urso_hconv2_try_launch(const urso_conv_geom* g, int dt, int relu, const void
     a.rcp_vw = 1.0f / (float)a.Vw; a.rcp_vh = 1.0f / (float)a.Vh;
     a.relu = relu; a.dbg = g_urso_opt.hconv_dbg;
     a.clk = (ws && has_ws && (a.dbg & 2048)) ? (unsigned long long*)((char*)ws + 8192) : nullptr;
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = ncu / 8 > 0 ? ncu / 8 : 1;                // all of a CU's LDS: one block per CU, each walks a contiguous run of whole tiles (>= 1 block per XCD whatever option `cus` says)
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(512);
+    const dim3 grid(urso_persistent_grid(a.ntiles, 1)), blk(512);      // all of a CU's LDS: one block per CU, each walks a contiguous run of whole tiles
     urso_prof_l2((double)a.ntiles * a.nchunks * (9.0 * 64 * nj * 128 + (double)a.R * 128));      // per tile and 64-channel chunk: nine filter tiles + one halo tile
 #define HX2_GO(MI_, NJ_) do { if (dt == URSO_BF16) URSO_KLAUNCH((hconv2_kernel<__bf16, MI_, NJ_>), grid, blk, 0, st, a); \
                               else URSO_KLAUNCH((hconv2_kernel<_Float16, MI_, NJ_>), grid, blk, 0, st, a); } while (0)

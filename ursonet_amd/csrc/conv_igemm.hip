@@ -57,10 +57,9 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int fr = lane & 15, fg = lane >> 4;
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(a.src, a.src_bytes);
@@ -397,29 +396,20 @@ static void plan_splitk(int ntiles, int nkt, int ncu, int& S, int& kps) {
 
 static int ilog2_exact(int v) { if (v == 1) return 0; if (v == 2) return 1; if (v == 4) return 2; return -1; }
 
-static int device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 template <typename T>
 static int launch_igemm(const urso_conv_geom* g, int flags, IgemmArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-    // tile choice: narrow-N layers use the 128x64 tile (no wasted MFMA columns); so do short-K
-    // (HBM-bound) layers: 48 KiB LDS / 120 VGPRs -> 3 resident blocks per CU = more bytes in flight
-    const int shortk = g_urso_opt.igemm_shortk;
-    const int ncu = device_cus();
-    const bool small = (g->N <= 64 || a.nkt <= shortk);
+    // tile choice: narrow-N layers use the 128x64 tile (no wasted MFMA columns): 48 KiB LDS / 120 VGPRs -> 3 resident blocks per CU
+    const bool small = g->N <= 64;
     const int bn = small ? 64 : 128;
     a.tilesN = ceil_div(g->N, bn); a.ntiles = ceil_div(a.M, 128) * a.tilesN;
     a.ksplit = 1; a.kps = a.nkt; a.part = nullptr;
     if (ws && a.FH == 0 && (g->N & 3) == 0) {
-        int S, kps; plan_splitk(a.ntiles, a.nkt, ncu, S, kps);
+        int S, kps; plan_splitk(a.ntiles, a.nkt, urso_usable_cus(), S, kps);
         if (S > 1 && (size_t)S * a.M * g->N * sizeof(float) <= ws_bytes) { a.ksplit = S; a.kps = kps; a.part = (float*)ws; }
     }
     const int out_tiles = a.ntiles;
     a.ntiles = out_tiles * a.ksplit;                                // the tile stream enumerates (tile, K-slice) pairs
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = (small ? 3 : 2) * ncu / 8;                     // 48 / 64 KiB LDS: 3 / 2 resident blocks per CU
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(256);
+    const dim3 grid(urso_persistent_grid(a.ntiles, small ? 3 : 2)), blk(256);      // 48 / 64 KiB LDS: 3 / 2 resident blocks per CU
     const bool coal = !(flags & URSO_EPI_OUT_F32) && (g->N % (16 / (int)sizeof(T))) == 0;
     const bool fastepi = coal && a.ksplit == 1;
     const bool mbits = (flags & URSO_EPI_MASK_BITS) && a.mask, emit = (flags & URSO_EPI_EMIT_BITS) != 0;
@@ -470,7 +460,7 @@ extern "C" size_t urso_conv_igemm_ws_bytes(const urso_conv_geom* g, int dt) {
     if (g->C % VE) return 0;
     const int M = g->B * g->OH * g->OW, nkt = ceil_div(g->KH * g->KW * (g->C / VE), 8);
     const int bn = (g->N <= 64) ? 64 : 128;
-    int S, kps; plan_splitk(ceil_div(M, 128) * ceil_div(g->N, bn), nkt, device_cus(), S, kps);
+    int S, kps; plan_splitk(ceil_div(M, 128) * ceil_div(g->N, bn), nkt, urso_usable_cus(), S, kps);
     return S > 1 ? (size_t)S * M * g->N * sizeof(float) : 0;
 }
 

@@ -88,10 +88,9 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
     const int l31 = lane & 31, h = lane >> 5, l15 = lane & 15, g = lane >> 4;
 
     // ---- tile stream: XCD x owns a contiguous segment, its blocks stride through it (conv_pw.hip)
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const uint32_t grp = blockIdx.y, gwide = grp * a.g_wide, gbits = grp * a.g_bits;
@@ -396,8 +395,6 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
     }
 }
 
-static int pr_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 extern "C" int urso_conv_pair_ok(long long M, int dt, int c_narrow, int c_wide) {
     if (M <= 0 || !(dt == URSO_BF16 || dt == URSO_F16) || c_wide != 4 * c_narrow) return 0;
     const int bm = c_narrow == PairS2::CM ? PairS2::BM : (c_narrow == PairS3::CM ? PairS3::BM : 0);
@@ -406,12 +403,7 @@ extern "C" int urso_conv_pair_ok(long long M, int dt, int c_narrow, int c_wide) 
 
 template <typename S, int VAR>
 static void pr_launch(const PairArgs& a, int dt, int mode, bool emit, int blocks_per_cu, hipStream_t st, bool sparse = false, int groups = 1) {
-    int bpx = ceil_div(a.ntiles, 8);
-    int cap = blocks_per_cu * pr_device_cus() / (8 * groups);
-    if (cap < 1) cap = 1;
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx, groups), blk(S::NW * 64);
+    const dim3 grid(urso_persistent_grid(a.ntiles, blocks_per_cu, groups), groups), blk(S::NW * 64);
     if constexpr (VAR == 0) {
         if (sparse && mode == 1) {
             if (dt == URSO_BF16) URSO_KLAUNCH((pair_kernel<__bf16, 1, false, S, 0, true>), grid, blk, 0, st, a);

@@ -31,10 +31,9 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5, l15 = lane & 15, g = lane >> 4;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.nar_bytes), rx = raw_rsrc(a.xin, a.nar_bytes);
@@ -205,8 +204,6 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
     }
 }
 
-static int ps_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 extern "C" int urso_conv_pair_shortcut(long long M, int dt, const void* src_d, const void* w1_d, const float* bias1_d,
                                        const void* xin_d, const void* ws_d, const float* bias_s_d, void* bits_d, void* mid_d,
                                        const void* w2_d, const float* bias2_d, void* dst_d, void* stream) {
@@ -225,11 +222,7 @@ extern "C" int urso_conv_pair_shortcut(long long M, int dt, const void* src_d, c
     const double flops = 2.0 * (double)M * 256 * (128 + 64);
     const double bytes = (double)M * (3.0 * 128 + 512 + (bits_d ? 32 : 0));
     ProfScope ps(st, URSO_K_IGEMM, flops, bytes);
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = 2 * ps_device_cus() / 8;
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(256);
+    const dim3 grid(urso_persistent_grid(a.ntiles, 2)), blk(256);
     if (dt == URSO_BF16) { if (bits_d) URSO_KLAUNCH((pairs_kernel<__bf16, true>), grid, blk, 0, st, a); else URSO_KLAUNCH((pairs_kernel<__bf16, false>), grid, blk, 0, st, a); }
     else { if (bits_d) URSO_KLAUNCH((pairs_kernel<_Float16, true>), grid, blk, 0, st, a); else URSO_KLAUNCH((pairs_kernel<_Float16, false>), grid, blk, 0, st, a); }
     return urso_check_launch("urso_conv_pair_shortcut");

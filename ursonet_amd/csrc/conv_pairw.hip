@@ -39,10 +39,9 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5, l15 = lane & 15, g = lane >> 4;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     const bool active = tile < t_end;
 
     const i32x4_t rs = raw_rsrc(a.src, a.nar_bytes), ru = raw_rsrc(a.u, a.nar_bytes), ra = raw_rsrc(a.add, SPARSE ? a.add_bytes : a.wide_bytes);
@@ -277,19 +276,9 @@ __global__ __launch_bounds__(512, 2) void pairw_kernel(const PairwArgs a) {
     if (a.colpart && h == 0) a.colpart[(size_t)blockIdx.x * 256 + 32 * wave + l31] = accc[0];
 }
 
-static int pw_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
-static int pw_grid(long long M) {
-    int bpx = ceil_div((int)(M / PW_BM), 8);
-    const int cap = pw_device_cus() / 8;
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    return 8 * (bpx < 1 ? 1 : bpx);
-}
-
 extern "C" int urso_conv_pair_wgrad_splits(long long M, int dt) {
     if (M <= 0 || M % PW_BM || (dt != URSO_BF16 && dt != URSO_F16) || M * 512 >= 0x7FFFFF00ll) return 0;
-    return pw_grid(M);
+    return urso_persistent_grid((int)(M / PW_BM), 1);        // M >= PW_BM here: at least one tile, so at least 8 blocks
 }
 
 extern "C" int urso_conv_pair_wgrad(long long M, int dt, const void* src_d, const void* w1_d, const void* add_d, const void* bits_d, void* mid_d,

@@ -59,10 +59,9 @@ __global__ __launch_bounds__(512, 2) void pairx_kernel(const PairxArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5, l15 = lane & 15, g = lane >> 4;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     const bool active = tile < t_end;
 
     const i32x4_t rs = raw_rsrc(a.src, a.nar_bytes), ru = raw_rsrc(a.u, a.nar_bytes), rp = raw_rsrc(a.p, a.nar_bytes), ra = raw_rsrc(a.add, a.wide_bytes);

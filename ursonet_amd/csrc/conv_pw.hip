@@ -50,10 +50,9 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     const int fr = lane & 15, fg = lane >> 4;
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.src_bytes), rw = raw_rsrc(a.wgt, a.wgt_bytes);
@@ -345,8 +344,6 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
     }
 }
 
-static int pw_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 // Called by urso_conv_igemm_ex for qualifying geometries (conv_igemm.hip decides); returns URSO_OK after launching.
 int urso_pw_launch(const urso_conv_geom* g, int dt, int conv, int dhs, int dws, int relu,
                    const void* src, const void* wgt, const float* bias, const void* add, const void* mask, void* dst,
@@ -375,11 +372,7 @@ int urso_pw_launch(const urso_conv_geom* g, int dt, int conv, int dhs, int dws, 
                        (force_small == 5 && a.M <= 65536 && !add);
     const int bn = small ? 64 : 128;
     a.tilesN = ceil_div(N, bn); a.ntiles = ceil_div(a.M, 128) * a.tilesN;
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = (small ? 3 : 2) * pw_device_cus() / 8;
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(256);
+    const dim3 grid(urso_persistent_grid(a.ntiles, small ? 3 : 2)), blk(256);
     urso_prof_l2((double)a.ntiles * a.Kc * 16.0 * (128 + bn));           // every tile copies 128 pixel rows and bn filter rows per K chunk of 16 bytes
     const int sel = (add ? 1 : 0) | (mask ? 2 : 0);
 #define URSO_PW2(TT, BN_, CV_) switch (sel) { case 0: URSO_KLAUNCH((pw_kernel<TT, BN_, false, 0, CV_>), grid, blk, 0, st, a); break; \

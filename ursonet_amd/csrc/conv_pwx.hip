@@ -59,10 +59,9 @@ __global__ __launch_bounds__(512, 2) void pwx_kernel(const PxArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     const int fr = lane & 15, fg = lane >> 4;
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    const int tile0 = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    const int tile0 = ts.tile;
     if (tile0 >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.src_bytes), rw = raw_rsrc(a.wgt, a.wgt_bytes);
@@ -377,10 +376,7 @@ static int pwx_try_impl(const urso_conv_geom* g, int dt, int relu, const void* s
     int bn = (N > 128 && cost(256) <= cost(128)) ? 256 : 128;
     if (g_urso_opt.pwx_bn == 128 || g_urso_opt.pwx_bn == 256) bn = g_urso_opt.pwx_bn;
     a.tilesN = ceil_div(N, bn); a.ntiles = tm * a.tilesN;
-    int bpx = ceil_div(a.ntiles, 8);
-    if (bpx > cus / 8) bpx = cus / 8;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(512);
+    const dim3 grid(urso_persistent_grid(a.ntiles, 1)), blk(512);
     urso_prof_l2((double)a.ntiles * K * 2.0 * (160 + bn));     // every tile pulls its 160 pixel rows and its bn filter rows of K channels through L2 -> LDS
 #define URSO_PX(TT, BN_, NST_, AD_, MK_, EM_) URSO_KLAUNCH((pwx_kernel<TT, 5, BN_, NST_, AD_, MK_, EM_>), grid, blk, 0, st, a)
 #define URSO_PXF(TT, BN_, NST_) switch (form) { case 0: URSO_PX(TT, BN_, NST_, false, 0, false); break; case 1: URSO_PX(TT, BN_, NST_, true, 0, true); break; \

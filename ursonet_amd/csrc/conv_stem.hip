@@ -39,10 +39,9 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
     int l31 = lane & 31;
     const int h = lane >> 5;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.src_bytes);
@@ -155,8 +154,6 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
     }
 }
 
-static int st_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 // conv_igemm.hip asks before choosing a kernel for the packed stem geometry (option "stem": 0 keeps it on conv_pw.hip).
 bool urso_stem_fits(const urso_conv_geom* g, int dt, int flags, const void* add, const void* mask) {
     if (!g_urso_opt.stem || add || mask || (dt != URSO_BF16 && dt != URSO_F16) || (flags & (URSO_EPI_OUT_F32 | URSO_EPI_MASK_BITS | URSO_EPI_EMIT_BITS))) return false;
@@ -171,11 +168,7 @@ int urso_stem_launch(const urso_conv_geom* g, int dt, int relu, const void* src,
     a.B = g->B; a.H = g->H; a.W = 2 * g->W; a.OH = g->OH; a.OW = g->OW;                 // g->W counts pixel pairs
     a.src_bytes = (uint32_t)((size_t)a.B * a.H * a.W * 8); a.dst_bytes = (uint32_t)((size_t)a.B * a.OH * a.OW * 128);
     a.tiles_x = ceil_div(a.OW, ST_TW); a.tiles_y = ceil_div(a.OH, ST_TH); a.ntiles = a.B * a.tiles_y * a.tiles_x;
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = 2 * st_device_cus() / 8 > 0 ? 2 * st_device_cus() / 8 : 1;      // (>= 1 block per XCD whatever option `cus` says)
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(256);
+    const dim3 grid(urso_persistent_grid(a.ntiles, 2)), blk(256);
     if (dt == URSO_BF16) URSO_KLAUNCH((stem_kernel<__bf16>), grid, blk, 0, st, a);
     else URSO_KLAUNCH((stem_kernel<_Float16>), grid, blk, 0, st, a);
     return urso_check_launch("urso_conv_igemm(stem)");
@@ -243,10 +236,9 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StempArgs a) {
     int l31 = lane & 31;
     const int h = lane >> 5;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
-    int tile = xcd * cpx + lb;
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
+    int tile = ts.tile;
     if (tile >= t_end) return;
 
     const i32x4_t rs = raw_rsrc(a.src, a.src_bytes);
@@ -450,11 +442,7 @@ int urso_stem_pool_launch(const urso_conv_geom* g, int dt, const void* src, cons
     a.B = g->B; a.H = g->H; a.W = 2 * g->W; a.OH = g->OH; a.OW = g->OW; a.PH = g->OH / 2; a.PW = g->OW / 2;     // g->W counts pixel pairs
     a.src_bytes = (uint32_t)((size_t)a.B * a.H * a.W * 8); a.dst_bytes = (uint32_t)((size_t)a.B * a.PH * a.PW * 128); a.am_bytes = a.dst_bytes / 2;
     a.tiles_x = ceil_div(a.PW, SP_PC); a.tiles_y = ceil_div(a.PH, SP_PR); a.ntiles = a.B * a.tiles_y * a.tiles_x;
-    int bpx = ceil_div(a.ntiles, 8);
-    const int cap = 2 * st_device_cus() / 8 > 0 ? 2 * st_device_cus() / 8 : 1;      // (>= 1 block per XCD whatever option `cus` says)
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    const dim3 grid(8 * bpx), blk(256);
+    const dim3 grid(urso_persistent_grid(a.ntiles, 2)), blk(256);
     if (dt == URSO_BF16) URSO_KLAUNCH((stem_pool_kernel<__bf16>), grid, blk, 0, st, a);
     else URSO_KLAUNCH((stem_pool_kernel<_Float16>), grid, blk, 0, st, a);
     return urso_check_launch("urso_stem_conv_pool");

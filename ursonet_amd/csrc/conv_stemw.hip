@@ -52,9 +52,8 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
     const int nh = wave & 1, ks = wave >> 1;
     const int l31 = lane & 31, h = lane >> 5, l15 = lane & 15, g = lane >> 4;
 
-    const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const int cpx = ceil_div(a.ntiles, 8);
-    const int t_end = min((xcd + 1) * cpx, a.ntiles);
+    const UrsoTileStream ts = urso_tile_stream(a.ntiles);
+    const int t_end = ts.t_end, bpx = ts.bpx;
 
     const i32x4_t rx = raw_rsrc(a.x, a.x_bytes), rz = raw_rsrc(POOLED ? a.dpool : a.dz, POOLED ? a.dpool_bytes : a.dz_bytes);
     const i32x4_t ram = raw_rsrc(POOLED ? (const void*)a.am : a.x, POOLED ? a.am_bytes : 0u);
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
     // `s_nop 11` that waits out the whole MFMA pipeline (tools/loop_movs.py)
     auto run_tiles = [&](auto ks_c) {
     constexpr int KS = decltype(ks_c)::value;
-    for (int tile = xcd * cpx + lb; tile < t_end; tile += bpx) {
+    for (int tile = ts.tile; tile < t_end; tile += bpx) {
         const int tx = tile % a.tiles_x, tq = tile / a.tiles_x;
         const int ty = tq % a.tiles_y, b = tq / a.tiles_y;
         const int oy0 = ty * SW_TH, ox0 = tx * SW_TW;
@@ -216,8 +215,6 @@ __global__ __launch_bounds__(256, POOLED ? 2 : 3) void stemw_kernel(const StemwA
     }
 }
 
-static int sw_device_cus() { return urso_usable_cus(); }      // runtime.hip: the device's CUs, or option `cus`
-
 // the packed stem geometry (conv_stem.hip urso_stem_fits), 16-bit, option "stem"
 bool urso_stemw_fits(const urso_conv_geom* g, int dt) {
     if (!g_urso_opt.stem || (dt != URSO_BF16 && dt != URSO_F16)) return false;
@@ -227,11 +224,7 @@ bool urso_stemw_fits(const urso_conv_geom* g, int dt) {
 }
 int urso_stemw_splits(const urso_conv_geom* g, bool pooled) {
     const int ntiles = g->B * ceil_div(g->OH, SW_TH) * ceil_div(g->OW, SW_TW);
-    int bpx = ceil_div(ntiles, 8);
-    const int cap = (pooled ? 2 : 3) * sw_device_cus() / 8;       // resident blocks per CU of the two forms
-    if (bpx > cap) bpx = cap;
-    if (g_urso_opt.grid_cap > 0 && bpx > ceil_div(g_urso_opt.grid_cap, 8)) bpx = ceil_div(g_urso_opt.grid_cap, 8);
-    return 8 * bpx;
+    return urso_persistent_grid(ntiles, pooled ? 2 : 3);       // resident blocks per CU of the two forms
 }
 int urso_stemw_launch(const urso_conv_geom* g, int dt, const void* x, const void* dz, const void* dpool, const uint8_t* am,
                       float* part, float* colpart, size_t part_stride, hipStream_t st) {

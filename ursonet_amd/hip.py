@@ -232,9 +232,6 @@ def _chk(rc, what):
         raise UrsoHipError("%s failed (%d): %s" % (what, rc, last_error()))
 
 
-OPTION_NAMES = ("pw_kernel", "pw_small", "igemm_shortk", "wgrad_narrow", "wgrad_blocks", "wgrad_pipe", "grid_cap", "hconv", "hconv_dbg", "hconv2", "hconv2_shape", "hconv_streamk", "pair", "c3", "c3v", "stem", "stem_pool", "cus", "bneck")
-
-
 def set_option(name, value):
     """urso_set_option: explicit kernel-policy switch (include/ursonet_hip.h)."""
     _chk(_lib.urso_set_option(name.encode(), int(value)), "urso_set_option")
@@ -264,12 +261,15 @@ class options(object):
         return False
 
 
-# A/B experiments inside one gpurun call: URSO_OPT_<NAME>=<int> in the environment of the PYTHON host is applied once at
-# import (the C library itself never reads the environment).
-for _o in OPTION_NAMES:
-    _e = os.environ.get("URSO_OPT_" + _o.upper())
-    if _e is not None:
-        _chk(_lib.urso_set_option(_o.encode(), int(_e)), "urso_set_option")
+# A/B experiments inside one process launch: every URSO_OPT_<NAME>=<int> in the environment of the PYTHON host is applied once at
+# import (the C library itself never reads the environment).  <NAME> lowercased is the option's name; one the library refuses
+# (a misspelt variable, a dropped option) raises here instead of leaving the run on the defaults.
+for _k in sorted(os.environ):
+    if _k.startswith("URSO_OPT_"):
+        try:
+            set_option(_k[len("URSO_OPT_"):].lower(), int(os.environ[_k]))
+        except (UrsoHipError, ValueError) as _err:
+            raise ImportError("environment variable %s=%r: %s" % (_k, os.environ[_k], _err))
 
 
 def ptr(t):
