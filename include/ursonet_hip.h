@@ -813,6 +813,27 @@ int urso_draw_prims_u8(int B, int H, int W, const int32_t* prims_host, const int
                        const int32_t* counts_d, uint8_t* img_d, void* stream);
 
 /*
+ * The PMF picture of pose_estimator.detect_dataset (utils.visualize_weights, utils.py:117-151; ursonet_amd/detect.py): for a batch of
+ * orientation PMFs over K = n^3 bins, the "slice sheet" as uint8 RGB out_d [B][SH][SW][3].  Sources, each fp32 [B][K] and each nullable
+ * (at least one is given): gt_d, a stored PMF, and logits_d, the head's raw output.  rows = the number of sources given, GT first.
+ *   SW = n n cell + (n + 1) gap,  SH = rows n cell + (rows + 1) gap.
+ *   Source row r starts at y = gap + r (n cell + gap), slice z at x = gap + z (n cell + gap); inside slice z the cell of cell x cell
+ *   pixels at cell row j, cell column i shows bin i n^2 + j n + z (utils.py:129,144).  Every other pixel is bg (three bytes, host memory).
+ *   Value of a bin, in fp64:  GT row  v = p / max_k p when the maximum is > 0, else 0 (a negative or NaN p counts as 0);
+ *                             estimate row  v = exp(z - max_k z): stable_softmax(z) divided by its own maximum, as imshow(vmin=0,
+ *                             vmax=max) scales it -- the softmax sum cancels and is never taken (a NaN logit gives 0).
+ *   Colour = lut_d[min(255, floor(256 v))], lut_d uint8 [256][3] on the device: matplotlib's indexing of a 256-entry colormap.
+ * The GT row is defined to the byte (one IEEE division); the estimate row up to the device's exp (<= 1 ulp), i.e. except where
+ * 256 v lies within a few ulps of an integer.  idx_d: scratch of the caller's, B * rows * K bytes, any alignment -- the 8-bit indices
+ * between the two launches (the reduction over K per image and row, then the store-bound expansion in aligned 16-byte vectors with
+ * per-image head and tail bytes; out_d may sit at any address).  URSO_EINVAL before any launch: a null lut_d, bg, idx_d or out_d, both
+ * sources null, B outside 1 .. 65535, n outside 2 .. 64, cell outside 1 .. 64, gap outside 0 .. 64, an image of 2 GiB or more.
+ * The launch profiler books both launches as one record under URSO_K_MOLD.
+ */
+int urso_pmf_sheet_u8(int B, int n, int cell, int gap, const float* gt_d, const float* logits_d, const uint8_t* lut_d, const uint8_t* bg,
+                      uint8_t* idx_d, uint8_t* out_d, void* stream);
+
+/*
  * Opt-in launch profiler: when enabled every urso_* launch is bracketed by HIP events on
  * its stream.  urso_prof_collect() synchronises and returns per-record milliseconds.
  */

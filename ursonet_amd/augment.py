@@ -348,3 +348,39 @@ def draw_prims(frames, prims, counts=None):
     cnt32 = np.ascontiguousarray(cnt, dtype=np.int32)
     hip.draw_prims_u8(B, H, W, host, cnt32, torch.as_tensor(host).to(frames.device), torch.as_tensor(cnt32).to(frames.device), frames)
     return frames
+
+
+def pmf_sheet(gt, logits, n, cell=4, gap=2, lut=None, bg=(255, 255, 255), out=None, scratch=None):
+    """utils.visualize_weights (utils.py:117-151) as a picture, on the GPU (urso_pmf_sheet_u8): the slice sheet of B orientation PMFs over
+    n^3 bins -> uint8 CUDA tensor [B,SH,SW,3], SW = n n cell + (n + 1) gap, SH = rows n cell + (rows + 1) gap.  gt: stored PMFs, logits:
+    the head's raw output, each fp32 [B, n^3] (array or device tensor) or None; rows = how many of the two are given, gt first.  Slice z
+    sits at x = gap + z (n cell + gap) and shows bin i n^2 + j n + z at cell row j, column i; a GT bin's value is p / max p, an
+    estimate's exp(z - max z); colour = lut[min(255, floor(256 v))] (lut: uint8 [256,3], default the grey ramp), every other pixel is bg.
+    `out`: a dense uint8 CUDA tensor of the result's shape, at any address; `scratch`: uint8 CUDA, >= B rows n^3 bytes."""
+    import torch
+    from . import hip
+    up = lambda a: None if a is None else torch.as_tensor(a).cuda().contiguous()
+    gt, logits = up(gt), up(logits)
+    first = gt if gt is not None else logits
+    if first is None:
+        raise ValueError("pmf_sheet: neither a stored PMF nor logits given")
+    for t in (gt, logits):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != tuple(first.shape)):
+            raise ValueError("pmf_sheet: fp32 [B, n^3] sources of one shape expected, not %s %s" % (t.dtype, tuple(t.shape)))
+    B, K = first.shape
+    if K != int(n) ** 3:
+        raise ValueError("pmf_sheet: %d bins are not n^3 for n = %d" % (K, n))
+    if lut is None:
+        lut = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+    lut = torch.as_tensor(lut).to(first.device).contiguous()
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise ValueError("pmf_sheet: lut is a uint8 [256,3] table, not %s %s" % (lut.dtype, tuple(lut.shape)))
+    rows = (gt is not None) + (logits is not None)
+    SH, SW = hip.pmf_sheet_shape(int(n), int(cell), int(gap), rows)
+    if out is None:
+        if not (1 <= cell <= 64 and 0 <= gap <= 64 and 2 <= n <= 64) or SH * SW * 3 >= 2 ** 31:
+            raise hip.UrsoHipError("urso_pmf_sheet_u8: n %d, cell %d, gap %d: outside 2 .. 64, 1 .. 64, 0 .. 64, or an image of 2 GiB or more" % (n, cell, gap))
+        out = torch.empty((B, SH, SW, 3), dtype=torch.uint8, device=first.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (B, SH, SW, 3) and out.is_contiguous()
+    hip.pmf_sheet(B, int(n), int(cell), int(gap), gt, logits, lut, bg, out, scratch=scratch)
+    return out

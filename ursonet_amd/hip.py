@@ -208,6 +208,7 @@ _SIGS = {
     "urso_frames_gather_u8": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "urso_video_prep_u8": (_i, [_i] * 8 + [C.c_double] * 3 + [_vp, _vp, _vp]),
     "urso_draw_prims_u8": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "urso_pmf_sheet_u8": (_i, [_i, _i, _i, _i, _fp, _fp, _vp, _vp, _vp, _vp, _vp]),
     "urso_conv_winograd_ws_bytes": (_sz, [_gp, _i]),
     "urso_conv_winograd_fwd": (_i, [_gp, _i, _i, _vp, _vp, _fp, _vp, _vp, _sz, _vp]),
     "urso_prof_enable": (_i, [_i]),
@@ -888,6 +889,34 @@ def draw_prims_u8(B, H, W, prims_host, counts_host, prims, counts, img, stream=N
     assert prims.numel() == prims_host.size and counts.numel() == B and img.numel() == B * H * W * 3
     _chk(_lib.urso_draw_prims_u8(int(B), int(H), int(W), prims_host.ctypes.data, counts_host.ctypes.data, ptr(prims), ptr(counts), ptr(img),
                                  stream_ptr(stream)), "urso_draw_prims_u8")
+
+
+def pmf_sheet_shape(n, cell, gap, rows):
+    """(SH, SW) of urso_pmf_sheet_u8's picture for `rows` sources (1 or 2)."""
+    return rows * n * cell + (rows + 1) * gap, n * n * cell + (n + 1) * gap
+
+
+def pmf_sheet(B, n, cell, gap, gt, logits, lut, bg, out, scratch=None, stream=None):
+    """urso_pmf_sheet_u8: the slice sheet of B orientation PMFs over n^3 bins -> out uint8 [B,SH,SW,3] ((SH, SW) = pmf_sheet_shape).
+    gt (a stored PMF) and logits (the head's raw output) are fp32 [B, n^3] device tensors, either may be None; lut uint8 [256,3] on the
+    device, bg three bytes.  out needs no alignment (a view into a larger buffer will do) but must be dense.  scratch: uint8, at least
+    B * rows * n^3 bytes (allocated here when None).  Nothing is checked here that the library checks: bad arguments raise UrsoHipError
+    before any launch."""
+    rows = (gt is not None) + (logits is not None)
+    K = int(n) ** 3
+    assert all(t is None or t.dtype == torch.float32 for t in (gt, logits)) and (lut is None or lut.dtype == torch.uint8)
+    assert out is None or out.dtype == torch.uint8
+    if 1 <= B <= 65535 and 2 <= n <= 64 and out is not None:             # sizes the library accepts: the buffers must hold them
+        if scratch is None:
+            scratch = torch.empty(B * max(rows, 1) * K, dtype=torch.uint8, device=out.device)
+        assert all(t is None or t.numel() >= B * K for t in (gt, logits)) and (lut is None or lut.numel() == 768)
+        assert scratch.dtype == torch.uint8 and scratch.numel() >= B * rows * K
+        sh, sw = pmf_sheet_shape(int(n), int(cell), int(gap), rows)
+        assert sh * sw * 3 >= 2 ** 31 or out.numel() >= B * sh * sw * 3 or not (1 <= cell <= 64 and 0 <= gap <= 64)
+    bg3 = (C.c_ubyte * 3)(*(int(v) & 255 for v in bg))
+    _chk(_lib.urso_pmf_sheet_u8(int(B), int(n), int(cell), int(gap), ptr(gt), ptr(logits), ptr(lut), C.cast(bg3, C.c_void_p),
+                                ptr(scratch), ptr(out), stream_ptr(stream)), "urso_pmf_sheet_u8")
+
 
 
 def prof_enable(on):

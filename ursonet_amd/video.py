@@ -108,13 +108,27 @@ def _int_point(x, y, rounded):
     return xi, yi
 
 
+def arrow_prims(centre, tip, colour, thickness=2):
+    """One arrow centre -> tip (integer pixel pairs) as segment rows of urso_draw_prims_u8: the shaft and two head strokes by
+    cv2.arrowedLine's rule with tipLength 0.1: tip + 0.1 |tip - c| (cos(a +- pi/4), sin(a +- pi/4)), a = atan2(c.y - tip.y, c.x - tip.x),
+    rounded to nearest, + before -.  A stroke whose end is not finite or lies beyond +-16,384 is dropped."""
+    colour = tuple(int(v) for v in colour)
+    rows = [(0, centre[0], centre[1], tip[0], tip[1], int(thickness)) + colour]
+    size = math.hypot(centre[0] - tip[0], centre[1] - tip[1]) * 0.1
+    angle = math.atan2(centre[1] - tip[1], centre[0] - tip[0])
+    for sign in (1.0, -1.0):
+        e = _int_point(tip[0] + size * math.cos(angle + sign * math.pi / 4), tip[1] + size * math.sin(angle + sign * math.pi / 4), True)
+        if e is not None:
+            rows.append((0, e[0], e[1], tip[0], tip[1], int(thickness)) + colour)
+    return rows
+
+
 def pose_axes_prims(q, loc, K, scale=5.0):
     """utils.plot_axes (utils.py:186-217) as primitives of urso_draw_prims_u8: int32 [n, 9] rows [kind 0, x0, y0, x1, y1, 2, cR, cG, cB].
     The axes diag(1, -1, 1) * scale are rotated by quat2SO3(q), translated by loc, divided by their depth and multiplied by K; centre and
     tips are truncated toward zero.  Three arrows centre -> tip in the colours (0, 0, 255), (0, 255, 0), (255, 0, 0), thickness 2, each a
-    shaft and two head strokes by cv2.arrowedLine's rule with tipLength 0.1: tip + 0.1 |tip - c| (cos(a +- pi/4), sin(a +- pi/4)), a =
-    atan2(c.y - tip.y, c.x - tip.x), rounded to nearest, + before -.  Nine rows; a primitive with a coordinate that is not finite or lies
-    beyond +-16,384 (an object at or behind the image plane) is dropped."""
+    shaft and two head strokes (arrow_prims).  Nine rows; a primitive with a coordinate that is not finite or lies beyond +-16,384 (an
+    object at or behind the image plane) is dropped."""
     loc = np.asarray(loc, dtype=np.float64).ravel()
     K = np.asarray(K, dtype=np.float64).reshape(3, 3)
     rows = []
@@ -128,14 +142,7 @@ def pose_axes_prims(q, loc, K, scale=5.0):
         tip = _int_point(p[0, i], p[1, i], False)
         if centre is None or tip is None:
             continue
-        colour = AXIS_COLOURS[i]
-        rows.append((0, centre[0], centre[1], tip[0], tip[1], 2) + colour)
-        size = math.hypot(centre[0] - tip[0], centre[1] - tip[1]) * 0.1
-        angle = math.atan2(centre[1] - tip[1], centre[0] - tip[0])
-        for sign in (1.0, -1.0):
-            e = _int_point(tip[0] + size * math.cos(angle + sign * math.pi / 4), tip[1] + size * math.sin(angle + sign * math.pi / 4), True)
-            if e is not None:
-                rows.append((0, e[0], e[1], tip[0], tip[1], 2) + colour)
+        rows += arrow_prims(centre, tip, AXIS_COLOURS[i])
     return np.asarray(rows, dtype=np.int32).reshape(-1, PRIM_INTS)
 
 
