@@ -466,3 +466,42 @@ def test_test_and_submit_end_to_end(tmp_path, capsys):
             q = res.q_est[i]
             assert [np.float32(v) for v in row[1:5]] == [np.float32(q[3]), np.float32(q[0]), np.float32(q[1]), np.float32(q[2])]
             assert [np.float32(v) for v in row[5:]] == [np.float32(v) for v in res.loc_est[i]]
+
+
+class _PreparedLabelled(object):
+    """A labelled dataset whose images are the host-prepared video frames (tests/test_video_gpu.py's _Prepared, with the labels kept):
+    what evaluate(), predict() and detect_dataset() must see to run on the pixels track() prepares on the device."""
+
+    def __init__(self, ds, frames, prep):
+        self._ds, self._frames, self._prep = ds, frames, prep
+
+    def load_image(self, image_id):
+        return self._prep.host(self._frames[image_id])
+
+    def __getattr__(self, name):
+        return getattr(self._ds, name)
+
+
+def test_four_commands_share_one_pass(tmp_path):
+    """evaluate(), predict(), detect_dataset() and track() over the same 5 images: ResNet-18 at 128 x 192, engine batch 2 (the tail batch
+    is padded), soft-classification orientation, regressed location, float32.  The frames are test_video_gpu's: 60 x 90, prepared (pad 8,
+    crop (0, 0, 1, 3)) to 76 x 102 on the host for the three dataset commands and on the device by track().  The estimates are the same
+    bits in all four, the confidences in predict and track, the errors in evaluate and detect."""
+    from ursonet_amd import detect, evaluate as ev, predict as pr, video
+    from ursonet_amd.dataset import SyntheticPoses
+    (cfg, model), = _models(tmp_path, [2], False, True)
+    ds = SyntheticPoses(5, 60, 90, cfg, seed=21)
+    frames = [ds.load_image(i) for i in ds.image_ids]
+    prep = video.VideoPrep(pad=8, crop=(0, 0, 1, 3))
+    data = _PreparedLabelled(ds, frames, prep)
+    e = ev.evaluate(model, data, out_dir=str(tmp_path), verbose=0)
+    p = pr.predict(model, data)
+    d = detect.detect_dataset(model, data, 0, image_ids=list(ds.image_ids), render=False, verbose=0)
+    t = video.track(model, frames, data, prep=prep)
+    assert e.loc_est.shape == (5, 3) and e.q_est.shape == (5, 4) and np.all(np.isfinite(e.loc_est)) and np.all(np.isfinite(e.q_est))
+    for other in (p, d, t):
+        assert np.array_equal(other.loc_est, e.loc_est) and np.array_equal(other.q_est, e.q_est)
+    assert np.all(np.isfinite(p.ori_peak)) and np.all(np.isfinite(p.ori_lambda))
+    assert np.array_equal(t.ori_peak, p.ori_peak) and np.array_equal(t.ori_lambda, p.ori_lambda)
+    assert np.all(np.isfinite(e.loc_err)) and np.all(np.isfinite(e.ori_err))
+    assert np.array_equal(d.loc_err, e.loc_err) and np.array_equal(d.ori_err, e.ori_err)

@@ -31,6 +31,7 @@ def run(a, tree, role):
     from util import make_config
     from ursonet_amd import net, utils
     from ursonet_amd.dataset import SyntheticPoses
+    from ursonet_amd.infer import loader_workers
     td = tempfile.mkdtemp()
     out = {}
     for B in (32, 1):
@@ -63,7 +64,7 @@ def run(a, tree, role):
         out["B%d_img_s" % B] = rates
         del model
         torch.cuda.empty_cache()
-    out["box"] = "one %s, LOADER_WORKERS %d" % (torch.cuda.get_device_name(0), int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1))))
+    out["box"] = "one %s, LOADER_WORKERS %d" % (torch.cuda.get_device_name(0), loader_workers(cfg))
     return out
 
 

@@ -116,6 +116,7 @@ def main():
     import torch
     from util import make_config
     from ursonet_amd import net, utils
+    from ursonet_amd.infer import loader_workers
     stat = lambda v: {"min": float(min(v)), "median": float(np.median(v)), "max": float(max(v)), "runs": [float(x) for x in v]}   # noqa: E731
     out = {"backbone": a.backbone, "h": a.h, "w": a.w, "dtype": "bfloat16", "ori_bins": a.ori_bins, "frame": [FRAME_H, FRAME_W], "n": a.n,
            "n_loop": a.n_loop, "reps": a.reps, "prepared_frame": list(prep.out_shape(FRAME_H, FRAME_W)) + [3], "unit": "frames/s"}
@@ -148,7 +149,7 @@ def main():
             out["%s_B%d" % (name, B)] = stat(rates[name])
         del model
         torch.cuda.empty_cache()
-    out["box"] = "one %s, LOADER_WORKERS %d" % (torch.cuda.get_device_name(0), int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1))))
+    out["box"] = "one %s, LOADER_WORKERS %d" % (torch.cuda.get_device_name(0), loader_workers(cfg))
     finish(a, out, prep)
 
 

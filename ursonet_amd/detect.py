@@ -4,8 +4,8 @@
 Per image the reference detects at batch 1, decodes in NumPy (40-318 ms for the soft-classification head), prints seven lines and opens
 matplotlib windows: the ground-truth and the estimated object axes on the frame, the projected locations, and -- soft classification --
 the predicted orientation PMF beside its encoded target, slice by slice.  detect_dataset() draws the image ids up front and runs them in
-whole engine batches exactly as evaluate() does (EvalFeeder -> engine.forward() -> [urso_quat_wavg_decode] -> urso_pose_eval into one fp64
-table, read once at the end), so its table columns are evaluate()'s bits.  With render=True the pictures are made on the device and come
+whole engine batches exactly as evaluate() does (EvalFeeder -> the pass of ursonet_amd/infer.py -> urso_pose_eval into one fp64 table, read
+once at the end), so its table columns are evaluate()'s bits.  With render=True the pictures are made on the device and come
 back per batch: `axes_gt`, `axes_est` and `overlap` are copies of the resized frame's window with segments / discs drawn by
 urso_draw_prims_u8, `sheet` is urso_pmf_sheet_u8's picture of the stored orientation target above the head's logits.  The few hundred
 flops per image of the projections stay on the host in float64.
@@ -15,13 +15,12 @@ Differences from matplotlib's figures, on purpose: no anti-aliasing (the rasteri
 instead of the originals, the sheet has no axis labels, and the dashed polar dials of utils.polar_plot are returned as numbers (pyr_gt /
 pyr_est) and not drawn.  matplotlib is not a dependency.
 """
-import os
 import random
 
 import numpy as np
 
 from .augment import quat2SO3
-from .evaluate import _check, head_modes
+from .infer import PosePass, eval_columns, loader_workers
 from .video import PRIM_INTS, _int_point, arrow_prims
 
 AXES_LENGTH = 100.0                                             # utils.visualize_axes' scale at its call sites (:572-573), original-frame pixels
@@ -139,14 +138,9 @@ class DetectResult(object):
     soft classification, sheet); else None."""
 
     def __init__(self, image_ids, table, loc_gt, q_gt, loc_enc, speed, ori_logits=None, pictures=None):
-        from . import hip
-        t = np.asarray(table, dtype=np.float64).reshape(-1, hip.EVAL_COLS)
+        eval_columns(self, table, loc_enc)
         self.image_ids = np.asarray(image_ids)
         self.loc_gt, self.q_gt = loc_gt, q_gt
-        self.loc_est = t[:, hip.EVAL_LOC_EST:hip.EVAL_LOC_EST + 3].copy()
-        self.q_est = t[:, hip.EVAL_Q_EST:hip.EVAL_Q_EST + 4].copy()
-        self.loc_err, self.ori_err = t[:, hip.EVAL_LOC_ERR].copy(), t[:, hip.EVAL_ORI_ERR].copy()
-        self.loc_encoded_err = t[:, hip.EVAL_LOC_ENC_ERR].copy() if loc_enc else None
         flip = quat_inv if speed else (lambda q: q)
         self.pyr_gt = np.array([quat2euler(flip(q)) for q in self.q_gt], dtype=np.float64).reshape(-1, 3)
         self.pyr_est = np.array([quat2euler(flip(q)) for q in self.q_est], dtype=np.float64).reshape(-1, 3)
@@ -188,29 +182,23 @@ def detect_dataset(model, dataset, nr_images, image_ids=None, render=True, cell=
     SHEET_BG).  A picture goes to sink(index, name, array) or, without a sink, into DetectResult.pictures.  The pictures are downloaded per
     batch.  render=False launches no picture kernel and returns the same table.  Frames that are not uint8 RGB raise ValueError when
     render is true (they reach the engine molded to float; there is nothing to draw on)."""
-    soft = _check(model, dataset, False, "detect_dataset")
+    ps = PosePass(model, dataset, who="detect_dataset")
     import torch
     from . import augment, hip, utils
     from .feeder import EvalFeeder
-    cfg, eng = model.config, model._engine
-    loc_mode, ori_mode = head_modes(cfg)
-    loc_enc = not cfg.REGRESS_LOC and not cfg.REGRESS_KEYPOINTS
+    cfg, B, dev, soft, loc_enc = ps.cfg, ps.B, ps.dev, ps.soft, ps.loc_class
     if image_ids is None:
         pool = dataset.image_ids
         ids = [random.choice(pool) for _ in range(int(nr_images))]
     else:
         ids = list(image_ids)
-    N, B, dev = len(ids), eng.B, eng.device
+    N = len(ids)
     speed = getattr(dataset, "name", None) == "Speed"
     if render and cfg.IMAGE_RESIZE_MODE not in ("square", "pad64"):
         raise ValueError("detect_dataset(render=True): IMAGE_RESIZE_MODE %r has no window to draw on (square / pad64 have)" % (cfg.IMAGE_RESIZE_MODE,))
-    table = torch.full((max(N, 1), hip.EVAL_COLS), float("nan"), dtype=torch.float64, device=dev)
+    table = ps.table(max(N, 1), hip.EVAL_COLS)
     loc_map_h = np.asarray(dataset.histogram_3D_map, dtype=np.float64) if loc_enc else None
-    loc_map = torch.as_tensor(loc_map_h).to(dev).contiguous() if loc_enc else None
-    hq = q_soft = lut_d = scratch = sheets = None
-    if soft:
-        hq = torch.as_tensor(np.ascontiguousarray(dataset.ori_histogram_map, dtype=np.float32)).to(dev).contiguous()
-        q_soft = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    lut_d = scratch = sheets = None
     nbins = int(cfg.ORI_BINS_PER_DIM)
     if render and soft:
         lut_h = grey_lut() if lut is None else np.ascontiguousarray(lut)
@@ -220,32 +208,20 @@ def detect_dataset(model, dataset, nr_images, image_ids=None, render=True, cell=
         sh, sw = hip.pmf_sheet_shape(nbins, cell, gap, 2)
         sheets = torch.empty((B, sh, sw, 3), dtype=torch.uint8, device=dev)
         scratch = torch.empty(B * 2 * nbins ** 3, dtype=torch.uint8, device=dev)        # the 8-bit indices between the two launches
-    if workers is None:
-        workers = int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1)))
     view = _Drawn(dataset, ids)
     logits, pictures = [], ([None] * N if render and sink is None else None)
-    feed = EvalFeeder(model, view, cfg, enc_loc=loc_enc, enc_ori=soft, workers=workers)
+    feed = EvalFeeder(model, view, cfg, enc_loc=loc_enc, enc_ori=soft, workers=loader_workers(cfg, workers))
     try:
         for bt in feed:
-            if bt.images.dtype == torch.uint8:
-                eng.load_batch_u8(bt.images)
-            elif render:
+            if render and bt.images.dtype != torch.uint8:
                 raise ValueError("detect_dataset(render=True) draws on uint8 RGB frames; this dataset's frames reach the engine as %s "
                                  "(molded on the host).  Call it with render=False." % (bt.images.dtype,))
-            else:
-                eng.set_input_u8(False)
-                eng.load_batch(bt.images)
-            eng.forward()
-            loc, rest = eng.outputs()
-            ori, ori2 = (rest[0], rest[1]) if cfg.REGRESS_KEYPOINTS else (rest, None)
-            n, z = bt.n, None
+            ps.run(bt.images)
+            heads = ps.heads(bt.n)
+            n, z = bt.n, heads[3]
             if soft:
-                z = ori[:n].contiguous()
-                hip.quat_wavg_decode(n, z.shape[1], z, hq, q_soft)
-                ori = q_soft
                 logits.append(z.clone())                       # z may be a view of the engine's output buffer
-            hip.pose_eval(B, n, bt.row0, loc_mode, ori_mode, loc, ori, bt.loc_gt, bt.q_gt, table, ori2=ori2, loc_map=loc_map,
-                          ori_map=hq if soft else None, enc_loc=bt.enc_loc, enc_ori=bt.enc_ori)
+            ps.eval_into(table, bt, heads)
             if not render:
                 continue
             rows = table[bt.row0:bt.row0 + n].cpu().numpy()    # this batch's poses: the one read per batch

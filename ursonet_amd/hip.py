@@ -675,21 +675,26 @@ def _rows(t):
     return t.data_ptr(), t.stride(0)
 
 
+def _pose_args(a, B, n, row0, loc_mode, ori_mode, loc, ori, ori2, loc_map, table):
+    """The fields urso_pose_eval_args and urso_pose_decode_args share."""
+    a.B, a.n, a.row0, a.loc_mode, a.ori_mode = int(B), int(n), int(row0), int(loc_mode), int(ori_mode)
+    a.loc, a.loc_ld = _rows(loc)
+    a.ori, a.ori_ld = _rows(ori)
+    a.ori2, a.loc_map, a.table = _rows(ori2)[0], ptr(loc_map), ptr(table)
+    a.loc_map_rows = 0 if loc_map is None else loc_map.shape[0]
+    a.loc_bins = loc.shape[1] if loc_mode == EVAL_LOC_CLASS else 0
+    return a
+
+
 def pose_eval(B, n, row0, loc_mode, ori_mode, loc, ori, loc_gt, q_gt, table, ori2=None, loc_map=None, ori_map=None, enc_loc=None,
               enc_ori=None, gmm_mean=None, gmm_nmodes=None, stream=None):
     """urso_pose_eval on one batch: loc / ori / ori2 are fp32 device tensors [B, width] with contiguous rows (views of the engine's
     outputs are fine), the rest contiguous; table is fp64 [rows, EVAL_COLS]."""
-    a = PoseEvalArgs()
-    a.B, a.n, a.row0, a.loc_mode, a.ori_mode = int(B), int(n), int(row0), int(loc_mode), int(ori_mode)
-    a.loc, a.loc_ld = _rows(loc)
-    a.ori, a.ori_ld = _rows(ori)
-    a.ori2 = _rows(ori2)[0]
-    a.loc_map, a.ori_map = ptr(loc_map), ptr(ori_map)
-    a.loc_map_rows = 0 if loc_map is None else loc_map.shape[0]
+    a = _pose_args(PoseEvalArgs(), B, n, row0, loc_mode, ori_mode, loc, ori, ori2, loc_map, table)
+    a.ori_map = ptr(ori_map)
     a.ori_map_rows = 0 if ori_map is None else ori_map.shape[0]
-    a.loc_bins = loc.shape[1] if loc_mode == EVAL_LOC_CLASS else 0
     a.ori_bins = 0 if enc_ori is None else enc_ori.shape[1]
-    a.enc_loc, a.enc_ori, a.loc_gt, a.q_gt, a.table = ptr(enc_loc), ptr(enc_ori), ptr(loc_gt), ptr(q_gt), ptr(table)
+    a.enc_loc, a.enc_ori, a.loc_gt, a.q_gt = ptr(enc_loc), ptr(enc_ori), ptr(loc_gt), ptr(q_gt)
     a.gmm_mean, a.gmm_nmodes = ptr(gmm_mean), ptr(gmm_nmodes)
     a.gmm_modes = 0 if gmm_mean is None else gmm_mean.shape[1]
     _chk(_lib.urso_pose_eval(C.byref(a), stream_ptr(stream)), "urso_pose_eval")
@@ -700,18 +705,11 @@ def pose_decode(B, n, row0, loc_mode, ori_mode, loc, ori, table, ori2=None, loc_
     """urso_pose_decode on one batch (no ground truth): loc / ori / ori2 / ori_logits are fp32 device tensors with contiguous rows,
     ori_scatter is urso_quat_wavg_decode's a_d [B, 16], ori_map_rows the rows of the bin map the logits index; table is fp64
     [rows, DEC_COLS]."""
-    a = PoseDecodeArgs()
-    a.B, a.n, a.row0, a.loc_mode, a.ori_mode = int(B), int(n), int(row0), int(loc_mode), int(ori_mode)
-    a.loc, a.loc_ld = _rows(loc)
-    a.ori, a.ori_ld = _rows(ori)
-    a.ori2 = _rows(ori2)[0]
-    a.loc_map = ptr(loc_map)
-    a.loc_map_rows = 0 if loc_map is None else loc_map.shape[0]
-    a.loc_bins = loc.shape[1] if loc_mode == EVAL_LOC_CLASS else 0
+    a = _pose_args(PoseDecodeArgs(), B, n, row0, loc_mode, ori_mode, loc, ori, ori2, loc_map, table)
     a.ori_logits, a.ori_logits_ld = _rows(ori_logits)
     a.ori_bins = 0 if ori_logits is None else ori_logits.shape[1]
     a.ori_map_rows = int(ori_map_rows)
-    a.ori_scatter, a.table = ptr(ori_scatter), ptr(table)
+    a.ori_scatter = ptr(ori_scatter)
     _chk(_lib.urso_pose_decode(C.byref(a), stream_ptr(stream)), "urso_pose_decode")
 
 

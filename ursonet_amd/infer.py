@@ -1,0 +1,145 @@
+"""The one inference pass under evaluate(), predict(), detect_dataset() and track(): everything between "a batch of frames is on the
+device" and "this batch's rows are in the table".  A command builds one PosePass per call and, per batch, on the current stream:
+  * run(images) uploads the batch by dtype and replays the inference graph as it is;
+  * heads() splits the engine's outputs and, for the soft-classification head, runs urso_quat_wavg_decode on its logits (with the scatter
+    matrix only for the DEC table, whose ORI_LAMBDA needs it: passing one selects another kernel variant) and, asked to, urso_quat_gmm_fit;
+  * eval_into() (labelled: estimates and errors, urso_pose_eval, EVAL columns) or decode_into() (no truth: estimates and confidences,
+    urso_pose_decode, DEC columns) decodes every head and writes one fp64 row per image into a device table of the caller's.
+The two kernels share their device routines, so LOC_EST / Q_EST are the same bits whichever command produced them.  Nothing here
+synchronises or reads back, and torch, hip and the engine are touched only after check_heads() has passed (no GPU is needed to be
+refused).  The commands own their feeders, tables, GMM buffers, result types, prints, files and pictures.
+"""
+import os
+
+import numpy as np
+
+# the multimodal fit of pose_estimator.py:333-334, :410-426: 5 EM iterations, nr_max_modes 4 (which fits 1 .. 3 modes: 3 slots per image)
+GMM_MODES, GMM_ITERATIONS, GMM_MAX_MODES = 3, 5, 4
+
+
+def head_modes(config):
+    """(loc_mode, ori_mode) of urso_pose_eval for a config."""
+    from . import hip
+    loc_mode = hip.EVAL_LOC_REGRESS if config.REGRESS_LOC else hip.EVAL_LOC_CLASS
+    if config.REGRESS_KEYPOINTS:
+        return loc_mode, hip.EVAL_ORI_KEYPOINTS
+    if not config.REGRESS_ORI:
+        return loc_mode, hip.EVAL_ORI_SOFT
+    return loc_mode, {"quaternion": hip.EVAL_ORI_QUAT, "euler_angles": hip.EVAL_ORI_EULER,
+                      "angle_axis": hip.EVAL_ORI_ANGLE_AXIS}[config.ORIENTATION_PARAM]
+
+
+def check_heads(model, dataset, multimodal, who="evaluate"):
+    """Refuses what the pass cannot run; returns whether the orientation head is the soft-classification one."""
+    assert model.mode == "inference", "Create model in inference mode."
+    cfg = model.config
+    soft = not (cfg.REGRESS_ORI or cfg.REGRESS_KEYPOINTS)
+    if multimodal and not soft:
+        raise ValueError("%s(multimodal=True) needs the soft-classification orientation head (REGRESS_ORI = False)" % who)
+    if not cfg.REGRESS_LOC and getattr(dataset, "histogram_3D_map", None) is None:
+        raise ValueError("location classification (REGRESS_LOC = False) needs dataset.histogram_3D_map, the bin map the location "
+                         "head was trained on")
+    if soft and getattr(dataset, "ori_histogram_map", None) is None:
+        raise ValueError("orientation classification (REGRESS_ORI = False) needs dataset.ori_histogram_map")
+    if cfg.REGRESS_KEYPOINTS and not cfg.REGRESS_LOC:
+        raise ValueError("keypoint evaluation needs a regressed location (REGRESS_LOC = True)")
+    return soft
+
+
+def loader_workers(cfg, workers=None):
+    """The number of loader threads: the caller's, else Config.LOADER_WORKERS, else min(8, cpu_count)."""
+    return int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1))) if workers is None else workers
+
+
+def eval_columns(res, table, loc_class):
+    """Sets the fields every result of an EVAL table has on `res`; returns the table as fp64 [N, EVAL_COLS] for the caller's own."""
+    from . import hip
+    t = np.asarray(table, dtype=np.float64).reshape(-1, hip.EVAL_COLS)
+    res.loc_est = t[:, hip.EVAL_LOC_EST:hip.EVAL_LOC_EST + 3].copy()
+    res.q_est = t[:, hip.EVAL_Q_EST:hip.EVAL_Q_EST + 4].copy()
+    res.loc_err, res.ori_err = t[:, hip.EVAL_LOC_ERR].copy(), t[:, hip.EVAL_ORI_ERR].copy()
+    res.loc_encoded_err = t[:, hip.EVAL_LOC_ENC_ERR].copy() if loc_class else None
+    return t
+
+
+def dec_columns(res, table, loc_class, soft):
+    """Sets the fields every result of a DEC table has on `res` (None where the head does not define them)."""
+    from . import hip
+    t = np.asarray(table, dtype=np.float64).reshape(-1, hip.DEC_COLS)
+    res.loc_est = t[:, hip.DEC_LOC_EST:hip.DEC_LOC_EST + 3].copy()
+    res.q_est = t[:, hip.DEC_Q_EST:hip.DEC_Q_EST + 4].copy()
+    res.loc_peak = t[:, hip.DEC_LOC_PEAK].copy() if loc_class else None
+    res.ori_peak = t[:, hip.DEC_ORI_PEAK].copy() if soft else None
+    res.ori_lambda = t[:, hip.DEC_ORI_LAMBDA].copy() if soft else None
+
+
+class PosePass(object):
+    """The per-call state of the pass: cfg, eng, B, dev, the head modes and, on the device, the bin maps loc_map (fp64) and hq (fp32),
+    q_soft [B,4] and, with scatter=True, urso_quat_wavg_decode's scatter matrices [B,16].  `who`: the command, for check_heads' messages."""
+
+    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate"):
+        self.soft = check_heads(model, dataset, multimodal, who)
+        import torch
+        from . import hip
+        self.torch, self.hip = torch, hip
+        cfg, eng = self.cfg, self.eng = model.config, model._engine
+        self.loc_mode, self.ori_mode = head_modes(cfg)
+        self.loc_class = self.loc_mode == hip.EVAL_LOC_CLASS
+        B, dev = self.B, self.dev = eng.B, eng.device
+        self.loc_map = self.hq = self.q_soft = self.scatter = self.var = None
+        if self.loc_class:
+            self.loc_map = torch.as_tensor(np.asarray(dataset.histogram_3D_map, dtype=np.float64)).to(dev).contiguous()
+        if self.soft:
+            self.hq = torch.as_tensor(np.ascontiguousarray(dataset.ori_histogram_map, dtype=np.float32)).to(dev).contiguous()
+            self.q_soft = torch.empty(B, 4, dtype=torch.float32, device=dev)
+            if scatter:
+                self.scatter = torch.empty(B, 16, dtype=torch.float32, device=dev)
+            if multimodal:
+                self.var = (cfg.BETA / cfg.ORI_BINS_PER_DIM) ** 2 / 12         # pose_estimator.py:333-334
+
+    def table(self, rows, cols):
+        """A NaN fp64 device table [rows, cols]."""
+        return self.torch.full((rows, cols), float("nan"), dtype=self.torch.float64, device=self.dev)
+
+    def gmm_buffers(self, rows, zeroed=False):
+        """urso_quat_gmm_fit's outputs for `rows` images: (mean [rows,3,4], var, prior, score [rows,3] fp32, n_modes [rows] int32)."""
+        new, f32 = (self.torch.zeros if zeroed else self.torch.empty), dict(dtype=self.torch.float32, device=self.dev)
+        return ((new(rows, GMM_MODES, 4, **f32),) + tuple(new(rows, GMM_MODES, **f32) for _ in range(3)) +
+                (new(rows, dtype=self.torch.int32, device=self.dev),))
+
+    def run(self, images):
+        """Uploads a batch [B,H,W,3] -- uint8 frames as they are, anything else was molded on the host -- and runs the inference graph."""
+        if images.dtype == self.torch.uint8:
+            self.eng.load_batch_u8(images)
+        else:
+            self.eng.set_input_u8(False)
+            self.eng.load_batch(images)
+        self.eng.forward()
+
+    def heads(self, n, gmm=None):
+        """After run(): the engine's outputs as (loc, ori, ori2, z): for the soft head z is the logits of the n valid images (it may alias the
+        engine's output buffer) and ori their decoded quaternions; gmm: gmm_buffers' tuple, or views of n rows of it, to fit into."""
+        loc, rest = self.eng.outputs()
+        ori, ori2 = (rest[0], rest[1]) if self.cfg.REGRESS_KEYPOINTS else (rest, None)
+        z = None
+        if self.soft:
+            z = ori[:n].contiguous()
+            self.hip.quat_wavg_decode(n, z.shape[1], z, self.hq, self.q_soft, self.scatter)
+            if gmm is not None:
+                self.hip.quat_gmm_fit(n, z.shape[1], z, False, self.hq, self.var, GMM_ITERATIONS, GMM_MAX_MODES, *gmm)
+            ori = self.q_soft
+        return loc, ori, ori2, z
+
+    def eval_into(self, table, bt, heads, gmm=None):
+        """The rows [bt.row0, bt.row0 + bt.n) of an EVAL table from heads() and the EvalFeeder batch bt's truth and encoded targets; with
+        gmm (the per-batch buffers heads() fitted into: urso_pose_eval indexes them by batch row) the fitted mode nearer the truth is scored."""
+        loc, ori, ori2, _z = heads
+        self.hip.pose_eval(self.B, bt.n, bt.row0, self.loc_mode, self.ori_mode, loc, ori, bt.loc_gt, bt.q_gt, table, ori2=ori2,
+                           loc_map=self.loc_map, ori_map=self.hq, enc_loc=bt.enc_loc, enc_ori=bt.enc_ori,
+                           gmm_mean=gmm[0] if gmm else None, gmm_nmodes=gmm[4] if gmm else None)
+
+    def decode_into(self, table, n, row0, heads):
+        """The rows [row0, row0 + n) of a DEC table from heads()."""
+        loc, ori, ori2, z = heads
+        self.hip.pose_decode(self.B, n, row0, self.loc_mode, self.ori_mode, loc, ori, table, ori2=ori2, loc_map=self.loc_map, ori_logits=z,
+                             ori_map_rows=self.hq.shape[0] if self.soft else 0, ori_scatter=self.scatter)

@@ -327,8 +327,9 @@ class UrsoNet(object):
         # the reference hands Keras two Python generators and `workers = cpu_count` processes (net.py:1100-1163); here a producer
         # thread + loader threads assemble uint8 batches in pinned memory and a side stream uploads batch k+1 while step k runs
         from .feeder import DeviceFeeder
+        from .infer import loader_workers
         import torch
-        workers = int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1)))
+        workers = loader_workers(cfg)
         rank, world, runner = self._rank, self._world, (self._dp or eng)
         # data-parallel run: every rank walks the SAME shuffled order and takes samples [rank * B, (rank + 1) * B) of each global batch (feeder.batches)
         train_feed = DeviceFeeder(eng, train_dataset, cfg, shuffle=True, workers=workers, rank=rank, world=world)

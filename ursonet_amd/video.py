@@ -4,20 +4,19 @@ pose_estimator.py:606-745).
 Per frame the reference crops, zero-pads by 400 pixels (a 960 x 1280 frame becomes 1760 x 1929 x 3), mixes to grey in float64, resizes,
 runs the network at batch 1, decodes, converts the pose to Unreal Euler angles and draws the object axes with OpenCV -- all on the host.
 track() runs the same chain for whole engine batches on one stream: pinned upload of the RAW frames -> urso_video_prep_u8 (crop + pad +
-grey, the bytes of VideoPrep.host) -> augment.resize_images (the bytes of utils.resize_image) -> engine.forward() -> [urso_quat_wavg_decode]
--> urso_pose_decode into a fp64 device table, read once at the end; with render=True the axes are drawn onto the resized frames where
+grey, the bytes of VideoPrep.host) -> augment.resize_images (the bytes of utils.resize_image) -> the pass of ursonet_amd/infer.py as
+predict() runs it (urso_pose_decode into a fp64 device table, read once at the end); with render=True the axes are drawn onto the resized frames where
 they lie (urso_draw_prims_u8) and only the annotated windows come back.  The few hundred flops per frame of the Euler conversion and of
 the axis projection stay on the host in float64.
 
 Decoding a video container is the caller's job (OpenCV is no dependency): `frames` is any iterable of uint8 RGB arrays of one size.
 """
 import math
-import os
 
 import numpy as np
 
 from .augment import quat2SO3
-from .evaluate import _check, head_modes
+from .infer import PosePass, dec_columns, loader_workers
 
 COORD_MAX = 16384                                                                 # URSO_DRAW_COORD_MAX
 MAX_PRIMS, PRIM_INTS = 16, 9
@@ -160,13 +159,7 @@ class TrackResult(object):
     define them).  frames: the annotated windows (uint8 [h,w,3] each) of a render=True run without a sink, else None."""
 
     def __init__(self, table, loc_class, soft, frames=None):
-        from . import hip
-        t = np.asarray(table, dtype=np.float64).reshape(-1, hip.DEC_COLS)
-        self.loc_est = t[:, hip.DEC_LOC_EST:hip.DEC_LOC_EST + 3].copy()
-        self.q_est = t[:, hip.DEC_Q_EST:hip.DEC_Q_EST + 4].copy()
-        self.loc_peak = t[:, hip.DEC_LOC_PEAK].copy() if loc_class else None
-        self.ori_peak = t[:, hip.DEC_ORI_PEAK].copy() if soft else None
-        self.ori_lambda = t[:, hip.DEC_ORI_LAMBDA].copy() if soft else None
+        dec_columns(self, table, loc_class, soft)
         self.pose_unreal = np.array([pose_unreal(l, q) for l, q in zip(self.loc_est, self.q_est)], dtype=np.float64).reshape(-1, 6)
         self.frames = frames
 
@@ -199,24 +192,14 @@ def track(model, frames, dataset, prep=None, render=False, K=None, sink=None, wo
     render=True draws each frame's axes (pose_axes_prims with K; default: camera_matrix(dataset.camera, window width, window height))
     onto its resized frame on the device and hands the annotated window (utils.resize_geometry's window) to sink(index, uint8 array);
     without a sink the windows are collected in TrackResult.frames.  workers: threads that copy the raw frames into pinned memory."""
-    soft = _check(model, dataset, False, "track")
+    ps = PosePass(model, dataset, scatter=True, who="track")
     import torch
     from . import augment, hip, utils
-    cfg, eng = model.config, model._engine
+    cfg, eng, B, dev = ps.cfg, ps.eng, ps.B, ps.dev
     if cfg.IMAGE_RESIZE_MODE not in ("square", "pad64"):
         raise ValueError("track: IMAGE_RESIZE_MODE %r is not resized on the device (square / pad64 are)" % (cfg.IMAGE_RESIZE_MODE,))
     prep = prep if prep is not None else VideoPrep()
-    loc_mode, ori_mode = head_modes(cfg)
-    loc_class = loc_mode == hip.EVAL_LOC_CLASS
-    B, dev = eng.B, eng.device
-    loc_map = torch.as_tensor(np.asarray(dataset.histogram_3D_map, dtype=np.float64)).to(dev).contiguous() if loc_class else None
-    hq = q_soft = scatter = None
-    if soft:
-        hq = torch.as_tensor(np.ascontiguousarray(dataset.ori_histogram_map, dtype=np.float32)).to(dev).contiguous()
-        q_soft = torch.empty(B, 4, dtype=torch.float32, device=dev)
-        scatter = torch.empty(B, 16, dtype=torch.float32, device=dev)
-    if workers is None:
-        workers = int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1)))
+    workers = loader_workers(cfg, workers)
     pool = None
     if workers > 1 and B > 1:
         from concurrent.futures import ThreadPoolExecutor
@@ -253,18 +236,10 @@ def track(model, frames, dataset, prep=None, render=False, K=None, sink=None, wo
                 prepared = augment.video_prep(raw, prep, out=prepared)
                 resized, window, _scale, _padding = augment.resize_images(prepared, min_dim=cfg.IMAGE_MIN_DIM, max_dim=cfg.IMAGE_MAX_DIM,
                                                                           min_scale=cfg.IMAGE_MIN_SCALE, mode=cfg.IMAGE_RESIZE_MODE, out=resized)
-                eng.load_batch_u8(resized)
-                eng.forward()
-                loc, rest = eng.outputs()
-                ori, ori2 = (rest[0], rest[1]) if cfg.REGRESS_KEYPOINTS else (rest, None)
-                z = None
-                if soft:
-                    z = ori[:n].contiguous()
-                    hip.quat_wavg_decode(n, z.shape[1], z, hq, q_soft, scatter)
-                    ori = q_soft
-                table = torch.full((B, hip.DEC_COLS), float("nan"), dtype=torch.float64, device=dev)
-                hip.pose_decode(B, n, 0, loc_mode, ori_mode, loc, ori, table, ori2=ori2, loc_map=loc_map, ori_logits=z,
-                                ori_map_rows=hq.shape[0] if soft else 0, ori_scatter=scatter)
+                ps.run(resized)
+                heads = ps.heads(n)
+                table = ps.table(B, hip.DEC_COLS)              # a table per batch: the frame count is not known up front
+                ps.decode_into(table, n, 0, heads)
                 tables.append(table[:n])
                 N += n
                 if render:
@@ -284,4 +259,4 @@ def track(model, frames, dataset, prep=None, render=False, K=None, sink=None, wo
         if pool is not None:
             pool.shutdown(wait=True)
     host = torch.cat(tables).cpu().numpy() if tables else np.zeros((0, hip.DEC_COLS))      # the one read of the table
-    return TrackResult(host[:N], loc_class, soft, collected)
+    return TrackResult(host[:N], ps.loc_class, ps.soft, collected)
