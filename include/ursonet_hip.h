@@ -580,6 +580,11 @@ int urso_adam_amsgrad_clip(size_t n, float* w_d, const float* g_d, float* m_d, f
                            float* hyper_d, const float* normsq_d, void* stream);
 int urso_scale_f32(size_t n, float* x_d, float s, void* stream);
 
+/* Loss scaling for 16-bit training (Config.LOSS_SCALE): the state layout (URSO_LS_*), the scaled forms of the losses,
+ * finalisations and optimizers and the update launch are an optional extension with a header of its own, included here so that one
+ * include still gives a host everything. */
+#include "ursonet_loss_scale.h"
+
 /*
  * Probabilistic soft-argmax decode (pose_estimator.py:406-409 = utils.stable_softmax
  * utils.py:26-28 + se3lib.quat_weighted_avg se3lib.py:217-260), batched on the GPU:

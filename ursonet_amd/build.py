@@ -22,11 +22,11 @@ def _hipcc():
 
 
 def source_hash():
-    """SHA-256 over everything the library is a function of: every file of csrc/ (name + bytes), the public header, the compile flags
+    """SHA-256 over everything the library is a function of: every file of csrc/ (name + bytes), the public headers, the compile flags
     (incl. URSO_VARIANT_FLAGS) and the compiler's version string."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + [os.path.join(HERE, "..", "include", "ursonet_hip.h")]
+    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + [os.path.join(HERE, "..", "include", f) for f in ("ursonet_hip.h", "ursonet_loss_scale.h")]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:

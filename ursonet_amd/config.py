@@ -9,6 +9,8 @@ Additions (all optional, never required by a reference caller):
   DP_EXACT_REL_LOSS  False: per-rank `rel_loss_graph` (what a tower-parallel Keras model
                  would compute); True: the two squared norms are summed over the ranks between
                  forward and backward, i.e. the loss and its gradient are those of the one global batch.
+  LOSS_SCALE     None (default) | a power of two | "dynamic": loss scaling for 16-bit training, with LOSS_SCALE_INIT,
+                 LOSS_SCALE_GROWTH_INTERVAL, LOSS_SCALE_MIN and LOSS_SCALE_MAX (ursonet_amd/loss_scale.py).
 """
 import json
 import os
@@ -63,6 +65,14 @@ class Config(object):
     # each holding either grey frames (one plane) or RGB frames: give a dataset that has both at least 2.  The budget is PER FEEDER:
     # UrsoNet.train owns a training and a validation feeder, so up to 2 x DEVICE_CACHE_GB of HBM per rank.  0 = off: nothing changes.
     DEVICE_CACHE_GB = 0
+    # Not reference fields: loss scaling for 16-bit training (ursonet_amd/loss_scale.py).  None = off (nothing changes);
+    # a positive power of two = a static scale; "dynamic" = start at LOSS_SCALE_INIT, halve on an overflowed (skipped) step down to
+    # LOSS_SCALE_MIN, double after LOSS_SCALE_GROWTH_INTERVAL finite steps in a row up to LOSS_SCALE_MAX.  One GPU only.
+    LOSS_SCALE = None
+    LOSS_SCALE_INIT = 2.0 ** 15
+    LOSS_SCALE_GROWTH_INTERVAL = 2000
+    LOSS_SCALE_MIN = 1.0
+    LOSS_SCALE_MAX = 2.0 ** 24
 
     def update(self):
         """Derived fields (config.py:151-166)."""

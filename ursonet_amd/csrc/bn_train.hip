@@ -136,13 +136,15 @@ __global__ __launch_bounds__(1024) void bn_stats_final_kernel(int M, int N, int 
 
 __global__ __launch_bounds__(1024) void bn_sum_final_kernel(int N, int nblk, const double* __restrict__ partial, float* __restrict__ dbeta,
                                                            float* __restrict__ dgamma, int bn_trainable, float* __restrict__ gbeta,
-                                                           float* __restrict__ ggamma) {
+                                                           float* __restrict__ ggamma, const float* __restrict__ ls) {
     const int n = blockIdx.x * 32 + (threadIdx.x & 31);
     double s, ss;
     bn_slab_sums(N, nblk, partial, n, s, ss);
     if (n >= N || threadIdx.x >= 32) return;
     dbeta[n] = (float)s; dgamma[n] = (float)ss;
-    if (gbeta) { gbeta[n] = bn_trainable ? (float)s : 0.f; ggamma[n] = bn_trainable ? (float)ss : 0.f; }
+    // ls (loss scaling): dbeta / dgamma stay in the scaled units of g (dz is computed from them); the gradient slices get true units
+    const float unscale = ls ? ls[URSO_LS_INV_SCALE] : 1.f;
+    if (gbeta) { gbeta[n] = bn_trainable ? (ls ? (float)s * unscale : (float)s) : 0.f; ggamma[n] = bn_trainable ? (ls ? (float)ss * unscale : (float)ss) : 0.f; }
 }
 
 // Elementwise passes.  FIXED: the grid's stride is a multiple of the row's vector count, so a thread stays on one vector column and keeps that
@@ -300,9 +302,9 @@ extern "C" int urso_bn_apply(int M, int N, int dt, const void* z_d, const float*
     return urso_check_launch("urso_bn_apply");
 }
 
-extern "C" int urso_bn_backward(int M, int N, int dt, const void* g_d, const void* z_d, const float* mean_d, const float* var_d,
-                                const float* gamma_d, float eps, void* ws_d, size_t ws_bytes, float* dbeta_d, float* dgamma_d,
-                                int bn_trainable, float* gbeta_d, float* ggamma_d, void* dz_d, void* stream) {
+extern "C" int urso_bn_backward_ls(int M, int N, int dt, const void* g_d, const void* z_d, const float* mean_d, const float* var_d,
+                                   const float* gamma_d, float eps, void* ws_d, size_t ws_bytes, float* dbeta_d, float* dgamma_d,
+                                   int bn_trainable, float* gbeta_d, float* ggamma_d, void* dz_d, const float* state_d, void* stream) {
     int rc = bn_check("urso_bn_backward", M, N, dt); if (rc) return rc;
     if (!g_d || !z_d || !mean_d || !var_d || !gamma_d || !ws_d || !dbeta_d || !dgamma_d || !dz_d || ws_bytes < urso_bn_ws_bytes(M, N)) {
         urso_set_error("urso_bn_backward: bad argument / workspace"); return URSO_EINVAL; }
@@ -315,7 +317,7 @@ extern "C" int urso_bn_backward(int M, int N, int dt, const void* g_d, const voi
     ProfScope ps(st, URSO_K_POOL, 0, (double)M * N * dt_size(dt) * 5);
 #define URSO_BNB(TT) do { \
         URSO_KLAUNCH((bn_colreduce_kernel<TT, 1>), dim3(nb, bn_col_groups(N, dt)), dim3(256), lds, st, M, N, (const TT*)g_d, (const TT*)z_d, mean_d, var_d, eps, (double*)ws_d); \
-        URSO_KLAUNCH(bn_sum_final_kernel, dim3(ceil_div(N, 32)), dim3(1024), 0, st, N, nb, (const double*)ws_d, dbeta_d, dgamma_d, bn_trainable, gbeta_d, ggamma_d); \
+        URSO_KLAUNCH(bn_sum_final_kernel, dim3(ceil_div(N, 32)), dim3(1024), 0, st, N, nb, (const double*)ws_d, dbeta_d, dgamma_d, bn_trainable, gbeta_d, ggamma_d, state_d); \
         if (fixed) URSO_KLAUNCH((bn_bwd_apply_kernel<TT, true>), dim3(blocks), dim3(256), 0, st, nvec, N, 1.0f / (float)M, (const TT*)g_d, (const TT*)z_d, mean_d, var_d, gamma_d, eps, \
                            (const float*)dbeta_d, (const float*)dgamma_d, (TT*)dz_d); \
         else URSO_KLAUNCH((bn_bwd_apply_kernel<TT, false>), dim3(blocks), dim3(256), 0, st, nvec, N, 1.0f / (float)M, (const TT*)g_d, (const TT*)z_d, mean_d, var_d, gamma_d, eps, \
@@ -323,4 +325,10 @@ extern "C" int urso_bn_backward(int M, int N, int dt, const void* g_d, const voi
     if (dt == URSO_F32) URSO_BNB(float); else if (dt == URSO_BF16) URSO_BNB(__bf16); else URSO_BNB(_Float16);
 #undef URSO_BNB
     return urso_check_launch("urso_bn_backward");
+}
+extern "C" int urso_bn_backward(int M, int N, int dt, const void* g_d, const void* z_d, const float* mean_d, const float* var_d,
+                                const float* gamma_d, float eps, void* ws_d, size_t ws_bytes, float* dbeta_d, float* dgamma_d,
+                                int bn_trainable, float* gbeta_d, float* ggamma_d, void* dz_d, void* stream) {
+    return urso_bn_backward_ls(M, N, dt, g_d, z_d, mean_d, var_d, gamma_d, eps, ws_d, ws_bytes, dbeta_d, dgamma_d, bn_trainable, gbeta_d, ggamma_d, dz_d,
+                               nullptr, stream);
 }

@@ -163,9 +163,14 @@ __device__ __forceinline__ void put_any(int dt, void* p, size_t i, float v) {
     if (dt == URSO_F32) put_dt<float>(p, i, v); else if (dt == URSO_BF16) put_dt<__bf16>(p, i, v); else put_dt<_Float16>(p, i, v);
 }
 
+// =============================================================== loss scaling
+// ls: the fp32 state buffer of urso_loss_scale_update (URSO_LS_*), or NULL = no scaling: the value passes through untouched, so the entry
+// points without a state keep their bits.  The factor is applied to the finished fp32 gradient, LAST, in front of the one rounding to dt.
+__device__ __forceinline__ float ls_scaled(const float* __restrict__ ls, float g) { return ls ? g * ls[URSO_LS_SCALE] : g; }
+
 // =============================================================== softmax cross-entropy with soft labels
 __global__ void softmax_xent_kernel(int K, const float* __restrict__ z, const float* __restrict__ p, float gscale,
-                                    int relu_mask, int dt, float* __restrict__ row_loss, void* __restrict__ dz) {
+                                    int relu_mask, int dt, float* __restrict__ row_loss, void* __restrict__ dz, const float* __restrict__ ls) {
     __shared__ float sh[8];
     const int b = blockIdx.x;
     const float* zr = z + (size_t)b * K; const float* pr = p + (size_t)b * K;
@@ -182,7 +187,7 @@ __global__ void softmax_xent_kernel(int K, const float* __restrict__ z, const fl
         const float zz = zr[k];
         float g = (__expf(zz - mx) * inv - pr[k]) * gscale;           // TF backprop: softmax - labels
         if (relu_mask && !(zz > 0.f)) g = 0.f;
-        put_any(dt, dz, (size_t)b * K + k, g);
+        put_any(dt, dz, (size_t)b * K + k, ls_scaled(ls, g));
     }
 }
 // K <= NV * blockDim (NV 4: the heads' 16^3 = 4096 orientation bins on 1024 threads; NV 16: 24^3 = 13,824 bins, 56 -> 12 us at batch 16): logits and labels are read ONCE into registers, the row maximum
@@ -190,7 +195,8 @@ __global__ void softmax_xent_kernel(int K, const float* __restrict__ z, const fl
 // over global memory and eight barriers (18 -> 7 us for 32 x 4096; the launch is latency, not bandwidth)
 template <int NV>
 __global__ __launch_bounds__(1024) void softmax_xent_reg_kernel(int K, const float* __restrict__ z, const float* __restrict__ p, float gscale,
-                                                                int relu_mask, int dt, float* __restrict__ row_loss, void* __restrict__ dz) {
+                                                                int relu_mask, int dt, float* __restrict__ row_loss, void* __restrict__ dz,
+                                                                const float* __restrict__ ls) {
     __shared__ float sh[4][16];
     const int b = blockIdx.x, nw = (int)(blockDim.x >> 6), w = (int)(threadIdx.x >> 6);
     const float* zr = z + (size_t)b * K; const float* pr = p + (size_t)b * K;
@@ -229,7 +235,7 @@ __global__ __launch_bounds__(1024) void softmax_xent_reg_kernel(int K, const flo
         if (k >= K) continue;
         float g = (ex[i] * inv - pc[i]) * gscale;                    // TF backprop: softmax - labels
         if (relu_mask && !(zc[i] > 0.f)) g = 0.f;
-        put_any(dt, dz, (size_t)b * K + k, g);
+        put_any(dt, dz, (size_t)b * K + k, ls_scaled(ls, g));
     }
 }
 __global__ void mean_scale_kernel(int n, const float* __restrict__ v, float scale, float* __restrict__ out) {
@@ -240,26 +246,30 @@ __global__ void mean_scale_kernel(int n, const float* __restrict__ v, float scal
     if (threadIdx.x == 0) out[0] = s * scale;
 }
 
-extern "C" int urso_softmax_xent_fwd_bwd(int B, int K, const float* logits_d, const float* labels_d, float weight,
-                                         int relu_mask, int dt, float* loss_d, void* dz_d, float* row_ws_d, void* stream) {
+extern "C" int urso_softmax_xent_fwd_bwd_ls(int B, int K, const float* logits_d, const float* labels_d, float weight,
+                                            int relu_mask, int dt, float* loss_d, void* dz_d, float* row_ws_d, const float* state_d, void* stream) {
     if (!logits_d || !labels_d || !loss_d || !dz_d || !row_ws_d || B <= 0 || K <= 0) { urso_set_error("urso_softmax_xent_fwd_bwd: bad argument"); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_LOSS, 0, (double)B * K * (8 + dt_size(dt)));
     if (K <= 4096) {
         int threads = ((K + 3) / 4 + 63) & ~63;
         if (threads < 64) threads = 64;
-        URSO_KLAUNCH(softmax_xent_reg_kernel<4>, dim3(B), dim3(threads), 0, st, K, logits_d, labels_d, weight / (float)B, relu_mask, dt, row_ws_d, dz_d);
+        URSO_KLAUNCH(softmax_xent_reg_kernel<4>, dim3(B), dim3(threads), 0, st, K, logits_d, labels_d, weight / (float)B, relu_mask, dt, row_ws_d, dz_d, state_d);
     } else if (K <= 16384)
-        URSO_KLAUNCH(softmax_xent_reg_kernel<16>, dim3(B), dim3(1024), 0, st, K, logits_d, labels_d, weight / (float)B, relu_mask, dt, row_ws_d, dz_d);
+        URSO_KLAUNCH(softmax_xent_reg_kernel<16>, dim3(B), dim3(1024), 0, st, K, logits_d, labels_d, weight / (float)B, relu_mask, dt, row_ws_d, dz_d, state_d);
     else
-        URSO_KLAUNCH(softmax_xent_kernel, dim3(B), dim3(256), 0, st, K, logits_d, labels_d, weight / (float)B, relu_mask, dt, row_ws_d, dz_d);
+        URSO_KLAUNCH(softmax_xent_kernel, dim3(B), dim3(256), 0, st, K, logits_d, labels_d, weight / (float)B, relu_mask, dt, row_ws_d, dz_d, state_d);
     URSO_KLAUNCH(mean_scale_kernel, dim3(1), dim3(256), 0, st, B, (const float*)row_ws_d, weight / (float)B, loss_d);
     return urso_check_launch("urso_softmax_xent_fwd_bwd");
+}
+extern "C" int urso_softmax_xent_fwd_bwd(int B, int K, const float* logits_d, const float* labels_d, float weight,
+                                         int relu_mask, int dt, float* loss_d, void* dz_d, float* row_ws_d, void* stream) {
+    return urso_softmax_xent_fwd_bwd_ls(B, K, logits_d, labels_d, weight, relu_mask, dt, loss_d, dz_d, row_ws_d, nullptr, stream);
 }
 
 // =============================================================== relative L2 (batch-Frobenius)
 __global__ void rel_l2_kernel(int B, int D, int ld, const float* __restrict__ gt, const float* __restrict__ pred, float weight,
-                              int dt, float* __restrict__ loss, void* __restrict__ dpred, float* __restrict__ norms) {
+                              int dt, float* __restrict__ loss, void* __restrict__ dpred, float* __restrict__ norms, const float* __restrict__ ls) {
     __shared__ float sh[8];
     float sd = 0.f, sg = 0.f;
     for (int i = threadIdx.x; i < B * D; i += blockDim.x) {
@@ -273,16 +283,20 @@ __global__ void rel_l2_kernel(int B, int D, int ld, const float* __restrict__ gt
     const float c = -weight / (nd * ng);                               // d/dpred ||gt-pred||/||gt||  (NaN if pred==gt, as in TF)
     for (int i = threadIdx.x; i < B * ld; i += blockDim.x) {
         const int b = i / ld, d = i - b * ld;
-        put_any(dt, dpred, i, d < D ? c * (gt[b * D + d] - pred[i]) : 0.f);
+        put_any(dt, dpred, i, d < D ? ls_scaled(ls, c * (gt[b * D + d] - pred[i])) : 0.f);
     }
 }
-extern "C" int urso_rel_l2_fwd_bwd(int B, int D, int ld, const float* gt_d, const float* pred_d, float weight,
-                                   int dt, float* loss_d, void* dpred_d, float* norms_d, void* stream) {
+extern "C" int urso_rel_l2_fwd_bwd_ls(int B, int D, int ld, const float* gt_d, const float* pred_d, float weight,
+                                      int dt, float* loss_d, void* dpred_d, float* norms_d, const float* state_d, void* stream) {
     if (!gt_d || !pred_d || !loss_d || !dpred_d || B <= 0 || D <= 0 || ld < D) { urso_set_error("urso_rel_l2_fwd_bwd: bad argument"); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_LOSS, 0, 0);
-    URSO_KLAUNCH(rel_l2_kernel, dim3(1), dim3(256), 0, st, B, D, ld, gt_d, pred_d, weight, dt, loss_d, dpred_d, norms_d);
+    URSO_KLAUNCH(rel_l2_kernel, dim3(1), dim3(256), 0, st, B, D, ld, gt_d, pred_d, weight, dt, loss_d, dpred_d, norms_d, state_d);
     return urso_check_launch("urso_rel_l2_fwd_bwd");
+}
+extern "C" int urso_rel_l2_fwd_bwd(int B, int D, int ld, const float* gt_d, const float* pred_d, float weight,
+                                   int dt, float* loss_d, void* dpred_d, float* norms_d, void* stream) {
+    return urso_rel_l2_fwd_bwd_ls(B, D, ld, gt_d, pred_d, weight, dt, loss_d, dpred_d, norms_d, nullptr, stream);
 }
 
 // Two-phase form for the exact data-parallel loss: the two squared norms are summed over ALL ranks between the phases
@@ -328,7 +342,7 @@ extern "C" int urso_rel_l2_from_norms(int B, int D, int ld, const float* gt_d, c
 
 // =============================================================== l2-normalise + 1-|dot|
 __global__ void absdot_kernel(int B, int D, int ld, int normalize, const float* __restrict__ gt, const float* __restrict__ x,
-                              float weight, int dt, float* __restrict__ q, float* __restrict__ loss, void* __restrict__ dx) {
+                              float weight, int dt, float* __restrict__ q, float* __restrict__ loss, void* __restrict__ dx, const float* __restrict__ ls) {
     __shared__ float sh[8];
     float lsum = 0.f;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
@@ -348,24 +362,28 @@ __global__ void absdot_kernel(int B, int D, int ld, int normalize, const float* 
             for (int d = 0; d < ld; ++d) {
                 float g = 0.f;
                 if (d < D) { const float dq = c * gt[(size_t)b * D + d]; g = normalize ? rinv * (dq - (clamped ? 0.f : x[(size_t)b * ld + d] * rinv * qdq)) : dq; }
-                if (dx) put_any(dt, dx, (size_t)b * ld + d, g);
+                if (dx) put_any(dt, dx, (size_t)b * ld + d, ls_scaled(ls, g));
             }
         }
     }
     if (gt && loss) { lsum = block_sum(lsum, sh); if (threadIdx.x == 0) loss[0] = weight * lsum / (float)B; }
 }
-extern "C" int urso_absdot_fwd_bwd(int B, int D, int ld, int normalize, const float* gt_d, const float* x_d, float weight,
-                                   int dt, float* q_d, float* loss_d, void* dx_d, void* stream) {
+extern "C" int urso_absdot_fwd_bwd_ls(int B, int D, int ld, int normalize, const float* gt_d, const float* x_d, float weight,
+                                      int dt, float* q_d, float* loss_d, void* dx_d, const float* state_d, void* stream) {
     if (!x_d || B <= 0 || D <= 0 || ld < D || (gt_d && (!loss_d || !dx_d))) { urso_set_error("urso_absdot_fwd_bwd: bad argument"); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_LOSS, 0, 0);
-    URSO_KLAUNCH(absdot_kernel, dim3(1), dim3(256), 0, st, B, D, ld, normalize, gt_d, x_d, weight, dt, q_d, loss_d, dx_d);
+    URSO_KLAUNCH(absdot_kernel, dim3(1), dim3(256), 0, st, B, D, ld, normalize, gt_d, x_d, weight, dt, q_d, loss_d, dx_d, state_d);
     return urso_check_launch("urso_absdot_fwd_bwd");
+}
+extern "C" int urso_absdot_fwd_bwd(int B, int D, int ld, int normalize, const float* gt_d, const float* x_d, float weight,
+                                   int dt, float* q_d, float* loss_d, void* dx_d, void* stream) {
+    return urso_absdot_fwd_bwd_ls(B, D, ld, normalize, gt_d, x_d, weight, dt, q_d, loss_d, dx_d, nullptr, stream);
 }
 
 // =============================================================== MSE
 __global__ void mse_kernel(int B, int D, int ld, const float* __restrict__ gt, const float* __restrict__ pred, float weight,
-                           int dt, float* __restrict__ loss, void* __restrict__ dpred) {
+                           int dt, float* __restrict__ loss, void* __restrict__ dpred, const float* __restrict__ ls) {
     __shared__ float sh[8];
     float s = 0.f;
     const float c = 2.f * weight / (float)(B * D);
@@ -373,18 +391,22 @@ __global__ void mse_kernel(int B, int D, int ld, const float* __restrict__ gt, c
         const int b = i / ld, d = i - b * ld;
         float g = 0.f;
         if (d < D) { const float e = pred[i] - gt[b * D + d]; s += e * e; g = c * e; }
-        put_any(dt, dpred, i, g);
+        put_any(dt, dpred, i, ls_scaled(ls, g));
     }
     s = block_sum(s, sh);
     if (threadIdx.x == 0) loss[0] = weight * s / (float)(B * D);
 }
-extern "C" int urso_mse_fwd_bwd(int B, int D, int ld, const float* gt_d, const float* pred_d, float weight,
-                                int dt, float* loss_d, void* dpred_d, void* stream) {
+extern "C" int urso_mse_fwd_bwd_ls(int B, int D, int ld, const float* gt_d, const float* pred_d, float weight,
+                                   int dt, float* loss_d, void* dpred_d, const float* state_d, void* stream) {
     if (!gt_d || !pred_d || !loss_d || !dpred_d || B <= 0 || D <= 0 || ld < D) { urso_set_error("urso_mse_fwd_bwd: bad argument"); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_LOSS, 0, 0);
-    URSO_KLAUNCH(mse_kernel, dim3(1), dim3(256), 0, st, B, D, ld, gt_d, pred_d, weight, dt, loss_d, dpred_d);
+    URSO_KLAUNCH(mse_kernel, dim3(1), dim3(256), 0, st, B, D, ld, gt_d, pred_d, weight, dt, loss_d, dpred_d, state_d);
     return urso_check_launch("urso_mse_fwd_bwd");
+}
+extern "C" int urso_mse_fwd_bwd(int B, int D, int ld, const float* gt_d, const float* pred_d, float weight,
+                                int dt, float* loss_d, void* dpred_d, void* stream) {
+    return urso_mse_fwd_bwd_ls(B, D, ld, gt_d, pred_d, weight, dt, loss_d, dpred_d, nullptr, stream);
 }
 
 // =============================================================== optimizer
@@ -425,8 +447,10 @@ extern "C" int urso_sqnorm(size_t n, const float* g_d, void* ws_d, size_t ws_byt
     return urso_check_launch("urso_sqnorm");
 }
 
+// guard (the loss-scaled forms): a step whose squared gradient norm is not finite -- an overflow of the scaled backward pass -- changes nothing
 __global__ void sgd_kernel(size_t n, float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v,
-                           const float* __restrict__ hyper, const float* __restrict__ normsq) {
+                           const float* __restrict__ hyper, const float* __restrict__ normsq, int guard) {
+    if (guard && !isfinite(normsq[0])) return;
     const float lr = hyper[0], mom = hyper[1], clip = hyper[2];
     const float norm = sqrtf(normsq[0]);
     const float c = (clip > 0.f && norm >= clip) ? clip / norm : 1.f;
@@ -439,24 +463,38 @@ __global__ void sgd_kernel(size_t n, float* __restrict__ w, const float* __restr
     }
     if (blockIdx.x == 0) for (size_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) { float nv = mom * v[i] - step * g[i]; v[i] = nv; w[i] += nv; }
 }
-extern "C" int urso_sgd_momentum_clip(size_t n, float* w_d, const float* g_d, float* v_d, const float* hyper_d,
-                                      const float* normsq_d, void* stream) {
+static int sgd_momentum_clip_impl(size_t n, float* w_d, const float* g_d, float* v_d, const float* hyper_d,
+                                  const float* normsq_d, int guard, void* stream) {
     if (!w_d || !g_d || !v_d || !hyper_d || !normsq_d) { urso_set_error("urso_sgd_momentum_clip: null argument"); return URSO_EINVAL; }
     if ((((uintptr_t)w_d) | ((uintptr_t)g_d) | ((uintptr_t)v_d)) & 15) { urso_set_error("urso_sgd_momentum_clip: buffers must be 16-byte aligned"); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_OPTIM, 0, (double)n * 20);
     size_t blocks = (n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    URSO_KLAUNCH(sgd_kernel, dim3((int)blocks), dim3(256), 0, st, n, w_d, g_d, v_d, hyper_d, normsq_d);
+    URSO_KLAUNCH(sgd_kernel, dim3((int)blocks), dim3(256), 0, st, n, w_d, g_d, v_d, hyper_d, normsq_d, guard);
     return urso_check_launch("urso_sgd_momentum_clip");
+}
+extern "C" int urso_sgd_momentum_clip(size_t n, float* w_d, const float* g_d, float* v_d, const float* hyper_d,
+                                      const float* normsq_d, void* stream) {
+    return sgd_momentum_clip_impl(n, w_d, g_d, v_d, hyper_d, normsq_d, 0, stream);
+}
+extern "C" int urso_sgd_momentum_clip_ls(size_t n, float* w_d, const float* g_d, float* v_d, const float* hyper_d,
+                                         const float* normsq_d, const float* state_d, void* stream) {
+    // state_d is only checked, never read: the guard is the norm alone (non-finite = skip); the state marks the call as part of a scaled step
+    if (!state_d) { urso_set_error("urso_sgd_momentum_clip_ls: null loss-scale state"); return URSO_EINVAL; }
+    return sgd_momentum_clip_impl(n, w_d, g_d, v_d, hyper_d, normsq_d, 1, stream);
 }
 
 // keras.optimizers.Adam(lr, amsgrad=True, clipnorm) (net.py:982-983; Keras 2.x get_updates): global-norm clip, then
 //   t += 1; lr_t = lr sqrt(1 - b2^t) / (1 - b1^t); m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; vhat = max(vhat, v);
 //   w -= lr_t m / (sqrt(vhat) + eps).       hyper = {lr, b1, b2, eps, clipnorm, t}: t lives on the device so that a
 // captured hipGraph advances it on every replay (adam_tick_kernel runs first, alone, so no block reads a half-written t).
-__global__ void adam_tick_kernel(float* hyper) { if (threadIdx.x == 0 && blockIdx.x == 0) hyper[5] += 1.0f; }
+__global__ void adam_tick_kernel(float* hyper, const float* __restrict__ normsq, int guard) {
+    if (guard && !isfinite(normsq[0])) return;                       // a skipped step does not count
+    if (threadIdx.x == 0 && blockIdx.x == 0) hyper[5] += 1.0f;
+}
 __global__ void adam_kernel(size_t n, float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            float* __restrict__ vhat, const float* __restrict__ hyper, const float* __restrict__ normsq) {
+                            float* __restrict__ vhat, const float* __restrict__ hyper, const float* __restrict__ normsq, int guard) {
+    if (guard && !isfinite(normsq[0])) return;
     const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], clip = hyper[4], t = hyper[5], c1 = hyper[6], c2 = hyper[7];
     const float norm = sqrtf(normsq[0]);
     const float c = (clip > 0.f && norm >= clip) ? clip / norm : 1.f;
@@ -470,15 +508,52 @@ __global__ void adam_kernel(size_t n, float* __restrict__ w, const float* __rest
         w[i] = w[i] - lr_t * mi / (sqrtf(vh) + eps);
     }
 }
-extern "C" int urso_adam_amsgrad_clip(size_t n, float* w_d, const float* g_d, float* m_d, float* v_d, float* vhat_d,
-                                      float* hyper_d, const float* normsq_d, void* stream) {
+static int adam_amsgrad_clip_impl(size_t n, float* w_d, const float* g_d, float* m_d, float* v_d, float* vhat_d,
+                                  float* hyper_d, const float* normsq_d, int guard, void* stream) {
     if (!w_d || !g_d || !m_d || !v_d || !vhat_d || !hyper_d || !normsq_d) { urso_set_error("urso_adam_amsgrad_clip: null argument"); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_OPTIM, 0, (double)n * 36);
-    URSO_KLAUNCH(adam_tick_kernel, dim3(1), dim3(64), 0, st, hyper_d);
+    URSO_KLAUNCH(adam_tick_kernel, dim3(1), dim3(64), 0, st, hyper_d, normsq_d, guard);
     size_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    URSO_KLAUNCH(adam_kernel, dim3((int)blocks), dim3(256), 0, st, n, w_d, g_d, m_d, v_d, vhat_d, (const float*)hyper_d, normsq_d);
+    URSO_KLAUNCH(adam_kernel, dim3((int)blocks), dim3(256), 0, st, n, w_d, g_d, m_d, v_d, vhat_d, (const float*)hyper_d, normsq_d, guard);
     return urso_check_launch("urso_adam_amsgrad_clip");
+}
+extern "C" int urso_adam_amsgrad_clip(size_t n, float* w_d, const float* g_d, float* m_d, float* v_d, float* vhat_d,
+                                      float* hyper_d, const float* normsq_d, void* stream) {
+    return adam_amsgrad_clip_impl(n, w_d, g_d, m_d, v_d, vhat_d, hyper_d, normsq_d, 0, stream);
+}
+extern "C" int urso_adam_amsgrad_clip_ls(size_t n, float* w_d, const float* g_d, float* m_d, float* v_d, float* vhat_d,
+                                         float* hyper_d, const float* normsq_d, const float* state_d, void* stream) {
+    // state_d is only checked, never read (as in urso_sgd_momentum_clip_ls): the guard is the norm alone
+    if (!state_d) { urso_set_error("urso_adam_amsgrad_clip_ls: null loss-scale state"); return URSO_EINVAL; }
+    return adam_amsgrad_clip_impl(n, w_d, g_d, m_d, v_d, vhat_d, hyper_d, normsq_d, 1, stream);
+}
+
+// The loss-scale rule (ursonet_amd/loss_scale.py next_state is its written specification), one thread, after the optimizer of the step:
+// a non-finite norm halves the scale (not below min) and counts a skipped step; growth_interval finite steps in a row double it (not above
+// max).  growth_interval <= 0: a static scale -- skips are recorded, the scale never moves.  Powers of two throughout, so 1 / scale is exact.
+__global__ void loss_scale_update_kernel(float* __restrict__ st, const float* __restrict__ normsq) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float scale = st[URSO_LS_SCALE], good = st[URSO_LS_GOOD_STEPS];
+    const float interval = st[URSO_LS_GROWTH_INTERVAL];
+    const bool dynamic = interval > 0.f;
+    if (!isfinite(normsq[0])) {
+        if (dynamic) scale = fmaxf(scale * 0.5f, st[URSO_LS_MIN]);
+        good = 0.f;
+        st[URSO_LS_SKIPPED_TOTAL] += 1.f; st[URSO_LS_LAST_SKIPPED] = 1.f;
+    } else {
+        good += 1.f;
+        st[URSO_LS_LAST_SKIPPED] = 0.f;
+        if (dynamic && good >= interval) { scale = fminf(2.f * scale, st[URSO_LS_MAX]); good = 0.f; }
+    }
+    st[URSO_LS_SCALE] = scale; st[URSO_LS_INV_SCALE] = 1.f / scale; st[URSO_LS_GOOD_STEPS] = good;
+}
+extern "C" int urso_loss_scale_update(float* state_d, const float* normsq_d, void* stream) {
+    if (!state_d || !normsq_d) { urso_set_error("urso_loss_scale_update: null argument"); return URSO_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(st, URSO_K_OPTIM, 0, 0);
+    URSO_KLAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), 0, st, state_d, normsq_d);
+    return urso_check_launch("urso_loss_scale_update");
 }
 
 __global__ void scale_kernel(size_t n, float* __restrict__ x, float s) {

@@ -225,7 +225,10 @@ __device__ __forceinline__ float block_sum_f(float v, float* sh) {
 __device__ __forceinline__ void finalize_mat_body(int bx, int by, int K, int N, int ldn, int kb, const float* __restrict__ dwr, const float* __restrict__ w,
                                     const float* __restrict__ gamma, const float* __restrict__ var, float eps,
                                     float regc, int trainable, float* __restrict__ gw, float* __restrict__ dotpart, int nsum = 1, size_t pstride = 0,
-                                    float* __restrict__ sqslot = nullptr) {
+                                    float* __restrict__ sqslot = nullptr, const float* __restrict__ ls = nullptr) {
+    // ls != NULL (loss scaling, urso_loss_scale_update): the raw gradient is that of the SCALED loss; it is multiplied by 1 / scale (a power of
+    // two: exact) as soon as it is summed -- in front of the weight-decay term, the BN dots and the squares -- so everything stored is in true units
+    const float unscale = ls ? ls[URSO_LS_INV_SCALE] : 1.f;
     // sqslot != NULL: the block also leaves the sum of squares of the gradient values it stores there (fixed order: a thread's rows, then the
     // threads in lane order) -- the global-norm pass then has nothing to read back (urso_param_batch_run_sq)
     const int kbeg = by * kb, kend = min(K, kbeg + kb);
@@ -265,6 +268,7 @@ __device__ __forceinline__ void finalize_mat_body(int bx, int by, int K, int N, 
                     for (; q < nsum; ++q) t += *(const f32x4_t*)(p + (size_t)q * pstride);
                     d = t;
                 }
+                if (ls) d = d * unscale;
                 return d;
             };
             int k = kbeg + tk;
@@ -309,6 +313,7 @@ __device__ __forceinline__ void finalize_mat_body(int bx, int by, int K, int N, 
         for (int k = kbeg + tk; k < kend; k += 4) {
             float d = 0.f;
             for (int q = 0; q < nsum; ++q) d += dwr[(size_t)q * pstride + (size_t)k * ldn + n];
+            if (ls) d *= unscale;
             const float ww = w[(size_t)k * N + n];
             dot += ww * d;
             const float gv = trainable ? (s * d + regc * ww) : 0.f;
@@ -324,19 +329,21 @@ __device__ __forceinline__ void finalize_mat_body(int bx, int by, int K, int N, 
 
 __global__ void finalize_mat_kernel(int K, int N, int ldn, int kb, const float* __restrict__ dwr, const float* __restrict__ w,
                                     const float* __restrict__ gamma, const float* __restrict__ var, float eps,
-                                    float regc, int trainable, float* __restrict__ gw, float* __restrict__ dotpart, float* __restrict__ sqpart) {
+                                    float regc, int trainable, float* __restrict__ gw, float* __restrict__ dotpart, float* __restrict__ sqpart,
+                                    const float* __restrict__ ls) {
     finalize_mat_body(blockIdx.x, blockIdx.y, K, N, ldn, kb, dwr, w, gamma, var, eps, regc, trainable, gw, dotpart, 1, 0,
-                      sqpart ? sqpart + blockIdx.y * gridDim.x + blockIdx.x : nullptr);
+                      sqpart ? sqpart + blockIdx.y * gridDim.x + blockIdx.x : nullptr, ls);
 }
 
-__global__ void finalize_mat_batch_kernel(const urso_param_desc* __restrict__ descs, const int32_t* __restrict__ blockmap, float* __restrict__ sqpart) {
+__global__ void finalize_mat_batch_kernel(const urso_param_desc* __restrict__ descs, const int32_t* __restrict__ blockmap, float* __restrict__ sqpart,
+                                          const float* __restrict__ ls) {
     const urso_param_desc& d = descs[blockmap[2 * blockIdx.x]];
     const int local = blockmap[2 * blockIdx.x + 1];
     const int gx = ceil_div(d.N, 64);
     const bool fused = urso_fuse_reduce(d.splits);
     finalize_mat_body(local % gx, local / gx, d.K, d.N, d.npad, d.kb, (d.splits == 1 || fused) ? d.part : d.dw_raw, d.w, d.gamma, d.var, d.eps,
                       d.regc, d.trainable, d.gw, d.dotpart, fused ? d.splits : 1, (size_t)d.K * d.npad + URSO_WGRAD_PART_PAD,
-                      sqpart ? sqpart + blockIdx.x : nullptr);
+                      sqpart ? sqpart + blockIdx.x : nullptr, ls);
 }
 
 // pass 2: one thread per channel
@@ -345,11 +352,12 @@ __device__ __forceinline__ void finalize_vec_body(int n, int N, int ks, const fl
                                     const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                     float regb, int trainable, int bn_trainable,
                                     float* __restrict__ gb, float* __restrict__ ggamma, float* __restrict__ gbeta, int nsum = 1, int cstride = 0,
-                                    float* __restrict__ sqslot = nullptr) {
+                                    float* __restrict__ sqslot = nullptr, const float* __restrict__ ls = nullptr) {
     float sq = 0.f;
     if (n < N) {
     float cs = 0.f;
     if (colsum) for (int q = 0; q < nsum; ++q) cs += colsum[(size_t)q * cstride + n];        // nsum > 1: the split partials of the column sums, in split order
+    if (ls) cs *= ls[URSO_LS_INV_SCALE];                      // loss scaling: the column sums unscaled here; dotpart was summed from unscaled rows (finalize_mat_body)
     const float s = bn_scale(gamma, var, eps, n);
     if (gb) { const float v = trainable ? (s * cs + regb * (b ? b[n] : 0.f)) : 0.f; gb[n] = v; sq += v * v; }
     if (ggamma) {
@@ -377,18 +385,20 @@ __global__ void finalize_vec_kernel(int N, int ks, const float* __restrict__ dot
                                     const float* __restrict__ b, const float* __restrict__ gamma,
                                     const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                     float regb, int trainable, int bn_trainable,
-                                    float* __restrict__ gb, float* __restrict__ ggamma, float* __restrict__ gbeta, float* __restrict__ sqpart) {
+                                    float* __restrict__ gb, float* __restrict__ ggamma, float* __restrict__ gbeta, float* __restrict__ sqpart,
+                                    const float* __restrict__ ls) {
     finalize_vec_body(blockIdx.x * blockDim.x + threadIdx.x, N, ks, dotpart, colsum, b, gamma, mean, var, eps, regb, trainable, bn_trainable, gb, ggamma, gbeta,
-                      1, 0, sqpart ? sqpart + blockIdx.x : nullptr);
+                      1, 0, sqpart ? sqpart + blockIdx.x : nullptr, ls);
 }
 
-__global__ void finalize_vec_batch_kernel(const urso_param_desc* __restrict__ descs, const int32_t* __restrict__ blockmap, float* __restrict__ sqpart) {
+__global__ void finalize_vec_batch_kernel(const urso_param_desc* __restrict__ descs, const int32_t* __restrict__ blockmap, float* __restrict__ sqpart,
+                                          const float* __restrict__ ls) {
     const urso_param_desc& d = descs[blockmap[2 * blockIdx.x]];
     const int local = blockmap[2 * blockIdx.x + 1];
     if (!d.gb && !d.ggamma) { if (sqpart && threadIdx.x == 0) sqpart[blockIdx.x] = 0.f; return; }
     const bool fused = urso_fuse_reduce(d.splits);
     finalize_vec_body(local * blockDim.x + threadIdx.x, d.N, d.ks, d.dotpart, (d.splits == 1 || fused) ? d.colpart : d.colsum, d.b, d.gamma, d.mean, d.var, d.eps,
-                      d.regb, d.trainable, d.bn_trainable, d.gb, d.ggamma, d.gbeta, fused ? d.splits : 1, d.npad, sqpart ? sqpart + blockIdx.x : nullptr);
+                      d.regb, d.trainable, d.bn_trainable, d.gb, d.ggamma, d.gbeta, fused ? d.splits : 1, d.npad, sqpart ? sqpart + blockIdx.x : nullptr, ls);
 }
 
 // Row splits of the finalisation: a block (64 columns x kb rows) should stream at least ~128 rows (eight rows per row lane) so that its fixed
@@ -408,14 +418,14 @@ static int param_grad_finalize_impl(int K, int N, int ldn, const float* dw_raw_d
                                         const float* w_d, const float* b_d, const float* gamma_d, const float* mean_d,
                                         const float* var_d, float eps, float weight_decay, int trainable, int bn_trainable,
                                         float* gw_d, float* gb_d, float* ggamma_d, float* gbeta_d,
-                                        float* ws_d, size_t ws_bytes, float* sqpart_d, void* stream);
+                                        float* ws_d, size_t ws_bytes, float* sqpart_d, const float* state_d, void* stream);
 extern "C" int urso_param_grad_finalize(int K, int N, int ldn, const float* dw_raw_d, const float* colsum_d,
                                         const float* w_d, const float* b_d, const float* gamma_d, const float* mean_d,
                                         const float* var_d, float eps, float weight_decay, int trainable, int bn_trainable,
                                         float* gw_d, float* gb_d, float* ggamma_d, float* gbeta_d,
                                         float* ws_d, size_t ws_bytes, void* stream) {
     return param_grad_finalize_impl(K, N, ldn, dw_raw_d, colsum_d, w_d, b_d, gamma_d, mean_d, var_d, eps, weight_decay, trainable, bn_trainable,
-                                    gw_d, gb_d, ggamma_d, gbeta_d, ws_d, ws_bytes, nullptr, stream);
+                                    gw_d, gb_d, ggamma_d, gbeta_d, ws_d, ws_bytes, nullptr, nullptr, stream);
 }
 extern "C" int urso_param_grad_finalize_sq(int K, int N, int ldn, const float* dw_raw_d, const float* colsum_d,
                                            const float* w_d, const float* b_d, const float* gamma_d, const float* mean_d,
@@ -424,13 +434,23 @@ extern "C" int urso_param_grad_finalize_sq(int K, int N, int ldn, const float* d
                                            float* ws_d, size_t ws_bytes, float* sqpart_d, void* stream) {
     if (!sqpart_d) { urso_set_error("urso_param_grad_finalize_sq: sqpart_d required"); return URSO_EINVAL; }
     return param_grad_finalize_impl(K, N, ldn, dw_raw_d, colsum_d, w_d, b_d, gamma_d, mean_d, var_d, eps, weight_decay, trainable, bn_trainable,
-                                    gw_d, gb_d, ggamma_d, gbeta_d, ws_d, ws_bytes, sqpart_d, stream);
+                                    gw_d, gb_d, ggamma_d, gbeta_d, ws_d, ws_bytes, sqpart_d, nullptr, stream);
+}
+// The loss-scaled form (state_d: urso_loss_scale_update's buffer, required; sqpart_d may be NULL = urso_param_grad_finalize's launches)
+extern "C" int urso_param_grad_finalize_ls(int K, int N, int ldn, const float* dw_raw_d, const float* colsum_d,
+                                           const float* w_d, const float* b_d, const float* gamma_d, const float* mean_d,
+                                           const float* var_d, float eps, float weight_decay, int trainable, int bn_trainable,
+                                           float* gw_d, float* gb_d, float* ggamma_d, float* gbeta_d,
+                                           float* ws_d, size_t ws_bytes, float* sqpart_d, const float* state_d, void* stream) {
+    if (!state_d) { urso_set_error("urso_param_grad_finalize_ls: null loss-scale state"); return URSO_EINVAL; }
+    return param_grad_finalize_impl(K, N, ldn, dw_raw_d, colsum_d, w_d, b_d, gamma_d, mean_d, var_d, eps, weight_decay, trainable, bn_trainable,
+                                    gw_d, gb_d, ggamma_d, gbeta_d, ws_d, ws_bytes, sqpart_d, state_d, stream);
 }
 static int param_grad_finalize_impl(int K, int N, int ldn, const float* dw_raw_d, const float* colsum_d,
                                         const float* w_d, const float* b_d, const float* gamma_d, const float* mean_d,
                                         const float* var_d, float eps, float weight_decay, int trainable, int bn_trainable,
                                         float* gw_d, float* gb_d, float* ggamma_d, float* gbeta_d,
-                                        float* ws_d, size_t ws_bytes, float* sqpart_d, void* stream) {
+                                        float* ws_d, size_t ws_bytes, float* sqpart_d, const float* state_d, void* stream) {
     if (!dw_raw_d || !w_d || !gw_d || !ws_d || K <= 0 || N <= 0 || ldn < N) { urso_set_error("urso_param_grad_finalize: bad argument"); return URSO_EINVAL; }
     if ((gb_d || ggamma_d) && !colsum_d) { urso_set_error("urso_param_grad_finalize: colsum required for bias/BN gradients"); return URSO_EINVAL; }
     if (ggamma_d && (!gamma_d || !mean_d || !var_d || !gbeta_d)) { urso_set_error("urso_param_grad_finalize: incomplete BN tensors"); return URSO_EINVAL; }
@@ -439,10 +459,10 @@ static int param_grad_finalize_impl(int K, int N, int ldn, const float* dw_raw_d
     const int ks = finalize_ks(K, N), kb = ceil_div(K, ks);
     const float regc = 2.0f * weight_decay / ((float)K * (float)N), regb = 2.0f * weight_decay / (float)N;
     ProfScope ps(st, URSO_K_FINALIZE, 0, (double)K * N * 12);
-    URSO_KLAUNCH(finalize_mat_kernel, dim3(ceil_div(N, 64), ks), dim3(256), 0, st, K, N, ldn, kb, dw_raw_d, w_d, gamma_d, var_d, eps, regc, trainable, gw_d, ws_d, sqpart_d);
+    URSO_KLAUNCH(finalize_mat_kernel, dim3(ceil_div(N, 64), ks), dim3(256), 0, st, K, N, ldn, kb, dw_raw_d, w_d, gamma_d, var_d, eps, regc, trainable, gw_d, ws_d, sqpart_d, state_d);
     float* sqv = sqpart_d ? sqpart_d + ceil_div(N, 64) * ks : nullptr;
     if (gb_d || ggamma_d)
-        URSO_KLAUNCH(finalize_vec_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, N, ks, (const float*)ws_d, colsum_d, b_d, gamma_d, mean_d, var_d, eps, regb, trainable, bn_trainable, gb_d, ggamma_d, gbeta_d, sqv);
+        URSO_KLAUNCH(finalize_vec_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, N, ks, (const float*)ws_d, colsum_d, b_d, gamma_d, mean_d, var_d, eps, regb, trainable, bn_trainable, gb_d, ggamma_d, gbeta_d, sqv, state_d);
     else if (sqv) hipMemsetAsync(sqv, 0, (size_t)ceil_div(N, 256) * sizeof(float), st);
     return urso_check_launch("urso_param_grad_finalize");
 }
@@ -489,15 +509,24 @@ extern "C" int urso_param_batch_plan(int phase, const urso_param_desc* descs_h, 
     return total;
 }
 
-static int param_batch_run_impl(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, float* sqpart_d, void* stream);
+static int param_batch_run_impl(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, float* sqpart_d,
+                                const float* state_d, void* stream);
 extern "C" int urso_param_batch_run(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, void* stream) {
-    return param_batch_run_impl(phase, dt, descs_d, blockmap_d, nblocks, nullptr, stream);
+    return param_batch_run_impl(phase, dt, descs_d, blockmap_d, nblocks, nullptr, nullptr, stream);
 }
 extern "C" int urso_param_batch_run_sq(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, float* sqpart_d, void* stream) {
     if (!sqpart_d || (phase != URSO_PB_FINALIZE_MAT && phase != URSO_PB_FINALIZE_VEC)) { urso_set_error("urso_param_batch_run_sq: FINALIZE phases only, sqpart_d required"); return URSO_EINVAL; }
-    return param_batch_run_impl(phase, dt, descs_d, blockmap_d, nblocks, sqpart_d, stream);
+    return param_batch_run_impl(phase, dt, descs_d, blockmap_d, nblocks, sqpart_d, nullptr, stream);
 }
-static int param_batch_run_impl(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, float* sqpart_d, void* stream) {
+// The loss-scaled form of both: the FINALIZE phases unscale what they read (finalize_mat_body); sqpart_d may be NULL.  PREP and REDUCE touch no
+// gradient in true units and have no such form: they go through urso_param_batch_run.
+extern "C" int urso_param_batch_run_ls(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, float* sqpart_d,
+                                       const float* state_d, void* stream) {
+    if (!state_d || (phase != URSO_PB_FINALIZE_MAT && phase != URSO_PB_FINALIZE_VEC)) { urso_set_error("urso_param_batch_run_ls: FINALIZE phases only, state_d required"); return URSO_EINVAL; }
+    return param_batch_run_impl(phase, dt, descs_d, blockmap_d, nblocks, sqpart_d, state_d, stream);
+}
+static int param_batch_run_impl(int phase, int dt, const urso_param_desc* descs_d, const int32_t* blockmap_d, int nblocks, float* sqpart_d,
+                                const float* state_d, void* stream) {
     if (!descs_d || !blockmap_d || nblocks < 0) { urso_set_error("urso_param_batch_run: bad argument"); return URSO_EINVAL; }
     if (nblocks == 0) return URSO_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -511,9 +540,9 @@ static int param_batch_run_impl(int phase, int dt, const urso_param_desc* descs_
         break; }
     case URSO_PB_REDUCE: { ProfScope ps(st, URSO_K_FINALIZE, 0, 0); urso_reduce_partials_batch_launch(descs_d, blockmap_d, nblocks, st); break; }
     case URSO_PB_FINALIZE_MAT: { ProfScope ps(st, URSO_K_FINALIZE, 0, 0);
-        URSO_KLAUNCH(finalize_mat_batch_kernel, dim3(nblocks), dim3(256), 0, st, descs_d, blockmap_d, sqpart_d); break; }
+        URSO_KLAUNCH(finalize_mat_batch_kernel, dim3(nblocks), dim3(256), 0, st, descs_d, blockmap_d, sqpart_d, state_d); break; }
     case URSO_PB_FINALIZE_VEC: { ProfScope ps(st, URSO_K_FINALIZE, 0, 0);
-        URSO_KLAUNCH(finalize_vec_batch_kernel, dim3(nblocks), dim3(256), 0, st, descs_d, blockmap_d, sqpart_d); break; }
+        URSO_KLAUNCH(finalize_vec_batch_kernel, dim3(nblocks), dim3(256), 0, st, descs_d, blockmap_d, sqpart_d, state_d); break; }
     default: urso_set_error("urso_param_batch_run: bad phase"); return URSO_EINVAL;
     }
     return urso_check_launch("urso_param_batch_run");

@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, loss_scale
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _PendingLaunches, _round_up
@@ -85,6 +85,7 @@ class Engine(object):
         # state that outlives a re-plan (set_trainable, ursonet_amd/dp.py); halo_ws: its first 4 KiB of flags must stay zero
         self.plan_version, self.halo_ws, self.rel_scale = 0, None, None
         self.hyper = self.flat_v2 = self.flat_vhat = None
+        self.ls_state = self._ls_init = None           # Config.LOSS_SCALE: the device-side loss-scale state (ursonet_amd/loss_scale.py), created once like hyper
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -182,6 +183,19 @@ class Engine(object):
         # writes its raw output and separate stats / apply / backward kernels run (csrc/bn_train.hip).  Inference and
         # TRAIN_BN = False use the moving statistics folded into the filters.
         self.train_bn = training and self.config.TRAIN_BN is None
+        # Config.LOSS_SCALE: None = every launch below is the one it is without the feature.  Set: the losses multiply
+        # their gradients by the scale in front of the rounding to the engine dtype, every finalisation that writes flat_g divides it out again
+        # before weight decay / BN derivation / squared norm, the optimizer skips a step whose norm is not finite and one more launch moves the scale
+        if training:
+            init = loss_scale.initial_state(self.config, self.world_size)
+            if init is None:
+                self.ls_state = self._ls_init = None
+            elif self.ls_state is None:
+                self._ls_init = init
+                self.ls_state = torch.tensor(init, dtype=torch.float32, device=self.device)
+            elif init != self._ls_init:                # the keys changed between plans: the new settings start afresh, in the same buffer
+                self._ls_init = init
+                self.ls_state.copy_(torch.tensor(init, dtype=torch.float32))
         self.acts = {}
         self.prep_ops, self.fwd_ops, self.loss_ops, self.bwd_ops, self.opt_ops = [], [], [], [], []
         self.wino_ws = None
@@ -511,7 +525,7 @@ class Engine(object):
                 ggam, gbet = self.gview(node.bn, "gamma").reshape(-1), self.gview(node.bn, "beta").reshape(-1)
                 self.bwd_ops.append((node.name, lambda c=c, G=G, bn_tr=bn_tr, ggam=ggam, gbet=gbet:
                                      hip.bn_backward(c.Mpix, c.N, dt, G, c.z, c.bmean, c.bvar, c.bn_gamma, BN_EPS, self.bn_ws, c.dbeta, c.dgamma,
-                                                     bn_tr, gbet, ggam, c.dz)))
+                                                     bn_tr, gbet, ggam, c.dz, ls=self.ls_state)))
                 self.labels["bwd"].append("bn_bwd:" + node.name)
                 G = c.dz                               # the conv itself sees the gradient w.r.t. its raw output
                 bn_tr = False                          # gamma/beta gradients are done; the finalisation treats the layer as a plain conv
@@ -564,7 +578,16 @@ class Engine(object):
         gb = self.gview(node.name, "bias").reshape(-1) if node.bias else None
         gg = self.gview(node.bn, "gamma").reshape(-1) if (node.bn and not c.batch_bn) else None
         gbe = self.gview(node.bn, "beta").reshape(-1) if (node.bn and not c.batch_bn) else None
-        if self.fused_sqnorm:
+        if self.ls_state is not None:
+            s0 = s1 = 0
+            if self.fused_sqnorm:
+                s0 = self._sq_slots
+                s1 = self._sq_slots = s0 + hip.param_grad_finalize_sq_slots(147, c.N)
+            self.bwd_ops.append((node.name, lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr, s0=s0, s1=s1:
+                                 hip.param_grad_finalize_ls(147, c.N, c.N, c.dw_unp, c.colsum, c.w, c.b, c.gamma, c.mean, c.var, BN_EPS,
+                                                            float(cfg.WEIGHT_DECAY), tr, bn_tr, gw, gb, gg, gbe, self.fin_ws,
+                                                            self.sqpart[s0:s1] if s1 > s0 else None, self.ls_state)))
+        elif self.fused_sqnorm:
             s0 = self._sq_slots
             s1 = self._sq_slots = s0 + hip.param_grad_finalize_sq_slots(147, c.N)
             self.bwd_ops.append((node.name, lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr, s0=s0, s1=s1:
@@ -829,9 +852,9 @@ class Engine(object):
                 if self.fused_sqnorm and ph in (hip.PB_FINALIZE_MAT, hip.PB_FINALIZE_VEC):
                     s0 = self._sq_slots
                     s1 = self._sq_slots = s0 + nb_
-                    op = (lambda ph=ph, k=k, s0=s0, s1=s1: self.pbatch.run(ph, k, dt, sqpart=self.sqpart[s0:s1]))
+                    op = (lambda ph=ph, k=k, s0=s0, s1=s1: self.pbatch.run(ph, k, dt, sqpart=self.sqpart[s0:s1], ls=self.ls_state))
                 else:
-                    op = (lambda ph=ph, k=k: self.pbatch.run(ph, k, dt))
+                    op = (lambda ph=ph, k=k: self.pbatch.run(ph, k, dt, ls=self.ls_state))
             resolved.append((tag, op)); labels.append(lab)
         self.bwd_ops, self.labels["bwd"] = resolved, labels
         self.sqpart = torch.zeros(max(self._sq_slots, 1), dtype=torch.float32, device=self.device) if self.fused_sqnorm else None
@@ -861,10 +884,13 @@ class Engine(object):
             self.opt_ops.append(lambda: hip.sqnorm(n, self.flat_g, self.sq_ws, self.normsq))
         if self.adam:
             self.opt_ops.append(lambda: hip.adam_amsgrad_clip(n, self.flat_w, self.flat_g, self.flat_v, self.flat_v2, self.flat_vhat,
-                                                              self.hyper, self.normsq))
+                                                              self.hyper, self.normsq, ls=self.ls_state))
         else:
-            self.opt_ops.append(lambda: hip.sgd_momentum_clip(n, self.flat_w, self.flat_g, self.flat_v, self.hyper, self.normsq))
+            self.opt_ops.append(lambda: hip.sgd_momentum_clip(n, self.flat_w, self.flat_g, self.flat_v, self.hyper, self.normsq, ls=self.ls_state))
         self.labels["opt"] += ["sqnorm", "adam" if self.adam else "sgd"]
+        if self.ls_state is not None:                  # after the optimizer: all of its blocks have read the norm and the state
+            self.opt_ops.append(lambda: hip.loss_scale_update(self.ls_state, self.normsq))
+            self.labels["opt"].append("loss_scale")
 
     def _fork_weight_gradients(self):
         """Weight-gradient launches are leaves of the backward pass: nothing reads their partials before the bucket's reduction, every tensor
@@ -892,6 +918,8 @@ class Engine(object):
         # run in processes of their own (tests/workers/fork_worker.py).
         if self._env_wgrad_stream != 2 or self.mode != "training" or self.no_wgrad_fork:       # (no_wgrad_fork: set by ursonet_amd/dp.py)
             return
+        if self.ls_state is not None:
+            return                           # loss scaling: the forked capture is not supported, the step stays on the single chain
         labs = self.labels["bwd"]
         assert len(labs) == len(self.bwd_ops)
         fin = ("reduce", "finalize_mat", "finalize_vec", "finalize", "unpack")
@@ -1072,7 +1100,7 @@ class Engine(object):
                 gzt = torch.empty(a.numel, dtype=self.tdt, device=dev)
                 a.grad, a.grad_written = gzt, True
                 self.loss_ops.append(lambda a=a, gt=gt, w=float(lw.get(wname, 1.)), li=li, gzt=gzt:
-                                     hip.mse(B, 3, 8, gt, a.data, w, dt, self.loss_buf[li:li + 1], gzt))
+                                     hip.mse(B, 3, 8, gt, a.data, w, dt, self.loss_buf[li:li + 1], gzt, ls=self.ls_state))
             return
         if (not cfg.REGRESS_LOC and nloc % 8) or (not cfg.REGRESS_ORI and nori % 8):
             raise ValueError("classification heads need a bin count that is a multiple of 8 (got %d / %d)" % (nloc, nori))
@@ -1092,10 +1120,12 @@ class Engine(object):
                 self.loss_ops.append(lambda: hip.rel_l2_from_norms(B, 3, 8, self.gt_loc, loc.data, wl, self.rel_scale, dt, self.rel_norms,
                                                                    self.loss_buf[0:1], gz_loc))
             else:
-                self.loss_ops.append(lambda: hip.rel_l2(B, 3, 8, self.gt_loc, loc.data, wl, dt, self.loss_buf[0:1], gz_loc, self.rel_norms))
+                self.loss_ops.append(lambda: hip.rel_l2(B, 3, 8, self.gt_loc, loc.data, wl, dt, self.loss_buf[0:1], gz_loc, self.rel_norms,
+                                                        ls=self.ls_state))
         else:
             self.gt_loc = torch.zeros(B, nloc, dtype=torch.float32, device=dev)
-            self.loss_ops.append(lambda: hip.softmax_xent(B, nloc, loc.data, self.gt_loc, wl, 1, dt, self.loss_buf[0:1], gz_loc, self.row_ws))
+            self.loss_ops.append(lambda: hip.softmax_xent(B, nloc, loc.data, self.gt_loc, wl, 1, dt, self.loss_buf[0:1], gz_loc, self.row_ws,
+                                                          ls=self.ls_state))
         # orientation head
         gz_ori = torch.empty(ori.numel, dtype=self.tdt, device=dev)
         ori.grad, ori.grad_written = gz_ori, True
@@ -1105,10 +1135,11 @@ class Engine(object):
             self.gt_ori = torch.zeros(B, d, dtype=torch.float32, device=dev)
             qo = self.q_out if self.quat_head else None
             self.loss_ops.append(lambda: hip.absdot(B, d, 8, 1 if self.quat_head else 0, self.gt_ori, ori.data, wo, dt, qo,
-                                                    self.loss_buf[1:2], gz_ori))
+                                                    self.loss_buf[1:2], gz_ori, ls=self.ls_state))
         else:
             self.gt_ori = torch.zeros(B, nori, dtype=torch.float32, device=dev)
-            self.loss_ops.append(lambda: hip.softmax_xent(B, nori, ori.data, self.gt_ori, wo, 1, dt, self.loss_buf[1:2], gz_ori, self.row_ws))
+            self.loss_ops.append(lambda: hip.softmax_xent(B, nori, ori.data, self.gt_ori, wo, 1, dt, self.loss_buf[1:2], gz_ori, self.row_ws,
+                                                          ls=self.ls_state))
 
     def _plan_compact_gradients(self, need):
         """A block output X whose only consumers are the stride-2 pointwise layers of the next stage's first block (net.py:121-126:
@@ -1720,17 +1751,30 @@ class Engine(object):
         st = [self.flat_w.clone(), self.flat_v.clone(), self.flat_stats.clone()]
         if self.adam:
             st += [self.flat_v2.clone(), self.flat_vhat.clone(), self.hyper.clone()]
+        if self.ls_state is not None:
+            st.append(self.ls_state.clone())
         return st
 
     def restore_train_state(self, st):
         self.flat_w.copy_(st[0]); self.flat_v.copy_(st[1]); self.flat_stats.copy_(st[2])
         if self.adam:
             self.flat_v2.copy_(st[3]); self.flat_vhat.copy_(st[4]); self.hyper.copy_(st[5])
+        if self.ls_state is not None:
+            self.ls_state.copy_(st[-1])
 
     def reset_optimizer(self):
         self.flat_v.zero_()
         if self.adam:
             self.flat_v2.zero_(); self.flat_vhat.zero_(); self.hyper[5] = 0.0
+        if self.ls_state is not None:
+            self.ls_state.copy_(torch.tensor(self._ls_init, dtype=torch.float32))
+
+    def loss_scale(self):
+        """{scale, skipped_total, last_step_skipped, good_steps} of the device-side loss-scale state, read once (one synchronising copy);
+        None when Config.LOSS_SCALE is off."""
+        if self.ls_state is None:
+            return None
+        return loss_scale.as_dict(self.ls_state.detach().cpu().tolist())
 
     def flops(self):
         return conv_flops(self.graph, self.B)

@@ -217,8 +217,23 @@ _SIGS = {
     "urso_conv_pointwise2_ok": (_i, [_i] * 8),
     "urso_conv_pointwise2": (_i, [_i] * 8 + [_vp, _vp, _vp, _vp, _fp, _vp, _vp, _vp, _vp]),
 }
-EXPORTED_SYMBOLS = sorted(_SIGS)
-for _name, (_res, _args) in _SIGS.items():
+EXPORTED_SYMBOLS = sorted(_SIGS)                      # the entry points of include/ursonet_hip.h
+# the loss-scaling extension, include/ursonet_loss_scale.h (ursonet_amd/loss_scale.py): the plain signatures + the state buffer in front of the stream
+_LS_SIGS = {
+    "urso_softmax_xent_fwd_bwd_ls": (_i, [_i, _i, _fp, _fp, _f, _i, _i, _fp, _vp, _fp, _fp, _vp]),
+    "urso_rel_l2_fwd_bwd_ls": (_i, [_i, _i, _i, _fp, _fp, _f, _i, _fp, _vp, _fp, _fp, _vp]),
+    "urso_absdot_fwd_bwd_ls": (_i, [_i, _i, _i, _i, _fp, _fp, _f, _i, _fp, _fp, _vp, _fp, _vp]),
+    "urso_mse_fwd_bwd_ls": (_i, [_i, _i, _i, _fp, _fp, _f, _i, _fp, _vp, _fp, _vp]),
+    "urso_param_batch_run_ls": (_i, [_i, _i, _vp, _vp, _i, _fp, _fp, _vp]),
+    "urso_param_grad_finalize_ls": (_i, [_i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i,
+                                         _fp, _fp, _fp, _fp, _fp, _sz, _fp, _fp, _vp]),
+    "urso_bn_backward_ls": (_i, [_i, _i, _i, _vp, _vp, _fp, _fp, _fp, _f, _vp, _sz, _fp, _fp, _i, _fp, _fp, _vp, _fp, _vp]),
+    "urso_sgd_momentum_clip_ls": (_i, [_sz, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+    "urso_adam_amsgrad_clip_ls": (_i, [_sz, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+    "urso_loss_scale_update": (_i, [_fp, _fp, _vp]),
+}
+LOSS_SCALE_SYMBOLS = sorted(_LS_SIGS)
+for _name, (_res, _args) in list(_SIGS.items()) + list(_LS_SIGS.items()):
     _fn = getattr(_lib, _name)          # AttributeError here == symbol missing from the .so
     _fn.restype = _res
     _fn.argtypes = _args
@@ -452,10 +467,15 @@ class ParamBatch(object):
         self.maps[(phase, key)] = (t, nb)
         return nb
 
-    def run(self, phase, key, dt, stream=None, sqpart=None):
-        """sqpart (fp32, >= the phase's block count; FINALIZE phases): every block also leaves the sum of squares of what it stored there."""
+    def run(self, phase, key, dt, stream=None, sqpart=None, ls=None):
+        """sqpart (fp32, >= the phase's block count; FINALIZE phases): every block also leaves the sum of squares of what it stored there.
+        ls (the loss-scale state; FINALIZE phases): the raw gradients are unscaled as they are read (urso_param_batch_run_ls)."""
         t, nb = self.maps[(phase, key)]
-        if nb and sqpart is not None:
+        if nb and ls is not None and phase in (PB_FINALIZE_MAT, PB_FINALIZE_VEC):
+            assert sqpart is None or (sqpart.dtype == torch.float32 and sqpart.numel() >= nb)
+            _chk(_lib.urso_param_batch_run_ls(phase, dt, ptr(self.dev), ptr(t), nb, ptr(sqpart), _ls_ptr(ls), stream_ptr(stream)),
+                 "urso_param_batch_run_ls")
+        elif nb and sqpart is not None:
             assert sqpart.dtype == torch.float32 and sqpart.numel() >= nb
             _chk(_lib.urso_param_batch_run_sq(phase, dt, ptr(self.dev), ptr(t), nb, ptr(sqpart), stream_ptr(stream)), "urso_param_batch_run_sq")
         elif nb:
@@ -540,7 +560,18 @@ def bn_apply(M, N, dt, z, mean, var, gamma, beta, eps, res, relu, y, stream=None
          "urso_bn_apply")
 
 
-def bn_backward(M, N, dt, g, z, mean, var, gamma, eps, ws, dbeta, dgamma, bn_trainable, gbeta, ggamma, dz, stream=None):
+def _ls_ptr(ls):
+    """Device pointer of a loss-scale state buffer (ursonet_amd/loss_scale.py: FIELDS fp32 values)."""
+    assert ls.dtype == torch.float32 and ls.numel() >= 8
+    return ptr(ls)
+
+
+def bn_backward(M, N, dt, g, z, mean, var, gamma, eps, ws, dbeta, dgamma, bn_trainable, gbeta, ggamma, dz, stream=None, ls=None):
+    if ls is not None:
+        _chk(_lib.urso_bn_backward_ls(M, N, dt, ptr(g), ptr(z), ptr(mean), ptr(var), ptr(gamma), eps, ptr(ws), ws.numel() * ws.element_size(),
+                                      ptr(dbeta), ptr(dgamma), int(bn_trainable), ptr(gbeta), ptr(ggamma), ptr(dz), _ls_ptr(ls), stream_ptr(stream)),
+             "urso_bn_backward_ls")
+        return
     _chk(_lib.urso_bn_backward(M, N, dt, ptr(g), ptr(z), ptr(mean), ptr(var), ptr(gamma), eps, ptr(ws), ws.numel() * ws.element_size(),
                                ptr(dbeta), ptr(dgamma), int(bn_trainable), ptr(gbeta), ptr(ggamma), ptr(dz), stream_ptr(stream)), "urso_bn_backward")
 
@@ -585,6 +616,16 @@ def param_grad_finalize_sq(K, N, ldn, dw_raw, colsum, w, b, gamma, mean, var, ep
                                           stream_ptr(stream)), "urso_param_grad_finalize_sq")
 
 
+def param_grad_finalize_ls(K, N, ldn, dw_raw, colsum, w, b, gamma, mean, var, eps, wd, trainable, bn_trainable,
+                           gw, gb, ggamma, gbeta, ws, sqpart, ls, stream=None):
+    """The loss-scaled per-layer finalisation; sqpart = None: no squared-norm slots (urso_param_grad_finalize's launches)."""
+    assert sqpart is None or (sqpart.dtype == torch.float32 and sqpart.numel() >= param_grad_finalize_sq_slots(K, N))
+    _chk(_lib.urso_param_grad_finalize_ls(K, N, ldn, ptr(dw_raw), ptr(colsum), ptr(w), ptr(b), ptr(gamma), ptr(mean),
+                                          ptr(var), eps, wd, int(trainable), int(bn_trainable), ptr(gw), ptr(gb),
+                                          ptr(ggamma), ptr(gbeta), ptr(ws), ws.numel() * ws.element_size(), ptr(sqpart), _ls_ptr(ls),
+                                          stream_ptr(stream)), "urso_param_grad_finalize_ls")
+
+
 def sqnorm_final(parts, out, stream=None):
     """urso_sqnorm_final: out[0] = sum of parts (the slots the *_sq finalisation launches wrote), in index order."""
     assert parts.dtype == torch.float32 and out.dtype == torch.float32
@@ -606,7 +647,13 @@ def maxpool_bwd(B, H, W, Cc, dt, y, dy, argmax, relu_mask, dx, stream=None):
                                     stream_ptr(stream)), "urso_maxpool3x3s2_bwd")
 
 
-def softmax_xent(B, K, logits, labels, weight, relu_mask, dt, loss, dz, row_ws, stream=None):
+def softmax_xent(B, K, logits, labels, weight, relu_mask, dt, loss, dz, row_ws, stream=None, ls=None):
+    """ls (here and in rel_l2 / absdot / mse): the loss-scale state buffer -- the gradient is multiplied by its scale in front of the
+    rounding to dt (the *_ls entry points); None: the plain entry point."""
+    if ls is not None:
+        _chk(_lib.urso_softmax_xent_fwd_bwd_ls(B, K, ptr(logits), ptr(labels), weight, int(relu_mask), dt, ptr(loss), ptr(dz),
+                                               ptr(row_ws), _ls_ptr(ls), stream_ptr(stream)), "urso_softmax_xent_fwd_bwd_ls")
+        return
     _chk(_lib.urso_softmax_xent_fwd_bwd(B, K, ptr(logits), ptr(labels), weight, int(relu_mask), dt, ptr(loss), ptr(dz),
                                         ptr(row_ws), stream_ptr(stream)), "urso_softmax_xent_fwd_bwd")
 
@@ -620,17 +667,29 @@ def rel_l2_from_norms(B, D, ld, gt, pred, weight, gscale, dt, norms, loss, dpred
                                      stream_ptr(stream)), "urso_rel_l2_from_norms")
 
 
-def rel_l2(B, D, ld, gt, pred, weight, dt, loss, dpred, norms=None, stream=None):
+def rel_l2(B, D, ld, gt, pred, weight, dt, loss, dpred, norms=None, stream=None, ls=None):
+    if ls is not None:
+        _chk(_lib.urso_rel_l2_fwd_bwd_ls(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), ptr(norms), _ls_ptr(ls),
+                                         stream_ptr(stream)), "urso_rel_l2_fwd_bwd_ls")
+        return
     _chk(_lib.urso_rel_l2_fwd_bwd(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), ptr(norms),
                                   stream_ptr(stream)), "urso_rel_l2_fwd_bwd")
 
 
-def absdot(B, D, ld, normalize, gt, x, weight, dt, q, loss, dx, stream=None):
+def absdot(B, D, ld, normalize, gt, x, weight, dt, q, loss, dx, stream=None, ls=None):
+    if ls is not None:
+        _chk(_lib.urso_absdot_fwd_bwd_ls(B, D, ld, int(normalize), ptr(gt), ptr(x), weight, dt, ptr(q), ptr(loss), ptr(dx), _ls_ptr(ls),
+                                         stream_ptr(stream)), "urso_absdot_fwd_bwd_ls")
+        return
     _chk(_lib.urso_absdot_fwd_bwd(B, D, ld, int(normalize), ptr(gt), ptr(x), weight, dt, ptr(q), ptr(loss), ptr(dx),
                                   stream_ptr(stream)), "urso_absdot_fwd_bwd")
 
 
-def mse(B, D, ld, gt, pred, weight, dt, loss, dpred, stream=None):
+def mse(B, D, ld, gt, pred, weight, dt, loss, dpred, stream=None, ls=None):
+    if ls is not None:
+        _chk(_lib.urso_mse_fwd_bwd_ls(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), _ls_ptr(ls), stream_ptr(stream)),
+             "urso_mse_fwd_bwd_ls")
+        return
     _chk(_lib.urso_mse_fwd_bwd(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), stream_ptr(stream)),
          "urso_mse_fwd_bwd")
 
@@ -643,12 +702,26 @@ def sqnorm(n, g, ws, out, stream=None):
     _chk(_lib.urso_sqnorm(n, ptr(g), ptr(ws), ws.numel() * ws.element_size(), ptr(out), stream_ptr(stream)), "urso_sqnorm")
 
 
-def sgd_momentum_clip(n, w, g, v, hyper, normsq, stream=None):
+def sgd_momentum_clip(n, w, g, v, hyper, normsq, stream=None, ls=None):
+    """ls (here and in adam_amsgrad_clip): the loss-scaled form -- a step whose squared norm is not finite changes nothing."""
+    if ls is not None:
+        _chk(_lib.urso_sgd_momentum_clip_ls(n, ptr(w), ptr(g), ptr(v), ptr(hyper), ptr(normsq), _ls_ptr(ls), stream_ptr(stream)),
+             "urso_sgd_momentum_clip_ls")
+        return
     _chk(_lib.urso_sgd_momentum_clip(n, ptr(w), ptr(g), ptr(v), ptr(hyper), ptr(normsq), stream_ptr(stream)),
          "urso_sgd_momentum_clip")
 
 
-def adam_amsgrad_clip(n, w, g, m, v, vhat, hyper, normsq, stream=None):
+def loss_scale_update(state, normsq, stream=None):
+    """urso_loss_scale_update: the rule of ursonet_amd.loss_scale.next_state on the device, after the optimizer of the step."""
+    _chk(_lib.urso_loss_scale_update(_ls_ptr(state), ptr(normsq), stream_ptr(stream)), "urso_loss_scale_update")
+
+
+def adam_amsgrad_clip(n, w, g, m, v, vhat, hyper, normsq, stream=None, ls=None):
+    if ls is not None:
+        _chk(_lib.urso_adam_amsgrad_clip_ls(n, ptr(w), ptr(g), ptr(m), ptr(v), ptr(vhat), ptr(hyper), ptr(normsq), _ls_ptr(ls),
+                                            stream_ptr(stream)), "urso_adam_amsgrad_clip_ls")
+        return
     _chk(_lib.urso_adam_amsgrad_clip(n, ptr(w), ptr(g), ptr(m), ptr(v), ptr(vhat), ptr(hyper), ptr(normsq), stream_ptr(stream)),
          "urso_adam_amsgrad_clip")
 

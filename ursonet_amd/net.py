@@ -207,8 +207,10 @@ class UrsoNet(object):
         self._dp, self._rank, self._world = None, 0, 1
         if build_engine:
             from .engine import Engine
-            from . import dp
+            from . import dp, loss_scale
             world = dp.launcher_world()[2]
+            if mode == "training":
+                loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
             if mode == "training" and world > 1:
                 # under a launcher (`python -m torch.distributed.run --nproc-per-node N pose_estimator.py train ...`): one process per GPU, this
                 # rank's engine takes IMAGES_PER_GPU samples of every global batch of IMAGES_PER_GPU x WORLD_SIZE, the gradient exchange is
@@ -354,6 +356,11 @@ class UrsoNet(object):
         hist = torch.zeros(max(steps, 1), n_loss, dtype=torch.float32, device=eng.device)
         vhist = torch.zeros(max(vsteps, 1), n_loss, dtype=torch.float32, device=eng.device)
         kp = bool(cfg.REGRESS_KEYPOINTS)
+        # Config.LOSS_SCALE: the loss-scale state of every step beside its losses (device-side, read once per epoch)
+        ls_hist = (torch.zeros(max(steps, 1), int(eng.ls_state.numel()), dtype=torch.float32, device=eng.device)
+                   if eng.ls_state is not None else None)
+        if ls_hist is not None:
+            history_full.loss_scale_acc, history_full.skipped_acc = [], []
         clr_it = 0
         for epoch in range(self.epoch, epochs):
             for i in range(steps):
@@ -363,6 +370,8 @@ class UrsoNet(object):
                 train_feed.next_into()
                 runner.step()
                 hist[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
+                if ls_hist is not None:
+                    ls_hist[i].copy_(eng.ls_state, non_blocking=True)
             for i in range(vsteps):
                 val_feed.next_into()
                 eng.evaluate(read=False)
@@ -381,10 +390,17 @@ class UrsoNet(object):
             if vsteps:
                 v = vhist[:vsteps].cpu().numpy().mean(0)
                 val = ({"loc_loss": v[0], "k2_loss": v[2], "k3_loss": v[3]} if kp else {"loc_loss": v[0], "ori_loss": v[1]})
+            ls_text = ""
+            if ls_hist is not None and steps:
+                from . import loss_scale as LS
+                lh = ls_hist[:steps].cpu().numpy()
+                history_full.loss_scale_acc += [float(x) for x in lh[:, LS.SCALE]]
+                history_full.skipped_acc += [bool(x) for x in lh[:, LS.LAST_SKIPPED]]
+                ls_text = "  loss_scale %g  skipped %d" % (float(lh[-1, LS.SCALE]), int(lh[:, LS.LAST_SKIPPED].sum()))
             if chief:
-                log("epoch %d  loc_loss %.5f  %s" % (
+                log("epoch %d  loc_loss %.5f  %s%s" % (
                     epoch + 1, float(np.mean(h[:, 0])) if steps else float("nan"),
-                    "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items()))))
+                    "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items())), ls_text))
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))     # replicas are identical: one writer
             if world > 1:
                 import torch.distributed as dist
