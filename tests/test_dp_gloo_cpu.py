@@ -208,9 +208,11 @@ def _schedule_worker(rank, world, port, out):
     def noop(tag):
         return lambda: log.append(("op", tag))
     eng.prep_ops, eng.fwd_ops, eng.loss_ops = [noop("prep")], [noop("fwd")], [noop("loss")]
-    eng.bwd_ops = [("f", noop("wgrad:f")), (None, noop("dgrad:f")), (("f", "e"), producer("fe", "finalize:f,e")), ("d", producer("d", "wgrad:d")),
-                   (None, noop("dgrad:d")), ("b", noop("wgrad:b")), (("c", "b"), producer("cb", "finalize:c,b")), (None, noop("dgrad:b")),
-                   ("a", producer("a", "wgrad:a")), (None, noop("tail"))]
+    from ursonet_amd.plan_state import _Launch as L
+    eng.bwd_ops = [L(noop("wgrad:f"), "wgrad", done=("f",)), L(noop("dgrad:f"), "dgrad"), L(producer("fe", "finalize:f,e"), "finalize", done=("f", "e")),
+                   L(producer("d", "wgrad:d"), "wgrad", done=("d",)), L(noop("dgrad:d"), "dgrad"), L(noop("wgrad:b"), "wgrad", done=("b",)),
+                   L(producer("cb", "finalize:c,b"), "finalize", done=("c", "b")), L(noop("dgrad:b"), "dgrad"),
+                   L(producer("a", "wgrad:a"), "wgrad", done=("a",)), L(noop("tail"), "tail")]
     seen = {}
 
     def opt():
@@ -281,7 +283,8 @@ def _replan_worker(port, out):
     eng.buckets = plan_buckets(sizes, bucket_bytes=600 * 4)
     eng.convs = {k: _FakeConv(None) for k in "abc"}
     eng.prep_ops, eng.fwd_ops, eng.loss_ops, eng.opt_ops = [], [], [], []
-    eng.bwd_ops = [("c", lambda: None), ("b", lambda: None), ("a", lambda: None)]
+    from ursonet_amd.plan_state import _Launch
+    eng.bwd_ops = [_Launch(lambda: None, "wgrad", done=(k,)) for k in "cba"]
     eng._graphs = None
     eng._build_plan = lambda: None
     live = [[(0, 1000)]]

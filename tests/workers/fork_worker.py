@@ -2,7 +2,8 @@
 script and reads one JSON line.  A forked hipGraph replay has segfaulted inside the ROCm 7.2 runtime in long-lived processes (engine.py); a
 fresh process is where the path is known to work -- and a crash here fails one test instead of taking the suite down.
     python fork_worker.py identity '<make_config kwargs as JSON>'      three replayed steps: single chain / fork / fork rejected -> same bits
-    python fork_worker.py stress                                        240 replays of the cfg2-width plan, chain comparison every 20th"""
+    python fork_worker.py stress                                        240 replays of the cfg2-width plan, chain comparison every 20th
+    python fork_worker.py plan                                          the forked plan's labels and which launches run on the side stream"""
 import json
 import os
 import sys
@@ -82,6 +83,12 @@ def stress():
     return res
 
 
+def plan():
+    sys.path.insert(0, os.path.join(HERE, "..", "golden"))
+    from make_plan_golden import forked_plan_here
+    return forked_plan_here()
+
+
 if __name__ == "__main__":
-    r = identity(json.loads(sys.argv[2])) if sys.argv[1] == "identity" else stress()
+    r = {"identity": lambda: identity(json.loads(sys.argv[2])), "stress": stress, "plan": plan}[sys.argv[1]]()
     print("RESULT " + json.dumps(r), flush=True)

@@ -14,7 +14,7 @@ img, loc, ori, _ = synthetic_batch(cfg, 32, seed=1)
 eng.load_batch(img, loc, ori)
 for _ in range(3): eng.step_eager()
 def prof(single):
-    labels = (eng.labels["prep"] + eng.labels["fwd"] + ["loss"] * (len(eng.loss_pre_ops) + len(eng.loss_ops)) + [l for l in eng.labels["bwd"] if l is not None] + eng.labels["opt"])
+    labels = [l.label for l in eng.prep_ops + eng.fwd_ops + eng.loss_pre_ops + eng.loss_ops + eng.bwd_ops + eng.opt_ops]
     acc = [0.0] * len(labels)
     for _ in range(3):
         torch.cuda.synchronize(); hip.prof_collect(); hip.prof_enable(True)

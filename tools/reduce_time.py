@@ -39,11 +39,11 @@ def layer_bytes(c):
 
 
 buckets = {}
-for (tag, op), lab in zip(eng.bwd_ops, eng.labels["bwd"]):
-    if lab and lab.startswith("reduce:"):
-        names = list(tag)
+for launch in eng.bwd_ops:
+    if launch.kind == "reduce":
+        lab, names = launch.label, list(launch.done)
         by = sum(layer_bytes(eng.convs[n]) for n in names)
-        us = timeit(op)
+        us = timeit(launch)
         print("%-16s %3d layers  %7.1f MB  %7.1f us  %5.2f TB/s" % (lab, len(names), by / 1e6, us, by / us / 1e6))
         buckets[lab] = names
 if a.layers:

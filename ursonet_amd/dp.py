@@ -394,8 +394,8 @@ class DataParallelEngine(object):
                 self.reducer.resid.mul_(live)
         # split the backward op list where each bucket becomes complete
         last_op_of_layer = {}
-        for i, (tag, _) in enumerate(eng.bwd_ops):
-            for name in ((tag,) if isinstance(tag, str) else (tag or ())):       # an op may complete several layers (batched)
+        for i, launch in enumerate(eng.bwd_ops):
+            for name in launch.done:                                             # a launch may complete several layers (batched)
                 last_op_of_layer[name] = i
                 bn = eng.convs[name].bn
                 if bn:
@@ -413,13 +413,12 @@ class DataParallelEngine(object):
         eng = self.eng
         segs, prev = [], 0
         for k, c in enumerate(self.cuts):
-            ops = [op for _, op in eng.bwd_ops[prev:c]]
+            ops = eng.bwd_ops[prev:c]
             if k == 0:
                 ops = ([] if self.rel_exact else eng.prep_ops + eng.fwd_ops + eng.loss_pre_ops) + eng.loss_ops + ops
             segs.append(ops)
             prev = c
-        tail = [op for _, op in eng.bwd_ops[prev:]]
-        return segs, tail + eng.opt_ops
+        return segs, eng.bwd_ops[prev:] + eng.opt_ops
 
     def capture(self):
         eng = self.eng

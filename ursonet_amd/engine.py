@@ -23,7 +23,7 @@ import torch
 from . import hip, loss_scale
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
-from .plan_state import _Act, _Conv, _PendingLaunches, _round_up
+from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
 
 BN_MOMENTUM = 0.99          # Keras BatchNormalization default (net.py:60-76 passes none)
 
@@ -197,13 +197,12 @@ class Engine(object):
                 self._ls_init = init
                 self.ls_state.copy_(torch.tensor(init, dtype=torch.float32))
         self.acts = {}
-        self.prep_ops, self.fwd_ops, self.loss_ops, self.bwd_ops, self.opt_ops = [], [], [], [], []
+        self.prep_ops, self.fwd_ops, self.loss_ops, self.bwd_ops, self.opt_ops = [], [], [], [], []      # lists of _Launch (plan_state.py)
         self.wino_ws = None
         self.n_entry_dgrad2 = 0
         self.n_wgrad_groups = 0
         self._cleared_once = []    # gradient buffers cleared at plan time only (scattered data gradients): (layer, buffer, H, W, C, sy, sx)
         self.loss_pre_ops = []     # DP_EXACT_REL_LOSS: the part of the loss that precedes the cross-rank sum of the two norms
-        self.labels = {"prep": [], "fwd": [], "loss": [], "bwd": [], "opt": []}
         self.convs = OrderedDict()
         self._descs = []                           # hip.ParamDesc of every non-stem weight layer
         self._fused_pools = {}                     # id(pool node) -> the stem conv whose kernel also pools
@@ -233,6 +232,13 @@ class Engine(object):
         self.flat_g.zero_()
         self._fork_weight_gradients()
 
+    @property
+    def labels(self):
+        """{pass: [label of every launch, in launch order]}: for profiles, tools and tests.  The plan itself never reads a label."""
+        return {"prep": [l.label for l in self.prep_ops], "fwd": [l.label for l in self.fwd_ops],
+                "loss": [l.label for l in self.loss_pre_ops + self.loss_ops], "bwd": [l.label for l in self.bwd_ops],
+                "opt": [l.label for l in self.opt_ops]}
+
     def _act(self, spec, numel=None):
         if spec.id not in self.acts:
             self.acts[spec.id] = _Act(self, spec, numel if numel is not None else self.B * spec.h * spec.w * spec.c, self.tdt)
@@ -247,9 +253,8 @@ class Engine(object):
         mp = np.asarray(self.config.MEAN_PIXEL, dtype=np.float32)
         self.mean3 = torch.tensor(mp if mp.size == 3 else np.full(3, float(mp.mean()), dtype=np.float32), device=dev)
         x0 = self._act(self.graph.tensors[0], B * self.H * self.W * 4)     # channels padded 3 -> 4, viewed as pixel pairs
-        self.fwd_ops.append(lambda: hip.mold_images(B, self.H, self.W, self.in_images_u8 if self.input_u8 else self.in_images,
-                                                    self.mean3 if self.input_u8 else None, dt, x0.data))
-        self.labels["fwd"].append("mold")
+        self.fwd_ops.append(_Launch(lambda: hip.mold_images(B, self.H, self.W, self.in_images_u8 if self.input_u8 else self.in_images,
+                                                            self.mean3 if self.input_u8 else None, dt, x0.data), "mold"))
 
     def _plan_pool(self, node):
         if id(node) in self._fused_pools:      # computed by the stem's own kernel (urso_stem_conv_pool): no launch, no conv1 output
@@ -258,8 +263,7 @@ class Engine(object):
         src, dst = self._act(node.src), self._act(node.dst)
         am = torch.empty(dst.numel, dtype=torch.uint8, device=self.device)
         h, w, c = node.src.h, node.src.w, node.src.c
-        self.fwd_ops.append(lambda s=src, d=dst, am=am, h=h, w=w, c=c: hip.maxpool_fwd(B, h, w, c, dt, s.data, d.data, am))
-        self.labels["fwd"].append("maxpool")
+        self.fwd_ops.append(_Launch(lambda s=src, d=dst, am=am, h=h, w=w, c=c: hip.maxpool_fwd(B, h, w, c, dt, s.data, d.data, am), "maxpool"))
         node._am = am
 
     def _plan_conv(self, node):
@@ -328,9 +332,8 @@ class Engine(object):
         # -- weight prep (per step in training; once in inference): the stem has its own packing kernel, every other
         #    layer gets a descriptor and ONE batched launch covers them all (urso_param_batch_run)
         if node.stem:
-            self.prep_ops.append(lambda c=c: hip.stem_weight_pack(c.N, dt, c.w, c.b, c.gamma, c.beta, c.mean, c.var, BN_EPS,
-                                                                  c.wf, c.biasf, c.scale))
-            self.labels["prep"].append("prep:" + node.name)
+            self.prep_ops.append(_Launch(lambda c=c: hip.stem_weight_pack(c.N, dt, c.w, c.b, c.gamma, c.beta, c.mean, c.var, BN_EPS,
+                                                                          c.wf, c.biasf, c.scale), "prep", "prep:" + node.name))
         else:
             d = hip.ParamDesc()
             c.splits = hip.conv_wgrad_splits(c.gf, dt) if training else 1
@@ -358,16 +361,16 @@ class Engine(object):
             # (urso_conv_pointwise_sampled: a second store from the LDS tile that holds the output rows), else by a gather pass
             P = [cc_ for cc_ in self.convs.values() if cc_.dst is X]
             Pc = P[0] if len(P) == 1 else None
-            if (Pc is not None and not Pc.batch_bn and Pc.fwd_index is not None and hip.get_option("pair") and
+            if (Pc is not None and not Pc.batch_bn and Pc.fwd is not None and hip.get_option("pair") and
                     hip.conv_pointwise_sampled_ok(Pc.gf, dt, Pc.fwd_flags | hip.EPI_EMIT_BITS, Pc.res is not None)):
-                self.fwd_ops[Pc.fwd_index] = (lambda Pc=Pc, X=X: hip.conv_pointwise_sampled(
+                Pc.fwd.run = (lambda Pc=Pc, X=X: hip.conv_pointwise_sampled(
                     Pc.gf, dt, Pc.fwd_flags | (hip.EPI_EMIT_BITS if Pc.dst.bits is not None else 0), Pc.xin, Pc.wf, Pc.biasf,
                     Pc.res.data if Pc.res is not None else None, Pc.dst.data, Pc.dst.bits, X.data_compact))
-                self.labels["fwd"][Pc.fwd_index] = "fwd:%s+sampled" % Pc.name
+                Pc.fwd.kind, Pc.fwd.label = "fwd+sampled", "fwd:%s+sampled" % Pc.name
             else:
-                self.fwd_ops.append(lambda X=X, hh=node.src.h, ww=node.src.w, rb=node.cin * 2:
-                                    hip.rows_subsample2(B, hh, ww, rb, X.data, X.data_compact))
-                self.labels["fwd"].append("subsample:T%d" % node.src.id)
+                X.gather = _Launch(lambda X=X, hh=node.src.h, ww=node.src.w, rb=node.cin * 2:
+                                   hip.rows_subsample2(B, hh, ww, rb, X.data, X.data_compact), "subsample", "subsample:T%d" % node.src.id)
+                self.fwd_ops.append(X.gather)
         c.gf = hip.geom(B, node.dst.h, node.dst.w, node.cin, node.dst.h, node.dst.w, c.npad, 1, 1)
         c.xin = X.data_compact
 
@@ -386,15 +389,15 @@ class Engine(object):
         if (c.halo_f or c.halo_d) and self.halo_ws is None:
             self.halo_ws = torch.zeros(hip.conv_igemm_halo_ws_bytes() // 4 + 16, dtype=torch.float32, device=dev)
         if c.batch_bn:
-            self.fwd_ops.append(lambda c=c: hip.conv_igemm_ex(c.gf, dt, 0, c.xin, c.wf, c.biasf, None, None, c.z, None,
-                                                              self.igemm_ws if c.ws_f else None))
-            self.labels["fwd"].append("fwd:" + node.name)
-            self.fwd_ops.append(lambda c=c: hip.bn_batch_stats(c.Mpix, c.N, dt, c.z, self.bn_ws, c.bmean, c.bvar, c.bn_mmean, c.bn_mvar,
-                                                               BN_MOMENTUM, BN_EPS))
-            self.labels["fwd"].append("bn_stats:" + node.name)
-            self.fwd_ops.append(lambda c=c, n=node: hip.bn_apply(c.Mpix, c.N, dt, c.z, c.bmean, c.bvar, c.bn_gamma, c.bn_beta, BN_EPS,
-                                                                 c.res.data if c.res is not None else None, n.relu, c.dst.data))
-            self.labels["fwd"].append("bn_apply:" + node.name)
+            self.fwd_ops += [
+                _Launch(lambda c=c: hip.conv_igemm_ex(c.gf, dt, 0, c.xin, c.wf, c.biasf, None, None, c.z, None, self.igemm_ws if c.ws_f else None),
+                        "fwd", "fwd:" + node.name, fwd=(node.name,)),
+                _Launch(lambda c=c: hip.bn_batch_stats(c.Mpix, c.N, dt, c.z, self.bn_ws, c.bmean, c.bvar, c.bn_mmean, c.bn_mvar, BN_MOMENTUM, BN_EPS),
+                        "bn_stats", "bn_stats:" + node.name),
+                _Launch(lambda c=c, n=node: hip.bn_apply(c.Mpix, c.N, dt, c.z, c.bmean, c.bvar, c.bn_gamma, c.bn_beta, BN_EPS,
+                                                         c.res.data if c.res is not None else None, n.relu, c.dst.data),
+                        "bn_apply", "bn_apply:" + node.name)]
+            return
         elif (self._env_winograd and dt != hip.F32 and not node.stem and not node.dense and node.kh == 3 and node.kw == 3 and
               node.stride == 1 and tuple(node.pad) == (1, 1) and c.res is None and not (flags & ~hip.EPI_RELU) and c.npad == c.N and
               hip.conv_winograd_ws_bytes(c.gf, dt) > 0):
@@ -403,9 +406,8 @@ class Engine(object):
             need_ws = hip.conv_winograd_ws_bytes(c.gf, dt) // 4 + 64
             if self.wino_ws is None or self.wino_ws.numel() < need_ws:
                 self.wino_ws = torch.empty(need_ws, dtype=torch.float32, device=dev)
-            c.fwd_index = len(self.fwd_ops)
-            self.fwd_ops.append(lambda c=c, f=flags: hip.conv_winograd_fwd(c.gf, dt, f, c.xin, c.wf, c.biasf, c.dst.data, self.wino_ws))
-            self.labels["fwd"].append("fwd:" + node.name)
+            c.fwd = _Launch(lambda c=c, f=flags: hip.conv_winograd_fwd(c.gf, dt, f, c.xin, c.wf, c.biasf, c.dst.data, self.wino_ws),
+                            "fwd", "fwd:" + node.name, fwd=(node.name,))
             c.winograd = True
         elif (pool := self._stem_pool_node(self.graph, node, c, dt)) is not None:
             # conv1 + ReLU + the max-pool behind it in one kernel: conv1's output (the largest tensor of the net, read by the pool
@@ -415,16 +417,14 @@ class Engine(object):
             pool._am = torch.empty(pdst.numel, dtype=torch.uint8, device=dev)
             c.dst.data = torch.empty(0, dtype=self.tdt, device=dev)      # (frees the 335 MB; any later read raises: _Act.data)
             c.dst.fused_pool = True
-            c.fwd_index = len(self.fwd_ops)
-            self.fwd_ops.append(lambda c=c, d=pdst, am=pool._am: hip.stem_conv_pool(c.gf, dt, c.xin, c.wf, c.biasf, d.data, am))
-            self.labels["fwd"].append("fwd:%s+maxpool" % node.name)
+            c.fwd = _Launch(lambda c=c, d=pdst, am=pool._am: hip.stem_conv_pool(c.gf, dt, c.xin, c.wf, c.biasf, d.data, am),
+                            "fwd+maxpool", "fwd:%s+maxpool" % node.name, fwd=(node.name,))
         else:
-            c.fwd_index = len(self.fwd_ops)
-            self.fwd_ops.append(lambda c=c, f=flags: hip.conv_igemm_ex(
+            c.fwd = _Launch(lambda c=c, f=flags: hip.conv_igemm_ex(
                 c.gf, dt, f | (hip.EPI_EMIT_BITS if c.dst.bits is not None else 0), c.xin, c.wf, c.biasf,
                 c.res.data if c.res is not None else None, None, c.dst.data, c.dst.bits,
-                self.halo_ws if c.halo_f else (self.igemm_ws if c.ws_f else None)))
-            self.labels["fwd"].append("fwd:" + node.name)
+                self.halo_ws if c.halo_f else (self.igemm_ws if c.ws_f else None)), "fwd", "fwd:" + node.name, fwd=(node.name,))
+        self.fwd_ops.append(c.fwd)
 
     def _plan_forward_workspaces(self):
         """The workspaces the forward launches share (sized for the largest layer) and the batched weight prep."""
@@ -434,8 +434,8 @@ class Engine(object):
         self.igemm_ws = torch.empty(max_igemm_ws // 4 + 16, dtype=torch.float32, device=dev)
         self.bn_ws = torch.empty(max_bn_ws // 8 + 32, dtype=torch.float64, device=dev) if max_bn_ws else None
         if self._descs:
-            self.prep_ops.append(lambda: self.pbatch.run(hip.PB_PREP, "all", self.dt))
-            self.labels["prep"].append("prep:batched[%d layers]" % len(self._descs))
+            self.prep_ops.append(_Launch(lambda: self.pbatch.run(hip.PB_PREP, "all", self.dt), "prep", "prep:batched[%d layers]" % len(self._descs),
+                                         bucket="all"))
         if self.mode != "training":
             self._upload_param_table()
 
@@ -523,10 +523,9 @@ class Engine(object):
             Gsum = G                                   # gradient w.r.t. (BN output + residual): what a residual branch receives
             if c.batch_bn:
                 ggam, gbet = self.gview(node.bn, "gamma").reshape(-1), self.gview(node.bn, "beta").reshape(-1)
-                self.bwd_ops.append((node.name, lambda c=c, G=G, bn_tr=bn_tr, ggam=ggam, gbet=gbet:
-                                     hip.bn_backward(c.Mpix, c.N, dt, G, c.z, c.bmean, c.bvar, c.bn_gamma, BN_EPS, self.bn_ws, c.dbeta, c.dgamma,
-                                                     bn_tr, gbet, ggam, c.dz, ls=self.ls_state)))
-                self.labels["bwd"].append("bn_bwd:" + node.name)
+                self.bwd_ops.append(_Launch(lambda c=c, G=G, bn_tr=bn_tr, ggam=ggam, gbet=gbet:
+                                            hip.bn_backward(c.Mpix, c.N, dt, G, c.z, c.bmean, c.bvar, c.bn_gamma, BN_EPS, self.bn_ws, c.dbeta, c.dgamma,
+                                                            bn_tr, gbet, ggam, c.dz, ls=self.ls_state), "bn_bwd", "bn_bwd:" + node.name, done=(node.name,)))
                 G = c.dz                               # the conv itself sees the gradient w.r.t. its raw output
                 bn_tr = False                          # gamma/beta gradients are done; the finalisation treats the layer as a plain conv
             # -- weight gradient + finalisation (skipped for fully frozen layers; their grads stay zero)
@@ -555,25 +554,24 @@ class Engine(object):
             src.grad_written = True
             return
         gsrc = src.grad_buf()
-        self.bwd_ops.append((None, lambda d=dst, gs=gsrc, am=node._am, h=h, w=w, cc=cc:
-                             hip.maxpool_bwd(B, h, w, cc, dt, d.data, d.grad, am, 1, gs)))
-        self.labels["bwd"].append("maxpool_bwd")
+        self.bwd_ops.append(_Launch(lambda d=dst, gs=gsrc, am=node._am, h=h, w=w, cc=cc:
+                                    hip.maxpool_bwd(B, h, w, cc, dt, d.data, d.grad, am, 1, gs), "maxpool_bwd"))
         src.grad_written = True
 
     def _plan_stem_wgrad(self, c, G, tr, bn_tr):
         node, cfg, dt, dev = c.node, self.config, self.dt, self.device
+        done = (node.name,)
         c.dw_raw = torch.empty(c.K_raw * c.npad, dtype=torch.float32, device=dev)
         c.colsum = torch.empty(c.npad, dtype=torch.float32, device=dev)
         if c.pooled_grad is not None:
-            self.bwd_ops.append((node.name, lambda c=c, pg=c.pooled_grad: hip.stem_wgrad_pooled(c.gf, dt, c.src.data, pg[0].grad, pg[1], self.ws,
-                                                                                                c.dw_raw, c.colsum)))
-            self.labels["bwd"].append("wgrad:%s+maxpool_bwd" % node.name)
+            self.bwd_ops.append(_Launch(lambda c=c, pg=c.pooled_grad: hip.stem_wgrad_pooled(c.gf, dt, c.src.data, pg[0].grad, pg[1], self.ws,
+                                                                                            c.dw_raw, c.colsum),
+                                        "wgrad", "wgrad:%s+maxpool_bwd" % node.name, wgrad=done, done=done))
         else:
-            self.bwd_ops.append((node.name, lambda c=c, G=G: hip.conv_wgrad(c.gf, dt, c.src.data, G, self.ws, c.dw_raw, c.colsum)))
-            self.labels["bwd"].append("wgrad:" + node.name)
+            self.bwd_ops.append(_Launch(lambda c=c, G=G: hip.conv_wgrad(c.gf, dt, c.src.data, G, self.ws, c.dw_raw, c.colsum),
+                                        "wgrad", "wgrad:" + node.name, wgrad=done, done=done))
         c.dw_unp = torch.empty(147 * c.N, dtype=torch.float32, device=dev)
-        self.bwd_ops.append((node.name, lambda c=c: hip.stem_wgrad_unpack(c.N, c.dw_raw, c.dw_unp)))
-        self.labels["bwd"].append("unpack:" + node.name)
+        self.bwd_ops.append(_Launch(lambda c=c: hip.stem_wgrad_unpack(c.N, c.dw_raw, c.dw_unp), "unpack", "unpack:" + node.name, done=done))
         gw = self.gview(node.name, "kernel").reshape(-1)
         gb = self.gview(node.name, "bias").reshape(-1) if node.bias else None
         gg = self.gview(node.bn, "gamma").reshape(-1) if (node.bn and not c.batch_bn) else None
@@ -583,21 +581,21 @@ class Engine(object):
             if self.fused_sqnorm:
                 s0 = self._sq_slots
                 s1 = self._sq_slots = s0 + hip.param_grad_finalize_sq_slots(147, c.N)
-            self.bwd_ops.append((node.name, lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr, s0=s0, s1=s1:
-                                 hip.param_grad_finalize_ls(147, c.N, c.N, c.dw_unp, c.colsum, c.w, c.b, c.gamma, c.mean, c.var, BN_EPS,
-                                                            float(cfg.WEIGHT_DECAY), tr, bn_tr, gw, gb, gg, gbe, self.fin_ws,
-                                                            self.sqpart[s0:s1] if s1 > s0 else None, self.ls_state)))
+            run = (lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr, s0=s0, s1=s1:
+                   hip.param_grad_finalize_ls(147, c.N, c.N, c.dw_unp, c.colsum, c.w, c.b, c.gamma, c.mean, c.var, BN_EPS,
+                                              float(cfg.WEIGHT_DECAY), tr, bn_tr, gw, gb, gg, gbe, self.fin_ws,
+                                              self.sqpart[s0:s1] if s1 > s0 else None, self.ls_state))
         elif self.fused_sqnorm:
             s0 = self._sq_slots
             s1 = self._sq_slots = s0 + hip.param_grad_finalize_sq_slots(147, c.N)
-            self.bwd_ops.append((node.name, lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr, s0=s0, s1=s1:
-                                 hip.param_grad_finalize_sq(147, c.N, c.N, c.dw_unp, c.colsum, c.w, c.b, c.gamma, c.mean, c.var, BN_EPS,
-                                                            float(cfg.WEIGHT_DECAY), tr, bn_tr, gw, gb, gg, gbe, self.fin_ws, self.sqpart[s0:s1])))
+            run = (lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr, s0=s0, s1=s1:
+                   hip.param_grad_finalize_sq(147, c.N, c.N, c.dw_unp, c.colsum, c.w, c.b, c.gamma, c.mean, c.var, BN_EPS,
+                                              float(cfg.WEIGHT_DECAY), tr, bn_tr, gw, gb, gg, gbe, self.fin_ws, self.sqpart[s0:s1]))
         else:
-            self.bwd_ops.append((node.name, lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr:
-                                 hip.param_grad_finalize(147, c.N, c.N, c.dw_unp, c.colsum, c.w, c.b, c.gamma, c.mean, c.var, BN_EPS,
-                                                         float(cfg.WEIGHT_DECAY), tr, bn_tr, gw, gb, gg, gbe, self.fin_ws)))
-        self.labels["bwd"].append("finalize:" + node.name)
+            run = (lambda c=c, gw=gw, gb=gb, gg=gg, gbe=gbe, tr=tr, bn_tr=bn_tr:
+                   hip.param_grad_finalize(147, c.N, c.N, c.dw_unp, c.colsum, c.w, c.b, c.gamma, c.mean, c.var, BN_EPS,
+                                           float(cfg.WEIGHT_DECAY), tr, bn_tr, gw, gb, gg, gbe, self.fin_ws))
+        self.bwd_ops.append(_Launch(run, "finalize", "finalize:" + node.name, done=done))
 
     def _plan_wgrad(self, c, G, tr, bn_tr, q, lvl_n):
         """Weight gradient of a non-stem layer: the split workspace and finalisation fields of its descriptor, and the launch that writes
@@ -647,9 +645,8 @@ class Engine(object):
         if node.name in self._last_of_group:
             q.flush_bucket()                       # the bucket's reduction reads every partial of the bucket
             k = self._last_of_group[node.name]
-            for ph, nm in ((hip.PB_REDUCE, "reduce"), (hip.PB_FINALIZE_MAT, "finalize_mat"), (hip.PB_FINALIZE_VEC, "finalize_vec")):
-                self.bwd_ops.append((tuple(self._bucket_groups[k]), (ph, k)))          # resolved to launches by _resolve_bucket_ops
-                self.labels["bwd"].append("%s:bucket%d" % (nm, k))
+            for kind in self._BUCKET_PHASES:       # (run: filled in by _resolve_bucket_ops)
+                self.bwd_ops.append(_Launch(None, kind, "%s:bucket%d" % (kind, k), done=tuple(self._bucket_groups[k]), bucket=k))
 
     def _plan_residual_handover(self, c, Gsum):
         """Residual branch: its gradient IS Gsum (Add); fold it into the next dgrad (post-ReLU tensors) or alias it."""
@@ -664,8 +661,8 @@ class Engine(object):
             # (the dense form is zero off the even grid in every step and nothing else writes it: cleared once, here; a step rewrites
             # the even pixels only -- urso_rows_scatter2, a quarter of the bytes of the full expansion urso_rows_expand2)
             c.dst.grad_dense = torch.zeros(c.dst.numel, dtype=self.tdt, device=self.device)
-            self.bwd_ops.append((None, lambda X=c.dst: hip.rows_scatter2(B, X.compact[0], X.compact[1], X.spec.c * 2, X.grad, X.grad_dense)))
-            self.labels["bwd"].append("expand:" + node.name)
+            self.bwd_ops.append(_Launch(lambda X=c.dst: hip.rows_scatter2(B, X.compact[0], X.compact[1], X.spec.c * 2, X.grad, X.grad_dense),
+                                        "expand", "expand:" + node.name))
             R.pending = c.dst.grad_dense
         elif R.spec.relu:
             R.pending = Gsum
@@ -686,10 +683,10 @@ class Engine(object):
         if c.solo:
             assert add is None
             dstg = X.grad_buf()
-            self.bwd_ops.append((node.name, lambda c=c, G=G, X=X, dstg=dstg, Ms=B * node.dst.h * node.dst.w:
-                                 hip.conv_dgrad_wgrad_pw(Ms, dt, G, c.wd, X.data, X.spec.relu, dstg, c.wg_ws, c.wg_ws[c.wg_npart:],
-                                                         c.K_raw * c.npad + hip.WGRAD_PART_PAD)))
-            self.labels["bwd"].append("dgrad+wgrad:" + node.name)
+            self.bwd_ops.append(_Launch(lambda c=c, G=G, X=X, dstg=dstg, Ms=B * node.dst.h * node.dst.w:
+                                        hip.conv_dgrad_wgrad_pw(Ms, dt, G, c.wd, X.data, X.spec.relu, dstg, c.wg_ws, c.wg_ws[c.wg_npart:],
+                                                                c.K_raw * c.npad + hip.WGRAD_PART_PAD),
+                                        "dgrad+wgrad", "dgrad+wgrad:" + node.name, dgrad=(node.name,), wgrad=(node.name,), done=(node.name,)))
             X.grad_written = True
             return
         if X.compact is not None:
@@ -705,7 +702,7 @@ class Engine(object):
         mask = (X.bits if X.bits is not None else X.data) if X.spec.relu else None
         mflag = hip.EPI_MASK_BITS if (X.spec.relu and X.bits is not None) else 0
         if lvl_n is not None and mflag == 0 and not c.gd_scatter and self._dense_multi_ok(c):
-            q.add_dense_dgrad(dict(name=node.name, level=lvl_n, src0=G, wgt0=c.wd, K0=c.npad, N=node.cin, M=B, add=add, mask=mask, dst=dstg, flags=0))
+            q.add_dense_dgrad(dict(names=(node.name,), level=lvl_n, src0=G, wgt0=c.wd, K0=c.npad, N=node.cin, M=B, add=add, mask=mask, dst=dstg, flags=0))
             X.grad_written, X.pending = True, None
             return
         if c.gd_scatter:
@@ -713,45 +710,45 @@ class Engine(object):
                 self._clear_scattered_dgrad(c, X, dstg)
             elif add is not dstg:
                 raise AssertionError("scattered dgrad into %s needs an in-place accumulate" % node.name)
-        self.bwd_ops.append((None, lambda c=c, G=G, add=add, mask=mask, dstg=dstg, mflag=mflag:
-                             hip.conv_igemm_ex(c.gd, dt, mflag, G, c.wd, None, add, mask, dstg, None,
-                                               self.halo_ws if (c.halo_d and add is None and not mflag) else (self.igemm_ws if c.ws_d else None))))
-        self.labels["bwd"].append("dgrad:" + node.name)
+        self._emit_dgrad(lambda c=c, G=G, add=add, mask=mask, dstg=dstg, mflag=mflag:
+                         hip.conv_igemm_ex(c.gd, dt, mflag, G, c.wd, None, add, mask, dstg, None,
+                                           self.halo_ws if (c.halo_d and add is None and not mflag) else (self.igemm_ws if c.ws_d else None)), (node.name,))
         X.grad_written, X.pending = True, None
+
+    def _emit_dgrad(self, run, dgrad, wgrad=()):
+        """A data-gradient launch of the layers `dgrad` that also writes the weight-gradient partials of the layers `wgrad` (a tail of dgrad)."""
+        label = "dgrad:" + "+".join(dgrad) + ("+wgrad:" + "+".join(wgrad) if wgrad else "")
+        self.bwd_ops.append(_Launch(run, "dgrad", label, dgrad=dgrad, wgrad=wgrad))
+        return self.bwd_ops[-1]
 
     def _dgrad_compact(self, c, G, X):
         """Stride-2 pointwise consumer of a block output whose gradient is kept compact: a plain pointwise GEMM over the
         sampled pixels (no scatter, no zero fill of a dense tensor), masked with the sampled rows of X's ReLU bit mask."""
         B, dt, node = self.B, self.dt, c.node
         if not X.grad_written and not X.fwd_sampled:          # (a sampled block output wrote the compact mask in its forward pass)
-            self.bwd_ops.append((None, lambda X=X: hip.rows_subsample2(B, X.compact[0], X.compact[1], X.spec.c // 8, X.bits, X.bits_compact)))
-            self.labels["bwd"].append("bits_subsample")
+            self.bwd_ops.append(_Launch(lambda X=X: hip.rows_subsample2(B, X.compact[0], X.compact[1], X.spec.c // 8, X.bits, X.bits_compact),
+                                        "bits_subsample"))
         gq = c.gd_compact
         first = X._compact_first
         if (first is not None and X.grad_written and
                 hip.conv_pointwise2_ok(B, gq.OH, gq.OW, first[1].npad, c.npad, node.cin, dt, hip.EPI_MASK_BITS)):
             # the SECOND stride-2 consumer of X (a stage's first block: the projection shortcut and branch2a, net.py:121-126, 148-157):
             # both data gradients in ONE launch with two reduction segments (urso_conv_pointwise2) -- dL/dX is written once and
-            # rounded once instead of written by the first launch, read back and rewritten by this one.  The first launch becomes
-            # a no-op where it stood (its operands -- the block output's gradient, its filter -- outlive it: every tensor has its
-            # own gradient buffer); the sum runs in the same order (shortcut first).
-            i0, c0, G0 = first
-            self.bwd_ops[i0] = (None, lambda: None)
-            self.labels["bwd"][i0] = None
-            self.bwd_ops.append((None, lambda c=c, c0=c0, G0=G0, G=G, X=X, gq=gq, N=node.cin:
-                                 hip.conv_pointwise2(B, gq.OH, gq.OW, c0.npad, c.npad, N, dt, hip.EPI_MASK_BITS, G0, c0.wd, G, c.wd, None,
-                                                     X.bits_compact, X.grad)))
-            self.labels["bwd"].append("dgrad:%s+%s" % (c0.name, node.name))
+            # rounded once instead of written by the first launch, read back and rewritten by this one.  The first launch leaves
+            # the plan (its operands -- the block output's gradient, its filter -- outlive it: every tensor has its own gradient
+            # buffer); the sum runs in the same order (shortcut first).
+            launch0, c0, G0 = first
+            self.bwd_ops.remove(launch0)
+            self._emit_dgrad(lambda c=c, c0=c0, G0=G0, G=G, X=X, gq=gq, N=node.cin:
+                             hip.conv_pointwise2(B, gq.OH, gq.OW, c0.npad, c.npad, N, dt, hip.EPI_MASK_BITS, G0, c0.wd, G, c.wd, None,
+                                                 X.bits_compact, X.grad), (c0.name, node.name))
             X._compact_first = None
             self.n_entry_dgrad2 += 1
             return
-        if not X.grad_written:
-            X._compact_first = (len(self.bwd_ops), c, G)
-        else:
-            X._compact_first = None                # a third writer: no merge
-        self.bwd_ops.append((None, lambda c=c, G=G, X=X, add=(X.grad if X.grad_written else None):
-                             hip.conv_igemm_ex(c.gd_compact, dt, hip.EPI_MASK_BITS, G, c.wd, None, add, X.bits_compact, X.grad, None, None)))
-        self.labels["bwd"].append("dgrad:" + node.name)
+        launch = self._emit_dgrad(lambda c=c, G=G, X=X, add=(X.grad if X.grad_written else None):
+                                  hip.conv_igemm_ex(c.gd_compact, dt, hip.EPI_MASK_BITS, G, c.wd, None, add, X.bits_compact, X.grad, None, None),
+                                  (node.name,))
+        X._compact_first = (launch, c, G) if not X.grad_written else None       # (None: a third writer, no merge)
         X.grad_written = True
 
     def _dgrad_pair(self, c, A, G, X, add):
@@ -777,21 +774,19 @@ class Engine(object):
                 Sc.src.grad_written = True
                 dstg.zero_()                   # dL/dX never reaches memory in this form: the buffer stays what it is (zeros, not whatever the allocator left)
                 dstg._urso_on_chip = True      # (tests/test_layerwise_gpu.py skips what it cannot read; the shortcut's gradient aliases this buffer)
-                self.bwd_ops.append((None, lambda c=c, A=A, Sc=Sc, G=G, add=add, X=X, dst2=dst2, dxin=dxin:
-                                     hip.conv_pair_wgrad_entry(A.Mpix, dt, G, c.wd, add, X.bits, A.wd, A.src.data, dst2, Sc.wd, Sc.src.data, Sc.src.spec.relu, dxin,
-                                                               A.wg_ws, A.wg_ws[A.wg_npart:], Sc.wg_ws, Sc.wg_ws[Sc.wg_npart:],
-                                                               A.K_raw * A.npad + hip.WGRAD_PART_PAD)))
-                self.labels["bwd"].append("dgrad:%s+%s+%s+wgrad:%s+%s" % (node.name, A.name, Sc.name, A.name, Sc.name))
+                self._emit_dgrad(lambda c=c, A=A, Sc=Sc, G=G, add=add, X=X, dst2=dst2, dxin=dxin:
+                                 hip.conv_pair_wgrad_entry(A.Mpix, dt, G, c.wd, add, X.bits, A.wd, A.src.data, dst2, Sc.wd, Sc.src.data, Sc.src.spec.relu, dxin,
+                                                           A.wg_ws, A.wg_ws[A.wg_npart:], Sc.wg_ws, Sc.wg_ws[Sc.wg_npart:],
+                                                           A.K_raw * A.npad + hip.WGRAD_PART_PAD), (node.name, A.name, Sc.name), (A.name, Sc.name))
             else:
-                self.bwd_ops.append((None, lambda c=c, A=A, G=G, add=add, X=X, dstg=dstg, dst2=dst2, hw=X.pending_hw:
-                                     hip.conv_pair_wgrad(A.Mpix, dt, G, c.wd, add, X.bits, dstg, A.wd, A.src.data, dst2,
-                                                         A.wg_ws, A.wg_ws[A.wg_npart:], A.K_raw * A.npad + hip.WGRAD_PART_PAD, add_hw=hw)))
-                self.labels["bwd"].append("dgrad:%s+%s+wgrad:%s" % (node.name, A.name, A.name))
+                self._emit_dgrad(lambda c=c, A=A, G=G, add=add, X=X, dstg=dstg, dst2=dst2, hw=X.pending_hw:
+                                 hip.conv_pair_wgrad(A.Mpix, dt, G, c.wd, add, X.bits, dstg, A.wd, A.src.data, dst2,
+                                                     A.wg_ws, A.wg_ws[A.wg_npart:], A.K_raw * A.npad + hip.WGRAD_PART_PAD, add_hw=hw),
+                                 (node.name, A.name), (A.name,))
         else:
-            self.bwd_ops.append((None, lambda c=c, A=A, G=G, add=add, X=X, dstg=dstg, dst2=dst2, hw=X.pending_hw:
-                                 hip.conv_pair(A.Mpix, A.node.cin, dt, 1, G, c.wd, None, add, X.bits, dstg, A.wd, None, A.src.data, dst2,
-                                               add_hw=hw)))
-            self.labels["bwd"].append("dgrad:%s+%s" % (node.name, A.name))
+            self._emit_dgrad(lambda c=c, A=A, G=G, add=add, X=X, dstg=dstg, dst2=dst2, hw=X.pending_hw:
+                             hip.conv_pair(A.Mpix, A.node.cin, dt, 1, G, c.wd, None, add, X.bits, dstg, A.wd, None, A.src.data, dst2,
+                                           add_hw=hw), (node.name, A.name))
         X.grad_written, X.pending = True, None
         A.src.grad_written = True
         A.dgrad_done_by_pair = True
@@ -826,8 +821,7 @@ class Engine(object):
                 and not any(n.op == "pool" and n.src.id == X.spec.id for n in g.nodes)
                 and not any(t.id == X.spec.id for t in g.outputs.values()))
         if not once:
-            self.bwd_ops.append((None, lambda t=dstg: hip.zero_fill(t)))
-            self.labels["bwd"].append("zero:" + c.name)
+            self.bwd_ops.append(_Launch(lambda t=dstg: hip.zero_fill(t), "zero", "zero:" + c.name))
         else:
             # URSO_CHECK_CLEARED=1 (debugging; check_cleared_once()): the pixels no step writes must still be zero after any
             # number of steps -- a tool that writes gradient buffers (teacher-forced tests, dumps) would break that silently
@@ -835,28 +829,24 @@ class Engine(object):
             self._cleared_once.append((c.name, dstg, X.spec.h, X.spec.w, X.spec.c, st, st))
 
     # ---------------------------------------------------------------- tail
+    _BUCKET_PHASES = OrderedDict((("reduce", hip.PB_REDUCE), ("finalize_mat", hip.PB_FINALIZE_MAT), ("finalize_vec", hip.PB_FINALIZE_VEC)))
+
     def _resolve_bucket_ops(self):
         """The descriptor table is complete: upload it, plan the block maps and resolve the batched placeholders of the buckets (each
         finalisation block of a fused-norm plan gets a slot of sqpart for the sum of squares of what it stores)."""
         dt = self.dt
         self._upload_param_table()
-        resolved, labels = [], []
-        assert len(self.bwd_ops) == len(self.labels["bwd"])
-        for (tag, op), lab in zip(self.bwd_ops, self.labels["bwd"]):
-            if isinstance(op, tuple):
-                ph, k = op
-                ids = [self.convs[nm].desc_id for nm in self._bucket_groups[k]]
-                nb_ = self.pbatch.plan(ph, k, ids)
-                if nb_ == 0:
-                    continue                                   # nothing to launch (e.g. no split layer in the bucket)
-                if self.fused_sqnorm and ph in (hip.PB_FINALIZE_MAT, hip.PB_FINALIZE_VEC):
-                    s0 = self._sq_slots
-                    s1 = self._sq_slots = s0 + nb_
-                    op = (lambda ph=ph, k=k, s0=s0, s1=s1: self.pbatch.run(ph, k, dt, sqpart=self.sqpart[s0:s1], ls=self.ls_state))
-                else:
-                    op = (lambda ph=ph, k=k: self.pbatch.run(ph, k, dt, ls=self.ls_state))
-            resolved.append((tag, op)); labels.append(lab)
-        self.bwd_ops, self.labels["bwd"] = resolved, labels
+        for launch in [l for l in self.bwd_ops if l.run is None]:
+            ph, k = self._BUCKET_PHASES[launch.kind], launch.bucket
+            nb_ = self.pbatch.plan(ph, k, [self.convs[nm].desc_id for nm in self._bucket_groups[k]])
+            if nb_ == 0:
+                self.bwd_ops.remove(launch)                    # nothing to launch (e.g. no split layer in the bucket)
+            elif self.fused_sqnorm and ph in (hip.PB_FINALIZE_MAT, hip.PB_FINALIZE_VEC):
+                s0 = self._sq_slots
+                s1 = self._sq_slots = s0 + nb_
+                launch.run = (lambda ph=ph, k=k, s0=s0, s1=s1: self.pbatch.run(ph, k, dt, sqpart=self.sqpart[s0:s1], ls=self.ls_state))
+            else:
+                launch.run = (lambda ph=ph, k=k: self.pbatch.run(ph, k, dt, ls=self.ls_state))
         self.sqpart = torch.zeros(max(self._sq_slots, 1), dtype=torch.float32, device=self.device) if self.fused_sqnorm else None
 
     def _plan_optimizer(self):
@@ -879,18 +869,17 @@ class Engine(object):
         self.normsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sq_ws = torch.empty(hip.sqnorm_ws_bytes(n) // 4, dtype=torch.float32, device=dev)
         if self.fused_sqnorm:
-            self.opt_ops.append(lambda: hip.sqnorm_final(self.sqpart, self.normsq))
+            self.opt_ops.append(_Launch(lambda: hip.sqnorm_final(self.sqpart, self.normsq), "sqnorm"))
         else:
-            self.opt_ops.append(lambda: hip.sqnorm(n, self.flat_g, self.sq_ws, self.normsq))
+            self.opt_ops.append(_Launch(lambda: hip.sqnorm(n, self.flat_g, self.sq_ws, self.normsq), "sqnorm"))
         if self.adam:
-            self.opt_ops.append(lambda: hip.adam_amsgrad_clip(n, self.flat_w, self.flat_g, self.flat_v, self.flat_v2, self.flat_vhat,
-                                                              self.hyper, self.normsq, ls=self.ls_state))
+            self.opt_ops.append(_Launch(lambda: hip.adam_amsgrad_clip(n, self.flat_w, self.flat_g, self.flat_v, self.flat_v2, self.flat_vhat,
+                                                                      self.hyper, self.normsq, ls=self.ls_state), "adam"))
         else:
-            self.opt_ops.append(lambda: hip.sgd_momentum_clip(n, self.flat_w, self.flat_g, self.flat_v, self.hyper, self.normsq, ls=self.ls_state))
-        self.labels["opt"] += ["sqnorm", "adam" if self.adam else "sgd"]
+            self.opt_ops.append(_Launch(lambda: hip.sgd_momentum_clip(n, self.flat_w, self.flat_g, self.flat_v, self.hyper, self.normsq,
+                                                                      ls=self.ls_state), "sgd"))
         if self.ls_state is not None:                  # after the optimizer: all of its blocks have read the norm and the state
-            self.opt_ops.append(lambda: hip.loss_scale_update(self.ls_state, self.normsq))
-            self.labels["opt"].append("loss_scale")
+            self.opt_ops.append(_Launch(lambda: hip.loss_scale_update(self.ls_state, self.normsq), "loss_scale"))
 
     def _fork_weight_gradients(self):
         """Weight-gradient launches are leaves of the backward pass: nothing reads their partials before the bucket's reduction, every tensor
@@ -920,8 +909,7 @@ class Engine(object):
             return
         if self.ls_state is not None:
             return                           # loss scaling: the forked capture is not supported, the step stays on the single chain
-        labs = self.labels["bwd"]
-        assert len(labs) == len(self.bwd_ops)
+        ops = self.bwd_ops
         fin = ("reduce", "finalize_mat", "finalize_vec", "finalize", "unpack")
         if any(c.batch_bn for c in self.convs.values()):
             return                           # batch-statistics BN: the chain is HBM-bound passes end to end; measured 17.05 -> 17.42 ms with the fork
@@ -935,50 +923,44 @@ class Engine(object):
             m_out, m_in, k = g.B * g.OH * g.OW, g.B * g.H * g.W, g.KH * g.KW * g.C
             return 2.0 * m_out * k * g.N, (m_in * g.C + m_out * g.N) * es + (es if back else 4.0) * k * g.N
 
-        def names(lab):
-            return [n for part in lab.split("+wgrad:")[0:1] + lab.split("+wgrad:")[1:] for n in part.split(":", 1)[-1].split("+") if n != "maxpool_bwd"]
-
-        def totals(lab, back=False):
+        def totals(l, back=False):          # over the layers of the launch: its data gradients, then its weight gradients
             fl = by = 0.0
-            for n in names(lab):
+            for n in l.dgrad + l.wgrad:
                 f, b = work(n, back)
                 fl += f; by += b
             return fl, by
 
-        def est_ms(lab):                     # what the launch takes at the rates launches of its kind reach here (1.0 PFLOP/s, 4.5 TB/s)
-            fl, by = totals(lab, lab.startswith("dgrad"))
+        def est_ms(l):                       # what the launch takes at the rates launches of its kind reach here (1.0 PFLOP/s, 4.5 TB/s)
+            fl, by = totals(l, bool(l.dgrad))
             return max(fl / 1.0e12, by / 4.5e9)
 
-        def intensity(lab):
-            fl, by = totals(lab)
+        def intensity(l):
+            fl, by = totals(l)
             return fl / by if by else 1e9
 
-        def wg(lab):
-            return lab is not None and lab.startswith(("wgrad:", "wgrad_heads:")) and "dgrad" not in lab
-        at = next((i for i, l in enumerate(labs) if l is not None and re.match(r"dgrad:res[23]", l)), None)
+        def wg(l):
+            return l.kind in ("wgrad", "wgrad_heads")
+        # the deferral point: the first data-gradient launch (plain or fused pair) whose first layer belongs to stage 2 or 3
+        at = next((i for i, l in enumerate(ops) if l.kind == "dgrad" and l.dgrad[0][:4] in ("res2", "res3")), None)
         if at is None:
             return
         EARLY, LATE = 150.0, 400.0           # FLOP per byte (swept 50 ... 300 / 250 ... none: 6.93 ... 6.98 ms, nothing to choose between them)
         # the HBM-bound stretch of the chain behind the deferral point, and as much arithmetic-heavy weight-gradient work as fits beside it (1.2 x
         # its estimate: cfg4, ResNet-101 at batch 16, has more such work than stretch -- 0.4 / 0.8 / 1.2 / 2.0: 8.48 / 8.37 / 8.33 / 8.33 ms, chain 8.49):
         # the LAST such launches in front of the point (the others stay where they are, on the chain)
-        room = 1.2 * sum(est_ms(l) for l in labs[at:] if l is not None and l.startswith(("dgrad:", "wgrad:")) and not (wg(l) and intensity(l) >= LATE))
+        room = 1.2 * sum(est_ms(l) for l in ops[at:] if l.kind in ("dgrad", "wgrad") and not (wg(l) and intensity(l) >= LATE))
         early = []
-        for i in range(at - 1, -1, -1):
-            if wg(labs[i]) and (labs[i].startswith("wgrad_heads:") or intensity(labs[i]) >= EARLY):
-                room -= est_ms(labs[i])
+        for l in reversed(ops[:at]):
+            if wg(l) and (l.kind == "wgrad_heads" or intensity(l) >= EARLY):
+                room -= est_ms(l)
                 if room < 0:
                     break
-                early.append(i)
+                early.append(l)
         early.reverse()
-        if not early or any(labs[i] is not None and labs[i].split(":")[0] in fin for i in range(early[0], at)):
+        if not early or any(l.kind in fin for l in ops[ops.index(early[0]):at]):
             return                           # nothing to defer, or a bucket is finalised inside the region: the chain stays as it is
-        moved = set(early)
-        late = set(i for i in range(at, len(labs)) if wg(labs[i]) and intensity(labs[i]) >= LATE)      # 3x3 layers of >= 128 channels behind the point
-        side_ids = set(id(self.bwd_ops[i]) for i in moved | late)
-        order = [i for i in range(at) if i not in moved] + early + list(range(at, len(labs)))
-        self.bwd_ops = [self.bwd_ops[i] for i in order]
-        self.labels["bwd"] = [labs[i] for i in order]
+        side = early + [l for l in ops[at:] if wg(l) and intensity(l) >= LATE]      # (behind the point: 3x3 layers of >= 128 channels)
+        self.bwd_ops = [l for l in ops[:at] if l not in early] + early + ops[at:]
         self.wgrad_stream = _side_stream(self.device)
         self._side_open = False
         self._main_moved = True
@@ -1009,18 +991,9 @@ class Engine(object):
                 self._main_moved = True
                 return op()
             return run
-        ops = []
-        for item, lab in zip(self.bwd_ops, self.labels["bwd"]):
-            tag, op = item
-            if id(item) in side_ids:
-                op = on_side(op)
-            elif lab is not None and lab.split(":")[0] in fin:
-                op = joined(op)
-            elif callable(op):
-                op = on_main(op)
-            ops.append((tag, op))
-        self.bwd_ops = ops
-        self.opt_ops[0] = joined(self.opt_ops[0])
+        for l in self.bwd_ops:
+            l.run = (on_side if l in side else joined if l.kind in fin else on_main)(l.run)
+        self.opt_ops[0].run = joined(self.opt_ops[0].run)
 
     def _stream_edge(self, src, dst):
         """dst waits for what src holds now.  Stream.wait_stream() records a temporary event and lets Python destroy it right away; while a
@@ -1079,7 +1052,7 @@ class Engine(object):
             self.q_out = torch.zeros(B, 4, dtype=torch.float32, device=dev)
             if self.mode == "inference":
                 x = self.out_ori
-                self.fwd_ops.append(lambda: hip.absdot(B, 4, 8, 1, None, x.data, 1.0, self.dt, self.q_out, None, None))
+                self.fwd_ops.append(_Launch(lambda: hip.absdot(B, 4, 8, 1, None, x.data, 1.0, self.dt, self.q_out, None, None), "quat"))
 
     def _build_losses(self):
         cfg, g, B, dt, dev = self.config, self.graph, self.B, self.dt, self.device
@@ -1099,8 +1072,8 @@ class Engine(object):
                 a = self.acts[g.outputs[key].id]
                 gzt = torch.empty(a.numel, dtype=self.tdt, device=dev)
                 a.grad, a.grad_written = gzt, True
-                self.loss_ops.append(lambda a=a, gt=gt, w=float(lw.get(wname, 1.)), li=li, gzt=gzt:
-                                     hip.mse(B, 3, 8, gt, a.data, w, dt, self.loss_buf[li:li + 1], gzt, ls=self.ls_state))
+                self.loss_ops.append(_Launch(lambda a=a, gt=gt, w=float(lw.get(wname, 1.)), li=li, gzt=gzt:
+                                             hip.mse(B, 3, 8, gt, a.data, w, dt, self.loss_buf[li:li + 1], gzt, ls=self.ls_state), "loss"))
             return
         if (not cfg.REGRESS_LOC and nloc % 8) or (not cfg.REGRESS_ORI and nori % 8):
             raise ValueError("classification heads need a bin count that is a multiple of 8 (got %d / %d)" % (nloc, nori))
@@ -1116,16 +1089,16 @@ class Engine(object):
                 # rel_scale = world size (1 on a single GPU, where the two phases reproduce the one-kernel loss)
                 if self.rel_scale is None:
                     self.rel_scale = torch.ones(1, dtype=torch.float32, device=dev)
-                self.loss_pre_ops.append(lambda: hip.rel_l2_norms(B, 3, 8, self.gt_loc, loc.data, self.rel_norms))
-                self.loss_ops.append(lambda: hip.rel_l2_from_norms(B, 3, 8, self.gt_loc, loc.data, wl, self.rel_scale, dt, self.rel_norms,
-                                                                   self.loss_buf[0:1], gz_loc))
+                self.loss_pre_ops.append(_Launch(lambda: hip.rel_l2_norms(B, 3, 8, self.gt_loc, loc.data, self.rel_norms), "loss"))
+                self.loss_ops.append(_Launch(lambda: hip.rel_l2_from_norms(B, 3, 8, self.gt_loc, loc.data, wl, self.rel_scale, dt, self.rel_norms,
+                                                                           self.loss_buf[0:1], gz_loc), "loss"))
             else:
-                self.loss_ops.append(lambda: hip.rel_l2(B, 3, 8, self.gt_loc, loc.data, wl, dt, self.loss_buf[0:1], gz_loc, self.rel_norms,
-                                                        ls=self.ls_state))
+                self.loss_ops.append(_Launch(lambda: hip.rel_l2(B, 3, 8, self.gt_loc, loc.data, wl, dt, self.loss_buf[0:1], gz_loc, self.rel_norms,
+                                                                ls=self.ls_state), "loss"))
         else:
             self.gt_loc = torch.zeros(B, nloc, dtype=torch.float32, device=dev)
-            self.loss_ops.append(lambda: hip.softmax_xent(B, nloc, loc.data, self.gt_loc, wl, 1, dt, self.loss_buf[0:1], gz_loc, self.row_ws,
-                                                          ls=self.ls_state))
+            self.loss_ops.append(_Launch(lambda: hip.softmax_xent(B, nloc, loc.data, self.gt_loc, wl, 1, dt, self.loss_buf[0:1], gz_loc, self.row_ws,
+                                                                  ls=self.ls_state), "loss"))
         # orientation head
         gz_ori = torch.empty(ori.numel, dtype=self.tdt, device=dev)
         ori.grad, ori.grad_written = gz_ori, True
@@ -1134,12 +1107,12 @@ class Engine(object):
             d = 4 if self.quat_head else 3
             self.gt_ori = torch.zeros(B, d, dtype=torch.float32, device=dev)
             qo = self.q_out if self.quat_head else None
-            self.loss_ops.append(lambda: hip.absdot(B, d, 8, 1 if self.quat_head else 0, self.gt_ori, ori.data, wo, dt, qo,
-                                                    self.loss_buf[1:2], gz_ori, ls=self.ls_state))
+            self.loss_ops.append(_Launch(lambda: hip.absdot(B, d, 8, 1 if self.quat_head else 0, self.gt_ori, ori.data, wo, dt, qo,
+                                                            self.loss_buf[1:2], gz_ori, ls=self.ls_state), "loss"))
         else:
             self.gt_ori = torch.zeros(B, nori, dtype=torch.float32, device=dev)
-            self.loss_ops.append(lambda: hip.softmax_xent(B, nori, ori.data, self.gt_ori, wo, 1, dt, self.loss_buf[1:2], gz_ori, self.row_ws,
-                                                          ls=self.ls_state))
+            self.loss_ops.append(_Launch(lambda: hip.softmax_xent(B, nori, ori.data, self.gt_ori, wo, 1, dt, self.loss_buf[1:2], gz_ori, self.row_ws,
+                                                                  ls=self.ls_state), "loss"))
 
     def _plan_compact_gradients(self, need):
         """A block output X whose only consumers are the stride-2 pointwise layers of the next stage's first block (net.py:121-126:
@@ -1232,7 +1205,7 @@ class Engine(object):
         A = prod[0]
         n = A.node
         training = self.mode == "training"
-        if (n.stem or n.dense or n.kh != 1 or n.kw != 1 or n.stride != 1 or A.batch_bn or A.fwd_index is None or n.cin % 64 or A.npad % 32 or
+        if (n.stem or n.dense or n.kh != 1 or n.kw != 1 or n.stride != 1 or A.batch_bn or A.fwd is None or not A.fwd.computes_only(A, or_sampled_store=True) or n.cin % 64 or A.npad % 32 or
                 A.npad != A.N or X.spec.h % 2 or X.spec.w % 2 or (A.res is not None and A.res.numel != X.numel)):
             return
         if training and (X.compact is None or X.bits is None or X.bits_compact is None):
@@ -1240,18 +1213,14 @@ class Engine(object):
         H, W = X.spec.h, X.spec.w
         gs = hip.geom(B, H, W, n.cin, H // 2, W // 2, A.npad, 1, 1, 2, 2, 0, 0)
         flags = A.fwd_flags | (hip.EPI_ADD_SRCGRID if A.res is not None else 0) | (hip.EPI_EMIT_BITS if training else 0)
-        # (fwd_index goes stale once the pair fusion has dropped launches: the layer's launch is found by its label)
-        idx = [i for i, lab in enumerate(self.labels["fwd"]) if lab in ("fwd:%s" % A.name, "fwd:%s+sampled" % A.name)]
-        if len(idx) != 1:
-            return
-        self.fwd_ops[idx[0]] = (lambda A=A, X=X, gs=gs, flags=flags: hip.conv_igemm_ex(
+        A.fwd.run = (lambda A=A, X=X, gs=gs, flags=flags: hip.conv_igemm_ex(
             gs, dt, flags, A.xin, A.wf, A.biasf, A.res.data if A.res is not None else None, None, X.data_compact,
             X.bits_compact if (flags & hip.EPI_EMIT_BITS) else None))
-        self.labels["fwd"][idx[0]] = "fwd:%s@sampled" % A.name
+        A.fwd.kind, A.fwd.label = "fwd@sampled", "fwd:%s@sampled" % A.name
         self._sample_layer_below(A, X)
-        gather = [i for i, lab in enumerate(self.labels["fwd"]) if lab == "subsample:T%d" % X.spec.id]
-        for i in reversed(gather):                   # the gather pass that filled X.data_compact from the dense tensor (plans without the
-            del self.fwd_ops[i]; del self.labels["fwd"][i]      # register-filter kernel's second store) has nothing to read any more
+        if X.gather is not None:                     # the gather pass that filled X.data_compact from the dense tensor (plans without the
+            self.fwd_ops.remove(X.gather)            # register-filter kernel's second store) has nothing to read any more
+            X.gather = None
         X.fwd_sampled = True
 
     def _sample_layer_below(self, A, X):
@@ -1271,14 +1240,12 @@ class Engine(object):
         n = P.node
         H, W = X.spec.h, X.spec.w
         if (n.stem or n.dense or n.kh != 3 or n.kw != 3 or n.stride != 1 or tuple(n.pad) != (1, 1) or P.batch_bn or P.res is not None or n.cin % 64 or
-                P.npad != P.N or n.src.h != H or n.src.w != W or n.dst.h != H or n.dst.w != W or P.xin is not P.src.data):
-            return
-        idx = [i for i, lab in enumerate(self.labels["fwd"]) if lab == "fwd:%s" % P.name]
-        if len(idx) != 1:
+                P.npad != P.N or n.src.h != H or n.src.w != W or n.dst.h != H or n.dst.w != W or P.xin is not P.src.data or
+                not P.fwd.computes_only(P)):
             return
         gs = hip.geom(self.B, H, W, n.cin, H // 2, W // 2, P.npad, 3, 3, 2, 2, 1, 1, FH=H, FW=W, OSH=2, OSW=2)
-        self.fwd_ops[idx[0]] = (lambda P=P, gs=gs: hip.conv_igemm_ex(gs, self.dt, P.fwd_flags, P.xin, P.wf, P.biasf, None, None, P.dst.data, None, None))
-        self.labels["fwd"][idx[0]] = "fwd:%s@sampled" % P.name
+        P.fwd.run = (lambda P=P, gs=gs: hip.conv_igemm_ex(gs, self.dt, P.fwd_flags, P.xin, P.wf, P.biasf, None, None, P.dst.data, None, None))
+        P.fwd.kind, P.fwd.label = "fwd@sampled", "fwd:%s@sampled" % P.name
         Y.fwd_scattered = True
 
     def _stem_pool_node(self, g, node, c, dt):
@@ -1330,24 +1297,22 @@ class Engine(object):
             return
         lv = self._dense_levels()
         convs = [self.convs[nm] for nm in lv]
-        lab = self.labels["fwd"]
-        pos = [lab.index("fwd:" + c.name) if ("fwd:" + c.name) in lab else -1 for c in convs]
+        pos = [self.fwd_ops.index(c.fwd) if c.fwd is not None and c.fwd.computes_only(c) else -1 for c in convs]
         if (len(convs) < 2 or min(pos) < 0 or sorted(pos) != list(range(min(pos), min(pos) + len(pos))) or
                 not all(self._dense_multi_ok(c) for c in convs)):
             self.dense_multi = False
             return
-        ops, labels = [], []
+        ops = []
         for depth in sorted(set(lv.values())):
             cs = [c for c in convs if lv[c.name] == depth]
             for i in range(0, len(cs), hip.DENSE_MULTI_MAX):
                 part = cs[i:i + hip.DENSE_MULTI_MAX]
                 m = hip.DenseMulti([dict(src0=c.xin, wgt0=c.wf, K0=c.node.cin, N=c.npad, M=self.B, bias=c.biasf, dst=c.dst.data, flags=c.fwd_flags)
                                     for c in part], self.dt)
-                ops.append(lambda m=m: m.run())
-                labels.append("fwd:" + "+".join(c.name for c in part))
-        a, b = min(pos), max(pos) + 1
-        self.fwd_ops[a:b] = ops
-        lab[a:b] = labels
+                ops.append(_Launch(m.run, "fwd", "fwd:" + "+".join(c.name for c in part), fwd=tuple(c.name for c in part)))
+                for c in part:
+                    c.fwd = ops[-1]
+        self.fwd_ops[min(pos):max(pos) + 1] = ops
 
     def _fuse_pointwise_pairs(self):
         """Forward plan rewrite: a block-closing pointwise layer (c -> 4c, + residual, ReLU; c = 64 or 128: stages 2 and 3) directly
@@ -1360,13 +1325,12 @@ class Engine(object):
         if dt == hip.F32 or not hip.get_option("pair"):
             return
         convs = [n for n in g.nodes if n.op != "pool"]
-        drop = []
         for a_node, b_node in zip(convs[:-1], convs[1:]):
             A, Bc = self.convs[a_node.name], self.convs[b_node.name]
 
             def plain(n, c):
                 return (not n.stem and not n.dense and n.kh == 1 and n.kw == 1 and n.stride == 1 and n.relu and not n.out_f32 and
-                        not c.batch_bn and c.npad == c.N and c.fwd_index is not None)
+                        not c.batch_bn and c.npad == c.N and c.fwd is not None)
             if not (plain(a_node, A) and plain(b_node, Bc)):
                 continue
             if a_node.residual is None or b_node.residual is not None or b_node.src.id != a_node.dst.id:
@@ -1384,22 +1348,25 @@ class Engine(object):
             if (len(S) == 1 and hip.get_option("pair") in (1, 2) and a_node.cin == 64 and M % 64 == 0 and len(readers) == 1 and
                     (lambda n, c: not n.stem and not n.dense and n.kh == 1 and n.kw == 1 and n.stride == 1 and not n.relu and not n.out_f32 and
                      n.residual is None and n.cin == 64 and n.cout == a_node.cout and not c.batch_bn and c.npad == c.N and
-                     c.fwd_index is not None)(S[0].node, S[0])):
+                     c.fwd is not None)(S[0].node, S[0])):
                 Sc = S[0]
-                self.fwd_ops[A.fwd_index] = (lambda A=A, Bc=Bc, Sc=Sc: hip.conv_pair_shortcut(
+                A.fwd.run = (lambda A=A, Bc=Bc, Sc=Sc: hip.conv_pair_shortcut(
                     A.Mpix, dt, A.src.data, A.wf, A.biasf, Sc.src.data, Sc.wf, Sc.biasf, A.dst.bits, A.dst.data, Bc.wf, Bc.biasf, Bc.dst.data))
-                self.labels["fwd"][A.fwd_index] = "fwd:%s+%s+%s" % (a_node.name, Sc.name, b_node.name)
-                drop.append(Sc.fwd_index)
+                self._share_forward(A, Sc, Bc)
                 self.shortcut_folded.append(Sc.name)
             else:
-                self.fwd_ops[A.fwd_index] = (lambda A=A, Bc=Bc: hip.conv_pair(A.Mpix, A.node.cin, dt, 0, A.src.data, A.wf, A.biasf, A.res.data, A.dst.bits,
-                                                                             A.dst.data, Bc.wf, Bc.biasf, None, Bc.dst.data))
-                self.labels["fwd"][A.fwd_index] = "fwd:%s+%s" % (a_node.name, b_node.name)
-            drop.append(Bc.fwd_index)
+                A.fwd.run = (lambda A=A, Bc=Bc: hip.conv_pair(A.Mpix, A.node.cin, dt, 0, A.src.data, A.wf, A.biasf, A.res.data, A.dst.bits,
+                                                             A.dst.data, Bc.wf, Bc.biasf, None, Bc.dst.data))
+                self._share_forward(A, Bc)
             self.pair_first[b_node.name] = A
-        for i in sorted(drop, reverse=True):
-            del self.fwd_ops[i]
-            del self.labels["fwd"][i]
+
+    def _share_forward(self, A, *others):
+        """A's forward launch now computes the layers `others` too: their own launches leave the plan, all of them share A's record."""
+        A.fwd.fwd = (A.name,) + tuple(c.name for c in others)
+        A.fwd.label = "fwd:" + "+".join(A.fwd.fwd)
+        for c in others:
+            self.fwd_ops.remove(c.fwd)
+            c.fwd = A.fwd
 
     def _fuse_entry_shortcuts(self):
         """Forward plan rewrite (round 6): the block-closing pointwise layer of a stage's FIRST block (`res{4,5}a_branch2c` + BatchNorm, then
@@ -1414,13 +1381,12 @@ class Engine(object):
         if dt == hip.F32:
             return
         convs = [n for n in g.nodes if n.op != "pool"]
-        lab = self.labels["fwd"]
-        drop = []
+        alone = lambda c: c.fwd is not None and c.fwd.computes_only(c)
         outs = set(t.id for t in g.outputs.values()) | ({g.feat.id} if getattr(g, "feat", None) is not None and hasattr(g.feat, "id") else set())
         for a_node in convs:
             A = self.convs[a_node.name]
             if (a_node.stem or a_node.dense or a_node.kh != 1 or a_node.kw != 1 or a_node.stride != 1 or not a_node.relu or a_node.out_f32 or
-                    a_node.residual is None or A.batch_bn or A.npad != A.N or ("fwd:" + A.name) not in lab or A.dst.fwd_sampled):
+                    a_node.residual is None or A.batch_bn or A.npad != A.N or not alone(A) or A.dst.fwd_sampled):
                 continue
             S = [self.convs[n.name] for n in convs if n.dst.id == a_node.residual.id]
             if len(S) != 1:
@@ -1430,7 +1396,7 @@ class Engine(object):
                        (n.op != "pool" and (n.src.id == a_node.residual.id or (n.residual is not None and n.residual.id == a_node.residual.id)))]
             M = B * a_node.dst.h * a_node.dst.w
             if (len(readers) != 1 or a_node.residual.id in outs or sn.stem or sn.dense or sn.kh != 1 or sn.kw != 1 or sn.relu or sn.out_f32 or
-                    sn.residual is not None or Sc.batch_bn or Sc.npad != Sc.N or Sc.N != A.N or ("fwd:" + Sc.name) not in lab or
+                    sn.residual is not None or Sc.batch_bn or Sc.npad != Sc.N or Sc.N != A.N or not alone(Sc) or
                     sn.dst.h != a_node.dst.h or sn.dst.w != a_node.dst.w or
                     Sc.xin.numel() != M * sn.cin or A.xin.numel() != M * a_node.cin):       # both read dense [M][C] tensors (a strided shortcut reads the compact input)
                 continue
@@ -1438,19 +1404,14 @@ class Engine(object):
             if not (hip.conv_pointwise2_ok(B, a_node.dst.h, a_node.dst.w, a_node.cin, sn.cin, A.N, dt, fl) and
                     (A.N % 32 == 0 and hip.conv_pointwise2_ok(B, a_node.dst.h, a_node.dst.w, a_node.cin, sn.cin, A.N, dt, fl | hip.EPI_EMIT_BITS))):
                 continue
-            iA = lab.index("fwd:" + A.name)
-            self.fwd_ops[iA] = (lambda A=A, Sc=Sc, oh=a_node.dst.h, ow=a_node.dst.w, c0=a_node.cin, c1=sn.cin: hip.conv_pointwise2(
+            A.fwd.run = (lambda A=A, Sc=Sc, oh=a_node.dst.h, ow=a_node.dst.w, c0=a_node.cin, c1=sn.cin: hip.conv_pointwise2(
                 B, oh, ow, c0, c1, A.N, dt, hip.EPI_RELU | (hip.EPI_EMIT_BITS if A.dst.bits is not None else 0),
                 A.xin, A.wf, Sc.xin, Sc.wf, A.biasf, None, A.dst.data, A.dst.bits))
-            lab[iA] = "fwd:%s+%s" % (A.name, Sc.name)
+            self._share_forward(A, Sc)
             A.desc.bias_from = Sc.desc_id + 1
-            drop.append(lab.index("fwd:" + Sc.name))
             self.shortcut_folded.append(Sc.name)
             Sc.dst.data = torch.empty(0, dtype=self.tdt, device=self.device)      # never written any more: a read fails instead of finding stale bytes
             self.n_entry_fwd2 += 1
-        for i in sorted(drop, reverse=True):
-            del self.fwd_ops[i]
-            del lab[i]
 
     # ------------------------------------------------------------------ execution
     def run_prep(self):
@@ -1464,7 +1425,7 @@ class Engine(object):
     def run_backward(self):
         for op in self.loss_pre_ops + self.loss_ops:
             op()
-        for _, op in self.bwd_ops:
+        for op in self.bwd_ops:
             op()
 
     def run_optimizer(self):
@@ -1502,21 +1463,17 @@ class Engine(object):
         self._check_plan_options()
         self.run_prep(); self.run_forward(); self.run_backward(); self.run_optimizer()
 
-    def param_pass_bytes(self, label):
+    def param_pass_bytes(self, launch):
         """Algorithmic bytes of a batched parameter-sized launch, from the descriptor table (the library's launch profiler reports none for
         them: a launch covers many layers).  prep: fp32 filter in, compute-type forward + flipped layouts out; reduce: the split partials of
         the layers with more than FUSE_MAX partials in, their fp32 sum out; finalize_mat: fp32 filter + the partials the launch sums itself
-        (2 ... FUSE_MAX) or the reduced sum in, fp32 gradient out.  None for other labels."""
+        (2 ... FUSE_MAX) or the reduced sum in, fp32 gradient out.  None for other launches."""
         FUSE_MAX = 16                           # the most partials a finalisation sums itself: the library's fused-reduction limit (csrc/common.h)
         es = 4 if self.dt == hip.F32 else 2
-        kind = label.split(":")[0]
-        if kind == "prep" and "batched" in label:
-            ds = list(self._descs)
-        elif kind in ("reduce", "finalize_mat") and "bucket" in label:
-            k = int(label.split("bucket")[1])
-            ds = [self.convs[nm].desc for nm in self._bucket_groups[k]]
-        else:
+        kind = launch.kind
+        if launch.bucket is None or kind not in ("prep", "reduce", "finalize_mat"):
             return None
+        ds = self._descs if kind == "prep" else [self.convs[nm].desc for nm in self._bucket_groups[launch.bucket]]
         total = 0.0
         for d in ds:
             K, N, npad, sp = int(d.K), int(d.N), int(d.npad), max(int(d.splits), 1)
@@ -1532,8 +1489,7 @@ class Engine(object):
     def profile_step(self):
         """One eager training step with the library's HIP-event launch profiler on.
         Returns [(label, kernel_id, ms, flops, bytes, n_kernels, device_symbol)] in launch order."""
-        labels = (self.labels["prep"] + self.labels["fwd"] + ["loss"] * (len(self.loss_pre_ops) + len(self.loss_ops)) +
-                  [l for l in self.labels["bwd"] if l is not None] + self.labels["opt"])
+        launches = self.prep_ops + self.fwd_ops + self.loss_pre_ops + self.loss_ops + self.bwd_ops + self.opt_ops
         torch.cuda.synchronize(self.device)
         hip.prof_collect()
         hip.prof_enable(True)
@@ -1545,14 +1501,14 @@ class Engine(object):
         finally:
             self._single_chain = False
             hip.prof_enable(False)
-        assert len(recs) == len(labels), (len(recs), len(labels))
+        assert len(recs) == len(launches), (len(recs), len(launches))
         out = []
-        for l, r in zip(labels, recs):
+        for l, r in zip(launches, recs):
             if not r[3]:                            # no bytes from the library: the batched parameter-sized passes are priced from the descriptor table
                 by = self.param_pass_bytes(l)
                 if by:
                     r = r[:3] + (by,) + r[4:]
-            out.append((l,) + r)
+            out.append((l.label,) + r)
         return out
 
     def capture(self):

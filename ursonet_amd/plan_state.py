@@ -1,5 +1,5 @@
-"""Records of Engine._build_plan (ursonet_amd/engine.py): the activation tensors and layers of a plan, and the backward-pass launches that
-wait for company until the plan flushes them."""
+"""Records of Engine._build_plan (ursonet_amd/engine.py): the launches, activation tensors and layers of a plan, and the backward-pass
+launches that wait for company until the plan flushes them."""
 import torch
 
 from . import hip
@@ -7,6 +7,33 @@ from . import hip
 
 def _round_up(v, m):
     return (v + m - 1) // m * m
+
+
+class _Launch(object):
+    """One planned launch: an entry of Engine.prep_ops / fwd_ops / loss_pre_ops / loss_ops / bwd_ops / opt_ops, called like the function it
+    wraps.  Everything the planner, the fork (Engine._fork_weight_gradients) and ursonet_amd/dp.py need to know about a launch is a field;
+    `label` is what profiles print and nothing reads it back.  A rewrite of the plan mutates the record or removes it from its list (by
+    identity: records compare by identity), so whoever holds a reference -- _Conv.fwd, _Act.gather -- keeps the right launch.
+      kind    what the launch is: prep | mold | maxpool | fwd | fwd+sampled (and a second store of the sampled pixels) | fwd@sampled (at the
+              sampled pixels only) | fwd+maxpool | bn_stats | bn_apply | subsample | quat | loss | bn_bwd | maxpool_bwd | wgrad | unpack |
+              finalize | reduce | finalize_mat | finalize_vec | expand | dgrad+wgrad | dgrad (with `wgrad` set: a fused backward pair that
+              writes weight-gradient partials too) | dgrad_heads | wgrad_heads | bits_subsample | zero | sqnorm | sgd | adam | loss_scale
+      fwd, dgrad, wgrad   names of the layers whose forward output / data gradient / weight gradient it computes, in label order
+      done    names of the layers whose gradient contribution is complete once it is enqueued (ursonet_amd/dp.py cuts the pass there)
+      bucket  key of the batched parameter-sized passes (hip.ParamBatch): a gradient bucket's index or "all", else None"""
+    __slots__ = ("run", "kind", "label", "fwd", "dgrad", "wgrad", "done", "bucket")
+
+    def __init__(self, run, kind, label=None, fwd=(), dgrad=(), wgrad=(), done=(), bucket=None):
+        self.run, self.kind, self.label = run, kind, label if label is not None else kind
+        self.fwd, self.dgrad, self.wgrad, self.done, self.bucket = fwd, dgrad, wgrad, done, bucket
+
+    def __call__(self):
+        return self.run()
+
+    def computes_only(self, c, or_sampled_store=False):
+        """The launch is layer c's forward pass as first planned: c alone (in no fused launch), at every pixel, with no second store of the
+        sampled pixels (unless or_sampled_store)."""
+        return self.fwd == (c.name,) and (self.kind == "fwd" or (or_sampled_store and self.kind == "fwd+sampled"))
 
 
 class _Act(object):
@@ -25,7 +52,8 @@ class _Act(object):
         self.grad_dense, self.residual_needs_dense = None, False      # dense form of a compact gradient for the residual branch
         self.data_compact = self.bits_compact = None    # the even rows / columns of the tensor and of its bit mask ([B, H/2, W/2, C])
         self.fwd_sampled = False     # only data_compact is computed (_sample_block_output)
-        self._compact_first = None   # (bwd_ops index, conv, dz) of the first compact data gradient into this tensor (_dgrad_compact)
+        self._compact_first = None   # (launch, conv, dz) of the first compact data gradient into this tensor (_dgrad_compact)
+        self.gather = None           # the forward launch that fills data_compact from the dense tensor, if any (_plan_compact_input)
         self.eng = eng
 
     @property
@@ -54,7 +82,7 @@ class _Conv(object):
         self.xin = None                            # the tensor the forward pass and the weight gradient read (gf describes it)
         self.gf = self.gd = self.gf_compact = self.gd_compact = None      # geometries: forward, data gradient, their compact forms
         self.gd_scatter, self.gd_scatter_stride = False, 0                 # gd writes every stride-th pixel of a pre-zeroed buffer
-        self.K_raw, self.fwd_flags, self.fwd_index, self.winograd = 0, 0, None, False    # fwd_index: None for batch-statistics layers
+        self.K_raw, self.fwd_flags, self.fwd, self.winograd = 0, 0, None, False    # fwd: the _Launch that computes dst; None for batch-statistics layers
         self.w = self.b = self.gamma = self.beta = self.mean = self.var = self.wf = self.wd = self.biasf = self.scale = None
         self.batch_bn, self.Mpix = False, None
         self.bn_gamma = self.bn_beta = self.bn_mmean = self.bn_mvar = self.z = self.dz = self.bmean = self.bvar = self.dbeta = self.dgamma = None
@@ -74,7 +102,7 @@ class _PendingLaunches(object):
       dd   data gradients of the Dense heads of one depth (urso_dense_multi);
       dwg  weight gradients of the Dense heads (urso_dense_wgrad_multi): leaves of the backward pass, so all of them wait for one
            launch behind the last Dense data gradient (or the end of their gradient bucket).
-    wg / hw hold (conv, name, input, dz, weight-gradient geometry); dd / dwg hold the layer dicts of hip.DenseMulti / DenseWgradMulti."""
+    wg / hw hold (conv, name, input, dz, weight-gradient geometry); dd / dwg hold the layer dicts of hip.DenseMulti / DenseWgradMulti (+ "names" / "name": the layers of the entry)."""
 
     WGRAD_GROUP_FILL = 0.7      # a layer that would drop a shared launch's fill of the resident block slots below this starts a new group
 
@@ -83,13 +111,15 @@ class _PendingLaunches(object):
         self.wg_max = wg_max    # most layers in one grouped weight-gradient launch (<= 1: no grouping, no pairing)
         self.wg, self.hw, self.dd, self.dwg = [], [], [], []
 
-    def _emit(self, tag, op, label):
-        self.eng.bwd_ops.append((tag, op))
-        self.eng.labels["bwd"].append(label)
+    def _emit(self, run, kind, names):
+        """The weight gradients of the layers `names` in one launch (kind dgrad_heads: their data gradients, which complete no layer)."""
+        dgrad = kind == "dgrad_heads"
+        self.eng.bwd_ops.append(_Launch(run, kind, "%s:%s" % (kind, "+".join(names)), dgrad=names if dgrad else (),
+                                        wgrad=() if dgrad else names, done=() if dgrad else names))
 
     def emit_wgrad(self, c, name, xw, G, gf_w):
         dt = self.dt
-        self._emit(name, lambda: hip.conv_wgrad_partial(gf_w, dt, xw, G, c.wg_ws), "wgrad:" + name)
+        self._emit(lambda: hip.conv_wgrad_partial(gf_w, dt, xw, G, c.wg_ws), "wgrad", (name,))
 
     def at_node(self, level):
         """Before the backward plan of a node of Dense depth `level` (None: not a Dense head layer)."""
@@ -116,7 +146,7 @@ class _PendingLaunches(object):
     def add_dense_dgrad(self, L):
         prev = [P for P in self.dd if P["dst"] is L["dst"]]
         if prev and L["add"] is L["dst"] and prev[-1].get("src1") is None:
-            prev[-1].update(src1=L["src0"], wgt1=L["wgt0"], K1=L["K0"], name=prev[-1]["name"] + "+" + L["name"])
+            prev[-1].update(src1=L["src0"], wgt1=L["wgt0"], K1=L["K0"], names=prev[-1]["names"] + L["names"])
             return
         if prev:
             self.flush_dense_dgrads()           # a third writer of the same tensor: accumulate behind the launch that holds the first two
@@ -152,7 +182,7 @@ class _PendingLaunches(object):
             c.desc.part, c.desc.colpart = c.wg_ws.data_ptr(), c.wg_ws.data_ptr() + 4 * c.wg_npart
         (c0, n0, x0, G0, g0), (c1, n1, x1, G1, g1) = items
         dt = self.dt
-        self._emit((n0, n1), lambda: hip.conv_wgrad_partial2(g0, g1, dt, x0, G0, c0.wg_ws, x1, G1, c1.wg_ws), "wgrad:%s+%s" % (n0, n1))
+        self._emit(lambda: hip.conv_wgrad_partial2(g0, g1, dt, x0, G0, c0.wg_ws, x1, G1, c1.wg_ws), "wgrad", (n0, n1))
         self.eng.n_wgrad_groups += 1
 
     def flush_wgrads(self):
@@ -182,18 +212,17 @@ class _PendingLaunches(object):
                 c.wg_npart = s * (c.K_raw * c.npad + hip.WGRAD_PART_PAD)
                 c.desc.part, c.desc.colpart = c.wg_ws.data_ptr(), c.wg_ws.data_ptr() + 4 * c.wg_npart
             grp.bind([t[2] for t in take], [t[3] for t in take], [t[0].wg_ws for t in take], dev)
-            names = tuple(t[1] for t in take)
-            self._emit(names, lambda grp=grp: grp.run(), "wgrad:" + "+".join(names))
+            self._emit(grp.run, "wgrad", tuple(t[1] for t in take))
             self.eng.n_wgrad_groups += 1
 
     def flush_dense_dgrads(self):
         layers, self.dd = self.dd, []
         for i in range(0, len(layers), hip.DENSE_MULTI_MAX):
             part = layers[i:i + hip.DENSE_MULTI_MAX]
-            self._emit(None, hip.DenseMulti(part, self.dt).run, "dgrad_heads:" + "+".join(L["name"] for L in part))
+            self._emit(hip.DenseMulti(part, self.dt).run, "dgrad_heads", tuple(n for L in part for n in L["names"]))
 
     def flush_dense_wgrads(self):
         layers, self.dwg = self.dwg, []
         for i in range(0, len(layers), hip.DENSE_MULTI_MAX):
             part = layers[i:i + hip.DENSE_MULTI_MAX]
-            self._emit(tuple(L["name"] for L in part), hip.DenseWgradMulti(part, self.dt).run, "wgrad_heads:" + "+".join(L["name"] for L in part))
+            self._emit(hip.DenseWgradMulti(part, self.dt).run, "wgrad_heads", tuple(L["name"] for L in part))
