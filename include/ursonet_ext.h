@@ -1,0 +1,90 @@
+/* ursonet_ext.h -- the C ABI of liburso_ext.so, the extension library next to liburso_hip.so (gfx950).  Plain C99.
+ *
+ * liburso_hip.so's surface is frozen at the entry points of ursonet_hip.h; what is added after that lives here, in a library of its
+ * own.  The extension reuses the main library's status codes, its error text (a failure here is read with urso_last_error()) and its
+ * launch profiler, so liburso_hip.so must be loaded first with its symbols visible to later loads: link both and name liburso_hip.so
+ * in front, or dlopen it with RTLD_GLOBAL before this one (ursonet_amd/hip.py does the latter on first use).  Every entry point
+ * returns URSO_OK or a negative URSO_E* code of ursonet_hip.h.
+ */
+#ifndef URSONET_EXT_H
+#define URSONET_EXT_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include "ursonet_hip.h"     /* URSO_OK / URSO_E*, and the URSO_EVAL_* columns the table below shares */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/*
+ * Test-time view fusion (ursonet_amd/views.py): the network saw V rotated views of every image of a batch (view v
+ * = the frame re-rendered through a camera rotated by R_v, as utils.rotate_cam does, utils.py:30-86) and urso_pose_decode /
+ * urso_pose_eval wrote one estimate per view and image.  This entry point rotates every estimate back into the unrotated camera and
+ * fuses the V estimates of an image into one pose plus how well the views agree.  One launch per batch, one wave per valid image
+ * b < n writes row row0 + b of the fp64 table [rows][URSO_FUSE_COLS]; rows past n are not touched.  No workspace, no allocation, no host
+ * synchronisation; n = 0 launches nothing.  All arithmetic is fp64, compiled without contraction.
+ *
+ * Inputs (device pointers):
+ *   est     fp64: the row of view v and batch row b is at est + (v * est_view_rows + b) * est_ld, with LOC_EST in columns 0..2 and
+ *           Q_EST ([x, y, z, w]) in columns 3..6 -- where urso_pose_decode and urso_pose_eval both write them.  est_ld >= 7,
+ *           est_view_rows >= B.
+ *   r       fp64 [V][9]: the view rotations R_v, row-major.    qr  fp64 [V][4]: SO32quat(R_v) (se3lib.py:77-115).
+ *   loc_gt  fp64 [B][3], q_gt fp64 [B][4]: the truth, optional; both or neither.
+ *   1 <= V <= URSO_FUSE_MAX_VIEWS.
+ *
+ * De-rotation, the inverse of the pose update t' = t R^T, q' = quat_mult(SO32quat(R), q) of utils.py:53-56:
+ *   t^_v[j] = sum_i t_v[i] R_v[i][j]                                        (t_v R_v)
+ *   q^_v    = quat_mult(conj(qr_v), q_v) / |.|   with conj(q) = [-x, -y, -z, w] and se3lib.quat_mult's formula (se3lib.py:164-179):
+ *             quat_mult(a, b) = [ aw bx + az by - ay bz + ax bw,  -az bx + aw by + ax bz + ay bw,
+ *                                 ay bx - ax by + aw bz + az bw,  -ax bx - ay by - az bz + aw bw ]
+ *   A view whose r is exactly the identity matrix is passed through with no arithmetic: t^ = t, q^ = q.
+ *
+ * Fusion (every sum runs over v = 0 .. V - 1 in that order, in one accumulator: the result is a function of the inputs alone):
+ *   LOC_EST = (1/V) sum_v t^_v
+ *   S       = (1/V) sum_v q^_v q^_v^T
+ *   Q_EST   = unit eigenvector of S's largest eigenvalue by the decode's solver (cyclic Jacobi), largest-magnitude component
+ *             positive: q and -q inputs fuse identically, bit for bit.
+ *   V == 1:   LOC_EST = t^_0 and Q_EST = q^_0 with no division and no eigen-solve, so one identity view reproduces the input bits.
+ *
+ * Agreement columns:
+ *   LOC_SPREAD  = sqrt((1/V) sum_v ||t^_v - LOC_EST||^2)
+ *   ORI_SPREAD  = sqrt((1/V) sum_v angle(q^_v, Q_EST)^2) * 180/pi, angle = the rotation angle 2 acos|a . b| between two orientations,
+ *                 evaluated as 4 atan2(|a |b| - s b |a||, |a |b| + s b |a||), s = sign(a . b): the same angle, but accurate near 0,
+ *                 where acos turns one ulp of the dot product into 1.7e-6 degrees.  Views that agree exactly give exactly 0.
+ *   VIEW_LAMBDA = Q_EST^T S Q_EST: 1 when all views agree, 1/4 when they are spread uniformly.
+ *   N_VIEWS     = V
+ *   V == 1: both spreads are 0.
+ *
+ * With a truth, by urso_pose_eval's formulas and its clip convention (the same device routine, so the same bits for the same
+ * estimate): LOC_ERR = ||LOC_EST - loc_gt||, ORI_ERR = 2 acos(min(1, |Q_EST . q_gt|)) * 180/pi, ESA = LOC_ERR / ||loc_gt|| +
+ * 2 acos(min(1, |Q_EST . q_gt|)), DIST = loc_gt[2].  Without one the four are NaN.
+ *
+ * Columns 0..10 sit at URSO_EVAL_*'s positions; column 15 is 0.  A NaN input gives NaN in everything it feeds: no view is dropped.
+ *
+ * Bad arguments return URSO_EINVAL before any launch: a null struct, a null est / r / qr / table, exactly one of loc_gt / q_gt, B <= 0,
+ * n outside [0, B], row0 < 0, V outside [1, URSO_FUSE_MAX_VIEWS], est_ld < 7, est_view_rows < B.
+ */
+enum { URSO_FUSE_LOC_EST = 0, URSO_FUSE_Q_EST = 3, URSO_FUSE_LOC_ERR = 7, URSO_FUSE_ORI_ERR = 8, URSO_FUSE_ESA = 9, URSO_FUSE_DIST = 10,
+       URSO_FUSE_LOC_SPREAD = 11, URSO_FUSE_ORI_SPREAD = 12, URSO_FUSE_VIEW_LAMBDA = 13, URSO_FUSE_N_VIEWS = 14, URSO_FUSE_COLS = 16 };
+enum { URSO_FUSE_MAX_VIEWS = 64 };
+typedef struct urso_pose_fuse_views_args {
+    int32_t B, n;                    /* rows of a view's block of est and of loc_gt / q_gt, valid rows (0 <= n <= B) */
+    int64_t row0;                    /* table row of batch row 0 */
+    int32_t V;                       /* views */
+    int32_t est_ld;                  /* doubles between rows of est */
+    int64_t est_view_rows;           /* rows between the blocks of consecutive views */
+    const double* est;
+    const double* r;
+    const double* qr;
+    const double* loc_gt;            /* optional, with q_gt */
+    const double* q_gt;
+    double* table;
+} urso_pose_fuse_views_args;
+int urso_pose_fuse_views(const urso_pose_fuse_views_args* args, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -1,4 +1,4 @@
-"""Builds liburso_hip.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
+"""Builds liburso_hip.so and the extension library liburso_ext.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
 import os
 import subprocess
 import sys
@@ -12,6 +12,11 @@ VARIANT = os.environ.get("URSO_LIB_VARIANT", "")
 LIB = os.path.join(LIBDIR, "liburso_hip%s.so" % (("_" + VARIANT) if VARIANT else ""))
 SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_pw.hip", "conv_pwx.hip", "conv_dense.hip", "conv_bneck.hip", "conv_halo.hip", "conv_halo2.hip", "conv_winograd.hip", "conv_pair.hip", "conv_pairw.hip", "conv_pairx.hip", "conv_pairs.hip", "conv_c3.hip", "conv_c3g.hip", "conv_hwgrad.hip", "conv_stem.hip", "conv_stemw.hip", "conv_wgrad.hip", "prep.hip", "pool_loss_optim.hip", "augment.hip", "resize.hip", "frame_cache.hip", "video.hip", "pmf_sheet.hip", "bn_train.hip", "comm.hip", "quat_gmm.hip", "pose_eval.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
+# The extension library (include/ursonet_ext.h): entry points added after liburso_hip.so's surface was frozen.  Same flags, no variant;
+# it calls into the main library (error text, launch profiler), which the loader resolves when it is loaded behind it (ursonet_amd/hip.py).
+CSRC_EXT = os.path.join(HERE, "csrc_ext")
+EXT_LIB = os.path.join(LIBDIR, "liburso_ext.so")
+EXT_SOURCES = ["pose_fuse.hip"]
 
 
 def _hipcc():
@@ -33,36 +38,69 @@ def source_hash():
             h.update(fh.read())
         h.update(b"\0")
     h.update(" ".join(FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split() + SOURCES).encode())
+    _hash_compiler(h)
+    return h.hexdigest()
+
+
+def _hash_compiler(h):
     try:
         h.update(subprocess.run([_hipcc(), "--version"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60).stdout)
     except Exception:
         pass
+
+
+def ext_source_hash():
+    """source_hash() of the extension library: every file of csrc_ext/, the headers of csrc/ it may include, the public headers, the
+    compile flags and the compiler's version string."""
+    import hashlib
+    h = hashlib.sha256()
+    inc = os.path.join(HERE, "..", "include")
+    files = (sorted(os.path.join(CSRC_EXT, f) for f in os.listdir(CSRC_EXT)) + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) +
+             sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")))
+    for f in files:
+        h.update(os.path.basename(f).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(FLAGS + EXT_SOURCES).encode())
+    _hash_compiler(h)
     return h.hexdigest()
 
 
-def needs_build():
-    """Stale unless the hash recorded next to the .so equals the hash of the sources as they are now (mtimes are meaningless after a
-    checkout or a snapshot push; a .so shipped without its hash file is rebuilt where a compiler exists and trusted where none does)."""
-    if not os.path.exists(LIB):
+def _stale(lib, digest):
+    if not os.path.exists(lib):
         return True
     try:
-        with open(LIB + ".srchash") as fh:
-            return fh.read().strip() != source_hash()
+        with open(lib + ".srchash") as fh:
+            return fh.read().strip() != digest()
     except IOError:
         return True
 
 
+def needs_build():
+    """Stale unless the hash recorded next to the .so equals the hash of the sources as they are now (mtimes are meaningless after a
+    checkout or a snapshot push; a .so shipped without its hash file is rebuilt where a compiler exists and trusted where none does).
+    True if either library is stale."""
+    return _stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash)
+
+
 def build(force=False, verbose=True):
-    """Compile every HIP source for gfx950 and link the shared library (no GPU needed)."""
-    if not force and not needs_build():
-        return LIB
+    """Compile every HIP source for gfx950 and link the two shared libraries, each only if it is stale (no GPU needed)."""
     os.makedirs(LIBDIR, exist_ok=True)
+    if force or _stale(LIB, source_hash):
+        _compile_and_link(LIB, CSRC, SOURCES, FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split(), ("_" + VARIANT) if VARIANT else "", source_hash, verbose)
+    if force or _stale(EXT_LIB, ext_source_hash):
+        _compile_and_link(EXT_LIB, CSRC_EXT, EXT_SOURCES, FLAGS, "_ext", ext_source_hash, verbose)
+    return LIB
+
+
+def _compile_and_link(lib, srcdir, sources, flags, tag, digest, verbose):
     objs = []
     procs = []
-    for s in SOURCES:
-        o = os.path.join(LIBDIR, s.replace(".hip", (("_" + VARIANT) if VARIANT else "") + ".o"))
+    for s in sources:
+        o = os.path.join(LIBDIR, s.replace(".hip", tag + ".o"))
         objs.append(o)
-        cmd = [_hipcc()] + FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split() + ["-c", os.path.join(CSRC, s), "-o", o]
+        cmd = [_hipcc()] + flags + ["-c", os.path.join(srcdir, s), "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -72,15 +110,14 @@ def build(force=False, verbose=True):
             raise RuntimeError("hipcc failed on %s:\n%s" % (s, out.decode(errors="replace")))
         if verbose and out.strip():
             print(out.decode(errors="replace"))
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    with open(LIB + ".srchash", "w") as fh:
-        fh.write(source_hash() + "\n")
-    return LIB
+    with open(lib + ".srchash", "w") as fh:
+        fh.write(digest() + "\n")
 
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
-    print("built", LIB)
+    print("built", LIB, EXT_LIB)

@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from .infer import PosePass, eval_columns, head_modes, loader_workers  # noqa: F401  (head_modes: its long-standing home is here)
+from .infer import PosePass, eval_columns, fuse_columns, head_modes, loader_workers  # noqa: F401  (head_modes: its long-standing home is here)
 
 SUMMARY = ("Mean est. location error: ", "Mean est. orientation error: ", "ESA score: ", "Mean encoded location error: ")
 CSV_FILES = ("ori_err.csv", "loc_err.csv", "dists_err.csv")
@@ -28,12 +28,19 @@ class EvalResult(object):
     """Per-image NumPy arrays in dataset.image_ids order: image_ids, loc_est [N,3], q_est [N,4] ([x, y, z, w]), loc_err, ori_err
     (degrees), esa, dist (loc_gt[2]); loc_encoded_err (location classification) and ori_encoded_err (soft classification), else None;
     with multimodal, ori_err_soft (the soft-argmax estimate's error) and mode (index of the selected mode), else None.  The four
-    summary means are computed on the host in fp64 from these arrays."""
+    summary means are computed on the host in fp64 from these arrays.  With views (fused=True: `table` is a FUSE table) the
+    estimate and its four errors are the fused pose's, loc_spread, ori_spread (degrees), view_lambda and n_views say how well the views
+    agree (else None), and the encoded errors, which do not depend on the estimate, are None."""
 
-    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal):
+    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal, fused=False):
         from . import hip
-        t = eval_columns(self, table, loc_enc)
         self.image_ids = np.asarray(image_ids)
+        self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
+        if fused:
+            fuse_columns(self, table, True)
+            self.loc_encoded_err = self.ori_encoded_err = self.ori_err_soft = self.mode = None
+            return
+        t = eval_columns(self, table, loc_enc)
         self.esa, self.dist = t[:, hip.EVAL_ESA].copy(), t[:, hip.EVAL_DIST].copy()
         self.ori_encoded_err = t[:, hip.EVAL_ORI_ENC_ERR].copy() if ori_enc else None
         self.ori_err_soft = t[:, hip.EVAL_ORI_ERR_SOFT].copy() if multimodal else None
@@ -71,29 +78,40 @@ def write_csvs(out_dir, ori_err, loc_err, dist):
     return paths
 
 
-def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None):
+def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None, views=None):
     """pose_estimator.evaluate(model, dataset): prints the reference's four summary lines (verbose > 0), writes ori_err.csv,
     loc_err.csv and dists_err.csv into out_dir and returns an EvalResult.  multimodal=True (soft classification only) fits up to
     three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 / 12, 5 iterations, nr_max_modes 4) and
     takes mode 0 if it is the only one or closer to the truth than mode 1, else mode 1 (the commented block of :410-426).
     cache: a frame_cache.FrameCache of the caller's (Config.DEVICE_RESIZE only) that keeps this dataset's raw frames on the device, so
-    that the next call with it -- the next checkpoint, say -- loads no image again; the table is the same with and without it."""
-    ps = PosePass(model, dataset, multimodal)
+    that the next call with it -- the next checkpoint, say -- loads no image again; the table is the same with and without it.
+    views: [V,3] (pitch, yaw, roll) in degrees, as in predict(): the estimate and its errors are those of the pose fused from V rotated
+    views of every image, and the result says how well the views agree; the encoded errors are not computed (run without views for
+    them: the fourth line prints nan).  ValueError as in predict()."""
+    vs = None
+    if views is not None:
+        from .views import ViewSet
+        vs = ViewSet(views, multimodal, "evaluate").with_camera(dataset, model.config)
+    ps = PosePass(model, dataset, multimodal, views=vs)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
     N = len(ids)
-    table = ps.table(max(N, 1), hip.EVAL_COLS)
+    table = ps.table(max(N, 1), hip.EVAL_COLS if vs is None else hip.FUSE_COLS)
     gmm = ps.gmm_buffers(ps.B) if multimodal else None
-    feed = EvalFeeder(model, dataset, ps.cfg, enc_loc=ps.loc_class, enc_ori=ps.soft, workers=loader_workers(ps.cfg, workers), cache=cache)
+    feed = EvalFeeder(model, dataset, ps.cfg, enc_loc=ps.loc_class and vs is None, enc_ori=ps.soft and vs is None,
+                      workers=loader_workers(ps.cfg, workers), cache=cache)
     try:
         for bt in feed:
+            if vs is not None:
+                ps.fuse_batch(table, bt)
+                continue
             ps.run(bt.images)
             ps.eval_into(table, bt, ps.heads(bt.n, gmm), gmm)
     finally:
         feed.close()
     host = table[:N].cpu().numpy()                                              # the one device-to-host read
-    res = EvalResult(ids, host, ps.loc_class, ps.soft, multimodal)
+    res = EvalResult(ids, host, ps.loc_class, ps.soft, multimodal, fused=vs is not None)
     if verbose:
         for line in summary_lines(res.means()):
             print(line)

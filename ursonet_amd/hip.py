@@ -11,6 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _VARIANT = os.environ.get("URSO_LIB_VARIANT", "")        # kernel experiments: see ursonet_amd/build.py
 LIB_PATH = os.path.join(_HERE, "lib", "liburso_hip%s.so" % (("_" + _VARIANT) if _VARIANT else ""))
+EXT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_ext.so")          # the extension library (include/ursonet_ext.h): loaded on first use
 
 F32, BF16, F16 = 0, 1, 2
 EPI_RELU, EPI_OUT_F32, EPI_MASK_BITS, EPI_EMIT_BITS, EPI_ADD_SRCGRID = 1, 2, 4, 8, 16
@@ -101,6 +102,17 @@ class PoseDecodeArgs(C.Structure):
 
 # urso_pose_decode table columns (include/ursonet_hip.h); the modes are urso_pose_eval's
 DEC_LOC_EST, DEC_Q_EST, DEC_LOC_PEAK, DEC_ORI_PEAK, DEC_ORI_LAMBDA, DEC_COLS = 0, 3, 7, 8, 9, 12
+
+
+class PoseFuseViewsArgs(C.Structure):
+    """urso_pose_fuse_views_args (include/ursonet_ext.h): one batch of urso_pose_fuse_views."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64), ("V", C.c_int32), ("est_ld", C.c_int32), ("est_view_rows", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("est", "r", "qr", "loc_gt", "q_gt", "table")])
+
+
+# urso_pose_fuse_views table columns (include/ursonet_ext.h); columns 0..10 are urso_pose_eval's
+FUSE_LOC_EST, FUSE_Q_EST, FUSE_LOC_ERR, FUSE_ORI_ERR, FUSE_ESA, FUSE_DIST = 0, 3, 7, 8, 9, 10
+FUSE_LOC_SPREAD, FUSE_ORI_SPREAD, FUSE_VIEW_LAMBDA, FUSE_N_VIEWS, FUSE_COLS, FUSE_MAX_VIEWS = 11, 12, 13, 14, 16, 64
 
 
 class DenseWgradLayer(C.Structure):
@@ -233,10 +245,37 @@ _LS_SIGS = {
     "urso_loss_scale_update": (_i, [_fp, _fp, _vp]),
 }
 LOSS_SCALE_SYMBOLS = sorted(_LS_SIGS)
-for _name, (_res, _args) in list(_SIGS.items()) + list(_LS_SIGS.items()):
-    _fn = getattr(_lib, _name)          # AttributeError here == symbol missing from the .so
-    _fn.restype = _res
-    _fn.argtypes = _args
+# the extension library liburso_ext.so, include/ursonet_ext.h: bound by ext_lib() on first use
+_EXT_SIGS = {
+    "urso_pose_fuse_views": (_i, [C.POINTER(PoseFuseViewsArgs), _vp]),
+}
+EXT_SYMBOLS = sorted(_EXT_SIGS)
+
+
+def _bind(lib, sigs):
+    for _name, (_res, _args) in sigs.items():
+        _fn = getattr(lib, _name)       # AttributeError here == symbol missing from the .so
+        _fn.restype = _res
+        _fn.argtypes = _args
+
+
+_bind(_lib, dict(_SIGS, **_LS_SIGS))
+_ext = None
+
+
+def ext_lib():
+    """liburso_ext.so, loaded and bound on first use.  It calls into the main library (error text, launch profiler), so that one's
+    symbols are first made visible to later loads (RTLD_NOLOAD | RTLD_GLOBAL promotes the copy already loaded, whichever variant it is)."""
+    global _ext
+    if _ext is None:
+        if not os.path.exists(EXT_LIB_PATH):
+            raise ImportError("liburso_ext.so not found at %s -- build it with `python -m ursonet_amd.build` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % EXT_LIB_PATH)
+        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
+        lib = C.CDLL(EXT_LIB_PATH)
+        _bind(lib, _EXT_SIGS)
+        _ext = lib
+    return _ext
 
 
 def last_error():
@@ -784,6 +823,21 @@ def pose_decode(B, n, row0, loc_mode, ori_mode, loc, ori, table, ori2=None, loc_
     a.ori_map_rows = int(ori_map_rows)
     a.ori_scatter = ptr(ori_scatter)
     _chk(_lib.urso_pose_decode(C.byref(a), stream_ptr(stream)), "urso_pose_decode")
+
+
+def pose_fuse_views(B, n, row0, est, r, qr, table, loc_gt=None, q_gt=None, est_view_rows=None, stream=None):
+    """urso_pose_fuse_views (liburso_ext.so) on one batch: est is the fp64 device table of the per-view rows, contiguous rows, view v's
+    block est_view_rows (default B) rows behind view v - 1's, LOC_EST / Q_EST at urso_pose_decode's columns; r [V,9] and qr [V,4] fp64
+    device tensors (ursonet_amd/views.py); loc_gt / q_gt the truth or None; table is fp64 [rows, FUSE_COLS]."""
+    assert est.dtype == torch.float64 and r.dtype == torch.float64 and qr.dtype == torch.float64 and table.dtype == torch.float64
+    assert r.is_contiguous() and qr.is_contiguous() and table.is_contiguous() and r.shape[0] == qr.shape[0]
+    a = PoseFuseViewsArgs()
+    a.B, a.n, a.row0, a.V = int(B), int(n), int(row0), int(r.shape[0])
+    a.est, a.est_ld = _rows(est)
+    a.est_view_rows = int(B if est_view_rows is None else est_view_rows)
+    assert est.shape[0] >= (a.V - 1) * a.est_view_rows + a.B and table.shape[0] >= a.row0 + a.n and table.shape[1] == FUSE_COLS
+    a.r, a.qr, a.loc_gt, a.q_gt, a.table = ptr(r), ptr(qr), ptr(loc_gt), ptr(q_gt), ptr(table)
+    _chk(ext_lib().urso_pose_fuse_views(C.byref(a), stream_ptr(stream)), "urso_pose_fuse_views")
 
 
 def warp_perspective(B, H, W, Cc, interp, src, m, dst, stream=None):

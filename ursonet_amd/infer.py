@@ -5,7 +5,9 @@ device" and "this batch's rows are in the table".  A command builds one PosePass
     matrix only for the DEC table, whose ORI_LAMBDA needs it: passing one selects another kernel variant) and, asked to, urso_quat_gmm_fit;
   * eval_into() (labelled: estimates and errors, urso_pose_eval, EVAL columns) or decode_into() (no truth: estimates and confidences,
     urso_pose_decode, DEC columns) decodes every head and writes one fp64 row per image into a device table of the caller's.
-The two kernels share their device routines, so LOC_EST / Q_EST are the same bits whichever command produced them.  Nothing here
+The two kernels share their device routines, so LOC_EST / Q_EST are the same bits whichever command produced them.  With views
+(ursonet_amd/views.py: predict / evaluate, views=...) fuse_batch() takes the place of the three: it runs the batch once per view, warped
+on the device, decodes every view into a table of the pass's and ends with one urso_pose_fuse_views into the caller's table.  Nothing here
 synchronises or reads back, and torch, hip and the engine are touched only after check_heads() has passed (no GPU is needed to be
 refused).  The commands own their feeders, tables, GMM buffers, result types, prints, files and pictures.
 """
@@ -73,11 +75,26 @@ def dec_columns(res, table, loc_class, soft):
     res.ori_lambda = t[:, hip.DEC_ORI_LAMBDA].copy() if soft else None
 
 
+def fuse_columns(res, table, truth):
+    """Sets the fields every result of a FUSE table has on `res` (the errors only with a truth); returns the table as fp64 [N, FUSE_COLS]."""
+    from . import hip
+    t = np.asarray(table, dtype=np.float64).reshape(-1, hip.FUSE_COLS)
+    res.loc_est = t[:, hip.FUSE_LOC_EST:hip.FUSE_LOC_EST + 3].copy()
+    res.q_est = t[:, hip.FUSE_Q_EST:hip.FUSE_Q_EST + 4].copy()
+    res.loc_spread, res.ori_spread = t[:, hip.FUSE_LOC_SPREAD].copy(), t[:, hip.FUSE_ORI_SPREAD].copy()
+    res.view_lambda, res.n_views = t[:, hip.FUSE_VIEW_LAMBDA].copy(), t[:, hip.FUSE_N_VIEWS].astype(np.int32)
+    if truth:
+        res.loc_err, res.ori_err = t[:, hip.FUSE_LOC_ERR].copy(), t[:, hip.FUSE_ORI_ERR].copy()
+        res.esa, res.dist = t[:, hip.FUSE_ESA].copy(), t[:, hip.FUSE_DIST].copy()
+    return t
+
+
 class PosePass(object):
     """The per-call state of the pass: cfg, eng, B, dev, the head modes and, on the device, the bin maps loc_map (fp64) and hq (fp32),
     q_soft [B,4] and, with scatter=True, urso_quat_wavg_decode's scatter matrices [B,16].  `who`: the command, for check_heads' messages."""
 
-    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate"):
+    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate", views=None):
+        """views: a views.ViewSet with its homographies (with_camera), for fuse_batch()."""
         self.soft = check_heads(model, dataset, multimodal, who)
         import torch
         from . import hip
@@ -96,6 +113,15 @@ class PosePass(object):
                 self.scatter = torch.empty(B, 16, dtype=torch.float32, device=dev)
             if multimodal:
                 self.var = (cfg.BETA / cfg.ORI_BINS_PER_DIM) ** 2 / 12         # pose_estimator.py:333-334
+        self.views = views
+        if views is not None:                                                  # on the device: R [V,9], qR [V,4], one warp matrix per view and batch row [V,B,9]
+            from .views import is_identity
+            up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev).contiguous()   # noqa: E731
+            self.view_ident = [is_identity(r) for r in views.R]
+            self.view_r, self.view_qr = up(views.R.reshape(views.V, 9)), up(views.qR)
+            self.view_m = up(np.repeat(views.M[:, None, :], B, axis=1))
+            self.view_table = self.table(views.V * B, hip.DEC_COLS)             # view v's rows at [v * B, v * B + n), reused every batch
+            self.view_scratch = None                                           # the warped batch, uint8 [B,H,W,3]
 
     def table(self, rows, cols):
         """A NaN fp64 device table [rows, cols]."""
@@ -143,3 +169,23 @@ class PosePass(object):
         loc, ori, ori2, z = heads
         self.hip.pose_decode(self.B, n, row0, self.loc_mode, self.ori_mode, loc, ori, table, ori2=ori2, loc_map=self.loc_map, ori_logits=z,
                              ori_map_rows=self.hq.shape[0] if self.soft else 0, ori_scatter=self.scatter)
+
+    def fuse_batch(self, table, bt):
+        """The rows [bt.row0, bt.row0 + bt.n) of a FUSE table: the feeder batch bt once per view through the network -- the identity view
+        as run() takes it (no warp: the plain path's bits), any other warped by urso_warp_perspective (bilinear, zero border) from bt.images
+        into a scratch batch of the pass's -- each decoded into the pass's per-view table, then one urso_pose_fuse_views, with bt's truth
+        where the feeder carries labels.  All on the current stream; nothing is read back."""
+        torch, hip, B = self.torch, self.hip, self.B
+        if bt.images.dtype != torch.uint8:
+            raise ValueError("views need uint8 frames (the warp kernel's input); this batch was molded on the host to %s" % bt.images.dtype)
+        _B, H, W, Cc = bt.images.shape
+        for v in range(self.views.V):
+            if self.view_ident[v]:
+                self.run(bt.images)
+            else:
+                if self.view_scratch is None or self.view_scratch.shape != bt.images.shape:
+                    self.view_scratch = torch.empty_like(bt.images)
+                hip.warp_perspective(B, H, W, Cc, 1, bt.images, self.view_m[v], self.view_scratch)
+                self.run(self.view_scratch)
+            self.decode_into(self.view_table, bt.n, v * B, self.heads(bt.n))
+        hip.pose_fuse_views(B, bt.n, bt.row0, self.view_table, self.view_r, self.view_qr, table, loc_gt=bt.loc_gt, q_gt=bt.q_gt)

@@ -7,11 +7,14 @@ feeds the pass of ursonet_amd/infer.py -- and ends each batch with urso_pose_dec
 confidence of the classification heads into one fp64 device table, read once at the end.  The estimates are the bits evaluate()
 produces for the same images.
 
+predict(views=...) shows the network V rotated views of every image (ursonet_amd/views.py) and returns the fused estimate and how well
+the views agree -- a confidence the regression heads do not otherwise have (the pass: infer.PosePass.fuse_batch).
+
 Under a launcher (world > 1) every process predicts the whole dataset; there is no sharding.
 """
 import numpy as np
 
-from .infer import PosePass, dec_columns, loader_workers
+from .infer import PosePass, dec_columns, fuse_columns, loader_workers
 
 
 class PredictResult(object):
@@ -19,30 +22,48 @@ class PredictResult(object):
     the heads give without a truth to compare with: loc_peak (location classification: the largest softmax probability of the
     location bins), ori_peak and ori_lambda (soft classification: the largest probability of the orientation bins, and the largest
     eigenvalue of the PMF's scatter matrix sum_i w_i q_i q_i^T -- 1 for a point mass, 1/4 for a uniform spread); None where the
-    head does not define them.  With multimodal: modes [N,3,4], mode_priors [N,3] (descending; unused slots 0) and n_modes [N]."""
+    head does not define them.  With multimodal: modes [N,3,4], mode_priors [N,3] (descending; unused slots 0) and n_modes [N].
+    With views (fused=True: `table` is a FUSE table): loc_est / q_est are the fused estimate, loc_spread, ori_spread (degrees: RMS
+    deviation of the de-rotated views from it), view_lambda (1 when all views agree, 1/4 for a uniform spread) and n_views are set, and
+    loc_peak / ori_peak / ori_lambda, which are per-view quantities, are None.  Without views the four are None."""
 
-    def __init__(self, image_ids, table, loc_class, soft, gmm=None):
-        dec_columns(self, table, loc_class, soft)
+    def __init__(self, image_ids, table, loc_class, soft, gmm=None, fused=False):
+        self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
+        if fused:
+            fuse_columns(self, table, False)
+            self.loc_peak = self.ori_peak = self.ori_lambda = None
+        else:
+            dec_columns(self, table, loc_class, soft)
         self.image_ids = np.asarray(image_ids)
         self.modes, self.mode_priors, self.n_modes = gmm if gmm is not None else (None, None, None)
 
 
-def predict(model, dataset, multimodal=False, workers=None, cache=None):
+def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None):
     """Pose estimates of every image of `dataset` -> PredictResult.  The dataset needs image_ids, load_image, image_info and, for
     the classification heads, histogram_3D_map / ori_histogram_map; no label loader is called.  multimodal=True (soft
     classification only) also fits up to three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 /
     12, 5 iterations, nr_max_modes 4) and returns them; without a truth to pick a mode by, q_est stays the soft-argmax estimate.  cache: as in evaluate() -- a
-    frame_cache.FrameCache of the caller's that keeps the raw frames on the device between calls (Config.DEVICE_RESIZE only)."""
-    ps = PosePass(model, dataset, multimodal, scatter=True, who="predict")
+    frame_cache.FrameCache of the caller's that keeps the raw frames on the device between calls (Config.DEVICE_RESIZE only).
+    views: [V,3] (pitch, yaw, roll) in degrees, e.g. views.ROLL_VIEWS(3, 30): every image is shown to the network once per view (the
+    frame re-rendered through the rotated camera; needs dataset.camera), the estimates are rotated back and fused.  None: one pass, as ever.
+    ValueError: views with multimodal, a bad views array, no dataset.camera, IMAGE_RESIZE_MODE 'crop' / 'none'."""
+    vs = None
+    if views is not None:
+        from .views import ViewSet
+        vs = ViewSet(views, multimodal, "predict").with_camera(dataset, model.config)
+    ps = PosePass(model, dataset, multimodal, scatter=vs is None, who="predict", views=vs)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
     N = len(ids)
-    table = ps.table(max(N, 1), hip.DEC_COLS)
+    table = ps.table(max(N, 1), hip.DEC_COLS if vs is None else hip.FUSE_COLS)
     gmm = ps.gmm_buffers(max(N, 1), zeroed=True) if multimodal else None          # whole-dataset outputs: each batch fits into its rows
     feed = EvalFeeder(model, dataset, ps.cfg, workers=loader_workers(ps.cfg, workers), labels=False, cache=cache)
     try:
         for bt in feed:
+            if vs is not None:
+                ps.fuse_batch(table, bt)
+                continue
             ps.run(bt.images)
             rows = [t[bt.row0:bt.row0 + bt.n] for t in gmm] if multimodal else None
             ps.decode_into(table, bt.n, bt.row0, ps.heads(bt.n, rows))
@@ -50,4 +71,4 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None):
         feed.close()
     host = table[:N].cpu().numpy()                                               # the one read of the table
     fit = tuple(gmm[i][:N].cpu().numpy() for i in (0, 2, 4)) if multimodal else None      # mean, prior, n_modes
-    return PredictResult(ids, host, ps.loc_class, ps.soft, fit)
+    return PredictResult(ids, host, ps.loc_class, ps.soft, fit, fused=vs is not None)
