@@ -164,14 +164,26 @@ def conv2d(x, p, stride=1, padding="valid"):
     return F.conv2d(x, w, p.get("bias"), stride=stride)
 
 
-def batchnorm(x, p, training):
+def moving_statistics_update(old_mean, old_var, mean, var, m, momentum=0.99, eps=BN_EPS):
+    """What Keras' BatchNormalization leaves in moving_mean / moving_variance after one training step on batch statistics
+    (mean, biased var) over m values per channel [A3]: mean' = mom mean_old + (1 - mom) mean; the variance enters with Keras'
+    sample-size correction var m / (m - (1 + eps)) (normalization.py: K.moving_average_update of variance * sample_size /
+    (sample_size - (1 + epsilon)))."""
+    return (old_mean * momentum + mean * (1.0 - momentum),
+            old_var * momentum + var * (m / (m - (1.0 + eps))) * (1.0 - momentum))
+
+
+def batchnorm(x, p, training, stats_out=None):
     """net.py:60-76 + [A3]. training False -> moving statistics (frozen; gamma/beta still
-    receive gradient); None -> batch statistics (biased variance), no sync."""
+    receive gradient); None -> batch statistics (biased variance), no sync.  stats_out: a list that
+    receives (batch mean, biased batch variance, values per channel) when batch statistics are used."""
     shape = (1, -1, 1, 1) if x.dim() == 4 else (1, -1)
     if training is None or training is True:
         dims = (0, 2, 3) if x.dim() == 4 else (0,)
         mean = x.mean(dim=dims)
         var = x.var(dim=dims, unbiased=False)
+        if stats_out is not None:
+            stats_out.append((mean.detach(), var.detach(), x.numel() // x.shape[1]))
     else:
         mean, var = p["moving_mean"], p["moving_variance"]
     inv = torch.rsqrt(var + BN_EPS)
@@ -224,10 +236,15 @@ class StorageRounding(object):
     output after its fused epilogue, every activation gradient, and the per-step folded filter W*gamma/sqrt(var+eps)
     (straight-through for the gradient w.r.t. W, gamma: the device's fp32 master weights receive the unrounded
     gradient).  In exact arithmetic this is the plain oracle; it exists so that the 16-bit device path can be
-    compared at 1e-2 per tensor instead of by cosine similarity.  Frozen BN only (TRAIN_BN False)."""
+    compared at 1e-2 per tensor instead of by cosine similarity.  With batch-statistics BN (TRAIN_BN None) the device leaves
+    the conv unfolded: the filter is rounded as it is, the raw conv output z and the gradient that reaches it are 16-bit
+    tensors, and the normalisation itself runs in the oracle's precision (conv_bn)."""
 
-    def __init__(self, dtype, unstored=()):
+    def __init__(self, dtype, unstored=(), batch_stats=None):
         self.dtype = dtype
+        # batch_stats: a list that receives (BN parameter dict, batch mean, biased batch variance, values per channel) of every
+        # batch-statistics normalisation of the graph (TRAIN_BN None), in graph order
+        self.batch_stats = batch_stats
         # projection shortcuts the device computes INSIDE the launch of the layer that adds them (Engine.shortcut_folded: stage 2's fused pair,
         # stages 4-5's two-segment branch2c): their output never reaches a 16-bit tensor, so it is not rounded here either
         self.unstored = set(unstored)
@@ -245,11 +262,20 @@ class StorageRounding(object):
 def conv_bn(x, Pc, Pb, train_bn, stride=1, padding="valid", q=None):
     """Conv2D followed by the BatchNorm wrapper (net.py:60-76, 101-103 ...).  With q (StorageRounding) and frozen BN
     the pair is evaluated in the device's folded form: conv(x, round(W*s)) + (s*b + beta - mean*s), s = gamma/sqrt(var+eps)
-    -- algebraically the same function of (x, W, b, gamma, beta)."""
+    -- algebraically the same function of (x, W, b, gamma, beta).  With q and batch-statistics BN (train_bn None) it is the
+    device's unfolded form: z = round(conv(x, round(W)) + b) is stored (and so is the gradient that reaches it), then the
+    batch-statistics normalisation of the stored z."""
     if q is None:
         y = conv2d(x, Pc, stride=stride, padding=padding)
         return batchnorm(y, Pb, train_bn) if Pb is not None else y
-    assert train_bn is False or Pb is None, "StorageRounding restates the frozen-BN (folded) device path only"
+    assert train_bn is False or train_bn is None or Pb is None, "StorageRounding restates the frozen-BN (folded) and the batch-statistics device paths"
+    if Pb is not None and train_bn is None:
+        z = q.act(conv2d(x, {"kernel": q.weight(Pc["kernel"]), **({"bias": Pc["bias"]} if "bias" in Pc else {})}, stride=stride, padding=padding))
+        rec = [] if q.batch_stats is not None else None
+        y = batchnorm(z, Pb, None, rec)
+        if rec:
+            q.batch_stats.append((Pb,) + rec[0])
+        return y
     w = Pc["kernel"]
     if Pb is not None:
         sc = Pb["gamma"] * torch.rsqrt(Pb["moving_variance"] + BN_EPS)

@@ -151,10 +151,15 @@ def _record(family, r):
         print("rounded-once ratio %s %.3f" % (family, r))
 
 
-def run_conv_layer(case, dt, exact, fwd_sym=None, dgrad_sym=None, residual=True, dgrad_add=True, family="igemm", wgrad=True):
+def run_conv_layer(case, dt, exact, fwd_sym=None, dgrad_sym=None, residual=True, dgrad_add=True, family="igemm", wgrad=True, fwd_flags=None,
+                   forward_only=False):
     """conv_igemm forward (bias [+ residual] + ReLU), gather-form data gradient ([+ add] + mask), compact strided data gradient
-    and its accumulate form (1x1 / stride 2), filter gradient + column sums -- under whatever options the caller set."""
+    and its accumulate form (1x1 / stride 2), filter gradient + column sums -- under whatever options the caller set.
+    fwd_flags: the forward launch's epilogue flags (default EPI_RELU); 0 is the bare conv + bias a batch-statistics BN layer
+    launches (Engine._plan_conv_forward), whose reference has no ReLU.  forward_only: stop after the forward probe."""
     hip = _hip()
+    fwd_flags = hip.EPI_RELU if fwd_flags is None else fwd_flags
+    act = F.relu if (fwd_flags & hip.EPI_RELU) else (lambda t: t)
     R = ConvRef(case, dt, exact, seed=sum(map(ord, case[-1])) + 31 * dt)
     B, H, W, Ci, N, k, s, pad, name = case
     OH, OW = R.OH, R.OW
@@ -165,12 +170,15 @@ def run_conv_layer(case, dt, exact, fwd_sym=None, dgrad_sym=None, residual=True,
     y = full((B, OH, OW, N), dt)
     pre, mag = (R.z, R.mz) if residual else (R.zn, R.mzn)
     with (X.ran(fwd_sym) if fwd_sym else _nullctx()):
-        hip.conv_igemm(g, dt, hip.EPI_RELU, x, wf, biasf, dev(R.res, dt) if residual else None, None, y)
+        hip.conv_igemm(g, dt, fwd_flags, x, wf, biasf, dev(R.res, dt) if residual else None, None, y)
     torch.cuda.synchronize()
+    relu_pre = pre if (fwd_flags & hip.EPI_RELU) else None          # (no ReLU: no decision at zero to expose)
     if exact:
         ref0 = R.last_channel_zeroed() - (0 if residual else R.res.double())
-        X.assert_sensitive(F.relu(pre), F.relu(ref0), pre, "forward")
-    _record(family, R.check(y, F.relu(pre), mag, R.Kf + 2, "forward", relu_pre=pre))
+        X.assert_sensitive(act(pre), act(ref0), relu_pre, "forward")
+    _record(family, R.check(y, act(pre), mag, R.Kf + 2, "forward", relu_pre=relu_pre))
+    if forward_only:
+        return R
     # ---- data gradient: flipped taps, + add tensor, x 'x > 0'
     gd = hip.geom(B, OH, OW, N, H, W, Ci, k, k, 1, 1, k - 1 - pad[0], k - 1 - pad[1], s, s)
     dx = full((B, H, W, Ci), dt)
@@ -293,6 +301,28 @@ def test_hconv2_kernel(case, shape, dt, exact):
 
 @pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("kernel", ["hconv", "hconv2_32", "hconv2_21"])
+@pytest.mark.parametrize("case", HALO_CASES, ids=[c[-1] for c in HALO_CASES])
+def test_halo_kernels_plain(case, kernel, dt, exact):
+    """flags = 0 -- bias only, no ReLU, no residual, no mask: the form in which a batch-statistics BN layer launches its conv (the raw z);
+    reference zn without the ReLU."""
+    hip = _hip()
+    B, H, W, Ci, N = case[:5]
+    cap = 8 if case[-1].startswith("cap") else 0
+    if kernel == "hconv":
+        opts, sym = dict(hconv=2, hconv2=0, c3=0, grid_cap=cap), "hconv_kernel"
+    else:
+        opts, sym = dict(hconv=2, hconv2=2, hconv2_shape=int(kernel[-2:]), c3=0, grid_cap=cap), "hconv2_kernel"
+    with hip.options(**opts):
+        g = hip.geom(B, H, W, Ci, H, W, N, 3, 3, 1, 1, 1, 1)
+        assert hip.conv_igemm_halo_ok(g, dt, 0)
+        if kernel != "hconv":
+            assert hip.conv_igemm_halo2_shape(g, dt, 0) == opts["hconv2_shape"], "tile shape %s does not fit %s" % (kernel, case[-1])
+        run_conv_layer(case, dt, exact, sym, residual=False, family=kernel + "_plain", fwd_flags=0, forward_only=True)
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
 def test_hconv_stream_k(dt, exact):
     """Stream-K hand-over (urso_conv_igemm_ws, hconv_dbg = 8): tiles cut by a run boundary are finished from fp32 partials,
     so the result is still rounded once."""
@@ -326,6 +356,32 @@ def test_hconv_stream_k(dt, exact):
     _record("hconv_streamk", R.check(ym, R.zn * keep, R.mzn * keep, R.Kf + 1, "stream-K masked", sens=False))
 
 
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+def test_hconv_stream_k_plain(dt, exact):
+    """The stream-K hand-over with flags = 0 and no mask (the conv of a batch-statistics BN layer, which gets the hand-over workspace
+    like a frozen layer): tiles finished from fp32 partials hold bias + sum, no ReLU, rounded once; the flags are left zero."""
+    hip = _hip()
+    case = (3, 19, 23, 128, 128, 3, 1, (1, 1), "streamk_ragged")
+    R = ConvRef(case, dt, exact, seed=77 + dt)
+    B, H, W, Ci, N = case[:5]
+    wf, wd, biasf = prep_weights(R.w, dt, R.bias)
+    g = hip.geom(B, H, W, Ci, H, W, N, 3, 3, 1, 1, 1, 1)
+    ws = torch.zeros(hip.conv_igemm_halo_ws_bytes() // 4 + 16, dtype=torch.float32, device="cuda")
+    ws[1024:] = float("nan")
+    with hip.options(hconv=2, hconv2=0, grid_cap=24, c3=0, hconv_dbg=8):
+        assert hip.conv_igemm_halo_ok(g, dt, 0)
+        y = full((B, H, W, N), dt)
+        with X.ran("hconv_kernel"):
+            hip.conv_igemm_ws(g, dt, 0, dev(R.x, dt), wf, biasf, None, None, y, ws)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(ws[1024:]).any()), "no fp32 partial was handed over: the stream-K schedule did not engage"
+    assert int(ws[:1024].view(torch.int32).abs().max()) == 0, "hand-over flags not left zero"
+    if exact:
+        X.assert_sensitive(R.zn, R.last_channel_zeroed() - R.res.double(), None, "stream-K plain forward")
+    _record("hconv_streamk_plain", R.check(y, R.zn, R.mzn, R.Kf + 1, "stream-K plain forward"))
+
+
 # ---------------------------------------------------------------- register-filter 3x3 (conv_c3.hip)
 C3_CASES = [
     ((2, 12, 20, 64, 64, 3, 1, (1, 1), "c3_narrow_image"), dict(c3=1), "c3_kernel"),
@@ -344,6 +400,16 @@ def test_c3_kernels(case, opts, sym, dt, exact):
     hip = _hip()
     with hip.options(**opts):
         run_conv_layer(case, dt, exact, sym, sym, residual=False, dgrad_add=False, family=sym, wgrad=False)
+
+
+@pytest.mark.parametrize("exact", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("case,opts,sym", C3_CASES, ids=[c[0][-1] for c in C3_CASES])
+def test_c3_kernels_plain(case, opts, sym, dt, exact):
+    """flags = 0 (bias only: no ReLU, no residual, no mask), the launch of a batch-statistics BN layer's conv; reference zn without ReLU."""
+    hip = _hip()
+    with hip.options(**opts):
+        run_conv_layer(case, dt, exact, sym, residual=False, family=sym + "_plain", fwd_flags=0, forward_only=True)
 
 
 # ---------------------------------------------------------------- big-tile pointwise (conv_pwx.hip)

@@ -384,13 +384,15 @@ class Engine(object):
         c.fwd_flags = flags
         # 3x3 layers taken by the halo-tile kernel get its stream-K hand-over workspace (dedicated: its first 4 KiB are flags that
         # must stay zero between launches, include/ursonet_hip.h)
-        c.halo_f = (not c.batch_bn) and dt != hip.F32 and hip.conv_igemm_halo_ok(c.gf, dt, flags, c.res is not None)
+        # (a batch-statistics layer launches the bare conv: no ReLU, no residual -- those belong to its bn_apply)
+        c.halo_f = dt != hip.F32 and (hip.conv_igemm_halo_ok(c.gf, dt, 0, False) if c.batch_bn else
+                                      hip.conv_igemm_halo_ok(c.gf, dt, flags, c.res is not None))
         c.halo_d = bool(c.gd is not None and training and dt != hip.F32 and hip.conv_igemm_halo_ok(c.gd, dt, 0, False))
         if (c.halo_f or c.halo_d) and self.halo_ws is None:
             self.halo_ws = torch.zeros(hip.conv_igemm_halo_ws_bytes() // 4 + 16, dtype=torch.float32, device=dev)
         if c.batch_bn:
             self.fwd_ops += [
-                _Launch(lambda c=c: hip.conv_igemm_ex(c.gf, dt, 0, c.xin, c.wf, c.biasf, None, None, c.z, None, self.igemm_ws if c.ws_f else None),
+                _Launch(lambda c=c: hip.conv_igemm_ex(c.gf, dt, 0, c.xin, c.wf, c.biasf, None, None, c.z, None, self.forward_workspace(c)),
                         "fwd", "fwd:" + node.name, fwd=(node.name,)),
                 _Launch(lambda c=c: hip.bn_batch_stats(c.Mpix, c.N, dt, c.z, self.bn_ws, c.bmean, c.bvar, c.bn_mmean, c.bn_mvar, BN_MOMENTUM, BN_EPS),
                         "bn_stats", "bn_stats:" + node.name),
@@ -422,9 +424,14 @@ class Engine(object):
         else:
             c.fwd = _Launch(lambda c=c, f=flags: hip.conv_igemm_ex(
                 c.gf, dt, f | (hip.EPI_EMIT_BITS if c.dst.bits is not None else 0), c.xin, c.wf, c.biasf,
-                c.res.data if c.res is not None else None, None, c.dst.data, c.dst.bits,
-                self.halo_ws if c.halo_f else (self.igemm_ws if c.ws_f else None)), "fwd", "fwd:" + node.name, fwd=(node.name,))
+                c.res.data if c.res is not None else None, None, c.dst.data, c.dst.bits, self.forward_workspace(c)), "fwd", "fwd:" + node.name,
+                fwd=(node.name,))
         self.fwd_ops.append(c.fwd)
+
+    def forward_workspace(self, c):
+        """The workspace of layer c's forward conv launch: the halo-tile kernel's dedicated hand-over workspace where that kernel takes the
+        layer (never the split-K one: it would read the partials of other layers as its flags), else the split-K workspace where the layer splits."""
+        return self.halo_ws if c.halo_f else (self.igemm_ws if c.ws_f else None)
 
     def _plan_forward_workspaces(self):
         """The workspaces the forward launches share (sized for the largest layer) and the batched weight prep."""
@@ -1025,6 +1032,8 @@ class Engine(object):
             if len(prod) != 1 or not cons or not prod[0].node.relu:
                 continue
             P = prod[0]
+            if P.batch_bn:
+                continue                                   # its output is written by urso_bn_apply, which emits no bit mask: the tensor itself is the mask
             pw = lambda n: (not n.dense) and n.kh == 1 and n.kw == 1
             # ... or bottleneck_layer behind the trunk's last block: its parity-class data gradient (conv_bneck.hip) takes the bit mask too
             bn_ = lambda c: (hip.get_option("bneck") and not c.node.dense and c.node.kh == 3 and c.node.kw == 3 and c.node.stride == 2 and
