@@ -83,6 +83,31 @@ typedef struct urso_pose_fuse_views_args {
 } urso_pose_fuse_views_args;
 int urso_pose_fuse_views(const urso_pose_fuse_views_args* args, void* stream);
 
+/*
+ * Learnable loss weights (Config.LEARNABLE_LOSS_WEIGHTS; after Kendall & Cipolla, and net.py:648-654 + the
+ * commented-out `loss / exp(weight) + weight` of net.py:709-760).  Each entry point is the plain loss of ursonet_hip.h with the same
+ * leading arguments, plus s_d, ds_d and ls_state_d in front of the stream; the kernels are the plain ones (one device code).
+ *   s_d         fp32[1], device: the trainable log-variance s of this loss (a slot of the flat parameter buffer).  Required.
+ *   ds_d        fp32[1], device: OVERWRITTEN (never accumulated) with d(reported loss)/ds; NULL = s is frozen, nothing is written.
+ *   ls_state_d  the loss-scale state of ursonet_loss_scale.h or NULL: as in the *_ls forms, the finished fp32 head gradient is multiplied
+ *               by state[URSO_LS_SCALE] last, in front of its one rounding to dt.  ds_d is never scaled.
+ * With w = weight and L the batch-mean loss without its weight:
+ *   w_eff          = w * expf(-s)                  that one fp32 product
+ *   P              = the plain entry point's loss under weight w_eff, in its order of operations (= w_eff L)
+ *   head gradient  = the plain entry point's under weight w_eff, in its order of operations
+ *   loss_d[0]      = P + w * s                     (= w (L exp(-s) + s); may be negative)
+ *   ds_d[0]        = w - P                         (= w (1 - L exp(-s)), from the P that is reported)
+ * At s = 0, w_eff = w exactly: the head gradient, norms_d / q_d and the loss have the bits of the plain form (ls_state_d NULL) or of the
+ * *_ls form (ls_state_d set).  Bad arguments (those of the plain form, or a null s_d) return URSO_EINVAL before any launch.
+ */
+int urso_softmax_xent_fwd_bwd_lw(int B, int K, const float* logits_d, const float* labels_d, float weight, int relu_mask, int dt,
+                                 float* loss_d, void* dz_d, float* row_ws_d, const float* s_d, float* ds_d, const float* ls_state_d,
+                                 void* stream);
+int urso_rel_l2_fwd_bwd_lw(int B, int D, int ld, const float* gt_d, const float* pred_d, float weight, int dt, float* loss_d,
+                           void* dpred_d, float* norms_d, const float* s_d, float* ds_d, const float* ls_state_d, void* stream);
+int urso_absdot_fwd_bwd_lw(int B, int D, int ld, int normalize, const float* gt_d, const float* x_d, float weight, int dt, float* q_d,
+                           float* loss_d, void* dx_d, const float* s_d, float* ds_d, const float* ls_state_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,8 +44,8 @@ FAMILIES = [
     ("stem_pack", "prep.hip", "elementwise", "7x7x3 stem filter -> packed 7x4x8 layout"),
     ("expand2", "pool_loss_optim.hip", "elementwise", "compact -> dense gradient rows (stages 4-5 residual side)"),
     ("subsample2", "pool_loss_optim.hip", "elementwise", "even rows / columns gather"),
-    ("softmax_xent", "pool_loss_optim.hip", "one block per row", "soft-label cross-entropy + gradient"),
-    ("rel_l2", "pool_loss_optim.hip", "one block", "relative L2 loss + gradient"),
+    ("softmax_xent", "loss_dev.h", "one block per row", "soft-label cross-entropy + gradient"),
+    ("rel_l2", "loss_dev.h", "one block", "relative L2 loss + gradient"),
     ("maxpool", "pool_loss_optim.hip", "4x8 output tiles", "3x3/s2 max-pool"),
     ("mold_kernel", "pool_loss_optim.hip", "elementwise", "uint8 -> mean-subtracted packed input"),
     ("sgd_kernel", "pool_loss_optim.hip", "elementwise", "clip + momentum SGD"),

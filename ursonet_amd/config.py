@@ -11,6 +11,10 @@ Additions (all optional, never required by a reference caller):
                  forward and backward, i.e. the loss and its gradient are those of the one global batch.
   LOSS_SCALE     None (default) | a power of two | "dynamic": loss scaling for 16-bit training, with LOSS_SCALE_INIT,
                  LOSS_SCALE_GROWTH_INTERVAL, LOSS_SCALE_MIN and LOSS_SCALE_MAX (ursonet_amd/loss_scale.py).
+  LEARNABLE_LOSS_WEIGHTS  a reference field that the reference leaves without effect (its formula is commented out, net.py:709-760).
+                 True: in training mode each of the loc / ori losses is w (L exp(-s) + s) with s a trainable scalar of the layer
+                 `loss_weights` (ori_weight -2.3, loc_weight 0.0), learnt by the same optimizer launch (ursonet_amd/loss_weights.py).
+                 One GPU; refused with REGRESS_KEYPOINTS and DP_EXACT_REL_LOSS.
 """
 import json
 import os

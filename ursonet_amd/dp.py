@@ -277,6 +277,9 @@ class DataParallelEngine(object):
         self.world = dist.get_world_size(group)
         if self.world > 1 and getattr(engine, "ls_state", None) is not None:
             raise ValueError("LOSS_SCALE is not supported under data parallelism (world size %d): leave Config.LOSS_SCALE = None" % self.world)
+        if self.world > 1 and getattr(engine, "learn_lw", False):
+            from . import loss_weights
+            loss_weights.validate(engine.config, self.world)    # ValueError: the two scalars' gradients are not part of the exchange
         # DP_EXACT_REL_LOSS: the location loss is ONE ratio of norms over the global batch (net.py:750-762); its two squared norms are
         # summed over the ranks between forward and backward and the gradient is pre-scaled by the world size (undone by the averaging)
         self.rel_exact = bool(getattr(engine, "rel_exact", False)) and bool(engine.loss_pre_ops)

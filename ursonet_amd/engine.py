@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import hip, loss_scale
+from . import hip, loss_scale, loss_weights
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -78,6 +78,12 @@ class Engine(object):
         self.tdt = hip.TORCH_DT[self.dt]
         self.B = int(batch if batch is not None else config.BATCH_SIZE)
         self.graph = build_graph(config)
+        # Config.LEARNABLE_LOSS_WEIGHTS: the two log-variances are one more parameter layer of the training graph, so
+        # they lie in flat_w / flat_g / the optimizer state and everything that walks graph.params or the flat buffers covers them
+        self.learn_lw = loss_weights.enabled(config, mode)
+        if self.learn_lw:
+            loss_weights.validate(config, self.world_size_hint())
+            loss_weights.add_layer(self.graph)
         self.H, self.W = int(config.IMAGE_SHAPE[0]), int(config.IMAGE_SHAPE[1])
         self.layer_trainable = {n: True for n in self.graph.params}
         self.world_size = 1
@@ -90,6 +96,12 @@ class Engine(object):
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
         self._build_plan()
+
+    @staticmethod
+    def world_size_hint():
+        """The launcher's world size (1 in a plain process): ursonet_amd/dp.py wraps the engine only after it is built."""
+        from .dp import launcher_world
+        return launcher_world()[2]
 
     # ------------------------------------------------------------------ parameters
     def _alloc_params(self, seed, randomize_bn):
@@ -196,6 +208,8 @@ class Engine(object):
             elif init != self._ls_init:                # the keys changed between plans: the new settings start afresh, in the same buffer
                 self._ls_init = init
                 self.ls_state.copy_(torch.tensor(init, dtype=torch.float32))
+        if training and self.learn_lw:
+            loss_weights.validate(self.config, self.world_size)
         self.acts = {}
         self.prep_ops, self.fwd_ops, self.loss_ops, self.bwd_ops, self.opt_ops = [], [], [], [], []      # lists of _Launch (plan_state.py)
         self.wino_ws = None
@@ -854,7 +868,8 @@ class Engine(object):
                 launch.run = (lambda ph=ph, k=k, s0=s0, s1=s1: self.pbatch.run(ph, k, dt, sqpart=self.sqpart[s0:s1], ls=self.ls_state))
             else:
                 launch.run = (lambda ph=ph, k=k: self.pbatch.run(ph, k, dt, ls=self.ls_state))
-        self.sqpart = torch.zeros(max(self._sq_slots, 1), dtype=torch.float32, device=self.device) if self.fused_sqnorm else None
+        n_sq = self._sq_slots + (1 if self.learn_lw and self.layer_trainable[loss_weights.LAYER] else 0)       # + the loss weights' slot (_plan_optimizer)
+        self.sqpart = torch.zeros(max(n_sq, 1), dtype=torch.float32, device=self.device) if self.fused_sqnorm else None
 
     def _plan_optimizer(self):
         cfg, dev = self.config, self.device
@@ -876,6 +891,13 @@ class Engine(object):
         self.normsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sq_ws = torch.empty(hip.sqnorm_ws_bytes(n) // 4, dtype=torch.float32, device=dev)
         if self.fused_sqnorm:
+            if self.learn_lw and self.layer_trainable[loss_weights.LAYER]:
+                # the two log-variances' gradients are written by the losses, not by a finalisation block: their squares reach the fused norm
+                # through one more slot of sqpart, the last one, filled by a squared norm over the layer's 8 floats of flat_g (padding is zero).
+                # The slot order is fixed, so a replay adds in the same order every time.
+                o, slot = self.slices[(loss_weights.LAYER, "ori_weight")][0], self._sq_slots
+                assert self.slices[(loss_weights.LAYER, "loc_weight")][0] == o + 4 and self.sqpart.numel() == slot + 1
+                self.opt_ops.append(_Launch(lambda: hip.sqnorm(8, self.flat_g[o:o + 8], self.sq_ws, self.sqpart[slot:slot + 1]), "sqnorm_lw"))
             self.opt_ops.append(_Launch(lambda: hip.sqnorm_final(self.sqpart, self.normsq), "sqnorm"))
         else:
             self.opt_ops.append(_Launch(lambda: hip.sqnorm(n, self.flat_g, self.sq_ws, self.normsq), "sqnorm"))
@@ -1090,6 +1112,7 @@ class Engine(object):
         gz_loc = torch.empty(loc.numel, dtype=self.tdt, device=dev)
         loc.grad, loc.grad_written = gz_loc, True
         wl = float(lw.get("loc_loss", 1.))
+        lw_loc, lw_ori = self._lw_views("loc_weight"), self._lw_views("ori_weight")      # None: LEARNABLE_LOSS_WEIGHTS off, the plain launches
         if cfg.REGRESS_LOC:
             self.gt_loc = torch.zeros(B, 3, dtype=torch.float32, device=dev)
             self.rel_exact = bool(getattr(cfg, "DP_EXACT_REL_LOSS", False))
@@ -1103,11 +1126,11 @@ class Engine(object):
                                                                            self.loss_buf[0:1], gz_loc), "loss"))
             else:
                 self.loss_ops.append(_Launch(lambda: hip.rel_l2(B, 3, 8, self.gt_loc, loc.data, wl, dt, self.loss_buf[0:1], gz_loc, self.rel_norms,
-                                                                ls=self.ls_state), "loss"))
+                                                                ls=self.ls_state, lw=lw_loc), "loss"))
         else:
             self.gt_loc = torch.zeros(B, nloc, dtype=torch.float32, device=dev)
             self.loss_ops.append(_Launch(lambda: hip.softmax_xent(B, nloc, loc.data, self.gt_loc, wl, 1, dt, self.loss_buf[0:1], gz_loc, self.row_ws,
-                                                                  ls=self.ls_state), "loss"))
+                                                                  ls=self.ls_state, lw=lw_loc), "loss"))
         # orientation head
         gz_ori = torch.empty(ori.numel, dtype=self.tdt, device=dev)
         ori.grad, ori.grad_written = gz_ori, True
@@ -1117,11 +1140,19 @@ class Engine(object):
             self.gt_ori = torch.zeros(B, d, dtype=torch.float32, device=dev)
             qo = self.q_out if self.quat_head else None
             self.loss_ops.append(_Launch(lambda: hip.absdot(B, d, 8, 1 if self.quat_head else 0, self.gt_ori, ori.data, wo, dt, qo,
-                                                            self.loss_buf[1:2], gz_ori, ls=self.ls_state), "loss"))
+                                                            self.loss_buf[1:2], gz_ori, ls=self.ls_state, lw=lw_ori), "loss"))
         else:
             self.gt_ori = torch.zeros(B, nori, dtype=torch.float32, device=dev)
             self.loss_ops.append(_Launch(lambda: hip.softmax_xent(B, nori, ori.data, self.gt_ori, wo, 1, dt, self.loss_buf[1:2], gz_ori, self.row_ws,
-                                                                  ls=self.ls_state), "loss"))
+                                                                  ls=self.ls_state, lw=lw_ori), "loss"))
+
+    def _lw_views(self, wn):
+        """(s, ds) of one learnable loss weight: one-element views into flat_w / flat_g (ds None while the layer is frozen: the loss is
+        re-weighted by exp(-s), s gets no gradient and its slot of flat_g stays zero).  None when the feature is off."""
+        if not self.learn_lw:
+            return None
+        o = self.slices[(loss_weights.LAYER, wn)][0]
+        return self.flat_w[o:o + 1], (self.flat_g[o:o + 1] if self.layer_trainable[loss_weights.LAYER] else None)
 
     def _plan_compact_gradients(self, need):
         """A block output X whose only consumers are the stride-2 pointwise layers of the next stage's first block (net.py:121-126:
@@ -1734,6 +1765,11 @@ class Engine(object):
         if self.ls_state is not None:
             self.ls_state.copy_(torch.tensor(self._ls_init, dtype=torch.float32))
 
+    def loss_weight_values(self):
+        """[ori_weight, loc_weight] as a strided two-element view of flat_w (Config.LEARNABLE_LOSS_WEIGHTS; no copy, no synchronisation)."""
+        o = self.slices[(loss_weights.LAYER, "ori_weight")][0]
+        return self.flat_w[o:o + 8:4]
+
     def loss_scale(self):
         """{scale, skipped_total, last_step_skipped, good_steps} of the device-side loss-scale state, read once (one synchronising copy);
         None when Config.LOSS_SCALE is off."""
@@ -1751,6 +1787,9 @@ def initial_weights(graph, seed=1234, randomize_bn=False):
     rng = np.random.default_rng(seed)
     out = OrderedDict()
     for ln, ws in graph.params.items():
+        if graph.kinds.get(ln) == loss_weights.KIND:
+            out[ln] = loss_weights.initial_values()
+            continue
         p = OrderedDict()
         for wn, shape in ws.items():
             if wn == "kernel":

@@ -248,6 +248,10 @@ LOSS_SCALE_SYMBOLS = sorted(_LS_SIGS)
 # the extension library liburso_ext.so, include/ursonet_ext.h: bound by ext_lib() on first use
 _EXT_SIGS = {
     "urso_pose_fuse_views": (_i, [C.POINTER(PoseFuseViewsArgs), _vp]),
+    # learnable loss weights (ursonet_amd/loss_weights.py): the plain signatures + s, ds and the loss-scale state in front of the stream
+    "urso_softmax_xent_fwd_bwd_lw": (_i, [_i, _i, _fp, _fp, _f, _i, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
+    "urso_rel_l2_fwd_bwd_lw": (_i, [_i, _i, _i, _fp, _fp, _f, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
+    "urso_absdot_fwd_bwd_lw": (_i, [_i, _i, _i, _i, _fp, _fp, _f, _i, _fp, _fp, _vp, _fp, _fp, _fp, _vp]),
 }
 EXT_SYMBOLS = sorted(_EXT_SIGS)
 
@@ -686,9 +690,22 @@ def maxpool_bwd(B, H, W, Cc, dt, y, dy, argmax, relu_mask, dx, stream=None):
                                     stream_ptr(stream)), "urso_maxpool3x3s2_bwd")
 
 
-def softmax_xent(B, K, logits, labels, weight, relu_mask, dt, loss, dz, row_ws, stream=None, ls=None):
+def _lw_ptrs(lw):
+    """lw = (s, ds): one-element fp32 device tensors, the trainable log-variance of a loss and its gradient slot (ds None: s is frozen)."""
+    s, ds = lw
+    assert s.dtype == torch.float32 and s.numel() == 1 and (ds is None or (ds.dtype == torch.float32 and ds.numel() == 1))
+    return ptr(s), ptr(ds)
+
+
+def softmax_xent(B, K, logits, labels, weight, relu_mask, dt, loss, dz, row_ws, stream=None, ls=None, lw=None):
     """ls (here and in rel_l2 / absdot / mse): the loss-scale state buffer -- the gradient is multiplied by its scale in front of the
-    rounding to dt (the *_ls entry points); None: the plain entry point."""
+    rounding to dt (the *_ls entry points); None: the plain entry point.
+    lw (here and in rel_l2 / absdot) = (s, ds): the learnable-loss-weight form of liburso_ext.so (the *_lw entry points; ls may be set too)."""
+    if lw is not None:
+        _chk(ext_lib().urso_softmax_xent_fwd_bwd_lw(B, K, ptr(logits), ptr(labels), weight, int(relu_mask), dt, ptr(loss), ptr(dz), ptr(row_ws),
+                                                    *_lw_ptrs(lw), _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)),
+             "urso_softmax_xent_fwd_bwd_lw")
+        return
     if ls is not None:
         _chk(_lib.urso_softmax_xent_fwd_bwd_ls(B, K, ptr(logits), ptr(labels), weight, int(relu_mask), dt, ptr(loss), ptr(dz),
                                                ptr(row_ws), _ls_ptr(ls), stream_ptr(stream)), "urso_softmax_xent_fwd_bwd_ls")
@@ -706,7 +723,11 @@ def rel_l2_from_norms(B, D, ld, gt, pred, weight, gscale, dt, norms, loss, dpred
                                      stream_ptr(stream)), "urso_rel_l2_from_norms")
 
 
-def rel_l2(B, D, ld, gt, pred, weight, dt, loss, dpred, norms=None, stream=None, ls=None):
+def rel_l2(B, D, ld, gt, pred, weight, dt, loss, dpred, norms=None, stream=None, ls=None, lw=None):
+    if lw is not None:
+        _chk(ext_lib().urso_rel_l2_fwd_bwd_lw(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), ptr(norms), *_lw_ptrs(lw),
+                                              _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_rel_l2_fwd_bwd_lw")
+        return
     if ls is not None:
         _chk(_lib.urso_rel_l2_fwd_bwd_ls(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), ptr(norms), _ls_ptr(ls),
                                          stream_ptr(stream)), "urso_rel_l2_fwd_bwd_ls")
@@ -715,7 +736,11 @@ def rel_l2(B, D, ld, gt, pred, weight, dt, loss, dpred, norms=None, stream=None,
                                   stream_ptr(stream)), "urso_rel_l2_fwd_bwd")
 
 
-def absdot(B, D, ld, normalize, gt, x, weight, dt, q, loss, dx, stream=None, ls=None):
+def absdot(B, D, ld, normalize, gt, x, weight, dt, q, loss, dx, stream=None, ls=None, lw=None):
+    if lw is not None:
+        _chk(ext_lib().urso_absdot_fwd_bwd_lw(B, D, ld, int(normalize), ptr(gt), ptr(x), weight, dt, ptr(q), ptr(loss), ptr(dx), *_lw_ptrs(lw),
+                                              _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_absdot_fwd_bwd_lw")
+        return
     if ls is not None:
         _chk(_lib.urso_absdot_fwd_bwd_ls(B, D, ld, int(normalize), ptr(gt), ptr(x), weight, dt, ptr(q), ptr(loss), ptr(dx), _ls_ptr(ls),
                                          stream_ptr(stream)), "urso_absdot_fwd_bwd_ls")

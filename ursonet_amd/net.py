@@ -182,8 +182,10 @@ def write_weights_file(path, params):
 class BatchLogger(object):
     """net.py:1106-1115 -- per-batch loss history returned by train()."""
 
-    def __init__(self):
+    def __init__(self, loss_weights=False):
         self.ori_loss_acc, self.loc_loss_acc = [], []
+        if loss_weights:                               # Config.LEARNABLE_LOSS_WEIGHTS: the two log-variances after every step
+            self.ori_weight_acc, self.loc_weight_acc = [], []
 
 
 ############################################################
@@ -205,10 +207,16 @@ class UrsoNet(object):
         graph = build_graph(config)                   # raises the 'dividable by 2 at least 6 times' Exception
         self._graph = graph
         self._dp, self._rank, self._world = None, 0, 1
+        from . import loss_weights
+        if loss_weights.enabled(config, mode):          # the layer the training engine adds to its own graph (ursonet_amd/loss_weights.py)
+            loss_weights.validate(config)              # ValueError: REGRESS_KEYPOINTS / DP_EXACT_REL_LOSS
+            loss_weights.add_layer(graph)
         if build_engine:
             from .engine import Engine
             from . import dp, loss_scale
             world = dp.launcher_world()[2]
+            if mode == "training":
+                loss_weights.validate(config, world)   # ValueError: set under a data-parallel launcher
             if mode == "training":
                 loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
             if mode == "training" and world > 1:
@@ -337,7 +345,7 @@ class UrsoNet(object):
         train_feed = DeviceFeeder(eng, train_dataset, cfg, shuffle=True, workers=workers, rank=rank, world=world)
         val_feed = (DeviceFeeder(eng, val_dataset, cfg, shuffle=True, workers=workers, rank=rank, world=world)
                     if int(cfg.VALIDATION_STEPS) > 0 else None)
-        history_full = BatchLogger()
+        history_full = BatchLogger(loss_weights=eng.learn_lw)
         chief = rank == 0
         if chief:
             log("\nStarting at epoch {}. LR={}\n".format(self.epoch, learning_rate))
@@ -361,6 +369,9 @@ class UrsoNet(object):
                    if eng.ls_state is not None else None)
         if ls_hist is not None:
             history_full.loss_scale_acc, history_full.skipped_acc = [], []
+        # Config.LEARNABLE_LOSS_WEIGHTS: the two log-variances after every step, likewise (a strided view of flat_w: ori_weight, loc_weight)
+        lw_view = eng.loss_weight_values() if eng.learn_lw else None
+        lw_hist = torch.zeros(max(steps, 1), 2, dtype=torch.float32, device=eng.device) if lw_view is not None else None
         clr_it = 0
         for epoch in range(self.epoch, epochs):
             for i in range(steps):
@@ -372,6 +383,8 @@ class UrsoNet(object):
                 hist[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
                 if ls_hist is not None:
                     ls_hist[i].copy_(eng.ls_state, non_blocking=True)
+                if lw_hist is not None:
+                    lw_hist[i].copy_(lw_view, non_blocking=True)
             for i in range(vsteps):
                 val_feed.next_into()
                 eng.evaluate(read=False)
@@ -397,10 +410,16 @@ class UrsoNet(object):
                 history_full.loss_scale_acc += [float(x) for x in lh[:, LS.SCALE]]
                 history_full.skipped_acc += [bool(x) for x in lh[:, LS.LAST_SKIPPED]]
                 ls_text = "  loss_scale %g  skipped %d" % (float(lh[-1, LS.SCALE]), int(lh[:, LS.LAST_SKIPPED].sum()))
+            lw_text = ""
+            if lw_hist is not None and steps:
+                wh = lw_hist[:steps].cpu().numpy()
+                history_full.ori_weight_acc += [float(x) for x in wh[:, 0]]
+                history_full.loc_weight_acc += [float(x) for x in wh[:, 1]]
+                lw_text = "  ori var %.5f  loc var %.5f" % (float(np.exp(wh[-1, 0])), float(np.exp(wh[-1, 1])))      # exp(s), as net.py:1141-1142 would print
             if chief:
-                log("epoch %d  loc_loss %.5f  %s%s" % (
+                log("epoch %d  loc_loss %.5f  %s%s%s" % (
                     epoch + 1, float(np.mean(h[:, 0])) if steps else float("nan"),
-                    "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items())), ls_text))
+                    "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items())), ls_text, lw_text))
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))     # replicas are identical: one writer
             if world > 1:
                 import torch.distributed as dist
