@@ -81,14 +81,14 @@ def test_kernel_against_reference_evaluate():
         t, q_soft = _run_case(g, c)
         regress_loc, regress_ori, kp = (bool(x) for x in g[c + "/config"])
         q = t[:, hip.EVAL_Q_EST:hip.EVAL_Q_EST + 4]
-        qr = g[c + "/q_ref"]
+        qr = g[c + "/q_ref"].astype(np.float64)                                          # fp32 for the soft head: norms and dots in float64
         dq = 1 - np.abs(np.sum(q * qr, axis=1)) / (np.linalg.norm(q, axis=1) * np.linalg.norm(qr, axis=1))   # q_out is unit only to fp32
         if regress_ori or kp:
             assert np.all(dq <= 1e-10), (c, dq)
             tol = 1e-9
         else:
             assert np.array_equal(q, q_soft.astype(np.float64)), c                        # bit-equal to urso_quat_wavg_decode
-            assert np.all(dq <= 1e-5), (c, dq)
+            assert np.all(dq <= 1e-9), (c, dq)        # margin over the golden's and the kernel's fp32 rounding: tests/test_poseref_cpu.py
             # triangle inequality: |err(q) - err(q_ref)| <= angle(q, q_ref), plus the first-order effect of |q| != 1 (the decode's
             # quaternion is unit to fp32) on 2 acos|q . q_gt|
             bound = np.degrees(_angle(q, qr) + _norm_term(q, g[c + "/q_gt"]) + _fp32_term(q, g[c + "/q_gt"])) + 1e-6
