@@ -108,6 +108,38 @@ int urso_rel_l2_fwd_bwd_lw(int B, int D, int ld, const float* gt_d, const float*
 int urso_absdot_fwd_bwd_lw(int B, int D, int ld, int normalize, const float* gt_d, const float* x_d, float weight, int dt, float* q_d,
                            float* loss_d, void* dx_d, const float* s_d, float* ds_d, const float* ls_state_d, void* stream);
 
+/*
+ * Exponential moving average of the weights (Config.WEIGHT_EMA; ursonet_amd/weight_ema.py is the same rule in NumPy
+ * float32).  The reference has none.  The state is ONE fp32 buffer of URSO_EMA_FIELDS floats in device memory:
+ *   URSO_EMA_DECAY       the configured decay, in (0, 1)
+ *   URSO_EMA_WARMUP      0 or 1: with 1 the decay follows the TensorFlow num_updates schedule below
+ *   URSO_EMA_UPDATES     t, the updates done so far; saturates at 2^24, where an fp32 counter stops
+ *   URSO_EMA_NEXT_DECAY  d, the decay the next update will use
+ *   4..7                 reserved, zero
+ *
+ * urso_ema_update, one streaming launch and a one-thread launch behind it on the same stream.  For every i < n, with d read from the state:
+ *   c      = 1.0f - d
+ *   ema[i] = ema[i] + c * (w[i] - ema[i])
+ * three fp32 operations, each rounded once, compiled without contraction: the result is a function of the inputs alone.  Nothing is
+ * guarded: a NaN in w reaches ema.  Where w[i] == ema[i] the difference is exactly 0 and ema[i] keeps its bits (a frozen layer's average
+ * is its weights).  Then, after every block has read d, the state advances:
+ *   t          = min(t + 1, 2^24)
+ *   NEXT_DECAY = decay                                               (warm-up off)
+ *   NEXT_DECAY = min(decay, fl32((1.0f + t) / (10.0f + t)))          (warm-up on, with the new t; the quotient of the two fp32 sums is
+ *                                                                     correctly rounded, whatever the compiler's fp32 division mode)
+ * ls_state_d is the loss-scale state of ursonet_loss_scale.h or NULL.  When it is set and state[URSO_LS_LAST_SKIPPED] != 0 the optimizer
+ * skipped this step: ema keeps its bits and the state is not advanced (call it behind urso_loss_scale_update).
+ *
+ * urso_ema_swap exchanges the bit patterns of two fp32 buffers in place, NaN payloads included (they move as 32-bit integers).
+ *
+ * Both: no allocation, no synchronisation; n == 0 launches nothing and advances nothing.  Bad arguments return URSO_EINVAL before any
+ * launch: a null w / ema / state (a / b), n < 0, a pointer that is not 4-byte aligned, a == b.  Buffers that are 16-byte aligned, or
+ * misaligned alike, are moved 16 bytes per access; the two buffers must not overlap unless they are the same (update only).
+ */
+enum { URSO_EMA_DECAY = 0, URSO_EMA_WARMUP = 1, URSO_EMA_UPDATES = 2, URSO_EMA_NEXT_DECAY = 3, URSO_EMA_FIELDS = 8 };
+int urso_ema_update(int64_t n, const float* w_d, float* ema_d, float* state_d, const float* ls_state_d, void* stream);
+int urso_ema_swap(int64_t n, float* a_d, float* b_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

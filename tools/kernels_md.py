@@ -49,6 +49,7 @@ FAMILIES = [
     ("maxpool", "pool_loss_optim.hip", "4x8 output tiles", "3x3/s2 max-pool"),
     ("mold_kernel", "pool_loss_optim.hip", "elementwise", "uint8 -> mean-subtracted packed input"),
     ("sgd_kernel", "pool_loss_optim.hip", "elementwise", "clip + momentum SGD"),
+    ("ema_update_kernel", "csrc_ext/weight_ema.hip", "elementwise, 16-byte accesses, grid-stride over <= 4096 blocks", "Config.WEIGHT_EMA (opt-in): the weights' moving average behind the optimizer"),
     ("sqnorm", "pool_loss_optim.hip", "two-level reduction", "global gradient norm"),
 ]
 

@@ -77,6 +77,9 @@ class Config(object):
     LOSS_SCALE_GROWTH_INTERVAL = 2000
     LOSS_SCALE_MIN = 1.0
     LOSS_SCALE_MAX = 2.0 ** 24
+    # Not reference fields: an exponential moving average of the weights kept on the device (ursonet_amd/weight_ema.py).
+    WEIGHT_EMA = None             # None = off (nothing changes) | the decay, a float in (0, 1): train() also validates and saves the average.  One GPU only.
+    WEIGHT_EMA_WARMUP = True      # the decay of update t + 1 is min(WEIGHT_EMA, (1 + t) / (10 + t)); False = WEIGHT_EMA from the first update on
 
     def update(self):
         """Derived fields (config.py:151-166)."""

@@ -280,6 +280,8 @@ class DataParallelEngine(object):
         if self.world > 1 and getattr(engine, "learn_lw", False):
             from . import loss_weights
             loss_weights.validate(engine.config, self.world)    # ValueError: the two scalars' gradients are not part of the exchange
+        if self.world > 1 and getattr(engine, "ema_state", None) is not None:
+            raise ValueError("WEIGHT_EMA is not supported under data parallelism (world size %d): leave Config.WEIGHT_EMA = None" % self.world)
         # DP_EXACT_REL_LOSS: the location loss is ONE ratio of norms over the global batch (net.py:750-762); its two squared norms are
         # summed over the ranks between forward and backward and the gradient is pre-scaled by the world size (undone by the averaging)
         self.rel_exact = bool(getattr(engine, "rel_exact", False)) and bool(engine.loss_pre_ops)

@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import hip, loss_scale, loss_weights
+from . import hip, loss_scale, loss_weights, weight_ema
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -92,6 +92,12 @@ class Engine(object):
         self.plan_version, self.halo_ws, self.rel_scale = 0, None, None
         self.hyper = self.flat_v2 = self.flat_vhat = None
         self.ls_state = self._ls_init = None           # Config.LOSS_SCALE: the device-side loss-scale state (ursonet_amd/loss_scale.py), created once like hyper
+        # Config.WEIGHT_EMA: a second flat buffer that follows flat_w behind every optimizer step, and its device-side
+        # schedule state (ursonet_amd/weight_ema.py); both created once like hyper.  ema_swapped: flat_w holds the average right now (swap_ema)
+        self.flat_ema = self.ema_state = self._ema_init = None
+        self.ema_swapped = False
+        if weight_ema.enabled(config, mode):
+            weight_ema.initial_state(config, self.world_size_hint())       # ValueError before anything is allocated
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -123,6 +129,8 @@ class Engine(object):
         if self.mode == "training":
             self.flat_g = torch.zeros_like(self.flat_w)
             self.flat_v = torch.zeros_like(self.flat_w)
+            if weight_ema.enabled(self.config, self.mode):
+                self.flat_ema = torch.zeros_like(self.flat_w)          # set_weights below fills it: the average starts at the weights
         self.set_weights(initial_weights(g, seed, randomize_bn))
 
     def wview(self, ln, wn, buf=None):
@@ -138,7 +146,10 @@ class Engine(object):
         return self.wview(ln, wn, self.flat_g)
 
     def set_weights(self, params, strict=True):
-        """params: {layer: {weight: array}} in Keras layouts.  Missing layers are skipped unless strict."""
+        """params: {layer: {weight: array}} in Keras layouts.  Missing layers are skipped unless strict.  With Config.WEIGHT_EMA the values
+        go into the average as well: a model that loads a checkpoint starts its average there (set_ema_weights loads another one)."""
+        assert not getattr(self, "ema_swapped", False), "set_weights while the average is swapped in (swap_ema / ema_weights)"
+        ema = getattr(self, "flat_ema", None)
         for ln, ws in self.graph.params.items():
             if ln not in params:
                 if strict:
@@ -149,11 +160,35 @@ class Engine(object):
                 if tuple(a.shape) != tuple(shape):
                     raise ValueError("layer %s weight %s: shape %s != expected %s" % (ln, wn, a.shape, shape))
                 self.wview(ln, wn).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+                if ema is not None and (ln, wn) in self.slices:
+                    self.wview(ln, wn, ema).copy_(self.wview(ln, wn))
 
-    def get_weights(self):
+    def set_ema_weights(self, params, strict=True):
+        """Load params (as set_weights takes them) into the average alone; the BN statistics, which both sets share, are not touched."""
+        assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
+        assert not self.ema_swapped, "set_ema_weights while the average is swapped in (swap_ema / ema_weights)"
+        for ln, ws in self.graph.params.items():
+            if ln not in params:
+                if strict:
+                    raise KeyError("missing layer %r" % ln)
+                continue
+            for wn, shape in ws.items():
+                if (ln, wn) not in self.slices:
+                    continue
+                a = np.asarray(params[ln][wn], dtype=np.float32)
+                if tuple(a.shape) != tuple(shape):
+                    raise ValueError("layer %s weight %s: shape %s != expected %s" % (ln, wn, a.shape, shape))
+                self.wview(ln, wn, self.flat_ema).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+
+    def get_weights(self, ema=False):
+        """{layer: {weight: array}}.  ema=True: the averaged parameters (Config.WEIGHT_EMA) beside the BN statistics, which both sets share.
+        Either set is found wherever it lies: inside ema_weights() the two buffers have changed places."""
+        if ema:
+            assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
+        buf = (self.flat_ema, self.flat_w)[bool(ema) == self.ema_swapped] if self.flat_ema is not None else None
         out = OrderedDict()
         for ln, ws in self.graph.params.items():
-            out[ln] = OrderedDict((wn, self.wview(ln, wn).detach().cpu().numpy().copy()) for wn in ws)
+            out[ln] = OrderedDict((wn, self.wview(ln, wn, buf).detach().cpu().numpy().copy()) for wn in ws)
         return out
 
     def get_grads(self):
@@ -210,6 +245,19 @@ class Engine(object):
                 self.ls_state.copy_(torch.tensor(init, dtype=torch.float32))
         if training and self.learn_lw:
             loss_weights.validate(self.config, self.world_size)
+        # Config.WEIGHT_EMA: None = no launch and no buffer.  Set: one more launch at the end of opt_ops (_plan_optimizer)
+        if training:
+            init = weight_ema.initial_state(self.config, self.world_size)
+            if init is None:
+                self.ema_state = self._ema_init = None
+            elif self.ema_state is None:
+                self._ema_init = init
+                self.ema_state = torch.tensor(init, dtype=torch.float32, device=self.device)
+                if self.flat_ema is None:              # the key was set after the engine was built: the average starts at the weights of now
+                    self.flat_ema = self.flat_w.clone()
+            elif init != self._ema_init:               # the keys changed between plans: the schedule starts afresh, the average stays
+                self._ema_init = init
+                self.ema_state.copy_(torch.tensor(init, dtype=torch.float32))
         self.acts = {}
         self.prep_ops, self.fwd_ops, self.loss_ops, self.bwd_ops, self.opt_ops = [], [], [], [], []      # lists of _Launch (plan_state.py)
         self.wino_ws = None
@@ -909,6 +957,8 @@ class Engine(object):
                                                                       ls=self.ls_state), "sgd"))
         if self.ls_state is not None:                  # after the optimizer: all of its blocks have read the norm and the state
             self.opt_ops.append(_Launch(lambda: hip.loss_scale_update(self.ls_state, self.normsq), "loss_scale"))
+        if self.ema_state is not None:                 # last: behind the optimizer, and behind loss_scale so that LAST_SKIPPED is this step's
+            self.opt_ops.append(_Launch(lambda: hip.ema_update(n, self.flat_w, self.flat_ema, self.ema_state, ls=self.ls_state), "ema"))
 
     def _fork_weight_gradients(self):
         """Weight-gradient launches are leaves of the backward pass: nothing reads their partials before the bucket's reduction, every tensor
@@ -1623,7 +1673,8 @@ class Engine(object):
             for _ in range(n):
                 gr.replay()
             torch.cuda.synchronize(self.device)
-            got = [t.clone() for t in (self.flat_w, self.flat_g, self.flat_v, self.flat_stats)]
+            written = (self.flat_w, self.flat_g, self.flat_v, self.flat_stats) + ((self.flat_ema, self.ema_state) if self.ema_state is not None else ())
+            got = [t.clone() for t in written]
             self.restore_train_state(saved)
             self._single_chain = True
             try:
@@ -1632,7 +1683,7 @@ class Engine(object):
             finally:
                 self._single_chain = False
             torch.cuda.synchronize(self.device)
-            ok = all(torch.equal(a, b) for a, b in zip(got, (self.flat_w, self.flat_g, self.flat_v, self.flat_stats)))
+            ok = all(torch.equal(a, b) for a, b in zip(got, written))
             ok = ok and bool(torch.isfinite(self.flat_g).all())       # (NaN never equals NaN: a non-finite check batch proves nothing either way)
             self.restore_train_state(saved)
         self.fork_checks += 1
@@ -1663,6 +1714,7 @@ class Engine(object):
 
     def step(self):
         """Replay the captured training step (captures on first use)."""
+        assert not self.ema_swapped, "step() while the average is swapped in: leave ema_weights() / call swap_ema() again first"
         if self._graphs is None:
             self.capture()
         self._graphs.replay()
@@ -1747,6 +1799,8 @@ class Engine(object):
         st = [self.flat_w.clone(), self.flat_v.clone(), self.flat_stats.clone()]
         if self.adam:
             st += [self.flat_v2.clone(), self.flat_vhat.clone(), self.hyper.clone()]
+        if self.ema_state is not None:                 # (in front of the loss-scale state, which restore_train_state finds at the end)
+            st += [self.flat_ema.clone(), self.ema_state.clone()]
         if self.ls_state is not None:
             st.append(self.ls_state.clone())
         return st
@@ -1755,10 +1809,14 @@ class Engine(object):
         self.flat_w.copy_(st[0]); self.flat_v.copy_(st[1]); self.flat_stats.copy_(st[2])
         if self.adam:
             self.flat_v2.copy_(st[3]); self.flat_vhat.copy_(st[4]); self.hyper.copy_(st[5])
+        if self.ema_state is not None:
+            k = 6 if self.adam else 3
+            self.flat_ema.copy_(st[k]); self.ema_state.copy_(st[k + 1])
         if self.ls_state is not None:
             self.ls_state.copy_(st[-1])
 
     def reset_optimizer(self):
+        """Zero the optimizer's moments (and restart the loss scale).  The weights' average and its schedule are no optimizer state: they stay."""
         self.flat_v.zero_()
         if self.adam:
             self.flat_v2.zero_(); self.flat_vhat.zero_(); self.hyper[5] = 0.0
@@ -1776,6 +1834,34 @@ class Engine(object):
         if self.ls_state is None:
             return None
         return loss_scale.as_dict(self.ls_state.detach().cpu().tolist())
+
+    def weight_ema(self):
+        """{decay, warmup, updates, next_decay} of the device-side state of the weights' average, read once (one synchronising copy); None
+        when Config.WEIGHT_EMA is off."""
+        if self.ema_state is None:
+            return None
+        return weight_ema.as_dict(self.ema_state.detach().cpu().tolist())
+
+    def swap_ema(self):
+        """Exchange flat_w and flat_ema in place (urso_ema_swap) and flip ema_swapped.  Every forward pass reads flat_w only through the prep
+        pass, which evaluate() and the captured step both begin with, so nothing else has to move; the BN statistics are shared."""
+        assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
+        hip.ema_swap(self.n_flat, self.flat_w, self.flat_ema)
+        self.ema_swapped = not self.ema_swapped
+
+    def ema_weights(self):
+        """Context manager: the averaged weights are the model's inside (evaluate() and every forward pass), the raw ones are back after it."""
+        eng = self
+
+        class _Ctx(object):
+            def __enter__(self):
+                eng.swap_ema()
+                return eng
+
+            def __exit__(self, *exc):
+                eng.swap_ema()
+                return False
+        return _Ctx()
 
     def flops(self):
         return conv_flops(self.graph, self.B)

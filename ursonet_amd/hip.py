@@ -113,6 +113,7 @@ class PoseFuseViewsArgs(C.Structure):
 # urso_pose_fuse_views table columns (include/ursonet_ext.h); columns 0..10 are urso_pose_eval's
 FUSE_LOC_EST, FUSE_Q_EST, FUSE_LOC_ERR, FUSE_ORI_ERR, FUSE_ESA, FUSE_DIST = 0, 3, 7, 8, 9, 10
 FUSE_LOC_SPREAD, FUSE_ORI_SPREAD, FUSE_VIEW_LAMBDA, FUSE_N_VIEWS, FUSE_COLS, FUSE_MAX_VIEWS = 11, 12, 13, 14, 16, 64
+EMA_DECAY, EMA_WARMUP, EMA_UPDATES, EMA_NEXT_DECAY, EMA_FIELDS = 0, 1, 2, 3, 8       # URSO_EMA_* of include/ursonet_ext.h
 
 
 class DenseWgradLayer(C.Structure):
@@ -252,6 +253,9 @@ _EXT_SIGS = {
     "urso_softmax_xent_fwd_bwd_lw": (_i, [_i, _i, _fp, _fp, _f, _i, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
     "urso_rel_l2_fwd_bwd_lw": (_i, [_i, _i, _i, _fp, _fp, _f, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
     "urso_absdot_fwd_bwd_lw": (_i, [_i, _i, _i, _i, _fp, _fp, _f, _i, _fp, _fp, _vp, _fp, _fp, _fp, _vp]),
+    # the weights' moving average (ursonet_amd/weight_ema.py): n, w, ema, state, loss-scale state | n, a, b
+    "urso_ema_update": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
+    "urso_ema_swap": (_i, [C.c_int64, _fp, _fp, _vp]),
 }
 EXT_SYMBOLS = sorted(_EXT_SIGS)
 
@@ -779,6 +783,21 @@ def sgd_momentum_clip(n, w, g, v, hyper, normsq, stream=None, ls=None):
 def loss_scale_update(state, normsq, stream=None):
     """urso_loss_scale_update: the rule of ursonet_amd.loss_scale.next_state on the device, after the optimizer of the step."""
     _chk(_lib.urso_loss_scale_update(_ls_ptr(state), ptr(normsq), stream_ptr(stream)), "urso_loss_scale_update")
+
+
+def ema_update(n, w, ema, state, stream=None, ls=None):
+    """urso_ema_update (liburso_ext.so): ema += (1 - d) (w - ema) over n fp32 elements with d = state[EMA_NEXT_DECAY], then the state advances
+    (ursonet_amd.weight_ema.update32 / next_state on the device).  ls: the loss-scale state; a step it marks as skipped changes nothing."""
+    assert w.dtype == torch.float32 and ema.dtype == torch.float32 and state.dtype == torch.float32 and state.numel() >= EMA_FIELDS
+    assert 0 <= n <= min(w.numel(), ema.numel())
+    _chk(ext_lib().urso_ema_update(n, ptr(w), ptr(ema), ptr(state), _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)),
+         "urso_ema_update")
+
+
+def ema_swap(n, a, b, stream=None):
+    """urso_ema_swap (liburso_ext.so): exchange the bit patterns of the first n elements of two 4-byte-element buffers in place."""
+    assert a.element_size() == 4 and b.element_size() == 4 and 0 <= n <= min(a.numel(), b.numel())
+    _chk(ext_lib().urso_ema_swap(n, ptr(a), ptr(b), stream_ptr(stream)), "urso_ema_swap")
 
 
 def adam_amsgrad_clip(n, w, g, m, v, vhat, hyper, normsq, stream=None, ls=None):

@@ -179,11 +179,19 @@ def write_weights_file(path, params):
     return written
 
 
+def ema_checkpoint_path(path):
+    """The averaged twin of a checkpoint (Config.WEIGHT_EMA): `ema_` in front of the file name, in the same directory.  find_last and
+    get_last_checkpoint pick files that start with `weights`, so they never see it."""
+    return os.path.join(os.path.dirname(path), "ema_" + os.path.basename(path))
+
+
 class BatchLogger(object):
     """net.py:1106-1115 -- per-batch loss history returned by train()."""
 
-    def __init__(self, loss_weights=False):
+    def __init__(self, loss_weights=False, weight_ema=False):
         self.ori_loss_acc, self.loc_loss_acc = [], []
+        if weight_ema:                                 # Config.WEIGHT_EMA: the decay that every step's update of the average used
+            self.ema_decay_acc = []
         if loss_weights:                               # Config.LEARNABLE_LOSS_WEIGHTS: the two log-variances after every step
             self.ori_weight_acc, self.loc_weight_acc = [], []
 
@@ -219,6 +227,8 @@ class UrsoNet(object):
                 loss_weights.validate(config, world)   # ValueError: set under a data-parallel launcher
             if mode == "training":
                 loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
+                from . import weight_ema
+                weight_ema.initial_state(config, world)     # ValueError: a bad WEIGHT_EMA, or one set under a data-parallel launcher
             if mode == "training" and world > 1:
                 # under a launcher (`python -m torch.distributed.run --nproc-per-node N pose_estimator.py train ...`): one process per GPU, this
                 # rank's engine takes IMAGES_PER_GPU samples of every global batch of IMAGES_PER_GPU x WORLD_SIZE, the gradient exchange is
@@ -276,10 +286,23 @@ class UrsoNet(object):
                 raise ValueError("weights file lacks layers %s (use by_name=True)" % missing[:5])
         known = OrderedDict((ln, ws) for ln, ws in params.items() if ln in self._graph.params)
         self._engine.set_weights(known, strict=False)
+        # Config.WEIGHT_EMA, training mode: set_weights started the average at the loaded weights; a checkpoint's averaged sibling
+        # (ema_weights_... beside weights_..., written by train()) takes their place where there is one
+        sibling = ema_checkpoint_path(weights_in_path)
+        if getattr(self._engine, "flat_ema", None) is not None and os.path.exists(sibling):
+            ema = read_weights_file(sibling)
+            self._engine.set_ema_weights(OrderedDict((ln, ws) for ln, ws in ema.items() if ln in self._graph.params and ln not in (exclude or ())),
+                                         strict=False)
         self.set_log_dir(weights_out_path)
 
-    def save_weights(self, path):
-        return write_weights_file(path, self._engine.get_weights())
+    def save_weights(self, path, ema=False):
+        """ema=True (Config.WEIGHT_EMA): the averaged weights, as an ordinary weights file (the BN statistics are the ones both sets share)."""
+        return write_weights_file(path, self._engine.get_weights(ema=True) if ema else self._engine.get_weights())
+
+    def ema_weights(self):
+        """Context manager (Config.WEIGHT_EMA, training mode): inside it the engine runs on the averaged weights -- for a custom evaluation
+        through the engine (evaluate(), forward()); the raw weights are back after it.  No training step may run inside."""
+        return self._engine.ema_weights()
 
     def get_imagenet_weights(self, architecture):
         """net.py:854-884 downloads from GitHub; there is no network here."""
@@ -345,7 +368,8 @@ class UrsoNet(object):
         train_feed = DeviceFeeder(eng, train_dataset, cfg, shuffle=True, workers=workers, rank=rank, world=world)
         val_feed = (DeviceFeeder(eng, val_dataset, cfg, shuffle=True, workers=workers, rank=rank, world=world)
                     if int(cfg.VALIDATION_STEPS) > 0 else None)
-        history_full = BatchLogger(loss_weights=eng.learn_lw)
+        use_ema = eng.ema_state is not None            # Config.WEIGHT_EMA: validate and save the average beside the raw weights
+        history_full = BatchLogger(loss_weights=eng.learn_lw, weight_ema=use_ema)
         chief = rank == 0
         if chief:
             log("\nStarting at epoch {}. LR={}\n".format(self.epoch, learning_rate))
@@ -372,6 +396,10 @@ class UrsoNet(object):
         # Config.LEARNABLE_LOSS_WEIGHTS: the two log-variances after every step, likewise (a strided view of flat_w: ori_weight, loc_weight)
         lw_view = eng.loss_weight_values() if eng.learn_lw else None
         lw_hist = torch.zeros(max(steps, 1), 2, dtype=torch.float32, device=eng.device) if lw_view is not None else None
+        # Config.WEIGHT_EMA: the schedule state in front of every step (its NEXT_DECAY is the decay that step's update uses) and a second
+        # validation history for the averaged weights, both device-side and read once per epoch
+        ema_hist = torch.zeros(max(steps, 1), int(eng.ema_state.numel()), dtype=torch.float32, device=eng.device) if use_ema else None
+        vhist_ema = torch.zeros(max(vsteps, 1), n_loss, dtype=torch.float32, device=eng.device) if use_ema else None
         clr_it = 0
         for epoch in range(self.epoch, epochs):
             for i in range(steps):
@@ -379,6 +407,8 @@ class UrsoNet(object):
                     eng.set_lr(utils.clr_triangular(clr_it, cfg.BASE_LEARNING_RATE, cfg.MAX_LEARNING_RATE, cfg.CLR_STEP_SIZE))
                     clr_it += 1
                 train_feed.next_into()
+                if ema_hist is not None:
+                    ema_hist[i].copy_(eng.ema_state, non_blocking=True)
                 runner.step()
                 hist[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
                 if ls_hist is not None:
@@ -389,6 +419,10 @@ class UrsoNet(object):
                 val_feed.next_into()
                 eng.evaluate(read=False)
                 vhist[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
+                if use_ema:                             # the same loaded batch under the averaged weights: two in-place exchanges around it
+                    with eng.ema_weights():
+                        eng.evaluate(read=False)
+                        vhist_ema[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
             if world == 1 and eng.forked:
                 eng.verify_fork()                       # the forked backward pass against the single chain on this epoch's last batch (engine.py)
             if world > 1:
@@ -403,6 +437,9 @@ class UrsoNet(object):
             if vsteps:
                 v = vhist[:vsteps].cpu().numpy().mean(0)
                 val = ({"loc_loss": v[0], "k2_loss": v[2], "k3_loss": v[3]} if kp else {"loc_loss": v[0], "ori_loss": v[1]})
+                if use_ema:
+                    v = vhist_ema[:vsteps].cpu().numpy().mean(0)
+                    val.update({"ema_loc_loss": v[0], "ema_k2_loss": v[2], "ema_k3_loss": v[3]} if kp else {"ema_loc_loss": v[0], "ema_ori_loss": v[1]})
             ls_text = ""
             if ls_hist is not None and steps:
                 from . import loss_scale as LS
@@ -416,11 +453,19 @@ class UrsoNet(object):
                 history_full.ori_weight_acc += [float(x) for x in wh[:, 0]]
                 history_full.loc_weight_acc += [float(x) for x in wh[:, 1]]
                 lw_text = "  ori var %.5f  loc var %.5f" % (float(np.exp(wh[-1, 0])), float(np.exp(wh[-1, 1])))      # exp(s), as net.py:1141-1142 would print
+            ema_text = ""
+            if ema_hist is not None and steps:
+                from . import weight_ema as WE
+                eh = ema_hist[:steps].cpu().numpy()
+                history_full.ema_decay_acc += [float(x) for x in eh[:, WE.NEXT_DECAY]]
+                ema_text = "  ema_decay %g" % float(eh[-1, WE.NEXT_DECAY])
             if chief:
-                log("epoch %d  loc_loss %.5f  %s%s%s" % (
+                log("epoch %d  loc_loss %.5f  %s%s%s%s" % (
                     epoch + 1, float(np.mean(h[:, 0])) if steps else float("nan"),
-                    "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items())), ls_text, lw_text))
+                    "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items())), ls_text, lw_text, ema_text))
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))     # replicas are identical: one writer
+                if use_ema:                             # "ema_" in front: find_last / get_last_checkpoint keep finding the raw file
+                    self.save_weights(ema_checkpoint_path(self.checkpoint_path.format(epoch=epoch + 1)), ema=True)
             if world > 1:
                 import torch.distributed as dist
                 dist.barrier()                          # nobody runs ahead of the checkpoint (find_last on another rank sees it)
