@@ -140,6 +140,39 @@ enum { URSO_EMA_DECAY = 0, URSO_EMA_WARMUP = 1, URSO_EMA_UPDATES = 2, URSO_EMA_N
 int urso_ema_update(int64_t n, const float* w_d, float* ema_d, float* state_d, const float* ls_state_d, void* stream);
 int urso_ema_swap(int64_t n, float* a_d, float* b_d, void* stream);
 
+/*
+ * Gradient accumulation over k micro-batches (Config.GRAD_ACCUM_STEPS; ursonet_amd/grad_accum.py is the same rule in
+ * NumPy float32).  The reference has none.  With g what a backward pass left in the flat gradient buffer and acc a second buffer of n floats:
+ *
+ * urso_grad_accum, one streaming launch behind the backward pass of a micro-step that does not close.  For every i < n:
+ *   first != 0:  acc[i] = g[i]                 the bits, NaN payloads included (they move as 32-bit integers)
+ *   first == 0:  acc[i] = acc[i] + g[i]        one fp32 add, rounded once
+ *
+ * urso_grad_accum_close, one streaming launch in front of the optimizer of the closing micro-step.  For every i < n:
+ *   g[i] = (acc[i] + g[i]) * c                 one fp32 add and one fp32 multiply, each rounded once; acc is only read
+ * c is fl32(1 / k), computed by the caller.  Compiled without contraction: every value is a function of the inputs alone.  Nothing is
+ * guarded: a non-finite value in either buffer reaches g.
+ *
+ * The grid.  Both launch B = urso_grad_accum_parts(n) = min(4096, ceil(ceil(n / 4) / 256)) blocks of 256 threads (0 for n <= 0), a function
+ * of n alone.  When g and acc sit alike against the 16-byte boundary, head = min(n, ((16 - address % 16) % 16) / 4) leading elements and the
+ * (n - head) % 4 trailing ones are scalars and the nvec = (n - head) / 4 groups of four between them are vectors; otherwise every element is
+ * a scalar (head = n, nvec = 0).  Thread t of the grid (t = 256 block + thread) handles the vectors t, t + 256 B, t + 512 B, ... and then
+ * the scalars t, t + 256 B, ... of the list [head elements, tail elements]: every element is read and written by exactly one thread, once.
+ *
+ * The slots.  The close launch also writes sqpart[b], b < B: the sum of squares of the values block b stored.  Every square v * v is
+ * rounded once and added to the thread's running sum (from 0.0f) in the order the thread stores: its vectors in order, x y z w each, then its
+ * scalars.  The 64 lanes of a wave are added by the xor shuffle (offsets 32, 16, 8, 4, 2, 1), the four wave sums in wave order from 0.0f:
+ * the order of the urso_param_batch_run_sq slots, so urso_sqnorm_final over the B slots yields the squared norm of the closed gradient
+ * without a pass over it.  A non-finite stored value makes its slot non-finite.
+ *
+ * All: no allocation, no synchronisation; n == 0 launches nothing (and wants nparts == 0).  Bad arguments return URSO_EINVAL before any
+ * launch: a null g / acc / sqpart, n < 0, a pointer that is not 4-byte aligned, g == acc, nparts != urso_grad_accum_parts(n).  The two
+ * buffers must not overlap.
+ */
+int urso_grad_accum(int64_t n, const float* g_d, float* acc_d, int first, void* stream);
+int urso_grad_accum_parts(int64_t n);
+int urso_grad_accum_close(int64_t n, float* g_d, const float* acc_d, float c, float* sqpart_d, int nparts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,8 @@ FAMILIES = [
     ("mold_kernel", "pool_loss_optim.hip", "elementwise", "uint8 -> mean-subtracted packed input"),
     ("sgd_kernel", "pool_loss_optim.hip", "elementwise", "clip + momentum SGD"),
     ("ema_update_kernel", "csrc_ext/weight_ema.hip", "elementwise, 16-byte accesses, grid-stride over <= 4096 blocks", "Config.WEIGHT_EMA (opt-in): the weights' moving average behind the optimizer"),
+    ("grad_accum_kernel", "csrc_ext/grad_accum.hip", "elementwise, 16-byte accesses, grid-stride over <= 4096 blocks", "Config.GRAD_ACCUM_STEPS (opt-in): acc = g | acc += g behind the backward pass"),
+    ("grad_close_kernel", "csrc_ext/grad_accum.hip", "elementwise + per-block sum of squares", "Config.GRAD_ACCUM_STEPS (opt-in): g = (acc + g) * fl32(1 / k) in front of the optimizer, and the norm's slots"),
     ("sqnorm", "pool_loss_optim.hip", "two-level reduction", "global gradient norm"),
 ]
 

@@ -80,6 +80,8 @@ class Config(object):
     # Not reference fields: an exponential moving average of the weights kept on the device (ursonet_amd/weight_ema.py).
     WEIGHT_EMA = None             # None = off (nothing changes) | the decay, a float in (0, 1): train() also validates and saves the average.  One GPU only.
     WEIGHT_EMA_WARMUP = True      # the decay of update t + 1 is min(WEIGHT_EMA, (1 + t) / (10 + t)); False = WEIGHT_EMA from the first update on
+    # Not a reference field: gradient accumulation on the device (ursonet_amd/grad_accum.py).
+    GRAD_ACCUM_STEPS = 1          # 1 = off (nothing changes) | an int k >= 2: one optimizer step consumes k micro-batches of IMAGES_PER_GPU images.  One GPU only.
 
     def update(self):
         """Derived fields (config.py:151-166)."""

@@ -282,6 +282,11 @@ class DataParallelEngine(object):
             loss_weights.validate(engine.config, self.world)    # ValueError: the two scalars' gradients are not part of the exchange
         if self.world > 1 and getattr(engine, "ema_state", None) is not None:
             raise ValueError("WEIGHT_EMA is not supported under data parallelism (world size %d): leave Config.WEIGHT_EMA = None" % self.world)
+        if getattr(engine, "mode", None) == "training":
+            from . import grad_accum
+            if grad_accum.validate(engine.config, self.world) > 1:      # (one rank too: this class replays graph cuts of its own)
+                raise ValueError("GRAD_ACCUM_STEPS > 1 is not supported under DataParallelEngine: the gradient exchange would have to move into "
+                                 "the closing micro-step, which is not built yet; leave Config.GRAD_ACCUM_STEPS = 1")
         # DP_EXACT_REL_LOSS: the location loss is ONE ratio of norms over the global batch (net.py:750-762); its two squared norms are
         # summed over the ranks between forward and backward and the gradient is pre-scaled by the world size (undone by the averaging)
         self.rel_exact = bool(getattr(engine, "rel_exact", False)) and bool(engine.loss_pre_ops)

@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import hip, loss_scale, loss_weights, weight_ema
+from . import grad_accum, hip, loss_scale, loss_weights, weight_ema
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -98,6 +98,11 @@ class Engine(object):
         self.ema_swapped = False
         if weight_ema.enabled(config, mode):
             weight_ema.initial_state(config, self.world_size_hint())       # ValueError before anything is allocated
+        # Config.GRAD_ACCUM_STEPS: k > 1 = a second flat buffer that sums the gradients of k micro-steps and the host-side
+        # index of the next micro-step; step() replays one captured graph per launch role (ursonet_amd/grad_accum.py).  1 = none of it exists
+        self.flat_acc, self.accum_k, self.accum_micro, self.accum_ops, self._accum_roles = None, 1, 0, [], []
+        if mode == "training":
+            grad_accum.validate(config, self.world_size_hint())            # ValueError before anything is allocated
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -258,6 +263,17 @@ class Engine(object):
             elif init != self._ema_init:               # the keys changed between plans: the schedule starts afresh, the average stays
                 self._ema_init = init
                 self.ema_state.copy_(torch.tensor(init, dtype=torch.float32))
+        # Config.GRAD_ACCUM_STEPS: 1 = no launch and no buffer.  k > 1: one launch behind the backward pass of the
+        # micro-steps that do not close (accum_ops) and one in front of the optimizer of the one that does (_plan_optimizer); a new plan
+        # starts a new optimizer step
+        self.accum_ops, self.accum_micro, self._accum_role = [], 0, None
+        if training:
+            self.accum_k = grad_accum.validate(self.config, self.world_size)
+            self._accum_roles = grad_accum.roles(self.accum_k)
+            if self.accum_k == 1:
+                self.flat_acc = None
+            elif self.flat_acc is None:
+                self.flat_acc = torch.zeros_like(self.flat_w)
         self.acts = {}
         self.prep_ops, self.fwd_ops, self.loss_ops, self.bwd_ops, self.opt_ops = [], [], [], [], []      # lists of _Launch (plan_state.py)
         self.wino_ws = None
@@ -297,9 +313,12 @@ class Engine(object):
     @property
     def labels(self):
         """{pass: [label of every launch, in launch order]}: for profiles, tools and tests.  The plan itself never reads a label."""
-        return {"prep": [l.label for l in self.prep_ops], "fwd": [l.label for l in self.fwd_ops],
-                "loss": [l.label for l in self.loss_pre_ops + self.loss_ops], "bwd": [l.label for l in self.bwd_ops],
-                "opt": [l.label for l in self.opt_ops]}
+        out = {"prep": [l.label for l in self.prep_ops], "fwd": [l.label for l in self.fwd_ops],
+               "loss": [l.label for l in self.loss_pre_ops + self.loss_ops], "bwd": [l.label for l in self.bwd_ops],
+               "opt": [l.label for l in self.opt_ops]}
+        if self.accum_ops:                             # Config.GRAD_ACCUM_STEPS > 1: what a micro-step that does not close runs in place of "opt"
+            out["accum"] = [l.label for l in self.accum_ops]
+        return out
 
     def _act(self, spec, numel=None):
         if spec.id not in self.acts:
@@ -531,8 +550,10 @@ class Engine(object):
         # Global gradient norm without a pass of its own: with ONE gradient bucket and nothing between finalisation and optimizer (no all-reduce,
         # no batch-statistics BN writing gamma / beta gradients elsewhere) every gradient slice is written by a finalisation launch, and each of
         # their blocks leaves the sum of squares of what it stored (urso_param_batch_run_sq): urso_sqnorm_final adds the slots (-24 us of reading
-        # the 134 MB buffer back).  ursonet_amd/dp.py sets no_fused_sqnorm: there the norm is that of the all-reduced gradient.
-        self.fused_sqnorm = (self._env_fuse_sqnorm and not self.no_fused_sqnorm and
+        # the 134 MB buffer back).  ursonet_amd/dp.py sets no_fused_sqnorm: there the norm is that of the all-reduced gradient.  Under
+        # GRAD_ACCUM_STEPS > 1 the finalisations' slots would hold the norm of the last micro-batch's gradient alone: the plan is the
+        # unfused one and the close launch writes the slots of the mean gradient instead (_plan_optimizer).
+        self.fused_sqnorm = (self._env_fuse_sqnorm and not self.no_fused_sqnorm and self.accum_k == 1 and
                              len(self.buckets) == 1 and not any(c_.batch_bn for c_ in self.convs.values()))
         self._sq_slots = 0
         bucket_of = {ln: k for k, (_, _, names) in enumerate(self.buckets) for ln in names}
@@ -938,7 +959,16 @@ class Engine(object):
             self.hyper = torch.tensor([float(cfg.LEARNING_RATE), float(cfg.LEARNING_MOMENTUM), clip], dtype=torch.float32, device=dev)
         self.normsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sq_ws = torch.empty(hip.sqnorm_ws_bytes(n) // 4, dtype=torch.float32, device=dev)
-        if self.fused_sqnorm:
+        if self.accum_k > 1:
+            # Config.GRAD_ACCUM_STEPS: a micro-step that does not close ends in ONE launch behind the backward pass (acc = g | acc += g: the
+            # role of the micro-step that runs, which a captured graph freezes); the closing one begins its optimizer with g = (acc + g) * c,
+            # whose blocks leave the slots of the fused norm -- over all of flat_g, the loss weights' and BN's slices included
+            c = float(grad_accum.inv32(self.accum_k))
+            self.sqpart = torch.zeros(hip.grad_accum_parts(n), dtype=torch.float32, device=dev)
+            self.accum_ops.append(_Launch(lambda: hip.grad_accum(n, self.flat_g, self.flat_acc, self._accum_role == "first"), "grad_accum"))
+            self.opt_ops.append(_Launch(lambda: hip.grad_accum_close(n, self.flat_g, self.flat_acc, c, self.sqpart), "grad_close"))
+            self.opt_ops.append(_Launch(lambda: hip.sqnorm_final(self.sqpart, self.normsq), "sqnorm"))
+        elif self.fused_sqnorm:
             if self.learn_lw and self.layer_trainable[loss_weights.LAYER]:
                 # the two log-variances' gradients are written by the losses, not by a finalisation block: their squares reach the fused norm
                 # through one more slot of sqpart, the last one, filled by a squared norm over the layer's 8 floats of flat_g (padding is zero).
@@ -988,6 +1018,8 @@ class Engine(object):
             return
         if self.ls_state is not None:
             return                           # loss scaling: the forked capture is not supported, the step stays on the single chain
+        if self.accum_k > 1:
+            return                           # gradient accumulation: likewise (one graph per role)
         ops = self.bwd_ops
         fin = ("reduce", "finalize_mat", "finalize_vec", "finalize", "unpack")
         if any(c.batch_bn for c in self.convs.values()):
@@ -1549,9 +1581,23 @@ class Engine(object):
                                "weight-gradient launches are sized at plan time -- build the Engine under the options it runs with" % diff)
 
     def step_eager(self):
-        """One training step, launched kernel by kernel (used for capture, profiling and debugging)."""
+        """One training step, launched kernel by kernel (used for capture, profiling and debugging).  Under Config.GRAD_ACCUM_STEPS > 1: one
+        micro-step, the one step() would replay now, and the index advances as it does there."""
         self._check_plan_options()
+        if self.accum_k > 1:
+            self._run_micro(self._accum_roles[self.accum_micro])
+            self.accum_micro = (self.accum_micro + 1) % self.accum_k
+            return
         self.run_prep(); self.run_forward(); self.run_backward(); self.run_optimizer()
+
+    def _run_micro(self, role):
+        """The launches of a micro-step of the given role (Config.GRAD_ACCUM_STEPS > 1), without touching the index: "first" and "add" end
+        behind the backward pass in accum_ops, "close" runs the optimizer."""
+        assert role in grad_accum.ROLES and self.accum_k > 1
+        self._accum_role = role
+        self.run_prep(); self.run_forward(); self.run_backward()
+        for op in (self.opt_ops if role == "close" else self.accum_ops):
+            op()
 
     def param_pass_bytes(self, launch):
         """Algorithmic bytes of a batched parameter-sized launch, from the descriptor table (the library's launch profiler reports none for
@@ -1576,10 +1622,16 @@ class Engine(object):
                 total += 2 * K * N * 4 + (sp if 1 < sp <= FUSE_MAX else 1) * K * npad * 4
         return total
 
-    def profile_step(self):
+    def profile_step(self, role=None):
         """One eager training step with the library's HIP-event launch profiler on.
-        Returns [(label, kernel_id, ms, flops, bytes, n_kernels, device_symbol)] in launch order."""
-        launches = self.prep_ops + self.fwd_ops + self.loss_pre_ops + self.loss_ops + self.bwd_ops + self.opt_ops
+        Returns [(label, kernel_id, ms, flops, bytes, n_kernels, device_symbol)] in launch order.  Under Config.GRAD_ACCUM_STEPS > 1 it is
+        the micro-step of the given role ("first" | "add" | "close", default the one step() would run now; the index advances with it)."""
+        if self.accum_k > 1:
+            if role is not None:
+                self.accum_micro = self._accum_roles.index(role)
+            role = self._accum_roles[self.accum_micro]
+        launches = (self.prep_ops + self.fwd_ops + self.loss_pre_ops + self.loss_ops + self.bwd_ops +
+                    (self.accum_ops if self.accum_k > 1 and role != "close" else self.opt_ops))
         torch.cuda.synchronize(self.device)
         hip.prof_collect()
         hip.prof_enable(True)
@@ -1601,15 +1653,21 @@ class Engine(object):
             out.append((l.label,) + r)
         return out
 
-    def capture(self):
-        """Capture the step (training) or prep+forward (inference) into a hipGraph."""
+    def capture(self, role=None):
+        """Capture the step (training) or prep+forward (inference) into a hipGraph.  Under Config.GRAD_ACCUM_STEPS > 1 it is the micro-step
+        of one role (default: the one step() would run now) and _graphs maps each role captured so far to its graph."""
+        accum = self.mode == "training" and self.accum_k > 1
+        if accum:
+            role = role if role is not None else self._accum_roles[self.accum_micro]
+            self._check_plan_options()
+        run_step = (lambda: self._run_micro(role)) if accum else self.step_eager
         torch.cuda.synchronize(self.device)
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):                     # warm-up launch outside capture (module load etc.)
             if self.mode == "training":
                 saved = self.save_train_state()
-                self.step_eager()
+                run_step()
                 self.restore_train_state(saved)
             else:
                 self.run_prep(); self.run_forward()
@@ -1620,9 +1678,13 @@ class Engine(object):
         with hip.capture_lock, _no_gc():               # see _no_gc: nothing may be destroyed while the stream is capturing
             with torch.cuda.graph(gr):
                 if self.mode == "training":
-                    self.step_eager()
+                    run_step()
                 else:
                     self.run_prep(); self.run_forward()
+        if accum:                                      # (never forked: _fork_weight_gradients)
+            self._graphs = dict(self._graphs or {})
+            self._graphs[role] = gr
+            return gr
         self._graphs = gr
         if self.mode == "training" and self.wgrad_stream is not None and not self._single_chain_always:
             self._verify_forked_graph(gr)
@@ -1715,9 +1777,16 @@ class Engine(object):
     def step(self):
         """Replay the captured training step (captures on first use)."""
         assert not self.ema_swapped, "step() while the average is swapped in: leave ema_weights() / call swap_ema() again first"
-        if self._graphs is None:
-            self.capture()
-        self._graphs.replay()
+        if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the graph of this micro-step's role, captured on first use
+            role = self._accum_roles[self.accum_micro]
+            if self._graphs is None or role not in self._graphs:
+                self.capture(role)
+            self._graphs[role].replay()
+            self.accum_micro = (self.accum_micro + 1) % self.accum_k
+        else:
+            if self._graphs is None:
+                self.capture()
+            self._graphs.replay()
         if self._cleared_once and os.environ.get("URSO_CHECK_CLEARED", "0") == "1":
             bad = self.check_cleared_once()
             assert not bad, "gradient buffers cleared at plan time hold values off their sampled grid: %s" % bad
@@ -1801,6 +1870,8 @@ class Engine(object):
             st += [self.flat_v2.clone(), self.flat_vhat.clone(), self.hyper.clone()]
         if self.ema_state is not None:                 # (in front of the loss-scale state, which restore_train_state finds at the end)
             st += [self.flat_ema.clone(), self.ema_state.clone()]
+        if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the running sum and the index of the next micro-step
+            st += [self.flat_acc.clone(), self.accum_micro]
         if self.ls_state is not None:
             st.append(self.ls_state.clone())
         return st
@@ -1809,15 +1880,20 @@ class Engine(object):
         self.flat_w.copy_(st[0]); self.flat_v.copy_(st[1]); self.flat_stats.copy_(st[2])
         if self.adam:
             self.flat_v2.copy_(st[3]); self.flat_vhat.copy_(st[4]); self.hyper.copy_(st[5])
+        k = 6 if self.adam else 3
         if self.ema_state is not None:
-            k = 6 if self.adam else 3
             self.flat_ema.copy_(st[k]); self.ema_state.copy_(st[k + 1])
+            k += 2
+        if self.accum_k > 1:
+            self.flat_acc.copy_(st[k]); self.accum_micro = int(st[k + 1])
         if self.ls_state is not None:
             self.ls_state.copy_(st[-1])
 
     def reset_optimizer(self):
-        """Zero the optimizer's moments (and restart the loss scale).  The weights' average and its schedule are no optimizer state: they stay."""
+        """Zero the optimizer's moments (and restart the loss scale).  The weights' average and its schedule are no optimizer state: they stay.
+        Under Config.GRAD_ACCUM_STEPS > 1 a begun optimizer step is dropped: the next micro-step is a first one (a bit copy into flat_acc)."""
         self.flat_v.zero_()
+        self.accum_micro = 0
         if self.adam:
             self.flat_v2.zero_(); self.flat_vhat.zero_(); self.hyper[5] = 0.0
         if self.ls_state is not None:
@@ -1834,6 +1910,13 @@ class Engine(object):
         if self.ls_state is None:
             return None
         return loss_scale.as_dict(self.ls_state.detach().cpu().tolist())
+
+    def grad_accum(self):
+        """{"steps": k, "micro": i}: Config.GRAD_ACCUM_STEPS and the index of the micro-step that step() runs next (0 = the next one begins
+        an optimizer step); None when accumulation is off."""
+        if self.mode != "training" or self.accum_k == 1:
+            return None
+        return {"steps": self.accum_k, "micro": self.accum_micro}
 
     def weight_ema(self):
         """{decay, warmup, updates, next_decay} of the device-side state of the weights' average, read once (one synchronising copy); None

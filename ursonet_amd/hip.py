@@ -256,6 +256,10 @@ _EXT_SIGS = {
     # the weights' moving average (ursonet_amd/weight_ema.py): n, w, ema, state, loss-scale state | n, a, b
     "urso_ema_update": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
     "urso_ema_swap": (_i, [C.c_int64, _fp, _fp, _vp]),
+    # gradient accumulation (ursonet_amd/grad_accum.py): n, g, acc, first | n | n, g, acc, c, sqpart, nparts
+    "urso_grad_accum": (_i, [C.c_int64, _fp, _fp, _i, _vp]),
+    "urso_grad_accum_parts": (_i, [C.c_int64]),
+    "urso_grad_accum_close": (_i, [C.c_int64, _fp, _fp, _f, _fp, _i, _vp]),
 }
 EXT_SYMBOLS = sorted(_EXT_SIGS)
 
@@ -798,6 +802,26 @@ def ema_swap(n, a, b, stream=None):
     """urso_ema_swap (liburso_ext.so): exchange the bit patterns of the first n elements of two 4-byte-element buffers in place."""
     assert a.element_size() == 4 and b.element_size() == 4 and 0 <= n <= min(a.numel(), b.numel())
     _chk(ext_lib().urso_ema_swap(n, ptr(a), ptr(b), stream_ptr(stream)), "urso_ema_swap")
+
+
+def grad_accum_parts(n):
+    """urso_grad_accum_parts (liburso_ext.so): the slots urso_grad_accum_close writes for n elements (its block count; needs no GPU)."""
+    return int(ext_lib().urso_grad_accum_parts(int(n)))
+
+
+def grad_accum(n, g, acc, first, stream=None):
+    """urso_grad_accum (liburso_ext.so): acc = g (first: the bits) or acc += g over n fp32 elements (ursonet_amd.grad_accum.first32 / add32)."""
+    assert g.dtype == torch.float32 and acc.dtype == torch.float32 and 0 <= n <= min(g.numel(), acc.numel())
+    _chk(ext_lib().urso_grad_accum(n, ptr(g), ptr(acc), 1 if first else 0, stream_ptr(stream)), "urso_grad_accum")
+
+
+def grad_accum_close(n, g, acc, c, sqpart, stream=None):
+    """urso_grad_accum_close (liburso_ext.so): g = (acc + g) * c over n fp32 elements (ursonet_amd.grad_accum.close32) and, per block, the
+    sum of squares of what it stored into sqpart (grad_accum_parts(n) slots, for sqnorm_final)."""
+    assert g.dtype == torch.float32 and acc.dtype == torch.float32 and sqpart.dtype == torch.float32
+    assert 0 <= n <= min(g.numel(), acc.numel())
+    _chk(ext_lib().urso_grad_accum_close(n, ptr(g), ptr(acc), float(c), ptr(sqpart), sqpart.numel(), stream_ptr(stream)),
+         "urso_grad_accum_close")
 
 
 def adam_amsgrad_clip(n, w, g, m, v, vhat, hyper, normsq, stream=None, ls=None):

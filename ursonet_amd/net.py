@@ -226,6 +226,8 @@ class UrsoNet(object):
             if mode == "training":
                 loss_weights.validate(config, world)   # ValueError: set under a data-parallel launcher
             if mode == "training":
+                from . import grad_accum
+                grad_accum.validate(config, world)          # ValueError: a bad GRAD_ACCUM_STEPS, or k > 1 under a data-parallel launcher
                 loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
                 from . import weight_ema
                 weight_ema.initial_state(config, world)     # ValueError: a bad WEIGHT_EMA, or one set under a data-parallel launcher
@@ -376,6 +378,9 @@ class UrsoNet(object):
             log("Checkpoint Path: {}".format(self.checkpoint_path))
             if world > 1:
                 log("Data parallel: {} ranks x {} images (global batch {})".format(world, eng.B, world * eng.B))
+            if eng.accum_k > 1:
+                log("Gradient accumulation: {} micro-batches x {} images per optimizer step (effective batch {})".format(
+                    eng.accum_k, eng.B, eng.accum_k * eng.B))
         self.set_trainable(layers, verbose=1 if chief else 0)
         self.compile(learning_rate, cfg.LEARNING_MOMENTUM)
         if chief:
@@ -384,8 +389,11 @@ class UrsoNet(object):
         # Keras' BatchLogger reads the batch's losses after every step (net.py:1106-1115): a device -> host round trip per 7 ms step.  Here each
         # step's loss scalars are copied into a device-side history row (same stream, no synchronisation) and read ONCE per epoch -- the same
         # per-batch lists, no bubble; under data parallelism the rows are averaged over the ranks first (the loss of the global batch)
+        # Config.GRAD_ACCUM_STEPS = k > 1: STEPS_PER_EPOCH counts optimizer steps, each draws k batches; the history gets a row per micro-batch
+        # and is folded on the host into one entry per optimizer step, the mean of its k rows (grad_accum.fold_history)
         n_loss = int(eng.loss_buf.numel())
-        hist = torch.zeros(max(steps, 1), n_loss, dtype=torch.float32, device=eng.device)
+        acc_k = int(eng.accum_k)
+        hist = torch.zeros(max(steps * acc_k, 1), n_loss, dtype=torch.float32, device=eng.device)
         vhist = torch.zeros(max(vsteps, 1), n_loss, dtype=torch.float32, device=eng.device)
         kp = bool(cfg.REGRESS_KEYPOINTS)
         # Config.LOSS_SCALE: the loss-scale state of every step beside its losses (device-side, read once per epoch)
@@ -406,11 +414,12 @@ class UrsoNet(object):
                 if cfg.CLR:
                     eng.set_lr(utils.clr_triangular(clr_it, cfg.BASE_LEARNING_RATE, cfg.MAX_LEARNING_RATE, cfg.CLR_STEP_SIZE))
                     clr_it += 1
-                train_feed.next_into()
-                if ema_hist is not None:
+                if ema_hist is not None:               # (the state moves only behind the optimizer: the closing micro-step's update uses this decay)
                     ema_hist[i].copy_(eng.ema_state, non_blocking=True)
-                runner.step()
-                hist[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
+                for j in range(acc_k):
+                    train_feed.next_into()
+                    runner.step()
+                    hist[i * acc_k + j].copy_(eng.loss_buf.view(-1), non_blocking=True)
                 if ls_hist is not None:
                     ls_hist[i].copy_(eng.ls_state, non_blocking=True)
                 if lw_hist is not None:
@@ -429,7 +438,10 @@ class UrsoNet(object):
                 from . import dp
                 dp.average_over_ranks(hist)
                 dp.average_over_ranks(vhist)
-            h = hist[:steps].cpu().numpy()
+            h = hist[:steps * acc_k].cpu().numpy()
+            if acc_k > 1:
+                from . import grad_accum
+                h = grad_accum.fold_history(h, acc_k)
             for row in h:
                 history_full.ori_loss_acc.append(None if kp else float(row[1]))   # None in keypoint mode, as logs.get('ori_loss') is (net.py:1112)
                 history_full.loc_loss_acc.append(float(row[0]))
