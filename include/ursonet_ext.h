@@ -173,6 +173,71 @@ int urso_grad_accum(int64_t n, const float* g_d, float* acc_d, int first, void* 
 int urso_grad_accum_parts(int64_t n);
 int urso_grad_accum_close(int64_t n, float* g_d, const float* acc_d, float c, float* sqpart_d, int nparts, void* stream);
 
+/*
+ * Layer-wise adaptive rate scaling for SGD with momentum (Config.LARS; ursonet_amd/lars.py is the same rule in
+ * NumPy).  The reference has none.  Five entry points (the library exports 14 with them): two on the host that plan the grid and three
+ * launches that take the place of urso_sgd_momentum_clip[_ls] behind the global norm.
+ *
+ * The tensors.  T tensors lie in the flat fp32 buffers w, g and v: tensor t is the n[t] floats from element off[t].  Each has an adapt
+ * flag; a tensor that does not adapt has trust 1 and moves exactly as under urso_sgd_momentum_clip.  Floats that belong to no tensor
+ * (the padding between slices) are neither read nor written.
+ *
+ * The rule.  With lr = hyper[0], mom = hyper[1], clip = hyper[2] and, in fp32 as urso_sgd_momentum_clip computes it,
+ *   norm = sqrtf(normsq[0]);  c = (clip > 0 && norm >= clip) ? clip / norm : 1
+ * per tensor, in fp64 (+ * / sqrt and comparisons only, compiled without contraction):
+ *   nw = sqrt(sum of w^2), ng = sqrt(sum of g^2)                      the sums: "The order" below
+ *   q = 1                                     if the tensor does not adapt, or nw == 0, or ng == 0 (fresh zeros, a frozen layer)
+ *   q = eta * nw / ((double)c * ng + eps)     otherwise
+ *   q = min(q / (double)lr, 1)                with clip_mode = 1 (LARC's "clip": the tensor's rate never exceeds the global one)
+ *   trust = (float)q                          rounded once
+ * per element of the tensor, in fp32, every operation rounded once:
+ *   step = (lr * c) * trust;  v[i] = mom * v[i] - step * g[i];  w[i] = w[i] + v[i]
+ *
+ * The order.  Tensor t is cut into ceil(n[t] / URSO_LARS_CHUNK) chunks, the last one short; one block of 256 threads owns one chunk and
+ * writes one slot pair part[block] = {sum of w^2, sum of g^2}, fp32.  Thread i of the block owns the 16-byte groups i, 256 + i, 512 + i,
+ * 768 + i of the chunk.  Every square is rounded once and added to the thread's running sum (from 0.0f) in the order the thread reads:
+ * its groups in order, x y z w each.  The 64 lanes of a wave are added by the xor shuffle (offsets 32, 16, 8, 4, 2, 1), the four wave
+ * sums in wave order from 0.0f: the order of urso_grad_accum_close's slots.  Elements past the tensor's end contribute nothing.  A
+ * tensor's slots are then added in index order in fp64 (from 0.0).  Every result is a function of the inputs alone.
+ *
+ * Host planning (no GPU needed):
+ *   urso_lars_blocks   NB = the sum over t of ceil(n_h[t] / URSO_LARS_CHUNK), a function of the sizes alone; 0 for T == 0.  A negative
+ *                      return is an error code (T < 0, a null n_h with T > 0, a negative size, NB above 2^31 - 1).
+ *   urso_lars_plan     fills blockmap_h[NB][2], one (tensor, chunk) pair per block, tensors in index order and chunks in order within a
+ *                      tensor, and first_h[T + 1], each tensor's first slot (first_h[T] = NB).  nblocks must be urso_lars_blocks(T, n_h).
+ *
+ * Device tables (the caller uploads them once per plan): tab_d int64 [T][2] = {off[t], n[t]}, the same values as off_h / n_h;
+ * blockmap_d and first_d as urso_lars_plan filled them; adapt_d int32 [T], nonzero = adapts.  The launches check the host tables and
+ * trust the device tables to hold the same.
+ *
+ * Launches, in this order on one stream; no allocation, no synchronisation:
+ *   urso_lars_norms    NB blocks of 256 threads.  Reads w and g once (8 bytes per parameter) and writes part_d[NB][2].
+ *   urso_lars_trust    T blocks of two waves: block t adds the slots first[t] .. first[t + 1] - 1 of tensor t in index order (one wave
+ *                      the w^2 slots, the other the g^2 slots) and writes trust_d[t] (fp32) and stat_d[t][3] = {nw, ng, q} (fp64), for
+ *                      every tensor, adapting or not.  With ls_state_d set and a non-finite normsq[0] it writes nothing.  nblocks is NB,
+ *                      the slot pairs part_d holds.
+ *   urso_lars_sgd      NB blocks of 256 threads over the same block map: each reads trust_d[tensor], recomputes c and applies the
+ *                      update with 16-byte accesses (20 bytes per parameter); a tensor's last n % 4 elements move as scalars.  With
+ *                      ls_state_d set (the loss-scaled form) a non-finite normsq[0] changes nothing: w and v keep their bits.
+ * T == 0 (and so NB == 0) launches nothing.
+ *
+ * Bad arguments return URSO_EINVAL with a message before any launch: a null pointer; T < 0; a negative size; an offset that is negative
+ * or not a multiple of 4 floats; w, g or v not 16-byte aligned; tab, part or stat not 8-byte aligned; two non-empty tensors that overlap;
+ * nblocks != urso_lars_blocks(T, n_h); w, g and v not pairwise distinct; eta not a finite number > 0, eps not a finite number >= 0,
+ * clip_mode outside {0, 1}.
+ */
+#define URSO_LARS_CHUNK 4096
+int urso_lars_blocks(int T, const int64_t* n_h);
+int urso_lars_plan(int T, const int64_t* n_h, int nblocks, int32_t* blockmap_h, int32_t* first_h);
+int urso_lars_norms(int T, const int64_t* off_h, const int64_t* n_h, const int64_t* tab_d, const int32_t* blockmap_d, int nblocks,
+                    const float* w_d, const float* g_d, float* part_d, void* stream);
+int urso_lars_trust(int T, const int32_t* first_d, const int32_t* adapt_d, int nblocks, const float* part_d, const float* hyper_d,
+                    const float* normsq_d, double eta, double eps, int clip_mode, float* trust_d, double* stat_d,
+                    const float* ls_state_d, void* stream);
+int urso_lars_sgd(int T, const int64_t* off_h, const int64_t* n_h, const int64_t* tab_d, const int32_t* blockmap_d, int nblocks,
+                  float* w_d, const float* g_d, float* v_d, const float* trust_d, const float* hyper_d, const float* normsq_d,
+                  const float* ls_state_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

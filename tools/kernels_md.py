@@ -52,6 +52,9 @@ FAMILIES = [
     ("ema_update_kernel", "csrc_ext/weight_ema.hip", "elementwise, 16-byte accesses, grid-stride over <= 4096 blocks", "Config.WEIGHT_EMA (opt-in): the weights' moving average behind the optimizer"),
     ("grad_accum_kernel", "csrc_ext/grad_accum.hip", "elementwise, 16-byte accesses, grid-stride over <= 4096 blocks", "Config.GRAD_ACCUM_STEPS (opt-in): acc = g | acc += g behind the backward pass"),
     ("grad_close_kernel", "csrc_ext/grad_accum.hip", "elementwise + per-block sum of squares", "Config.GRAD_ACCUM_STEPS (opt-in): g = (acc + g) * fl32(1 / k) in front of the optimizer, and the norm's slots"),
+    ("lars_norms_kernel", "csrc_ext/lars.hip", "one block per 4096-element chunk of one tensor, 16-byte loads, per-block sums of squares", "Config.LARS (opt-in): the slots of every tensor's |w|^2 and |g|^2"),
+    ("lars_trust_kernel", "csrc_ext/lars.hip", "one block of two waves per tensor, float64", "Config.LARS (opt-in): the per-tensor trust ratios from the slots, in index order"),
+    ("lars_sgd_kernel", "csrc_ext/lars.hip", "elementwise over the same block map, 16-byte accesses", "Config.LARS (opt-in): clip + momentum SGD with each tensor's trust"),
     ("sqnorm", "pool_loss_optim.hip", "two-level reduction", "global gradient norm"),
 ]
 

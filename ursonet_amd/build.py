@@ -16,7 +16,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # it calls into the main library (error text, launch profiler), which the loader resolves when it is loaded behind it (ursonet_amd/hip.py).
 CSRC_EXT = os.path.join(HERE, "csrc_ext")
 EXT_LIB = os.path.join(LIBDIR, "liburso_ext.so")
-EXT_SOURCES = ["pose_fuse.hip", "loss_weights.hip", "weight_ema.hip", "grad_accum.hip"]
+EXT_SOURCES = ["pose_fuse.hip", "loss_weights.hip", "weight_ema.hip", "grad_accum.hip", "lars.hip"]
 
 
 def _hipcc():

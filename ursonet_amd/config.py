@@ -82,6 +82,10 @@ class Config(object):
     WEIGHT_EMA_WARMUP = True      # the decay of update t + 1 is min(WEIGHT_EMA, (1 + t) / (10 + t)); False = WEIGHT_EMA from the first update on
     # Not a reference field: gradient accumulation on the device (ursonet_amd/grad_accum.py).
     GRAD_ACCUM_STEPS = 1          # 1 = off (nothing changes) | an int k >= 2: one optimizer step consumes k micro-batches of IMAGES_PER_GPU images.  One GPU only.
+    # Not reference fields: layer-wise adaptive rate scaling for SGD on the device (ursonet_amd/lars.py).
+    LARS = None                   # None = off (nothing changes) | the trust coefficient, a float > 0 (usually 0.001): every conv / Dense kernel steps at lr * LARS * |w| / (c |g| + LARS_EPS).  SGD and one GPU only.
+    LARS_EPS = 1e-8               # a float >= 0, added to the denominator of the trust ratio
+    LARS_CLIP = False             # True = LARC's "clip" mode: a tensor's effective rate never exceeds the global one (trust = min(ratio / lr, 1))
 
     def update(self):
         """Derived fields (config.py:151-166)."""

@@ -1,0 +1,330 @@
+// Layer-wise adaptive rate scaling for SGD with momentum (liburso_ext.so; Config.LARS): the host planning of the
+// block map and the three launches that replace the plain SGD launch -- the per-chunk sums of w^2 and g^2, the per-tensor trust ratios in
+// float64, and the update with each tensor's trust.  Rule, reduction order, tables and argument rules: include/ursonet_ext.h;
+// ursonet_amd/lars.py is the same rule in NumPy.
+//
+// The norms and the update are HBM-bound streams (8 and 20 bytes per parameter): 256 threads per block, 16 bytes per lane and access, one
+// block per chunk of URSO_LARS_CHUNK = 4096 elements of ONE tensor, so that a block's slot pair belongs to one tensor and the result does
+// not depend on how the tensors sit in the flat buffer.  Thread t of a block owns the 16-byte groups t, 256 + t, 512 + t, 768 + t of its
+// chunk: four independent loads per operand in flight, consecutive lanes on consecutive addresses.  A tensor's ragged end (numel % 4
+// elements) is read and written by scalars: nothing outside [offset, offset + numel) is touched, the padding between slices included.
+#include "../csrc/common.h"
+#include "../../include/ursonet_ext.h"
+
+#include <algorithm>
+#include <vector>
+
+static constexpr int LT = 256;                                             // threads per block
+static constexpr int LG = URSO_LARS_CHUNK / (4 * LT);                      // 16-byte groups per thread
+static_assert(LG * 4 * LT == URSO_LARS_CHUNK, "a chunk is a whole number of groups per thread");
+
+// ------------------------------------------------------------------------------------------------ host planning
+static int lars_count(const char* fn, int T, const int64_t* n_h, int64_t* out) {
+    if (T < 0) { urso_set_error("%s: T must be >= 0 (got %d)", fn, T); return URSO_EINVAL; }
+    if (T > 0 && !n_h) { urso_set_error("%s: null pointer (n)", fn); return URSO_EINVAL; }
+    int64_t nb = 0;
+    for (int t = 0; t < T; ++t) {
+        if (n_h[t] < 0) { urso_set_error("%s: tensor %d has a negative size (%lld)", fn, t, (long long)n_h[t]); return URSO_EINVAL; }
+        nb += (n_h[t] + URSO_LARS_CHUNK - 1) / URSO_LARS_CHUNK;
+        if (nb > 0x7fffffff) { urso_set_error("%s: more than 2^31 - 1 blocks", fn); return URSO_EINVAL; }
+    }
+    *out = nb;
+    return URSO_OK;
+}
+
+extern "C" int urso_lars_blocks(int T, const int64_t* n_h) {
+    int64_t nb = 0;
+    const int rc = lars_count("urso_lars_blocks", T, n_h, &nb);
+    return rc != URSO_OK ? rc : (int)nb;
+}
+
+extern "C" int urso_lars_plan(int T, const int64_t* n_h, int nblocks, int32_t* blockmap_h, int32_t* first_h) {
+    const char* fn = "urso_lars_plan";
+    int64_t nb = 0;
+    const int rc = lars_count(fn, T, n_h, &nb);
+    if (rc != URSO_OK) return rc;
+    if (!first_h || (nb > 0 && !blockmap_h)) { urso_set_error("%s: null pointer (blockmap, first)", fn); return URSO_EINVAL; }
+    if (nblocks != (int)nb) { urso_set_error("%s: nblocks must be urso_lars_blocks(T, n) = %d (got %d)", fn, (int)nb, nblocks); return URSO_EINVAL; }
+    int32_t b = 0;
+    for (int t = 0; t < T; ++t) {
+        first_h[t] = b;
+        const int32_t nc = (int32_t)((n_h[t] + URSO_LARS_CHUNK - 1) / URSO_LARS_CHUNK);
+        for (int32_t c = 0; c < nc; ++c, ++b) { blockmap_h[2 * b] = t; blockmap_h[2 * b + 1] = c; }
+    }
+    first_h[T] = b;
+    return URSO_OK;
+}
+
+// What the norms and the update launches share: the tensor table as the host sees it, checked before any launch.
+static int lars_check_tensors(const char* fn, int T, const int64_t* off_h, const int64_t* n_h, int nblocks) {
+    int64_t nb = 0;
+    const int rc = lars_count(fn, T, n_h, &nb);
+    if (rc != URSO_OK) return rc;
+    if (T > 0 && !off_h) { urso_set_error("%s: null pointer (offsets)", fn); return URSO_EINVAL; }
+    if (nblocks != (int)nb) { urso_set_error("%s: nblocks must be urso_lars_blocks(T, n) = %d (got %d)", fn, (int)nb, nblocks); return URSO_EINVAL; }
+    bool sorted = true;
+    for (int t = 0; t < T; ++t) {
+        if (off_h[t] < 0 || (off_h[t] & 3)) {
+            urso_set_error("%s: tensor %d: offset %lld is not a non-negative multiple of 4 floats", fn, t, (long long)off_h[t]); return URSO_EINVAL;
+        }
+        if (off_h[t] > INT64_MAX - n_h[t]) { urso_set_error("%s: tensor %d: offset + size overflows", fn, t); return URSO_EINVAL; }
+        if (t > 0 && off_h[t] < off_h[t - 1]) sorted = false;
+    }
+    std::vector<int> order;
+    if (!sorted) {                                                         // (the engine's slices ascend: no allocation on its path)
+        order.resize(T);
+        for (int t = 0; t < T; ++t) order[t] = t;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return off_h[a] != off_h[b] ? off_h[a] < off_h[b] : a < b; });
+    }
+    int prev = -1;                                                         // the last non-empty tensor in offset order
+    for (int k = 0; k < T; ++k) {
+        const int t = sorted ? k : order[k];
+        if (n_h[t] == 0) continue;
+        if (prev >= 0 && off_h[prev] + n_h[prev] > off_h[t]) {
+            urso_set_error("%s: tensors %d and %d overlap ([%lld, +%lld) and [%lld, +%lld))", fn, prev, t, (long long)off_h[prev],
+                           (long long)n_h[prev], (long long)off_h[t], (long long)n_h[t]);
+            return URSO_EINVAL;
+        }
+        prev = t;
+    }
+    return URSO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ device
+// The block's chunk: element range [lo, lo + cnt) of the flat buffers, and its tensor.
+struct LarsChunk { size_t lo; int cnt; int tensor; };
+__device__ __forceinline__ LarsChunk lars_chunk(const int64_t* __restrict__ tab, const int32_t* __restrict__ blockmap) {
+    const int t = blockmap[2 * blockIdx.x], c = blockmap[2 * blockIdx.x + 1];
+    const int64_t off = tab[2 * t], n = tab[2 * t + 1];
+    const int64_t done = (int64_t)c * URSO_LARS_CHUNK, left = n - done;
+    return LarsChunk{(size_t)(off + done), (int)(left < URSO_LARS_CHUNK ? left : URSO_LARS_CHUNK), t};
+}
+
+// the group's four floats; elements past the chunk's end read as +0 (their squares change no bit of a sum that began at +0) and a
+// ragged group is read by scalars: no address outside the tensor is formed
+__device__ __forceinline__ f32x4_t lars_load(const float* __restrict__ p, int e, int cnt) {
+    f32x4_t x = {0.f, 0.f, 0.f, 0.f};
+    if (e + 4 <= cnt) return *(const f32x4_t*)(p + e);
+    if (e < cnt) x.x = p[e];
+    if (e + 1 < cnt) x.y = p[e + 1];
+    if (e + 2 < cnt) x.z = p[e + 2];
+    return x;
+}
+
+__device__ __forceinline__ void lars_sq(float& s, const f32x4_t& x) {
+    const float a = x.x * x.x, b = x.y * x.y, c = x.z * x.z, d = x.w * x.w;     // each square rounded once (-ffp-contract=off)
+    s = s + a; s = s + b; s = s + c; s = s + d;
+}
+
+// part[block] = {sum of w^2, sum of g^2} over the block's chunk: per thread from 0.0f in the order it reads (its groups in order, x y z w
+// each), then the wave's xor shuffle (32, 16, ... 1), then the four wave sums in wave order from 0.0f -- the order of grad_close_kernel's
+// slots (grad_accum.hip)
+__global__ void __launch_bounds__(LT) lars_norms_kernel(const int64_t* __restrict__ tab, const int32_t* __restrict__ blockmap,
+                                                        const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ part) {
+    __shared__ float sh[2][LT / 64];
+    const LarsChunk ch = lars_chunk(tab, blockmap);
+    const float* wp = w + ch.lo;
+    const float* gp = g + ch.lo;
+    f32x4_t wv[LG], gv[LG];
+#pragma unroll
+    for (int j = 0; j < LG; ++j) {
+        const int e = 4 * (j * LT + (int)threadIdx.x);
+        wv[j] = lars_load(wp, e, ch.cnt);
+        gv[j] = lars_load(gp, e, ch.cnt);
+    }
+    float sw = 0.f, sg = 0.f;
+#pragma unroll
+    for (int j = 0; j < LG; ++j) { lars_sq(sw, wv[j]); lars_sq(sg, gv[j]); }
+    sw = wave_sum(sw); sg = wave_sum(sg);
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = sw; sh[1][threadIdx.x >> 6] = sg; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float rw = 0.f, rg = 0.f;
+        for (int i = 0; i < LT / 64; ++i) { rw += sh[0][i]; rg += sh[1][i]; }
+        part[2 * (size_t)blockIdx.x] = rw;
+        part[2 * (size_t)blockIdx.x + 1] = rg;
+    }
+}
+
+// c, the global-norm clip factor, as sgd_kernel (csrc/pool_loss_optim.hip) computes it
+__device__ __forceinline__ float lars_clip_factor(const float* __restrict__ hyper, const float* __restrict__ normsq) {
+    const float clip = hyper[2];
+    const float norm = sqrtf(normsq[0]);
+    return (clip > 0.f && norm >= clip) ? clip / norm : 1.f;
+}
+
+// One block of two waves per tensor: wave 0 adds the tensor's w^2 slots, wave 1 its g^2 slots, each in index order in float64.  One lane
+// alone would do that at one dependent load per slot; here the 64 lanes of a wave fetch 64 slots at once (the next batch in flight behind
+// the current one), widen them, and every lane adds them in index order out of the lanes' registers (two constant-lane reads per slot):
+// the order of a single thread, the loads of a wave.  The two chains are independent, so they run on two SIMDs side by side.  All lanes
+// of a wave hold the same sum; thread 0 finishes the tensor.
+__device__ __forceinline__ double lars_readlane(double x, int k) {
+    const long long b = __builtin_bit_cast(long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), k);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), k);
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)lo);
+}
+
+__global__ void __launch_bounds__(128) lars_trust_kernel(const int32_t* __restrict__ first, const int32_t* __restrict__ adapt,
+                                                         const float* __restrict__ part, const float* __restrict__ hyper,
+                                                         const float* __restrict__ normsq, double eta, double eps, int clip_mode, int guard,
+                                                         float* __restrict__ trust, double* __restrict__ stat) {
+    __shared__ double sh[2];
+    if (guard && !isfinite(normsq[0])) return;                              // the optimizer skips this step: trust and stat keep their bits
+    const int t = blockIdx.x, lane = threadIdx.x & 63, which = threadIdx.x >> 6;       // which: 0 = the w^2 slots, 1 = the g^2 slots
+    const int s0 = first[t], ns = first[t + 1] - s0;
+    const float* pp = part + 2 * (size_t)s0 + which;
+    double s = 0.0;
+    double cur = 0.0;
+    if (lane < ns) cur = (double)pp[2 * lane];
+    for (int base = 0; base < ns; base += 64) {
+        double nxt = 0.0;
+        if (base + 64 + lane < ns) nxt = (double)pp[2 * (base + 64 + lane)];
+        const int m = ns - base;                                            // slots of this batch: min(m, 64), uniform over the wave
+        if (m >= 64) {                                                      // a whole batch: straight-line code
+#pragma unroll
+            for (int k = 0; k < 64; ++k) s = s + lars_readlane(cur, k);
+        } else {                                                            // the tensor's last batch (k is uniform over the wave)
+            for (int k = 0; k < m; ++k) s = s + lars_readlane(cur, k);
+        }
+        cur = nxt;
+    }
+    if (lane == 0) sh[which] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double nw = sqrt(sh[0]), ng = sqrt(sh[1]);
+    double q = 1.0;
+    if (adapt[t] != 0 && nw != 0.0 && ng != 0.0) {
+        const double c = (double)lars_clip_factor(hyper, normsq);
+        const double prod = c * ng;
+        const double den = prod + eps;
+        const double num = eta * nw;
+        q = num / den;
+        if (clip_mode) {
+            q = q / (double)hyper[0];
+            q = q < 1.0 ? q : 1.0;
+        }
+    }
+    trust[t] = (float)q;                                                    // rounded once
+    stat[3 * (size_t)t] = nw; stat[3 * (size_t)t + 1] = ng; stat[3 * (size_t)t + 2] = q;
+}
+
+__device__ __forceinline__ void lars_one(f32x4_t& w, const f32x4_t& g, f32x4_t& v, float mom, float step) {
+    const f32x4_t a = v * mom;                                              // per element two products, one subtraction, one addition: each
+    const f32x4_t b = g * step;                                             // rounded once (-ffp-contract=off)
+    v = a - b;
+    w = w + v;
+}
+
+// step = (lr * c) * trust[tensor]; v = mom * v - step * g; w = w + v over the block's chunk.  guard (the loss-scaled form): a step whose
+// squared gradient norm is not finite changes nothing
+__global__ void __launch_bounds__(LT) lars_sgd_kernel(const int64_t* __restrict__ tab, const int32_t* __restrict__ blockmap,
+                                                      float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v,
+                                                      const float* __restrict__ trust, const float* __restrict__ hyper,
+                                                      const float* __restrict__ normsq, int guard) {
+    if (guard && !isfinite(normsq[0])) return;
+    const LarsChunk ch = lars_chunk(tab, blockmap);
+    const float lr = hyper[0], mom = hyper[1];
+    const float c = lars_clip_factor(hyper, normsq);
+    const float lrc = lr * c;
+    const float step = lrc * trust[ch.tensor];
+    float* wp = w + ch.lo;
+    const float* gp = g + ch.lo;
+    float* vp = v + ch.lo;
+    f32x4_t wv[LG], gv[LG], vv[LG];
+#pragma unroll
+    for (int j = 0; j < LG; ++j) {
+        const int e = 4 * (j * LT + (int)threadIdx.x);
+        wv[j] = lars_load(wp, e, ch.cnt);
+        gv[j] = lars_load(gp, e, ch.cnt);
+        vv[j] = lars_load(vp, e, ch.cnt);
+    }
+#pragma unroll
+    for (int j = 0; j < LG; ++j) {
+        const int e = 4 * (j * LT + (int)threadIdx.x);
+        lars_one(wv[j], gv[j], vv[j], mom, step);
+        if (e + 4 <= ch.cnt) {
+            *(f32x4_t*)(vp + e) = vv[j];
+            *(f32x4_t*)(wp + e) = wv[j];
+        } else {                                                            // the tensor's ragged end: scalars, the padding keeps its bits
+            if (e < ch.cnt) { vp[e] = vv[j].x; wp[e] = wv[j].x; }
+            if (e + 1 < ch.cnt) { vp[e + 1] = vv[j].y; wp[e + 1] = wv[j].y; }
+            if (e + 2 < ch.cnt) { vp[e + 2] = vv[j].z; wp[e + 2] = wv[j].z; }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ launches
+static inline bool lars_misaligned16(const void* p) { return (((uintptr_t)p) & 15) != 0; }
+
+extern "C" int urso_lars_norms(int T, const int64_t* off_h, const int64_t* n_h, const int64_t* tab_d, const int32_t* blockmap_d, int nblocks,
+                               const float* w_d, const float* g_d, float* part_d, void* stream) {
+    const char* fn = "urso_lars_norms";
+    const int rc = lars_check_tensors(fn, T, off_h, n_h, nblocks);
+    if (rc != URSO_OK) return rc;
+    if (!w_d || !g_d) { urso_set_error("%s: null pointer (w, g)", fn); return URSO_EINVAL; }
+    if (lars_misaligned16(w_d) || lars_misaligned16(g_d)) { urso_set_error("%s: w and g must be 16-byte aligned", fn); return URSO_EINVAL; }
+    if (w_d == g_d) { urso_set_error("%s: w and g are the same buffer", fn); return URSO_EINVAL; }
+    if (nblocks == 0) return URSO_OK;
+    if (!tab_d || !blockmap_d || !part_d) { urso_set_error("%s: null pointer (tab, blockmap, part)", fn); return URSO_EINVAL; }
+    if ((((uintptr_t)tab_d) | ((uintptr_t)part_d)) & 7) { urso_set_error("%s: tab and part must be 8-byte aligned", fn); return URSO_EINVAL; }
+    if (((uintptr_t)blockmap_d) & 3) { urso_set_error("%s: blockmap must be 4-byte aligned", fn); return URSO_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    double n = 0;
+    for (int t = 0; t < T; ++t) n += (double)n_h[t];
+    ProfScope ps(st, URSO_K_OPTIM, 0, n * 8);
+    URSO_KLAUNCH(lars_norms_kernel, dim3(nblocks), dim3(LT), 0, st, tab_d, blockmap_d, w_d, g_d, part_d);
+    return urso_check_launch(fn);
+}
+
+extern "C" int urso_lars_trust(int T, const int32_t* first_d, const int32_t* adapt_d, int nblocks, const float* part_d, const float* hyper_d,
+                               const float* normsq_d, double eta, double eps, int clip_mode, float* trust_d, double* stat_d,
+                               const float* ls_state_d, void* stream) {
+    const char* fn = "urso_lars_trust";
+    if (T < 0) { urso_set_error("%s: T must be >= 0 (got %d)", fn, T); return URSO_EINVAL; }
+    if (nblocks < 0) { urso_set_error("%s: nblocks must be >= 0 (got %d)", fn, nblocks); return URSO_EINVAL; }
+    if (!(eta > 0.0) || !(eta <= 1.7976931348623157e308)) { urso_set_error("%s: eta must be a finite number > 0", fn); return URSO_EINVAL; }
+    if (!(eps >= 0.0) || !(eps <= 1.7976931348623157e308)) { urso_set_error("%s: eps must be a finite number >= 0", fn); return URSO_EINVAL; }
+    if (clip_mode != 0 && clip_mode != 1) { urso_set_error("%s: clip_mode must be 0 or 1 (got %d)", fn, clip_mode); return URSO_EINVAL; }
+    if (!hyper_d || !normsq_d) { urso_set_error("%s: null pointer (hyper, normsq)", fn); return URSO_EINVAL; }
+    if (T == 0) return URSO_OK;
+    if (!first_d || !adapt_d || !trust_d || !stat_d || (nblocks > 0 && !part_d)) {
+        urso_set_error("%s: null pointer (first, adapt, part, trust, stat)", fn); return URSO_EINVAL;
+    }
+    if ((((uintptr_t)part_d) | ((uintptr_t)stat_d)) & 7) { urso_set_error("%s: part and stat must be 8-byte aligned", fn); return URSO_EINVAL; }
+    if ((((uintptr_t)first_d) | ((uintptr_t)adapt_d) | ((uintptr_t)trust_d) | ((uintptr_t)hyper_d) | ((uintptr_t)normsq_d) |
+         ((uintptr_t)ls_state_d)) & 3) {
+        urso_set_error("%s: pointers must be 4-byte aligned", fn); return URSO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(st, URSO_K_OPTIM, 0, (double)nblocks * 8 + (double)T * 36);
+    URSO_KLAUNCH(lars_trust_kernel, dim3(T), dim3(128), 0, st, first_d, adapt_d, part_d, hyper_d, normsq_d, eta, eps, clip_mode,
+                 ls_state_d ? 1 : 0, trust_d, stat_d);
+    return urso_check_launch(fn);
+}
+
+extern "C" int urso_lars_sgd(int T, const int64_t* off_h, const int64_t* n_h, const int64_t* tab_d, const int32_t* blockmap_d, int nblocks,
+                             float* w_d, const float* g_d, float* v_d, const float* trust_d, const float* hyper_d, const float* normsq_d,
+                             const float* ls_state_d, void* stream) {
+    const char* fn = "urso_lars_sgd";
+    const int rc = lars_check_tensors(fn, T, off_h, n_h, nblocks);
+    if (rc != URSO_OK) return rc;
+    if (!w_d || !g_d || !v_d || !hyper_d || !normsq_d) { urso_set_error("%s: null pointer (w, g, v, hyper, normsq)", fn); return URSO_EINVAL; }
+    if (lars_misaligned16(w_d) || lars_misaligned16(g_d) || lars_misaligned16(v_d)) {
+        urso_set_error("%s: w, g and v must be 16-byte aligned", fn); return URSO_EINVAL;
+    }
+    if (w_d == g_d || w_d == v_d || g_d == (const float*)v_d) { urso_set_error("%s: w, g and v must be three different buffers", fn); return URSO_EINVAL; }
+    if (nblocks == 0) return URSO_OK;
+    if (!tab_d || !blockmap_d || !trust_d) { urso_set_error("%s: null pointer (tab, blockmap, trust)", fn); return URSO_EINVAL; }
+    if (((uintptr_t)tab_d) & 7) { urso_set_error("%s: tab must be 8-byte aligned", fn); return URSO_EINVAL; }
+    if ((((uintptr_t)blockmap_d) | ((uintptr_t)trust_d) | ((uintptr_t)hyper_d) | ((uintptr_t)normsq_d) | ((uintptr_t)ls_state_d)) & 3) {
+        urso_set_error("%s: pointers must be 4-byte aligned", fn); return URSO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double n = 0;
+    for (int t = 0; t < T; ++t) n += (double)n_h[t];
+    ProfScope ps(st, URSO_K_OPTIM, 0, n * 20);
+    URSO_KLAUNCH(lars_sgd_kernel, dim3(nblocks), dim3(LT), 0, st, tab_d, blockmap_d, w_d, g_d, v_d, trust_d, hyper_d, normsq_d,
+                 ls_state_d ? 1 : 0);
+    return urso_check_launch(fn);
+}

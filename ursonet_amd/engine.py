@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import grad_accum, hip, loss_scale, loss_weights, weight_ema
+from . import grad_accum, hip, lars, loss_scale, loss_weights, weight_ema
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -103,6 +103,11 @@ class Engine(object):
         self.flat_acc, self.accum_k, self.accum_micro, self.accum_ops, self._accum_roles = None, 1, 0, [], []
         if mode == "training":
             grad_accum.validate(config, self.world_size_hint())            # ValueError before anything is allocated
+        # Config.LARS: the tables and outputs of the three launches that stand where the plain SGD launch stands
+        # (hip.LarsPlan, rebuilt with every plan); None = none of it exists
+        self.lars_plan = None
+        if mode == "training":
+            lars.validate(config, self.world_size_hint())                  # ValueError before anything is allocated
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -979,7 +984,19 @@ class Engine(object):
             self.opt_ops.append(_Launch(lambda: hip.sqnorm_final(self.sqpart, self.normsq), "sqnorm"))
         else:
             self.opt_ops.append(_Launch(lambda: hip.sqnorm(n, self.flat_g, self.sq_ws, self.normsq), "sqnorm"))
-        if self.adam:
+        self.lars_plan = None
+        lars_keys = lars.validate(cfg, self.world_size)            # (eta, eps, clip mode) | None; refuses Adam, so the branch below is SGD's
+        if lars_keys is not None:
+            # Config.LARS: behind the global norm, the per-chunk sums of w^2 and g^2 and the per-tensor trust ratios; where the plain SGD
+            # launch stands, the update with each tensor's trust.  One tensor per slice; kernels (>= 2 dimensions) adapt, the rest has trust 1.
+            # The block map is uploaded here, once per plan; a frozen layer's gradient is zero, so its trust is 1 and its v stays 0
+            eta, eps, clip_mode = lars_keys
+            lp = self.lars_plan = hip.LarsPlan([(o, cnt, lars.adapts(shape)) for (o, cnt, shape) in self.slices.values()], dev)
+            self.opt_ops.append(_Launch(lambda: lp.norms(self.flat_w, self.flat_g), "lars_norms"))
+            self.opt_ops.append(_Launch(lambda: lp.trust_ratios(self.hyper, self.normsq, eta, eps, clip_mode, ls=self.ls_state), "lars_trust"))
+            self.opt_ops.append(_Launch(lambda: lp.sgd(self.flat_w, self.flat_g, self.flat_v, self.hyper, self.normsq, ls=self.ls_state),
+                                        "lars_sgd"))
+        elif self.adam:
             self.opt_ops.append(_Launch(lambda: hip.adam_amsgrad_clip(n, self.flat_w, self.flat_g, self.flat_v, self.flat_v2, self.flat_vhat,
                                                                       self.hyper, self.normsq, ls=self.ls_state), "adam"))
         else:
@@ -1917,6 +1934,18 @@ class Engine(object):
         if self.mode != "training" or self.accum_k == 1:
             return None
         return {"steps": self.accum_k, "micro": self.accum_micro}
+
+    def lars_report(self, adapting_only=False):
+        """{(layer, weight): (|w|, |g|, trust)} of the last optimizer step under Config.LARS, one synchronising read of the device-side
+        table: the float64 norms the trust ratios were computed from (of the weights BEFORE the step and of the finalised gradient) and
+        the float32 trust the update used.  adapting_only: the kernels alone, without the tensors whose trust is 1 by rule.  None when
+        Config.LARS is off; zeros and trust 1 before the first step."""
+        lp = self.lars_plan
+        if lp is None:
+            return None
+        stat, trust = lp.stat.detach().cpu().numpy(), lp.trust.detach().cpu().numpy()
+        return OrderedDict((key, (float(stat[t, 0]), float(stat[t, 1]), float(trust[t])))
+                           for t, key in enumerate(self.slices) if lp.tensors[t][2] or not adapting_only)
 
     def weight_ema(self):
         """{decay, warmup, updates, next_decay} of the device-side state of the weights' average, read once (one synchronising copy); None

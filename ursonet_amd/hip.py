@@ -6,6 +6,7 @@ load, importing this module raises -- there is no CPU / PyTorch fallback.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -260,6 +261,13 @@ _EXT_SIGS = {
     "urso_grad_accum": (_i, [C.c_int64, _fp, _fp, _i, _vp]),
     "urso_grad_accum_parts": (_i, [C.c_int64]),
     "urso_grad_accum_close": (_i, [C.c_int64, _fp, _fp, _f, _fp, _i, _vp]),
+    # layer-wise adaptive rate scaling (ursonet_amd/lars.py): T, n_h | T, n_h, NB, blockmap_h, first_h | T, off_h, n_h, tab, blockmap, NB, w, g,
+    # part | T, first, adapt, NB, part, hyper, normsq, eta, eps, clip mode, trust, stat, loss-scale state | ... w, g, v, trust, hyper, normsq, ls
+    "urso_lars_blocks": (_i, [_i, _vp]),
+    "urso_lars_plan": (_i, [_i, _vp, _i, _vp, _vp]),
+    "urso_lars_norms": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _vp]),
+    "urso_lars_trust": (_i, [_i, _vp, _vp, _i, _fp, _fp, _fp, C.c_double, C.c_double, _i, _fp, _vp, _fp, _vp]),
+    "urso_lars_sgd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
 }
 EXT_SYMBOLS = sorted(_EXT_SIGS)
 
@@ -822,6 +830,54 @@ def grad_accum_close(n, g, acc, c, sqpart, stream=None):
     assert 0 <= n <= min(g.numel(), acc.numel())
     _chk(ext_lib().urso_grad_accum_close(n, ptr(g), ptr(acc), float(c), ptr(sqpart), sqpart.numel(), stream_ptr(stream)),
          "urso_grad_accum_close")
+
+
+class LarsPlan(object):
+    """The tables of the three LARS launches (urso_lars_norms / _trust / _sgd, liburso_ext.so; ursonet_amd/lars.py) for one list of tensors
+    [(offset, numel, adapt)] of the flat buffers: the host copies the entry points check, the block map and first-slot table of
+    urso_lars_plan, their device copies (uploaded once, here) and the launches' outputs part [NB][2] fp32, trust [T] fp32 and
+    stat [T][3] fp64 = (|w|, |g|, q)."""
+
+    def __init__(self, tensors, device):
+        self.tensors = [(int(o), int(n), bool(a)) for o, n, a in tensors]
+        T = self.T = len(self.tensors)
+        self.off_h = (C.c_int64 * max(T, 1))(*[o for o, _, _ in self.tensors])
+        self.n_h = (C.c_int64 * max(T, 1))(*[n for _, n, _ in self.tensors])
+        lib = ext_lib()
+        nb = lib.urso_lars_blocks(T, self.n_h)
+        _chk(min(nb, 0), "urso_lars_blocks")
+        self.nblocks = int(nb)
+        blockmap = np.zeros((max(self.nblocks, 1), 2), dtype=np.int32)
+        first = np.zeros(T + 1, dtype=np.int32)
+        _chk(lib.urso_lars_plan(T, self.n_h, self.nblocks, blockmap.ctypes.data, first.ctypes.data), "urso_lars_plan")
+        self.blockmap_h, self.first_h = blockmap[:self.nblocks], first
+        tab = np.array([[o, n] for o, n, _ in self.tensors], dtype=np.int64).reshape(T, 2)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self.tab = dev(tab) if T else torch.zeros(2, dtype=torch.int64, device=device)
+        self.blockmap, self.first = dev(blockmap), dev(first)
+        self.adapt = dev(np.array([1 if a else 0 for _, _, a in self.tensors] or [0], dtype=np.int32))
+        self.part = torch.zeros(max(self.nblocks, 1), 2, dtype=torch.float32, device=device)
+        self.trust = torch.ones(max(T, 1), dtype=torch.float32, device=device)
+        self.stat = torch.zeros(max(T, 1), 3, dtype=torch.float64, device=device)
+
+    def norms(self, w, g, stream=None):
+        """part[b] = (sum of w^2, sum of g^2) over block b's chunk (ursonet_amd.lars.slot_sums32)."""
+        assert w.dtype == torch.float32 and g.dtype == torch.float32
+        _chk(ext_lib().urso_lars_norms(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g),
+                                       ptr(self.part), stream_ptr(stream)), "urso_lars_norms")
+
+    def trust_ratios(self, hyper, normsq, eta, eps, clip_mode, stream=None, ls=None):
+        """trust[t] and stat[t] = (|w|, |g|, q) from the slots (ursonet_amd.lars.norms64 / trust32); ls: the loss-scaled form."""
+        _chk(ext_lib().urso_lars_trust(self.T, ptr(self.first), ptr(self.adapt), self.nblocks, ptr(self.part), ptr(hyper), ptr(normsq),
+                                       float(eta), float(eps), 1 if clip_mode else 0, ptr(self.trust), ptr(self.stat),
+                                       _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_lars_trust")
+
+    def sgd(self, w, g, v, hyper, normsq, stream=None, ls=None):
+        """The update with each tensor's trust (ursonet_amd.lars.update32); ls: the loss-scaled form."""
+        assert w.dtype == torch.float32 and g.dtype == torch.float32 and v.dtype == torch.float32
+        _chk(ext_lib().urso_lars_sgd(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(v),
+                                     ptr(self.trust), ptr(hyper), ptr(normsq), _ls_ptr(ls) if ls is not None else None,
+                                     stream_ptr(stream)), "urso_lars_sgd")
 
 
 def adam_amsgrad_clip(n, w, g, m, v, vhat, hyper, normsq, stream=None, ls=None):

@@ -228,6 +228,8 @@ class UrsoNet(object):
             if mode == "training":
                 from . import grad_accum
                 grad_accum.validate(config, world)          # ValueError: a bad GRAD_ACCUM_STEPS, or k > 1 under a data-parallel launcher
+                from . import lars
+                lars.validate(config, world)                # ValueError: bad LARS keys, LARS with Adam, or LARS under a data-parallel launcher
                 loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
                 from . import weight_ema
                 weight_ema.initial_state(config, world)     # ValueError: a bad WEIGHT_EMA, or one set under a data-parallel launcher
@@ -475,6 +477,12 @@ class UrsoNet(object):
                 log("epoch %d  loc_loss %.5f  %s%s%s%s" % (
                     epoch + 1, float(np.mean(h[:, 0])) if steps else float("nan"),
                     "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items())), ls_text, lw_text, ema_text))
+                if eng.lars_plan is not None:           # Config.LARS: the trust ratios of the epoch's last step, one read of the device table
+                    from . import lars
+                    ts = lars.summary(eng.lars_report(adapting_only=True))
+                    if ts is not None:
+                        log("epoch %d  lars trust  min %.3e  median %.3e  max %.3e  (%d kernels)" % (
+                            epoch + 1, ts["min"], ts["median"], ts["max"], ts["tensors"]))
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))     # replicas are identical: one writer
                 if use_ema:                             # "ema_" in front: find_last / get_last_checkpoint keep finding the raw file
                     self.save_weights(ema_checkpoint_path(self.checkpoint_path.format(epoch=epoch + 1)), ema=True)
