@@ -3,6 +3,7 @@
 #include "common.h"
 #include <math.h>
 #include "loss_dev.h"
+#include "flat_stream.h"
 
 // =============================================================== max-pool 3x3 / s2 / TF-SAME
 template <typename T>
@@ -290,21 +291,19 @@ extern "C" int urso_sqnorm(size_t n, const float* g_d, void* ws_d, size_t ws_byt
     return urso_check_launch("urso_sqnorm");
 }
 
-// guard (the loss-scaled forms): a step whose squared gradient norm is not finite -- an overflow of the scaled backward pass -- changes nothing
+// guard, clip factor and update rule: flat_stream.h (step_skipped, clip_factor, sgd_one)
 __global__ void sgd_kernel(size_t n, float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v,
                            const float* __restrict__ hyper, const float* __restrict__ normsq, int guard) {
-    if (guard && !isfinite(normsq[0])) return;
-    const float lr = hyper[0], mom = hyper[1], clip = hyper[2];
-    const float norm = sqrtf(normsq[0]);
-    const float c = (clip > 0.f && norm >= clip) ? clip / norm : 1.f;
-    const float step = lr * c;
+    if (step_skipped(guard, normsq)) return;
+    const float lr = hyper[0], mom = hyper[1];
+    const float step = lr * clip_factor(hyper[2], normsq);
     const size_t n4 = n / 4;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         f32x4_t gv = ((const f32x4_t*)g)[i], vv = ((f32x4_t*)v)[i], wv = ((f32x4_t*)w)[i];
-        vv = vv * mom - gv * step; wv += vv;
+        sgd_one(wv, gv, vv, mom, step);
         ((f32x4_t*)v)[i] = vv; ((f32x4_t*)w)[i] = wv;
     }
-    if (blockIdx.x == 0) for (size_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) { float nv = mom * v[i] - step * g[i]; v[i] = nv; w[i] += nv; }
+    if (blockIdx.x == 0) for (size_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) sgd_one(w[i], g[i], v[i], mom, step);
 }
 static int sgd_momentum_clip_impl(size_t n, float* w_d, const float* g_d, float* v_d, const float* hyper_d,
                                   const float* normsq_d, int guard, void* stream) {
@@ -312,8 +311,7 @@ static int sgd_momentum_clip_impl(size_t n, float* w_d, const float* g_d, float*
     if ((((uintptr_t)w_d) | ((uintptr_t)g_d) | ((uintptr_t)v_d)) & 15) { urso_set_error("urso_sgd_momentum_clip: buffers must be 16-byte aligned"); return URSO_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_OPTIM, 0, (double)n * 20);
-    size_t blocks = (n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    URSO_KLAUNCH(sgd_kernel, dim3((int)blocks), dim3(256), 0, st, n, w_d, g_d, v_d, hyper_d, normsq_d, guard);
+    URSO_KLAUNCH(sgd_kernel, dim3(flat_blocks(n / 4)), dim3(FLAT_T), 0, st, n, w_d, g_d, v_d, hyper_d, normsq_d, guard);
     return urso_check_launch("urso_sgd_momentum_clip");
 }
 extern "C" int urso_sgd_momentum_clip(size_t n, float* w_d, const float* g_d, float* v_d, const float* hyper_d,
@@ -332,15 +330,14 @@ extern "C" int urso_sgd_momentum_clip_ls(size_t n, float* w_d, const float* g_d,
 //   w -= lr_t m / (sqrt(vhat) + eps).       hyper = {lr, b1, b2, eps, clipnorm, t}: t lives on the device so that a
 // captured hipGraph advances it on every replay (adam_tick_kernel runs first, alone, so no block reads a half-written t).
 __global__ void adam_tick_kernel(float* hyper, const float* __restrict__ normsq, int guard) {
-    if (guard && !isfinite(normsq[0])) return;                       // a skipped step does not count
+    if (step_skipped(guard, normsq)) return;                         // a skipped step does not count
     if (threadIdx.x == 0 && blockIdx.x == 0) hyper[5] += 1.0f;
 }
 __global__ void adam_kernel(size_t n, float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             float* __restrict__ vhat, const float* __restrict__ hyper, const float* __restrict__ normsq, int guard) {
-    if (guard && !isfinite(normsq[0])) return;
-    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], clip = hyper[4], t = hyper[5], c1 = hyper[6], c2 = hyper[7];
-    const float norm = sqrtf(normsq[0]);
-    const float c = (clip > 0.f && norm >= clip) ? clip / norm : 1.f;
+    if (step_skipped(guard, normsq)) return;
+    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], t = hyper[5], c1 = hyper[6], c2 = hyper[7];
+    const float c = clip_factor(hyper[4], normsq);
     const float lr_t = lr * (sqrtf(1.f - powf(b2, t)) / (1.f - powf(b1, t)));
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float gi = g[i] * c;
@@ -357,8 +354,7 @@ static int adam_amsgrad_clip_impl(size_t n, float* w_d, const float* g_d, float*
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, URSO_K_OPTIM, 0, (double)n * 36);
     URSO_KLAUNCH(adam_tick_kernel, dim3(1), dim3(64), 0, st, hyper_d, normsq_d, guard);
-    size_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    URSO_KLAUNCH(adam_kernel, dim3((int)blocks), dim3(256), 0, st, n, w_d, g_d, m_d, v_d, vhat_d, (const float*)hyper_d, normsq_d, guard);
+    URSO_KLAUNCH(adam_kernel, dim3(flat_blocks(n)), dim3(FLAT_T), 0, st, n, w_d, g_d, m_d, v_d, vhat_d, (const float*)hyper_d, normsq_d, guard);
     return urso_check_launch("urso_adam_amsgrad_clip");
 }
 extern "C" int urso_adam_amsgrad_clip(size_t n, float* w_d, const float* g_d, float* m_d, float* v_d, float* vhat_d,

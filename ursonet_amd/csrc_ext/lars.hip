@@ -1,20 +1,20 @@
 // Layer-wise adaptive rate scaling for SGD with momentum (liburso_ext.so; Config.LARS): the host planning of the
 // block map and the three launches that replace the plain SGD launch -- the per-chunk sums of w^2 and g^2, the per-tensor trust ratios in
 // float64, and the update with each tensor's trust.  Rule, reduction order, tables and argument rules: include/ursonet_ext.h;
-// ursonet_amd/lars.py is the same rule in NumPy.
+// ursonet_amd/lars.py is the same rule in NumPy.  Slot order, clip factor, skipped step and the SGD rule itself: csrc/flat_stream.h.
 //
 // The norms and the update are HBM-bound streams (8 and 20 bytes per parameter): 256 threads per block, 16 bytes per lane and access, one
 // block per chunk of URSO_LARS_CHUNK = 4096 elements of ONE tensor, so that a block's slot pair belongs to one tensor and the result does
 // not depend on how the tensors sit in the flat buffer.  Thread t of a block owns the 16-byte groups t, 256 + t, 512 + t, 768 + t of its
 // chunk: four independent loads per operand in flight, consecutive lanes on consecutive addresses.  A tensor's ragged end (numel % 4
 // elements) is read and written by scalars: nothing outside [offset, offset + numel) is touched, the padding between slices included.
-#include "../csrc/common.h"
+#include "../csrc/flat_stream.h"
 #include "../../include/ursonet_ext.h"
 
 #include <algorithm>
 #include <vector>
 
-static constexpr int LT = 256;                                             // threads per block
+static constexpr int LT = FLAT_T;                                          // threads per block (the slot sum's)
 static constexpr int LG = URSO_LARS_CHUNK / (4 * LT);                      // 16-byte groups per thread
 static_assert(LG * 4 * LT == URSO_LARS_CHUNK, "a chunk is a whole number of groups per thread");
 
@@ -111,17 +111,10 @@ __device__ __forceinline__ f32x4_t lars_load(const float* __restrict__ p, int e,
     return x;
 }
 
-__device__ __forceinline__ void lars_sq(float& s, const f32x4_t& x) {
-    const float a = x.x * x.x, b = x.y * x.y, c = x.z * x.z, d = x.w * x.w;     // each square rounded once (-ffp-contract=off)
-    s = s + a; s = s + b; s = s + c; s = s + d;
-}
-
-// part[block] = {sum of w^2, sum of g^2} over the block's chunk: per thread from 0.0f in the order it reads (its groups in order, x y z w
-// each), then the wave's xor shuffle (32, 16, ... 1), then the four wave sums in wave order from 0.0f -- the order of grad_close_kernel's
-// slots (grad_accum.hip)
+// part[block] = {sum of w^2, sum of g^2} over the block's chunk, per thread in the order it reads (its groups in order): two slots in the
+// order of csrc/flat_stream.h
 __global__ void __launch_bounds__(LT) lars_norms_kernel(const int64_t* __restrict__ tab, const int32_t* __restrict__ blockmap,
                                                         const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ part) {
-    __shared__ float sh[2][LT / 64];
     const LarsChunk ch = lars_chunk(tab, blockmap);
     const float* wp = w + ch.lo;
     const float* gp = g + ch.lo;
@@ -134,23 +127,11 @@ __global__ void __launch_bounds__(LT) lars_norms_kernel(const int64_t* __restric
     }
     float sw = 0.f, sg = 0.f;
 #pragma unroll
-    for (int j = 0; j < LG; ++j) { lars_sq(sw, wv[j]); lars_sq(sg, gv[j]); }
-    sw = wave_sum(sw); sg = wave_sum(sg);
-    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = sw; sh[1][threadIdx.x >> 6] = sg; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float rw = 0.f, rg = 0.f;
-        for (int i = 0; i < LT / 64; ++i) { rw += sh[0][i]; rg += sh[1][i]; }
-        part[2 * (size_t)blockIdx.x] = rw;
-        part[2 * (size_t)blockIdx.x + 1] = rg;
+    for (int j = 0; j < LG; ++j) { sumsq4(sw, wv[j]); sumsq4(sg, gv[j]); }
+    if (flat_block_sums(sw, sg)) {
+        part[2 * (size_t)blockIdx.x] = sw;
+        part[2 * (size_t)blockIdx.x + 1] = sg;
     }
-}
-
-// c, the global-norm clip factor, as sgd_kernel (csrc/pool_loss_optim.hip) computes it
-__device__ __forceinline__ float lars_clip_factor(const float* __restrict__ hyper, const float* __restrict__ normsq) {
-    const float clip = hyper[2];
-    const float norm = sqrtf(normsq[0]);
-    return (clip > 0.f && norm >= clip) ? clip / norm : 1.f;
 }
 
 // One block of two waves per tensor: wave 0 adds the tensor's w^2 slots, wave 1 its g^2 slots, each in index order in float64.  One lane
@@ -170,7 +151,7 @@ __global__ void __launch_bounds__(128) lars_trust_kernel(const int32_t* __restri
                                                          const float* __restrict__ normsq, double eta, double eps, int clip_mode, int guard,
                                                          float* __restrict__ trust, double* __restrict__ stat) {
     __shared__ double sh[2];
-    if (guard && !isfinite(normsq[0])) return;                              // the optimizer skips this step: trust and stat keep their bits
+    if (step_skipped(guard, normsq)) return;                                // the optimizer skips this step: trust and stat keep their bits
     const int t = blockIdx.x, lane = threadIdx.x & 63, which = threadIdx.x >> 6;       // which: 0 = the w^2 slots, 1 = the g^2 slots
     const int s0 = first[t], ns = first[t + 1] - s0;
     const float* pp = part + 2 * (size_t)s0 + which;
@@ -195,7 +176,7 @@ __global__ void __launch_bounds__(128) lars_trust_kernel(const int32_t* __restri
     const double nw = sqrt(sh[0]), ng = sqrt(sh[1]);
     double q = 1.0;
     if (adapt[t] != 0 && nw != 0.0 && ng != 0.0) {
-        const double c = (double)lars_clip_factor(hyper, normsq);
+        const double c = (double)clip_factor(hyper[2], normsq);
         const double prod = c * ng;
         const double den = prod + eps;
         const double num = eta * nw;
@@ -209,23 +190,16 @@ __global__ void __launch_bounds__(128) lars_trust_kernel(const int32_t* __restri
     stat[3 * (size_t)t] = nw; stat[3 * (size_t)t + 1] = ng; stat[3 * (size_t)t + 2] = q;
 }
 
-__device__ __forceinline__ void lars_one(f32x4_t& w, const f32x4_t& g, f32x4_t& v, float mom, float step) {
-    const f32x4_t a = v * mom;                                              // per element two products, one subtraction, one addition: each
-    const f32x4_t b = g * step;                                             // rounded once (-ffp-contract=off)
-    v = a - b;
-    w = w + v;
-}
-
-// step = (lr * c) * trust[tensor]; v = mom * v - step * g; w = w + v over the block's chunk.  guard (the loss-scaled form): a step whose
-// squared gradient norm is not finite changes nothing
+// step = (lr * c) * trust[tensor], then the SGD rule of csrc/flat_stream.h (sgd_one) over the block's chunk: a tensor of trust 1 moves as
+// under sgd_kernel
 __global__ void __launch_bounds__(LT) lars_sgd_kernel(const int64_t* __restrict__ tab, const int32_t* __restrict__ blockmap,
                                                       float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v,
                                                       const float* __restrict__ trust, const float* __restrict__ hyper,
                                                       const float* __restrict__ normsq, int guard) {
-    if (guard && !isfinite(normsq[0])) return;
+    if (step_skipped(guard, normsq)) return;
     const LarsChunk ch = lars_chunk(tab, blockmap);
     const float lr = hyper[0], mom = hyper[1];
-    const float c = lars_clip_factor(hyper, normsq);
+    const float c = clip_factor(hyper[2], normsq);
     const float lrc = lr * c;
     const float step = lrc * trust[ch.tensor];
     float* wp = w + ch.lo;
@@ -242,7 +216,7 @@ __global__ void __launch_bounds__(LT) lars_sgd_kernel(const int64_t* __restrict_
 #pragma unroll
     for (int j = 0; j < LG; ++j) {
         const int e = 4 * (j * LT + (int)threadIdx.x);
-        lars_one(wv[j], gv[j], vv[j], mom, step);
+        sgd_one(wv[j], gv[j], vv[j], mom, step);
         if (e + 4 <= ch.cnt) {
             *(f32x4_t*)(vp + e) = vv[j];
             *(f32x4_t*)(wp + e) = wv[j];
