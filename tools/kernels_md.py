@@ -55,6 +55,9 @@ FAMILIES = [
     ("lars_norms_kernel", "csrc_ext/lars.hip", "one block per 4096-element chunk of one tensor, 16-byte loads, per-block sums of squares", "Config.LARS (opt-in): the slots of every tensor's |w|^2 and |g|^2"),
     ("lars_trust_kernel", "csrc_ext/lars.hip", "one block of two waves per tensor, float64", "Config.LARS (opt-in): the per-tensor trust ratios from the slots, in index order"),
     ("lars_sgd_kernel", "csrc_ext/lars.hip", "elementwise over the same block map, 16-byte accesses", "Config.LARS (opt-in): clip + momentum SGD with each tensor's trust"),
+    ("lamb_moments_kernel", "csrc_opt/lamb.hip", "one block per 4096-element chunk of one tensor, 16-byte accesses, five operands x four groups in registers, per-block sums of squares", "Config.LAMB (opt-in): Adam's moments and the slots of every tensor's |w|^2 and |r|^2"),
+    ("lamb_trust_kernel", "csrc_opt/lamb.hip", "one block of two waves per tensor, float64", "Config.LAMB (opt-in): the per-tensor trust ratios from the slots, in index order"),
+    ("lamb_apply_kernel", "csrc_opt/lamb.hip", "elementwise over the same block map, 16-byte accesses", "Config.LAMB (opt-in): w -= lr * trust * r, r recomputed from m and vhat"),
     ("sqnorm", "pool_loss_optim.hip", "two-level reduction", "global gradient norm"),
 ]
 

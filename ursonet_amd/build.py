@@ -1,4 +1,4 @@
-"""Builds liburso_hip.so and the extension library liburso_ext.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
+"""Builds liburso_hip.so, the extension library liburso_ext.so and the optimizer library liburso_opt.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
 import os
 import subprocess
 import sys
@@ -17,6 +17,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 CSRC_EXT = os.path.join(HERE, "csrc_ext")
 EXT_LIB = os.path.join(LIBDIR, "liburso_ext.so")
 EXT_SOURCES = ["pose_fuse.hip", "loss_weights.hip", "weight_ema.hip", "grad_accum.hip", "lars.hip"]
+# The optimizer library (include/ursonet_opt.h): entry points added after liburso_ext.so's surface was frozen too.  Built and loaded as that one.
+CSRC_OPT = os.path.join(HERE, "csrc_opt")
+OPT_LIB = os.path.join(LIBDIR, "liburso_opt.so")
+OPT_SOURCES = ["lamb.hip"]
 
 
 def _hipcc():
@@ -49,22 +53,32 @@ def _hash_compiler(h):
         pass
 
 
-def ext_source_hash():
-    """source_hash() of the extension library: every file of csrc_ext/, the headers of csrc/ it may include, the public headers, the
-    compile flags and the compiler's version string."""
+def _side_source_hash(srcdir, sources):
+    """source_hash() of a library behind the main one: every file of its source directory, the headers of csrc/ it may include, the public
+    headers, the compile flags and the compiler's version string."""
     import hashlib
     h = hashlib.sha256()
     inc = os.path.join(HERE, "..", "include")
-    files = (sorted(os.path.join(CSRC_EXT, f) for f in os.listdir(CSRC_EXT)) + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) +
+    files = (sorted(os.path.join(srcdir, f) for f in os.listdir(srcdir)) + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) +
              sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
             h.update(fh.read())
         h.update(b"\0")
-    h.update(" ".join(FLAGS + EXT_SOURCES).encode())
+    h.update(" ".join(FLAGS + sources).encode())
     _hash_compiler(h)
     return h.hexdigest()
+
+
+def ext_source_hash():
+    """source_hash() of the extension library."""
+    return _side_source_hash(CSRC_EXT, EXT_SOURCES)
+
+
+def opt_source_hash():
+    """source_hash() of the optimizer library."""
+    return _side_source_hash(CSRC_OPT, OPT_SOURCES)
 
 
 def _stale(lib, digest):
@@ -80,17 +94,19 @@ def _stale(lib, digest):
 def needs_build():
     """Stale unless the hash recorded next to the .so equals the hash of the sources as they are now (mtimes are meaningless after a
     checkout or a snapshot push; a .so shipped without its hash file is rebuilt where a compiler exists and trusted where none does).
-    True if either library is stale."""
-    return _stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash)
+    True if any of the libraries is stale."""
+    return _stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash) or _stale(OPT_LIB, opt_source_hash)
 
 
 def build(force=False, verbose=True):
-    """Compile every HIP source for gfx950 and link the two shared libraries, each only if it is stale (no GPU needed)."""
+    """Compile every HIP source for gfx950 and link the three shared libraries, each only if it is stale (no GPU needed)."""
     os.makedirs(LIBDIR, exist_ok=True)
     if force or _stale(LIB, source_hash):
         _compile_and_link(LIB, CSRC, SOURCES, FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split(), ("_" + VARIANT) if VARIANT else "", source_hash, verbose)
     if force or _stale(EXT_LIB, ext_source_hash):
         _compile_and_link(EXT_LIB, CSRC_EXT, EXT_SOURCES, FLAGS, "_ext", ext_source_hash, verbose)
+    if force or _stale(OPT_LIB, opt_source_hash):
+        _compile_and_link(OPT_LIB, CSRC_OPT, OPT_SOURCES, FLAGS, "_opt", opt_source_hash, verbose)
     return LIB
 
 
@@ -120,4 +136,4 @@ def _compile_and_link(lib, srcdir, sources, flags, tag, digest, verbose):
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
-    print("built", LIB, EXT_LIB)
+    print("built", LIB, EXT_LIB, OPT_LIB)

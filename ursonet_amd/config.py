@@ -86,6 +86,10 @@ class Config(object):
     LARS = None                   # None = off (nothing changes) | the trust coefficient, a float > 0 (usually 0.001): every conv / Dense kernel steps at lr * LARS * |w| / (c |g| + LARS_EPS).  SGD and one GPU only.
     LARS_EPS = 1e-8               # a float >= 0, added to the denominator of the trust ratio
     LARS_CLIP = False             # True = LARC's "clip" mode: a tensor's effective rate never exceeds the global one (trust = min(ratio / lr, 1))
+    # Not reference fields: LAMB, layer-wise trust ratios for Adam on the device (ursonet_amd/lamb.py).
+    LAMB = None                   # None = off (nothing changes) | the trust coefficient, a float > 0 (usually 1.0): every conv / Dense kernel steps at lr * LAMB * |w| / (|r| + LAMB_EPS), r the Adam direction.  Adam and one GPU only; not together with LARS.
+    LAMB_EPS = 1e-8               # a finite float >= 0, added to the denominator of the trust ratio
+    LAMB_CLIP = False             # True = a tensor's rate never exceeds plain Adam's (trust = min(ratio, 1))
 
     def update(self):
         """Derived fields (config.py:151-166)."""

@@ -1,37 +1,17 @@
 // Layer-wise adaptive rate scaling for SGD with momentum (liburso_ext.so; Config.LARS): the host planning of the
 // block map and the three launches that replace the plain SGD launch -- the per-chunk sums of w^2 and g^2, the per-tensor trust ratios in
 // float64, and the update with each tensor's trust.  Rule, reduction order, tables and argument rules: include/ursonet_ext.h;
-// ursonet_amd/lars.py is the same rule in NumPy.  Slot order, clip factor, skipped step and the SGD rule itself: csrc/flat_stream.h.
+// ursonet_amd/lars.py is the same rule in NumPy.  Slot order, clip factor, skipped step and the SGD rule itself: csrc/flat_stream.h;
+// the block map's device and host helpers, shared with LAMB (csrc_opt/lamb.hip): csrc/lars_chunk.h.
 //
 // The norms and the update are HBM-bound streams (8 and 20 bytes per parameter): 256 threads per block, 16 bytes per lane and access, one
 // block per chunk of URSO_LARS_CHUNK = 4096 elements of ONE tensor, so that a block's slot pair belongs to one tensor and the result does
 // not depend on how the tensors sit in the flat buffer.  Thread t of a block owns the 16-byte groups t, 256 + t, 512 + t, 768 + t of its
 // chunk: four independent loads per operand in flight, consecutive lanes on consecutive addresses.  A tensor's ragged end (numel % 4
 // elements) is read and written by scalars: nothing outside [offset, offset + numel) is touched, the padding between slices included.
-#include "../csrc/flat_stream.h"
-#include "../../include/ursonet_ext.h"
-
-#include <algorithm>
-#include <vector>
-
-static constexpr int LT = FLAT_T;                                          // threads per block (the slot sum's)
-static constexpr int LG = URSO_LARS_CHUNK / (4 * LT);                      // 16-byte groups per thread
-static_assert(LG * 4 * LT == URSO_LARS_CHUNK, "a chunk is a whole number of groups per thread");
+#include "../csrc/lars_chunk.h"
 
 // ------------------------------------------------------------------------------------------------ host planning
-static int lars_count(const char* fn, int T, const int64_t* n_h, int64_t* out) {
-    if (T < 0) { urso_set_error("%s: T must be >= 0 (got %d)", fn, T); return URSO_EINVAL; }
-    if (T > 0 && !n_h) { urso_set_error("%s: null pointer (n)", fn); return URSO_EINVAL; }
-    int64_t nb = 0;
-    for (int t = 0; t < T; ++t) {
-        if (n_h[t] < 0) { urso_set_error("%s: tensor %d has a negative size (%lld)", fn, t, (long long)n_h[t]); return URSO_EINVAL; }
-        nb += (n_h[t] + URSO_LARS_CHUNK - 1) / URSO_LARS_CHUNK;
-        if (nb > 0x7fffffff) { urso_set_error("%s: more than 2^31 - 1 blocks", fn); return URSO_EINVAL; }
-    }
-    *out = nb;
-    return URSO_OK;
-}
-
 extern "C" int urso_lars_blocks(int T, const int64_t* n_h) {
     int64_t nb = 0;
     const int rc = lars_count("urso_lars_blocks", T, n_h, &nb);
@@ -55,62 +35,8 @@ extern "C" int urso_lars_plan(int T, const int64_t* n_h, int nblocks, int32_t* b
     return URSO_OK;
 }
 
-// What the norms and the update launches share: the tensor table as the host sees it, checked before any launch.
-static int lars_check_tensors(const char* fn, int T, const int64_t* off_h, const int64_t* n_h, int nblocks) {
-    int64_t nb = 0;
-    const int rc = lars_count(fn, T, n_h, &nb);
-    if (rc != URSO_OK) return rc;
-    if (T > 0 && !off_h) { urso_set_error("%s: null pointer (offsets)", fn); return URSO_EINVAL; }
-    if (nblocks != (int)nb) { urso_set_error("%s: nblocks must be urso_lars_blocks(T, n) = %d (got %d)", fn, (int)nb, nblocks); return URSO_EINVAL; }
-    bool sorted = true;
-    for (int t = 0; t < T; ++t) {
-        if (off_h[t] < 0 || (off_h[t] & 3)) {
-            urso_set_error("%s: tensor %d: offset %lld is not a non-negative multiple of 4 floats", fn, t, (long long)off_h[t]); return URSO_EINVAL;
-        }
-        if (off_h[t] > INT64_MAX - n_h[t]) { urso_set_error("%s: tensor %d: offset + size overflows", fn, t); return URSO_EINVAL; }
-        if (t > 0 && off_h[t] < off_h[t - 1]) sorted = false;
-    }
-    std::vector<int> order;
-    if (!sorted) {                                                         // (the engine's slices ascend: no allocation on its path)
-        order.resize(T);
-        for (int t = 0; t < T; ++t) order[t] = t;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return off_h[a] != off_h[b] ? off_h[a] < off_h[b] : a < b; });
-    }
-    int prev = -1;                                                         // the last non-empty tensor in offset order
-    for (int k = 0; k < T; ++k) {
-        const int t = sorted ? k : order[k];
-        if (n_h[t] == 0) continue;
-        if (prev >= 0 && off_h[prev] + n_h[prev] > off_h[t]) {
-            urso_set_error("%s: tensors %d and %d overlap ([%lld, +%lld) and [%lld, +%lld))", fn, prev, t, (long long)off_h[prev],
-                           (long long)n_h[prev], (long long)off_h[t], (long long)n_h[t]);
-            return URSO_EINVAL;
-        }
-        prev = t;
-    }
-    return URSO_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ device
-// The block's chunk: element range [lo, lo + cnt) of the flat buffers, and its tensor.
-struct LarsChunk { size_t lo; int cnt; int tensor; };
-__device__ __forceinline__ LarsChunk lars_chunk(const int64_t* __restrict__ tab, const int32_t* __restrict__ blockmap) {
-    const int t = blockmap[2 * blockIdx.x], c = blockmap[2 * blockIdx.x + 1];
-    const int64_t off = tab[2 * t], n = tab[2 * t + 1];
-    const int64_t done = (int64_t)c * URSO_LARS_CHUNK, left = n - done;
-    return LarsChunk{(size_t)(off + done), (int)(left < URSO_LARS_CHUNK ? left : URSO_LARS_CHUNK), t};
-}
-
-// the group's four floats; elements past the chunk's end read as +0 (their squares change no bit of a sum that began at +0) and a
-// ragged group is read by scalars: no address outside the tensor is formed
-__device__ __forceinline__ f32x4_t lars_load(const float* __restrict__ p, int e, int cnt) {
-    f32x4_t x = {0.f, 0.f, 0.f, 0.f};
-    if (e + 4 <= cnt) return *(const f32x4_t*)(p + e);
-    if (e < cnt) x.x = p[e];
-    if (e + 1 < cnt) x.y = p[e + 1];
-    if (e + 2 < cnt) x.z = p[e + 2];
-    return x;
-}
-
+// chunk, group load and store, slot sum: csrc/lars_chunk.h
 // part[block] = {sum of w^2, sum of g^2} over the block's chunk, per thread in the order it reads (its groups in order): two slots in the
 // order of csrc/flat_stream.h
 __global__ void __launch_bounds__(LT) lars_norms_kernel(const int64_t* __restrict__ tab, const int32_t* __restrict__ blockmap,
@@ -134,18 +60,9 @@ __global__ void __launch_bounds__(LT) lars_norms_kernel(const int64_t* __restric
     }
 }
 
-// One block of two waves per tensor: wave 0 adds the tensor's w^2 slots, wave 1 its g^2 slots, each in index order in float64.  One lane
-// alone would do that at one dependent load per slot; here the 64 lanes of a wave fetch 64 slots at once (the next batch in flight behind
-// the current one), widen them, and every lane adds them in index order out of the lanes' registers (two constant-lane reads per slot):
-// the order of a single thread, the loads of a wave.  The two chains are independent, so they run on two SIMDs side by side.  All lanes
-// of a wave hold the same sum; thread 0 finishes the tensor.
-__device__ __forceinline__ double lars_readlane(double x, int k) {
-    const long long b = __builtin_bit_cast(long long, x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), k);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), k);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)lo);
-}
-
+// One block of two waves per tensor: wave 0 adds the tensor's w^2 slots, wave 1 its g^2 slots, each in index order in float64
+// (lars_slot_sum, csrc/lars_chunk.h).  The two chains are independent, so they run on two SIMDs side by side.  All lanes of a wave hold the
+// same sum; thread 0 finishes the tensor.
 __global__ void __launch_bounds__(128) lars_trust_kernel(const int32_t* __restrict__ first, const int32_t* __restrict__ adapt,
                                                          const float* __restrict__ part, const float* __restrict__ hyper,
                                                          const float* __restrict__ normsq, double eta, double eps, int clip_mode, int guard,
@@ -155,21 +72,7 @@ __global__ void __launch_bounds__(128) lars_trust_kernel(const int32_t* __restri
     const int t = blockIdx.x, lane = threadIdx.x & 63, which = threadIdx.x >> 6;       // which: 0 = the w^2 slots, 1 = the g^2 slots
     const int s0 = first[t], ns = first[t + 1] - s0;
     const float* pp = part + 2 * (size_t)s0 + which;
-    double s = 0.0;
-    double cur = 0.0;
-    if (lane < ns) cur = (double)pp[2 * lane];
-    for (int base = 0; base < ns; base += 64) {
-        double nxt = 0.0;
-        if (base + 64 + lane < ns) nxt = (double)pp[2 * (base + 64 + lane)];
-        const int m = ns - base;                                            // slots of this batch: min(m, 64), uniform over the wave
-        if (m >= 64) {                                                      // a whole batch: straight-line code
-#pragma unroll
-            for (int k = 0; k < 64; ++k) s = s + lars_readlane(cur, k);
-        } else {                                                            // the tensor's last batch (k is uniform over the wave)
-            for (int k = 0; k < m; ++k) s = s + lars_readlane(cur, k);
-        }
-        cur = nxt;
-    }
+    const double s = lars_slot_sum(pp, ns, lane);
     if (lane == 0) sh[which] = s;
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -217,20 +120,12 @@ __global__ void __launch_bounds__(LT) lars_sgd_kernel(const int64_t* __restrict_
     for (int j = 0; j < LG; ++j) {
         const int e = 4 * (j * LT + (int)threadIdx.x);
         sgd_one(wv[j], gv[j], vv[j], mom, step);
-        if (e + 4 <= ch.cnt) {
-            *(f32x4_t*)(vp + e) = vv[j];
-            *(f32x4_t*)(wp + e) = wv[j];
-        } else {                                                            // the tensor's ragged end: scalars, the padding keeps its bits
-            if (e < ch.cnt) { vp[e] = vv[j].x; wp[e] = wv[j].x; }
-            if (e + 1 < ch.cnt) { vp[e + 1] = vv[j].y; wp[e + 1] = wv[j].y; }
-            if (e + 2 < ch.cnt) { vp[e + 2] = vv[j].z; wp[e + 2] = wv[j].z; }
-        }
+        lars_store(vp, e, ch.cnt, vv[j]);                                   // (the tensor's ragged end: scalars, the padding keeps its bits)
+        lars_store(wp, e, ch.cnt, wv[j]);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ launches
-static inline bool lars_misaligned16(const void* p) { return (((uintptr_t)p) & 15) != 0; }
-
 extern "C" int urso_lars_norms(int T, const int64_t* off_h, const int64_t* n_h, const int64_t* tab_d, const int32_t* blockmap_d, int nblocks,
                                const float* w_d, const float* g_d, float* part_d, void* stream) {
     const char* fn = "urso_lars_norms";

@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import grad_accum, hip, lars, loss_scale, loss_weights, weight_ema
+from . import grad_accum, hip, lamb, lars, loss_scale, loss_weights, weight_ema
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -108,6 +108,11 @@ class Engine(object):
         self.lars_plan = None
         if mode == "training":
             lars.validate(config, self.world_size_hint())                  # ValueError before anything is allocated
+        # Config.LAMB: the same for the three launches that stand where the plain Adam launch stands (hip.LambPlan);
+        # its state {p1, p2, kt} is created ONCE, like hyper: a later set_trainable() rebuilds the plan and must not restart the tick
+        self.lamb_plan, self.lamb_state = None, None
+        if mode == "training":
+            lamb.validate(config, self.world_size_hint())                  # ValueError before anything is allocated
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -984,8 +989,9 @@ class Engine(object):
             self.opt_ops.append(_Launch(lambda: hip.sqnorm_final(self.sqpart, self.normsq), "sqnorm"))
         else:
             self.opt_ops.append(_Launch(lambda: hip.sqnorm(n, self.flat_g, self.sq_ws, self.normsq), "sqnorm"))
-        self.lars_plan = None
+        self.lars_plan, self.lamb_plan = None, None
         lars_keys = lars.validate(cfg, self.world_size)            # (eta, eps, clip mode) | None; refuses Adam, so the branch below is SGD's
+        lamb_keys = lamb.validate(cfg, self.world_size)            # the same; refuses SGD and LARS, so its branch is Adam's
         if lars_keys is not None:
             # Config.LARS: behind the global norm, the per-chunk sums of w^2 and g^2 and the per-tensor trust ratios; where the plain SGD
             # launch stands, the update with each tensor's trust.  One tensor per slice; kernels (>= 2 dimensions) adapt, the rest has trust 1.
@@ -996,6 +1002,19 @@ class Engine(object):
             self.opt_ops.append(_Launch(lambda: lp.trust_ratios(self.hyper, self.normsq, eta, eps, clip_mode, ls=self.ls_state), "lars_trust"))
             self.opt_ops.append(_Launch(lambda: lp.sgd(self.flat_w, self.flat_g, self.flat_v, self.hyper, self.normsq, ls=self.ls_state),
                                         "lars_sgd"))
+        elif lamb_keys is not None:
+            # Config.LAMB: where the plain Adam launch stands, the tick and the moments with the per-chunk sums of w^2 and r^2, the per-tensor
+            # trust ratios, and the update with each tensor's trust.  Tensors and block map as under LARS; flat_v is m, flat_v2 is v
+            eta_l, eps_l, clip_l = lamb_keys
+            bp = self.lamb_plan = hip.LambPlan([(o, cnt, lamb.adapts(shape)) for (o, cnt, shape) in self.slices.values()], dev)
+            if self.lamb_state is None:                                      # created once, like hyper (a rebuilt plan keeps the tick's state)
+                self.lamb_state = bp.state
+            bp.state = self.lamb_state
+            self.opt_ops.append(_Launch(lambda: bp.moments(self.flat_w, self.flat_g, self.flat_v, self.flat_v2, self.flat_vhat, self.hyper,
+                                                           self.normsq, ls=self.ls_state), "lamb_moments"))
+            self.opt_ops.append(_Launch(lambda: bp.trust_ratios(self.normsq, eta_l, eps_l, clip_l, ls=self.ls_state), "lamb_trust"))
+            self.opt_ops.append(_Launch(lambda: bp.apply(self.flat_w, self.flat_v, self.flat_vhat, self.hyper, self.normsq, ls=self.ls_state),
+                                        "lamb_apply"))
         elif self.adam:
             self.opt_ops.append(_Launch(lambda: hip.adam_amsgrad_clip(n, self.flat_w, self.flat_g, self.flat_v, self.flat_v2, self.flat_vhat,
                                                                       self.hyper, self.normsq, ls=self.ls_state), "adam"))
@@ -1885,6 +1904,8 @@ class Engine(object):
         st = [self.flat_w.clone(), self.flat_v.clone(), self.flat_stats.clone()]
         if self.adam:
             st += [self.flat_v2.clone(), self.flat_vhat.clone(), self.hyper.clone()]
+        if self.lamb_state is not None:                # Config.LAMB: the tick's running products and kt
+            st.append(self.lamb_state.clone())
         if self.ema_state is not None:                 # (in front of the loss-scale state, which restore_train_state finds at the end)
             st += [self.flat_ema.clone(), self.ema_state.clone()]
         if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the running sum and the index of the next micro-step
@@ -1898,6 +1919,9 @@ class Engine(object):
         if self.adam:
             self.flat_v2.copy_(st[3]); self.flat_vhat.copy_(st[4]); self.hyper.copy_(st[5])
         k = 6 if self.adam else 3
+        if self.lamb_state is not None:
+            self.lamb_state.copy_(st[k])
+            k += 1
         if self.ema_state is not None:
             self.flat_ema.copy_(st[k]); self.ema_state.copy_(st[k + 1])
             k += 2
@@ -1913,6 +1937,8 @@ class Engine(object):
         self.accum_micro = 0
         if self.adam:
             self.flat_v2.zero_(); self.flat_vhat.zero_(); self.hyper[5] = 0.0
+        if self.lamb_plan is not None:                 # Config.LAMB: {p1, p2, kt} = {1, 1, 0}, with t = 0 above
+            self.lamb_plan.reset()
         if self.ls_state is not None:
             self.ls_state.copy_(torch.tensor(self._ls_init, dtype=torch.float32))
 
@@ -1946,6 +1972,18 @@ class Engine(object):
         stat, trust = lp.stat.detach().cpu().numpy(), lp.trust.detach().cpu().numpy()
         return OrderedDict((key, (float(stat[t, 0]), float(stat[t, 1]), float(trust[t])))
                            for t, key in enumerate(self.slices) if lp.tensors[t][2] or not adapting_only)
+
+    def lamb_report(self, adapting_only=False):
+        """{(layer, weight): (|w|, |r|, trust)} of the last optimizer step under Config.LAMB, one synchronising read of the device-side
+        table: the float64 norms the trust ratios were computed from (of the weights BEFORE the step and of the Adam direction r) and the
+        float32 trust the update used.  adapting_only: the kernels alone.  None when Config.LAMB is off; zeros and trust 1 before the
+        first step."""
+        bp = self.lamb_plan
+        if bp is None:
+            return None
+        stat, trust = bp.stat.detach().cpu().numpy(), bp.trust.detach().cpu().numpy()
+        return OrderedDict((key, (float(stat[t, 0]), float(stat[t, 1]), float(trust[t])))
+                           for t, key in enumerate(self.slices) if bp.tensors[t][2] or not adapting_only)
 
     def weight_ema(self):
         """{decay, warmup, updates, next_decay} of the device-side state of the weights' average, read once (one synchronising copy); None

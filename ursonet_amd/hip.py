@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _VARIANT = os.environ.get("URSO_LIB_VARIANT", "")        # kernel experiments: see ursonet_amd/build.py
 LIB_PATH = os.path.join(_HERE, "lib", "liburso_hip%s.so" % (("_" + _VARIANT) if _VARIANT else ""))
 EXT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_ext.so")          # the extension library (include/ursonet_ext.h): loaded on first use
+OPT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_opt.so")          # the optimizer library (include/ursonet_opt.h): loaded on first use
 
 F32, BF16, F16 = 0, 1, 2
 EPI_RELU, EPI_OUT_F32, EPI_MASK_BITS, EPI_EMIT_BITS, EPI_ADD_SRCGRID = 1, 2, 4, 8, 16
@@ -270,6 +271,16 @@ _EXT_SIGS = {
     "urso_lars_sgd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
 }
 EXT_SYMBOLS = sorted(_EXT_SIGS)
+# the optimizer library liburso_opt.so, include/ursonet_opt.h: bound by opt_lib() on first use
+_OPT_SIGS = {
+    # LAMB (ursonet_amd/lamb.py): T, off_h, n_h, tab, blockmap, NB, w, g, m, v, vhat, hyper, state, normsq, part, loss-scale state | T, first,
+    # adapt, NB, part, normsq, eta, eps, clip mode, trust, stat, ls | T, off_h, n_h, tab, blockmap, NB, w, m, vhat, trust, hyper, state, normsq, ls
+    "urso_lamb_moments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+    "urso_lamb_trust": (_i, [_i, _vp, _vp, _i, _fp, _fp, C.c_double, C.c_double, _i, _fp, _vp, _fp, _vp]),
+    "urso_lamb_apply": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+}
+OPT_SYMBOLS = sorted(_OPT_SIGS)
+LAMB_STATE_INIT = (1.0, 1.0, 0.0)                                     # URSO_LAMB_STATE floats {p1, p2, kt} before the first step
 
 
 def _bind(lib, sigs):
@@ -296,6 +307,23 @@ def ext_lib():
         _bind(lib, _EXT_SIGS)
         _ext = lib
     return _ext
+
+
+_opt = None
+
+
+def opt_lib():
+    """liburso_opt.so, loaded and bound on first use, behind the main library as ext_lib() loads its own."""
+    global _opt
+    if _opt is None:
+        if not os.path.exists(OPT_LIB_PATH):
+            raise ImportError("liburso_opt.so not found at %s -- build it with `python -m ursonet_amd.build` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % OPT_LIB_PATH)
+        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
+        lib = C.CDLL(OPT_LIB_PATH)
+        _bind(lib, _OPT_SIGS)
+        _opt = lib
+    return _opt
 
 
 def last_error():
@@ -878,6 +906,48 @@ class LarsPlan(object):
         _chk(ext_lib().urso_lars_sgd(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(v),
                                      ptr(self.trust), ptr(hyper), ptr(normsq), _ls_ptr(ls) if ls is not None else None,
                                      stream_ptr(stream)), "urso_lars_sgd")
+
+
+class LambPlan(object):
+    """The three LAMB launches (urso_lamb_moments / _trust / _apply, liburso_opt.so; ursonet_amd/lamb.py) for one list of tensors
+    [(offset, numel, adapt)] of the flat buffers.  The host tables, the block map and their device copies are a LarsPlan's (`tables`: the
+    launches share the map of urso_lars_plan); the outputs are this plan's own: part [NB][2] fp32 = (sum w^2, sum r^2), trust [T] fp32,
+    stat [T][3] fp64 = (|w|, |r|, q) and state [3] fp32 = {p1, p2, kt}."""
+
+    def __init__(self, tensors, device):
+        tb = self.tables = LarsPlan(tensors, device)
+        self.tensors, self.T, self.nblocks, self.first_h, self.blockmap_h = tb.tensors, tb.T, tb.nblocks, tb.first_h, tb.blockmap_h
+        self.tab, self.blockmap, self.first, self.adapt = tb.tab, tb.blockmap, tb.first, tb.adapt
+        self.part, self.trust, self.stat = tb.part, tb.trust, tb.stat          # (allocated there, written by these launches alone)
+        self.state = torch.tensor(LAMB_STATE_INIT, dtype=torch.float32, device=device)
+        opt_lib()                                                            # a missing library is an error here, not at the first step
+
+    def reset(self):
+        """state = {1, 1, 0}: before the first step."""
+        self.state.copy_(torch.tensor(LAMB_STATE_INIT, dtype=torch.float32))
+
+    def moments(self, w, g, m, v, vhat, hyper, normsq, stream=None, ls=None):
+        """The tick, then m, v, vhat and part[b] = (sum of w^2, sum of r^2) over block b's chunk (ursonet_amd.lamb.tick32 / moments32 /
+        direction32); ls: the loss-scaled form."""
+        assert all(x.dtype == torch.float32 for x in (w, g, m, v, vhat, hyper)) and hyper.numel() >= 8
+        tb = self.tables
+        _chk(opt_lib().urso_lamb_moments(self.T, tb.off_h, tb.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(m),
+                                         ptr(v), ptr(vhat), ptr(hyper), ptr(self.state), ptr(normsq), ptr(self.part),
+                                         _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_lamb_moments")
+
+    def trust_ratios(self, normsq, eta, eps, clip_mode, stream=None, ls=None):
+        """trust[t] and stat[t] = (|w|, |r|, q) from the slots (ursonet_amd.lars.norms64, ursonet_amd.lamb.trust32)."""
+        _chk(opt_lib().urso_lamb_trust(self.T, ptr(self.first), ptr(self.adapt), self.nblocks, ptr(self.part), ptr(normsq), float(eta),
+                                       float(eps), 1 if clip_mode else 0, ptr(self.trust), ptr(self.stat),
+                                       _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_lamb_trust")
+
+    def apply(self, w, m, vhat, hyper, normsq, stream=None, ls=None):
+        """w = w - (lr * trust) * r with each tensor's trust (ursonet_amd.lamb.apply32)."""
+        assert w.dtype == torch.float32 and m.dtype == torch.float32 and vhat.dtype == torch.float32
+        tb = self.tables
+        _chk(opt_lib().urso_lamb_apply(self.T, tb.off_h, tb.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(m), ptr(vhat),
+                                       ptr(self.trust), ptr(hyper), ptr(self.state), ptr(normsq), _ls_ptr(ls) if ls is not None else None,
+                                       stream_ptr(stream)), "urso_lamb_apply")
 
 
 def adam_amsgrad_clip(n, w, g, m, v, vhat, hyper, normsq, stream=None, ls=None):

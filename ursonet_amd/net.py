@@ -230,6 +230,8 @@ class UrsoNet(object):
                 grad_accum.validate(config, world)          # ValueError: a bad GRAD_ACCUM_STEPS, or k > 1 under a data-parallel launcher
                 from . import lars
                 lars.validate(config, world)                # ValueError: bad LARS keys, LARS with Adam, or LARS under a data-parallel launcher
+                from . import lamb
+                lamb.validate(config, world)                # ValueError: bad LAMB keys, LAMB with SGD or LARS, or LAMB under a data-parallel launcher
                 loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
                 from . import weight_ema
                 weight_ema.initial_state(config, world)     # ValueError: a bad WEIGHT_EMA, or one set under a data-parallel launcher
@@ -482,6 +484,12 @@ class UrsoNet(object):
                     ts = lars.summary(eng.lars_report(adapting_only=True))
                     if ts is not None:
                         log("epoch %d  lars trust  min %.3e  median %.3e  max %.3e  (%d kernels)" % (
+                            epoch + 1, ts["min"], ts["median"], ts["max"], ts["tensors"]))
+                if getattr(eng, "lamb_plan", None) is not None:       # Config.LAMB: the same line for Adam's trust ratios
+                    from . import lamb
+                    ts = lamb.summary(eng.lamb_report(adapting_only=True))
+                    if ts is not None:
+                        log("epoch %d  lamb trust  min %.3e  median %.3e  max %.3e  (%d kernels)" % (
                             epoch + 1, ts["min"], ts["median"], ts["max"], ts["tensors"]))
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))     # replicas are identical: one writer
                 if use_ema:                             # "ema_" in front: find_last / get_last_checkpoint keep finding the raw file
