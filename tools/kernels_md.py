@@ -58,6 +58,9 @@ FAMILIES = [
     ("lamb_moments_kernel", "csrc_opt/lamb.hip", "one block per 4096-element chunk of one tensor, 16-byte accesses, five operands x four groups in registers, per-block sums of squares", "Config.LAMB (opt-in): Adam's moments and the slots of every tensor's |w|^2 and |r|^2"),
     ("lamb_trust_kernel", "csrc_opt/lamb.hip", "one block of two waves per tensor, float64", "Config.LAMB (opt-in): the per-tensor trust ratios from the slots, in index order"),
     ("lamb_apply_kernel", "csrc_opt/lamb.hip", "elementwise over the same block map, 16-byte accesses", "Config.LAMB (opt-in): w -= lr * trust * r, r recomputed from m and vhat"),
+    ("sam_ascend_kernel", "csrc_train/sam.hip", "elementwise grid-stride stream over three flat buffers, 16-byte accesses", "Config.SAM (opt-in): w0 = w, w += rho g / |g| between the step's two passes"),
+    ("sam_descend_kernel", "csrc_train/sam.hip", "integer copy, 16-byte accesses", "Config.SAM (opt-in): w = w0 behind the second pass"),
+    ("sam_settle_kernel", "csrc_train/sam.hip", "one thread", "Config.SAM with LOSS_SCALE: a skipped step leaves the ascent count as it was"),
     ("sqnorm", "pool_loss_optim.hip", "two-level reduction", "global gradient norm"),
 ]
 

@@ -1,4 +1,4 @@
-"""Builds liburso_hip.so, the extension library liburso_ext.so and the optimizer library liburso_opt.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
+"""Builds liburso_hip.so, the extension library liburso_ext.so, the optimizer library liburso_opt.so and the training library liburso_train.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
 import os
 import subprocess
 import sys
@@ -21,6 +21,11 @@ EXT_SOURCES = ["pose_fuse.hip", "loss_weights.hip", "weight_ema.hip", "grad_accu
 CSRC_OPT = os.path.join(HERE, "csrc_opt")
 OPT_LIB = os.path.join(LIBDIR, "liburso_opt.so")
 OPT_SOURCES = ["lamb.hip"]
+# The training library (include/ursonet_train.h): training features added after liburso_opt.so's surface was frozen as well; its own surface
+# stays open, so the next one goes here.  Built and loaded as the other two.
+CSRC_TRAIN = os.path.join(HERE, "csrc_train")
+TRAIN_LIB = os.path.join(LIBDIR, "liburso_train.so")
+TRAIN_SOURCES = ["sam.hip"]
 
 
 def _hipcc():
@@ -81,6 +86,11 @@ def opt_source_hash():
     return _side_source_hash(CSRC_OPT, OPT_SOURCES)
 
 
+def train_source_hash():
+    """source_hash() of the training library."""
+    return _side_source_hash(CSRC_TRAIN, TRAIN_SOURCES)
+
+
 def _stale(lib, digest):
     if not os.path.exists(lib):
         return True
@@ -95,11 +105,11 @@ def needs_build():
     """Stale unless the hash recorded next to the .so equals the hash of the sources as they are now (mtimes are meaningless after a
     checkout or a snapshot push; a .so shipped without its hash file is rebuilt where a compiler exists and trusted where none does).
     True if any of the libraries is stale."""
-    return _stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash) or _stale(OPT_LIB, opt_source_hash)
+    return _stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash) or _stale(OPT_LIB, opt_source_hash) or _stale(TRAIN_LIB, train_source_hash)
 
 
 def build(force=False, verbose=True):
-    """Compile every HIP source for gfx950 and link the three shared libraries, each only if it is stale (no GPU needed)."""
+    """Compile every HIP source for gfx950 and link the four shared libraries, each only if it is stale (no GPU needed)."""
     os.makedirs(LIBDIR, exist_ok=True)
     if force or _stale(LIB, source_hash):
         _compile_and_link(LIB, CSRC, SOURCES, FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split(), ("_" + VARIANT) if VARIANT else "", source_hash, verbose)
@@ -107,6 +117,8 @@ def build(force=False, verbose=True):
         _compile_and_link(EXT_LIB, CSRC_EXT, EXT_SOURCES, FLAGS, "_ext", ext_source_hash, verbose)
     if force or _stale(OPT_LIB, opt_source_hash):
         _compile_and_link(OPT_LIB, CSRC_OPT, OPT_SOURCES, FLAGS, "_opt", opt_source_hash, verbose)
+    if force or _stale(TRAIN_LIB, train_source_hash):
+        _compile_and_link(TRAIN_LIB, CSRC_TRAIN, TRAIN_SOURCES, FLAGS, "_train", train_source_hash, verbose)
     return LIB
 
 
@@ -136,4 +148,4 @@ def _compile_and_link(lib, srcdir, sources, flags, tag, digest, verbose):
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
-    print("built", LIB, EXT_LIB, OPT_LIB)
+    print("built", LIB, EXT_LIB, OPT_LIB, TRAIN_LIB)

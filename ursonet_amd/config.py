@@ -90,6 +90,9 @@ class Config(object):
     LAMB = None                   # None = off (nothing changes) | the trust coefficient, a float > 0 (usually 1.0): every conv / Dense kernel steps at lr * LAMB * |w| / (|r| + LAMB_EPS), r the Adam direction.  Adam and one GPU only; not together with LARS.
     LAMB_EPS = 1e-8               # a finite float >= 0, added to the denominator of the trust ratio
     LAMB_CLIP = False             # True = a tensor's rate never exceeds plain Adam's (trust = min(ratio, 1))
+    # Not reference fields: SAM, sharpness-aware minimization on the device (ursonet_amd/sam.py).
+    SAM = None                    # None = off (nothing changes) | rho, a finite float > 0 (usually 0.05): the optimizer steps with the gradient taken at w + rho g / |g|; every step runs its forward and backward pass twice.  One GPU only.
+    SAM_EPS = 1e-12               # a finite float >= 0, added to the norm in the denominator
 
     def update(self):
         """Derived fields (config.py:151-166)."""

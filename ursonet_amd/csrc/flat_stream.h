@@ -3,8 +3,8 @@
 //
 // The walk.  The passes are HBM-bound streams, so they move 16 bytes per lane and access: 256 threads per block, at most 4096 blocks
 // walking the vectors with a grid stride.  The entry points ask only for 4-byte alignment, so the host splits [0, n) into a scalar head up
-// to the first 16-byte boundary, the vectors and a scalar tail; two buffers that sit differently against that boundary are walked by
-// scalars alone.  Thread t of the grid handles the vectors t, t + 256 B, ... and then the scalars t, t + 256 B, ... of head and tail
+// to the first 16-byte boundary, the vectors and a scalar tail; buffers (two, or three) that sit differently against that boundary are
+// walked by scalars alone.  Thread t of the grid handles the vectors t, t + 256 B, ... and then the scalars t, t + 256 B, ... of head and tail
 // counted through.  Every element is read and written by exactly one thread, once.
 //
 // The slot.  A thread's running sum from 0.0f, squares rounded once, in the order it visits (x y z w of a vector); then the wave's xor
@@ -21,10 +21,11 @@ static constexpr int FLAT_T = 256;                                         // th
 // ---------------------------------------------------------------- host: split, grid, refusals
 // [0, head) scalar, [head, head + 4 nvec) as 16-byte vectors, [head + 4 nvec, n) scalar
 struct FlatSplit { size_t head, nvec; };
-static inline FlatSplit flat_split(size_t n, const void* a, const void* b) {
+// (c: a third buffer walked with the two, or null: vectors only where all of them sit alike)
+static inline FlatSplit flat_split(size_t n, const void* a, const void* b, const void* c = nullptr) {
     FlatSplit s{n, 0};
-    const uintptr_t ma = (uintptr_t)a & 15, mb = (uintptr_t)b & 15;
-    if (ma == mb) {
+    const uintptr_t ma = (uintptr_t)a & 15, mb = (uintptr_t)b & 15, mc = c ? (uintptr_t)c & 15 : ma;
+    if (ma == mb && ma == mc) {
         s.head = ((16 - ma) & 15) / 4;
         if (s.head > n) s.head = n;
         s.nvec = (n - s.head) / 4;

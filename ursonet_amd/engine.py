@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import grad_accum, hip, lamb, lars, loss_scale, loss_weights, weight_ema
+from . import grad_accum, hip, lamb, lars, loss_scale, loss_weights, sam, weight_ema
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -113,6 +113,12 @@ class Engine(object):
         self.lamb_plan, self.lamb_state = None, None
         if mode == "training":
             lamb.validate(config, self.world_size_hint())                  # ValueError before anything is allocated
+        # Config.SAM: the step runs its forward / backward pass twice, around the ascent to w + rho g / |g|.  flat_w0 keeps
+        # the weights meanwhile (pure scratch); sam_state {rho, eps, normsq, scale, applied, applied_total, pending, 0} is created ONCE, like hyper;
+        # sam_ops are the three launches between and behind the passes (_plan_sam).  None / [] = none of it exists
+        self.sam_state, self._sam_keys, self.flat_w0, self.sam_loss, self.sam_stats, self.sam_ops = None, None, None, None, None, []
+        if mode == "training":
+            sam.validate(config, self.world_size_hint())                   # ValueError before anything is allocated
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -317,6 +323,7 @@ class Engine(object):
         self._plan_backward()
         self._resolve_bucket_ops()
         self._plan_optimizer()
+        self._plan_sam()
         self.flat_g.zero_()
         self._fork_weight_gradients()
 
@@ -328,6 +335,8 @@ class Engine(object):
                "opt": [l.label for l in self.opt_ops]}
         if self.accum_ops:                             # Config.GRAD_ACCUM_STEPS > 1: what a micro-step that does not close runs in place of "opt"
             out["accum"] = [l.label for l in self.accum_ops]
+        if self.sam_ops:                               # Config.SAM: norm and ascent between the two passes (prep ... bwd run twice), the way back behind them
+            out["sam"] = [l.label for l in self.sam_ops]
         return out
 
     def _act(self, spec, numel=None):
@@ -1026,6 +1035,48 @@ class Engine(object):
         if self.ema_state is not None:                 # last: behind the optimizer, and behind loss_scale so that LAST_SKIPPED is this step's
             self.opt_ops.append(_Launch(lambda: hip.ema_update(n, self.flat_w, self.flat_ema, self.ema_state, ls=self.ls_state), "ema"))
 
+    def _plan_sam(self):
+        """Config.SAM (ursonet_amd/sam.py): the three launches of the doubled chain.  Where `prep, forward, losses + backward` stand, the step
+        (each micro-step) runs them at w, then sam_norm (the unfused squared norm of ALL of flat_g into sam_state) and sam_ascend (w0 = w,
+        w += s g1), then the same launches again at w + e, then sam_descend (w = w0); the optimizer's launches follow unchanged, on g2.
+        What the second pass must not leave behind: its losses go into sam_loss instead of loss_buf (the loss launches take their slot of
+        whichever buffer self.loss_buf names when they run: _run_passes), and in batch-statistics BN mode the moving statistics of pass 1 are
+        kept aside by a device-to-device copy behind the ascent and put back behind the way back.
+        Under LOSS_SCALE one thread more, behind the optimizer's norm: a step that the optimizer skips takes its ascents out of applied_total."""
+        keys = sam.validate(self.config, self.world_size)
+        self.sam_ops = []
+        if keys is None:
+            self.sam_state = self._sam_keys = self.flat_w0 = self.sam_loss = self.sam_stats = None
+            return
+        dev, n = self.device, self.n_flat
+        if self.sam_state is None:                     # created once, like hyper: a re-plan keeps the counts and set_sam_rho()
+            self.sam_state = torch.tensor(sam.initial_state(*keys), dtype=torch.float32, device=dev)
+        elif keys != self._sam_keys:                   # the keys changed between plans
+            self.sam_state[sam.RHO], self.sam_state[sam.EPS] = keys
+        self._sam_keys = keys
+        if self.flat_w0 is None:
+            self.flat_w0 = torch.zeros_like(self.flat_w)
+        self.sam_loss = torch.zeros_like(self.loss_buf)                    # L(w + e), slot for slot as loss_buf
+        self.sam_stats = torch.zeros_like(self.flat_stats) if self.train_bn else None
+        hip.train_lib()                                # a missing library is an error here, not at the first step
+        nsq = self.sam_state[sam.NORMSQ:sam.NORMSQ + 1]
+        sam_ws = torch.empty_like(self.sq_ws)          # (a workspace of its own: nothing of the optimizer's norm is shared)
+
+        def ascend():
+            hip.sam_ascend(n, self.flat_w, self.flat_g, self.flat_w0, self.sam_state)
+            if self.sam_stats is not None:
+                self.sam_stats.copy_(self.flat_stats)
+
+        def descend():
+            hip.sam_descend(n, self.flat_w, self.flat_w0)
+            if self.sam_stats is not None:
+                self.flat_stats.copy_(self.sam_stats)
+        self.sam_ops = [_Launch(lambda: hip.sqnorm(n, self.flat_g, sam_ws, nsq), "sam_norm"), _Launch(ascend, "sam_ascend"),
+                        _Launch(descend, "sam_descend")]
+        if self.ls_state is not None:
+            at = [l.kind for l in self.opt_ops].index("sqnorm") + 1
+            self.opt_ops.insert(at, _Launch(lambda: hip.sam_settle(self.sam_state, self.normsq, True), "sam_settle"))
+
     def _fork_weight_gradients(self):
         """Weight-gradient launches are leaves of the backward pass: nothing reads their partials before the bucket's reduction, every tensor
         has a gradient buffer of its own and nothing later overwrites what they read.  So they may run LATER than where they stand in the
@@ -1056,6 +1107,8 @@ class Engine(object):
             return                           # loss scaling: the forked capture is not supported, the step stays on the single chain
         if self.accum_k > 1:
             return                           # gradient accumulation: likewise (one graph per role)
+        if self.sam_ops:
+            return                           # SAM: likewise (two backward passes in one graph)
         ops = self.bwd_ops
         fin = ("reduce", "finalize_mat", "finalize_vec", "finalize", "unpack")
         if any(c.batch_bn for c in self.convs.values()):
@@ -1590,6 +1643,21 @@ class Engine(object):
         for op in self.opt_ops:
             op()
 
+    def _run_passes(self):
+        """prep, forward, losses + backward: what a step runs in front of its optimizer (or its accumulation launch).  Under Config.SAM
+        twice, around the ascent: at w, then at w + e with the losses going into sam_loss, and w is back behind it (_plan_sam)."""
+        self.run_prep(); self.run_forward(); self.run_backward()
+        if not self.sam_ops:
+            return
+        norm, ascend, descend = self.sam_ops
+        norm(); ascend()
+        at_w, self.loss_buf = self.loss_buf, self.sam_loss
+        try:
+            self.run_prep(); self.run_forward(); self.run_backward()
+        finally:
+            self.loss_buf = at_w
+        descend()
+
     PLAN_OPTIONS = ("cus", "wgrad_blocks", "wgrad_narrow", "wgrad_big", "hwgrad", "grid_cap", "pair", "stem", "stem_pool", "c3", "bneck", "dense",
                     "pwx")
 
@@ -1624,14 +1692,14 @@ class Engine(object):
             self._run_micro(self._accum_roles[self.accum_micro])
             self.accum_micro = (self.accum_micro + 1) % self.accum_k
             return
-        self.run_prep(); self.run_forward(); self.run_backward(); self.run_optimizer()
+        self._run_passes(); self.run_optimizer()
 
     def _run_micro(self, role):
         """The launches of a micro-step of the given role (Config.GRAD_ACCUM_STEPS > 1), without touching the index: "first" and "add" end
         behind the backward pass in accum_ops, "close" runs the optimizer."""
         assert role in grad_accum.ROLES and self.accum_k > 1
         self._accum_role = role
-        self.run_prep(); self.run_forward(); self.run_backward()
+        self._run_passes()
         for op in (self.opt_ops if role == "close" else self.accum_ops):
             op()
 
@@ -1666,8 +1734,10 @@ class Engine(object):
             if role is not None:
                 self.accum_micro = self._accum_roles.index(role)
             role = self._accum_roles[self.accum_micro]
-        launches = (self.prep_ops + self.fwd_ops + self.loss_pre_ops + self.loss_ops + self.bwd_ops +
-                    (self.accum_ops if self.accum_k > 1 and role != "close" else self.opt_ops))
+        passes = self.prep_ops + self.fwd_ops + self.loss_pre_ops + self.loss_ops + self.bwd_ops
+        if self.sam_ops:                        # Config.SAM: the doubled chain (_run_passes)
+            passes = passes + self.sam_ops[:2] + passes + self.sam_ops[2:]
+        launches = passes + (self.accum_ops if self.accum_k > 1 and role != "close" else self.opt_ops)
         torch.cuda.synchronize(self.device)
         hip.prof_collect()
         hip.prof_enable(True)
@@ -1906,6 +1976,8 @@ class Engine(object):
             st += [self.flat_v2.clone(), self.flat_vhat.clone(), self.hyper.clone()]
         if self.lamb_state is not None:                # Config.LAMB: the tick's running products and kt
             st.append(self.lamb_state.clone())
+        if self.sam_state is not None:                 # Config.SAM: rho, the last step's record and the counts (flat_w0 is scratch)
+            st.append(self.sam_state.clone())
         if self.ema_state is not None:                 # (in front of the loss-scale state, which restore_train_state finds at the end)
             st += [self.flat_ema.clone(), self.ema_state.clone()]
         if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the running sum and the index of the next micro-step
@@ -1921,6 +1993,9 @@ class Engine(object):
         k = 6 if self.adam else 3
         if self.lamb_state is not None:
             self.lamb_state.copy_(st[k])
+            k += 1
+        if self.sam_state is not None:
+            self.sam_state.copy_(st[k])
             k += 1
         if self.ema_state is not None:
             self.flat_ema.copy_(st[k]); self.ema_state.copy_(st[k + 1])
@@ -1941,6 +2016,8 @@ class Engine(object):
             self.lamb_plan.reset()
         if self.ls_state is not None:
             self.ls_state.copy_(torch.tensor(self._ls_init, dtype=torch.float32))
+        if self.sam_state is not None:                 # Config.SAM: the last step's record and the counts; rho and eps stay
+            self.sam_state[sam.NORMSQ:].zero_()
 
     def loss_weight_values(self):
         """[ori_weight, loc_weight] as a strided two-element view of flat_w (Config.LEARNABLE_LOSS_WEIGHTS; no copy, no synchronisation)."""
@@ -1984,6 +2061,26 @@ class Engine(object):
         stat, trust = bp.stat.detach().cpu().numpy(), bp.trust.detach().cpu().numpy()
         return OrderedDict((key, (float(stat[t, 0]), float(stat[t, 1]), float(trust[t])))
                            for t, key in enumerate(self.slices) if bp.tensors[t][2] or not adapting_only)
+
+    def set_sam_rho(self, rho):
+        """Config.SAM's radius from the next step on: the device field, so a captured graph needs no re-capture."""
+        assert self.sam_state is not None, "Config.SAM is off"
+        if isinstance(rho, bool) or not isinstance(rho, (float, np.floating)) or not np.isfinite(rho) or rho <= 0:
+            raise ValueError("%s must be a finite float > 0, got %r" % (sam.KEY, rho))
+        self.sam_state[sam.RHO] = float(rho)
+
+    def sam_report(self):
+        """{rho, grad_norm, scale, applied, applied_total, loss, loss_perturbed} of the last step under Config.SAM, one synchronising read:
+        grad_norm = |g1|, the norm at w that the ascent divided by; loss = L(w) and loss_perturbed = L(w + e), keyed as losses().  Under
+        GRAD_ACCUM_STEPS the last micro-step's.  None when Config.SAM is off; zeros before the first step."""
+        if self.sam_state is None:
+            return None
+        v = torch.cat([self.sam_state, self.loss_buf, self.sam_loss]).detach().cpu().numpy()
+        st, l0, l1 = v[:sam.STATE_LEN], v[sam.STATE_LEN:sam.STATE_LEN + 4], v[sam.STATE_LEN + 4:]
+        names = ((0, "loc_loss"), (2, "k2_loss"), (3, "k3_loss")) if self.config.REGRESS_KEYPOINTS else ((0, "loc_loss"), (1, "ori_loss"))
+        return {"rho": float(st[sam.RHO]), "grad_norm": float(np.sqrt(st[sam.NORMSQ])), "scale": float(st[sam.SCALE]),
+                "applied": bool(st[sam.APPLIED] != 0), "applied_total": int(st[sam.APPLIED_TOTAL]),
+                "loss": {k: float(l0[i]) for i, k in names}, "loss_perturbed": {k: float(l1[i]) for i, k in names}}
 
     def weight_ema(self):
         """{decay, warmup, updates, next_decay} of the device-side state of the weights' average, read once (one synchronising copy); None

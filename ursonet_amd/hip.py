@@ -14,6 +14,7 @@ _VARIANT = os.environ.get("URSO_LIB_VARIANT", "")        # kernel experiments: s
 LIB_PATH = os.path.join(_HERE, "lib", "liburso_hip%s.so" % (("_" + _VARIANT) if _VARIANT else ""))
 EXT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_ext.so")          # the extension library (include/ursonet_ext.h): loaded on first use
 OPT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_opt.so")          # the optimizer library (include/ursonet_opt.h): loaded on first use
+TRAIN_LIB_PATH = os.path.join(_HERE, "lib", "liburso_train.so")      # the training library (include/ursonet_train.h): loaded on first use
 
 F32, BF16, F16 = 0, 1, 2
 EPI_RELU, EPI_OUT_F32, EPI_MASK_BITS, EPI_EMIT_BITS, EPI_ADD_SRCGRID = 1, 2, 4, 8, 16
@@ -281,6 +282,15 @@ _OPT_SIGS = {
 }
 OPT_SYMBOLS = sorted(_OPT_SIGS)
 LAMB_STATE_INIT = (1.0, 1.0, 0.0)                                     # URSO_LAMB_STATE floats {p1, p2, kt} before the first step
+# the training library liburso_train.so, include/ursonet_train.h: bound by train_lib() on first use
+_TRAIN_SIGS = {
+    # SAM (ursonet_amd/sam.py): n, w, g, w0, state | n, w, w0 | state, normsq, guard
+    "urso_sam_ascend": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
+    "urso_sam_descend": (_i, [C.c_int64, _fp, _fp, _vp]),
+    "urso_sam_settle": (_i, [_fp, _fp, _i, _vp]),
+}
+TRAIN_SYMBOLS = sorted(_TRAIN_SIGS)
+SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
 
 
 def _bind(lib, sigs):
@@ -324,6 +334,23 @@ def opt_lib():
         _bind(lib, _OPT_SIGS)
         _opt = lib
     return _opt
+
+
+_train = None
+
+
+def train_lib():
+    """liburso_train.so, loaded and bound on first use, behind the main library as opt_lib() loads its own."""
+    global _train
+    if _train is None:
+        if not os.path.exists(TRAIN_LIB_PATH):
+            raise ImportError("liburso_train.so not found at %s -- build it with `python -m ursonet_amd.build` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % TRAIN_LIB_PATH)
+        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
+        lib = C.CDLL(TRAIN_LIB_PATH)
+        _bind(lib, _TRAIN_SIGS)
+        _train = lib
+    return _train
 
 
 def last_error():
@@ -843,6 +870,27 @@ def ema_swap(n, a, b, stream=None):
 def grad_accum_parts(n):
     """urso_grad_accum_parts (liburso_ext.so): the slots urso_grad_accum_close writes for n elements (its block count; needs no GPU)."""
     return int(ext_lib().urso_grad_accum_parts(int(n)))
+
+
+def sam_ascend(n, w, g, w0, state, stream=None):
+    """urso_sam_ascend (liburso_train.so): w0 = w (the bits) and, where state's normsq is finite and > 0, w = w + s g over n fp32 elements
+    with s = rho / (sqrtf(normsq) + eps); scale, applied and the counts go into state (ursonet_amd.sam.ascend32 / ascend_state32)."""
+    assert all(x.dtype == torch.float32 for x in (w, g, w0, state)) and state.numel() >= SAM_STATE
+    assert 0 <= n <= min(w.numel(), g.numel(), w0.numel())
+    _chk(train_lib().urso_sam_ascend(n, ptr(w), ptr(g), ptr(w0), ptr(state), stream_ptr(stream)), "urso_sam_ascend")
+
+
+def sam_descend(n, w, w0, stream=None):
+    """urso_sam_descend (liburso_train.so): w = w0, the bits, over n 4-byte elements."""
+    assert w.element_size() == 4 and w0.element_size() == 4 and 0 <= n <= min(w.numel(), w0.numel())
+    _chk(train_lib().urso_sam_descend(n, ptr(w), ptr(w0), stream_ptr(stream)), "urso_sam_descend")
+
+
+def sam_settle(state, normsq, guard=True, stream=None):
+    """urso_sam_settle (liburso_train.so): a skipped step (guard and a non-finite normsq) takes its ascents out of applied_total; pending = 0
+    (ursonet_amd.sam.settle32)."""
+    assert state.dtype == torch.float32 and state.numel() >= SAM_STATE and normsq.dtype == torch.float32
+    _chk(train_lib().urso_sam_settle(ptr(state), ptr(normsq), 1 if guard else 0, stream_ptr(stream)), "urso_sam_settle")
 
 
 def grad_accum(n, g, acc, first, stream=None):

@@ -190,6 +190,8 @@ class BatchLogger(object):
 
     def __init__(self, loss_weights=False, weight_ema=False):
         self.ori_loss_acc, self.loc_loss_acc = [], []
+        # (Config.LOSS_SCALE and Config.SAM: train() adds loss_scale_acc / skipped_acc and sam_grad_norm_acc / sam_applied_acc /
+        # sam_sharpness_acc, one entry per step -- per micro-step for SAM -- when the feature is on)
         if weight_ema:                                 # Config.WEIGHT_EMA: the decay that every step's update of the average used
             self.ema_decay_acc = []
         if loss_weights:                               # Config.LEARNABLE_LOSS_WEIGHTS: the two log-variances after every step
@@ -232,6 +234,8 @@ class UrsoNet(object):
                 lars.validate(config, world)                # ValueError: bad LARS keys, LARS with Adam, or LARS under a data-parallel launcher
                 from . import lamb
                 lamb.validate(config, world)                # ValueError: bad LAMB keys, LAMB with SGD or LARS, or LAMB under a data-parallel launcher
+                from . import sam
+                sam.validate(config, world)                 # ValueError: bad SAM keys, or SAM under a data-parallel launcher
                 loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
                 from . import weight_ema
                 weight_ema.initial_state(config, world)     # ValueError: a bad WEIGHT_EMA, or one set under a data-parallel launcher
@@ -405,6 +409,11 @@ class UrsoNet(object):
                    if eng.ls_state is not None else None)
         if ls_hist is not None:
             history_full.loss_scale_acc, history_full.skipped_acc = [], []
+        # Config.SAM: the ascent's record and the losses at w + e of every (micro-)step, likewise; L(w) is the loss history's row
+        sam_hist = (torch.zeros(max(steps * acc_k, 1), int(eng.sam_state.numel()) + n_loss, dtype=torch.float32, device=eng.device)
+                    if getattr(eng, "sam_state", None) is not None else None)
+        if sam_hist is not None:
+            history_full.sam_grad_norm_acc, history_full.sam_applied_acc, history_full.sam_sharpness_acc = [], [], []
         # Config.LEARNABLE_LOSS_WEIGHTS: the two log-variances after every step, likewise (a strided view of flat_w: ori_weight, loc_weight)
         lw_view = eng.loss_weight_values() if eng.learn_lw else None
         lw_hist = torch.zeros(max(steps, 1), 2, dtype=torch.float32, device=eng.device) if lw_view is not None else None
@@ -424,6 +433,10 @@ class UrsoNet(object):
                     train_feed.next_into()
                     runner.step()
                     hist[i * acc_k + j].copy_(eng.loss_buf.view(-1), non_blocking=True)
+                    if sam_hist is not None:
+                        ns = int(eng.sam_state.numel())
+                        sam_hist[i * acc_k + j, :ns].copy_(eng.sam_state, non_blocking=True)
+                        sam_hist[i * acc_k + j, ns:].copy_(eng.sam_loss.view(-1), non_blocking=True)
                 if ls_hist is not None:
                     ls_hist[i].copy_(eng.ls_state, non_blocking=True)
                 if lw_hist is not None:
@@ -443,6 +456,19 @@ class UrsoNet(object):
                 dp.average_over_ranks(hist)
                 dp.average_over_ranks(vhist)
             h = hist[:steps * acc_k].cpu().numpy()
+            sam_text = None
+            if sam_hist is not None and steps:         # (read in front of the fold: one row per micro-step, as the ascents were)
+                from . import sam as SAM
+                sh = sam_hist[:steps * acc_k].cpu().numpy()
+                ns = SAM.STATE_LEN
+                rise = sh[:, ns:] - h                  # L(w + e) - L(w), per loss
+                cols = ((0, "loc_loss"), (2, "k2_loss"), (3, "k3_loss")) if kp else ((0, "loc_loss"), (1, "ori_loss"))
+                history_full.sam_grad_norm_acc += [float(x) for x in np.sqrt(sh[:, SAM.NORMSQ])]
+                history_full.sam_applied_acc += [bool(x) for x in sh[:, SAM.APPLIED]]
+                history_full.sam_sharpness_acc += [{k: float(r[c]) for c, k in cols} for r in rise]
+                sam_text = "epoch %d  sam rho %g  median |g| %.4e  %s  (%d of %d ascents applied)" % (
+                    epoch + 1, float(sh[-1, SAM.RHO]), float(np.median(np.sqrt(sh[:, SAM.NORMSQ]))),
+                    "  ".join("d_%s %+.3e" % (k, float(np.mean(rise[:, c]))) for c, k in cols), int(sh[:, SAM.APPLIED].sum()), len(sh))
             if acc_k > 1:
                 from . import grad_accum
                 h = grad_accum.fold_history(h, acc_k)
@@ -479,6 +505,8 @@ class UrsoNet(object):
                 log("epoch %d  loc_loss %.5f  %s%s%s%s" % (
                     epoch + 1, float(np.mean(h[:, 0])) if steps else float("nan"),
                     "  ".join("val_%s %.5f" % (k, float(x)) for k, x in sorted(val.items())), ls_text, lw_text, ema_text))
+                if sam_text is not None:                # Config.SAM: rho, the median gradient norm at w, the mean rise of every loss along the ascent
+                    log(sam_text)
                 if eng.lars_plan is not None:           # Config.LARS: the trust ratios of the epoch's last step, one read of the device table
                     from . import lars
                     ts = lars.summary(eng.lars_report(adapting_only=True))

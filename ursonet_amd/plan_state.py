@@ -18,7 +18,8 @@ class _Launch(object):
               sampled pixels only) | fwd+maxpool | bn_stats | bn_apply | subsample | quat | loss | bn_bwd | maxpool_bwd | wgrad | unpack |
               finalize | reduce | finalize_mat | finalize_vec | expand | dgrad+wgrad | dgrad (with `wgrad` set: a fused backward pair that
               writes weight-gradient partials too) | dgrad_heads | wgrad_heads | bits_subsample | zero | sqnorm_lw | sqnorm | sgd | adam | loss_scale |
-              ema | grad_accum | grad_close | lars_norms | lars_trust | lars_sgd | lamb_moments | lamb_trust | lamb_apply
+              ema | grad_accum | grad_close | lars_norms | lars_trust | lars_sgd | lamb_moments | lamb_trust | lamb_apply |
+              sam_norm | sam_ascend | sam_descend | sam_settle
       fwd, dgrad, wgrad   names of the layers whose forward output / data gradient / weight gradient it computes, in label order
       done    names of the layers whose gradient contribution is complete once it is enqueued (ursonet_amd/dp.py cuts the pass there)
       bucket  key of the batched parameter-sized passes (hip.ParamBatch): a gradient bucket's index or "all", else None"""
