@@ -53,6 +53,50 @@ int urso_sam_ascend(int64_t n, float* w_d, const float* g_d, float* w0_d, float*
 int urso_sam_descend(int64_t n, float* w_d, const float* w0_d, void* stream);
 int urso_sam_settle(float* state_d, const float* normsq_d, int guard, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * BN recalibration: pooled BatchNorm population statistics (recalibrate_bn, Config.BN_RECAL_BATCHES, DESIGN.md section 22;
+ * ursonet_amd/bn_recal.py is the same rule in NumPy float64 and the written specification).  The batch-statistics forward pass leaves
+ * every BN layer's float32 batch mean and (biased) batch variance on the device; these launches pool them, exactly and without a
+ * momentum, into the statistics over all pixels of all batches seen (law of total variance), and write them into the statistics buffer.
+ *
+ * A layer (one row of the table): bmean, bvar float [N], the batch statistics over M pixels; off_mean, off_var the element offsets of
+ * its moving_mean and moving_variance slices [off, off + N) in the statistics buffer stats_d, float [n_stats].  The accumulator acc_d,
+ * double [n_stats], mirrors that layout: acc[off_mean + c] is channel c's running mean, acc[off_var + c] its running m2 (the sum of
+ * squared deviations from the running mean).  Elements of acc and stats outside the slices are never read or written.
+ *
+ * t is the number of batches already added, passed by value; n = t * M pixels have been pooled before this batch.  Every float64
+ * operation is rounded once (-ffp-contract=off), / is correctly rounded, in this order, per channel:
+ *
+ *   urso_bn_recal_add      mu_b = (double) bmean[c]   v_b = (double) bvar[c]
+ *                          n1    = n + M
+ *                          d     = mu_b - mean
+ *                          mean' = mean + (d * M) / n1
+ *                          m2'   = m2 + (v_b * M + (d * d) * ((n * M) / n1))
+ *   urso_bn_recal_settle   stats[off_mean + c] = (float) mean      stats[off_var + c] = (float) (m2 / n)       n = t * M, t >= 1
+ *
+ * From the zero state (mean = m2 = 0, t = 0) one batch gives its own statistics back: the products with M are exact for M < 2^22.
+ * A channel is one thread's, no atomics: the result does not depend on the grid.  A batch statistic that is not finite makes that
+ * channel's result not finite and touches no other channel.  One launch covers every layer of the table.
+ *
+ * urso_bn_recal_plan validates the host table and copies it to layers_d (L rows, a synchronous copy): call it once per table.  add and
+ * settle take both copies: the host one to check, the device one to run with.
+ * URSO_EINVAL, before any launch or copy: L <= 0 or L > 65535; a null pointer; bmean / bvar off the 4-byte boundary, layers_d or acc_d
+ * off the 8-byte one, stats_d off the 4-byte one; N <= 0; M <= 0; a negative offset; a slice that ends behind n_stats; two slices (of
+ * one layer or of two) that overlap; t < 0 (add) or t < 1 (settle); t * M or (t + 1) * M above 2^53.
+ */
+typedef struct urso_bn_recal_layer {
+    const float* bmean;     /* [N] batch mean */
+    const float* bvar;      /* [N] batch variance (biased) */
+    int64_t N, M;           /* channels; pixels per batch */
+    int64_t off_mean;       /* offset of moving_mean [N] in the statistics buffer and of the running mean in the accumulator */
+    int64_t off_var;        /* offset of moving_variance [N] and of the running m2 */
+} urso_bn_recal_layer;
+int urso_bn_recal_plan(int L, const urso_bn_recal_layer* layers_h, int64_t n_stats, urso_bn_recal_layer* layers_d);
+int urso_bn_recal_add(int L, const urso_bn_recal_layer* layers_h, const urso_bn_recal_layer* layers_d, int64_t n_stats, double* acc_d,
+                      int64_t t, void* stream);
+int urso_bn_recal_settle(int L, const urso_bn_recal_layer* layers_h, const urso_bn_recal_layer* layers_d, int64_t n_stats,
+                         const double* acc_d, float* stats_d, int64_t t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

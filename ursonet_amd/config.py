@@ -93,6 +93,9 @@ class Config(object):
     # Not reference fields: SAM, sharpness-aware minimization on the device (ursonet_amd/sam.py).
     SAM = None                    # None = off (nothing changes) | rho, a finite float > 0 (usually 0.05): the optimizer steps with the gradient taken at w + rho g / |g|; every step runs its forward and backward pass twice.  One GPU only.
     SAM_EPS = 1e-12               # a finite float >= 0, added to the norm in the denominator
+    # Not a reference field: BN statistics of their own for the averaged checkpoints (ursonet_amd/bn_recal.py).  The same
+    # module's recalibrate_bn(model, dataset) re-estimates the statistics of any TRAIN_BN = None model on unlabelled frames and needs no key.
+    BN_RECAL_BATCHES = 0          # 0 = off (nothing changes) | an int k > 0: before train() writes ema_weights_*.h5 it pools the BN statistics of k training batches under the averaged weights into that file; the raw statistics come back bit for bit.  Needs WEIGHT_EMA and TRAIN_BN = None.  One GPU only.
 
     def update(self):
         """Derived fields (config.py:151-166)."""

@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import grad_accum, hip, lamb, lars, loss_scale, loss_weights, sam, weight_ema
+from . import bn_recal, grad_accum, hip, lamb, lars, loss_scale, loss_weights, sam, weight_ema
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -119,6 +119,11 @@ class Engine(object):
         self.sam_state, self._sam_keys, self.flat_w0, self.sam_loss, self.sam_stats, self.sam_ops = None, None, None, None, None, []
         if mode == "training":
             sam.validate(config, self.world_size_hint())                   # ValueError before anything is allocated
+        # Config.BN_RECAL_BATCHES: train()'s recalibration of the averaged weights' BN statistics; the engine only
+        # refuses a bad key.  _recal_plan: (plan_version, hip.BnRecalPlan) once bn_recal_begin() ran; _recal_stats: its clone of flat_stats
+        self._recal_plan = self._recal_stats = None
+        if mode == "training":
+            bn_recal.validate(config, self.world_size_hint())              # ValueError before anything is allocated
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -1965,6 +1970,40 @@ class Engine(object):
         if stats is not None:
             self.flat_stats.copy_(stats)
         return self.losses() if read else None     # read=False: the scalars stay in loss_buf (UrsoNet.train copies them on the device, no sync)
+
+    # ------------------------------------------------------------------ BN recalibration (ursonet_amd/bn_recal.py)
+    def bn_recal_begin(self):
+        """Start pooling BN statistics: the table of every batch-statistics layer in plan order (built once per plan), zeroed float64
+        accumulators, and a clone of flat_stats for bn_recal_abort().  Eager launches, no graph: no buffer of the captured step moves."""
+        if not self.train_bn:
+            raise ValueError("bn_recal_begin needs a training engine with batch-statistics BatchNorm (TRAIN_BN = None): no other plan leaves "
+                             "the batch mean and variance of every BN layer on the device")
+        rp = self._recal_plan
+        if rp is None or rp[0] != self.plan_version:
+            layers = [(c.bmean, c.bvar, c.Mpix, self.stat_slices[(c.node.bn, "moving_mean")][0], self.stat_slices[(c.node.bn, "moving_variance")][0])
+                      for c in self.convs.values() if c.batch_bn]
+            assert {c.node.bn for c in self.convs.values() if c.batch_bn} == {ln for ln, _ in self.stat_slices}, "a BN layer without batch statistics"
+            rp = self._recal_plan = (self.plan_version, hip.BnRecalPlan(layers, self.flat_stats.numel(), self.device))
+        rp[1].reset()
+        self._recal_stats = self.flat_stats.clone()
+
+    def bn_recal_add(self):
+        """The loaded batch's statistics into the pool: what evaluate() runs in front of the losses, then the one add launch."""
+        assert self._recal_stats is not None, "bn_recal_add without bn_recal_begin"
+        self.run_prep(); self.run_forward()
+        self._recal_plan[1].add()
+
+    def bn_recal_end(self):
+        """flat_stats = the pooled statistics of the batches added (at least one).  The momentum updates the forward kernels made on the
+        way are overwritten: every BN layer is a batch-statistics layer in this mode, so every slice is settled."""
+        assert self._recal_stats is not None, "bn_recal_end without bn_recal_begin"
+        self._recal_plan[1].settle(self.flat_stats)
+
+    def bn_recal_abort(self):
+        """flat_stats as bn_recal_begin() found it, bit for bit (in mid-pass, or after bn_recal_end); without a begin: nothing."""
+        if self._recal_stats is not None:
+            self.flat_stats.copy_(self._recal_stats)
+            self._recal_stats = None
 
     def set_lr(self, lr):
         self.hyper[0] = float(lr)

@@ -288,6 +288,10 @@ _TRAIN_SIGS = {
     "urso_sam_ascend": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
     "urso_sam_descend": (_i, [C.c_int64, _fp, _fp, _vp]),
     "urso_sam_settle": (_i, [_fp, _fp, _i, _vp]),
+    # BN recalibration (ursonet_amd/bn_recal.py): L, layers_h, n_stats, layers_d | L, layers_h, layers_d, n_stats, acc, t | ... acc, stats, t
+    "urso_bn_recal_plan": (_i, [_i, _vp, C.c_int64, _vp]),
+    "urso_bn_recal_add": (_i, [_i, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "urso_bn_recal_settle": (_i, [_i, _vp, _vp, C.c_int64, _vp, _fp, C.c_int64, _vp]),
 }
 TRAIN_SYMBOLS = sorted(_TRAIN_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
@@ -954,6 +958,49 @@ class LarsPlan(object):
         _chk(ext_lib().urso_lars_sgd(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(v),
                                      ptr(self.trust), ptr(hyper), ptr(normsq), _ls_ptr(ls) if ls is not None else None,
                                      stream_ptr(stream)), "urso_lars_sgd")
+
+
+class BnRecalLayer(C.Structure):
+    """urso_bn_recal_layer (include/ursonet_train.h): one BN layer of the recalibration launches."""
+    _fields_ = [("bmean", C.c_void_p), ("bvar", C.c_void_p), ("N", C.c_int64), ("M", C.c_int64), ("off_mean", C.c_int64), ("off_var", C.c_int64)]
+
+
+class BnRecalPlan(object):
+    """The table of the two BN recalibration launches (urso_bn_recal_add / _settle, liburso_train.so; ursonet_amd/bn_recal.py) for one list
+    of layers [(bmean, bvar, M, off_mean, off_var)] -- float32 device tensors of N batch statistics over M pixels and the offsets of the
+    layer's moving_mean / moving_variance slices in a statistics buffer of n_stats floats: the host copy the entry points check, its device
+    copy (validated and uploaded once, here, by urso_bn_recal_plan), the float64 accumulator acc [n_stats] in the statistics buffer's layout
+    (running mean where moving_mean lies, running m2 where moving_variance lies) and t, the number of batches added since reset()."""
+
+    def __init__(self, layers, n_stats, device):
+        self.layers = [(m, v, int(M), int(om), int(ov)) for m, v, M, om, ov in layers]      # (keeps the statistics tensors alive)
+        L = self.L = len(self.layers)
+        self.n_stats = int(n_stats)
+        self.table_h = (BnRecalLayer * max(L, 1))()
+        for row, (m, v, M, om, ov) in zip(self.table_h, self.layers):
+            assert m.dtype == torch.float32 and v.dtype == torch.float32 and m.numel() == v.numel()
+            row.bmean, row.bvar, row.N, row.M, row.off_mean, row.off_var = ptr(m), ptr(v), m.numel(), M, om, ov
+        self.table = torch.zeros(max(L, 1) * C.sizeof(BnRecalLayer) // 8, dtype=torch.int64, device=device)
+        _chk(train_lib().urso_bn_recal_plan(L, C.addressof(self.table_h), self.n_stats, ptr(self.table)), "urso_bn_recal_plan")
+        self.acc = torch.zeros(max(self.n_stats, 1), dtype=torch.float64, device=device)
+        self.t = 0
+
+    def reset(self):
+        """acc = 0, t = 0: nothing pooled."""
+        self.acc.zero_()
+        self.t = 0
+
+    def add(self, stream=None):
+        """One more batch: the layers' bmean / bvar as they are now go into acc (ursonet_amd.bn_recal.pool_add64); t advances."""
+        _chk(train_lib().urso_bn_recal_add(self.L, C.addressof(self.table_h), ptr(self.table), self.n_stats, ptr(self.acc), self.t,
+                                           stream_ptr(stream)), "urso_bn_recal_add")
+        self.t += 1
+
+    def settle(self, stats, stream=None):
+        """stats[slices] = the pooled float32 statistics (ursonet_amd.bn_recal.pool_settle32); refused before anything was added."""
+        assert stats.dtype == torch.float32 and stats.numel() >= self.n_stats
+        _chk(train_lib().urso_bn_recal_settle(self.L, C.addressof(self.table_h), ptr(self.table), self.n_stats, ptr(self.acc), ptr(stats),
+                                              self.t, stream_ptr(stream)), "urso_bn_recal_settle")
 
 
 class LambPlan(object):

@@ -239,6 +239,8 @@ class UrsoNet(object):
                 loss_scale.initial_state(config, world)     # ValueError: a bad LOSS_SCALE, or one set under a data-parallel launcher
                 from . import weight_ema
                 weight_ema.initial_state(config, world)     # ValueError: a bad WEIGHT_EMA, or one set under a data-parallel launcher
+                from . import bn_recal
+                bn_recal.validate(config, world)            # ValueError: a bad BN_RECAL_BATCHES, one without WEIGHT_EMA / with a frozen BN, or under a launcher
             if mode == "training" and world > 1:
                 # under a launcher (`python -m torch.distributed.run --nproc-per-node N pose_estimator.py train ...`): one process per GPU, this
                 # rank's engine takes IMAGES_PER_GPU samples of every global batch of IMAGES_PER_GPU x WORLD_SIZE, the gradient exchange is
@@ -379,6 +381,8 @@ class UrsoNet(object):
         val_feed = (DeviceFeeder(eng, val_dataset, cfg, shuffle=True, workers=workers, rank=rank, world=world)
                     if int(cfg.VALIDATION_STEPS) > 0 else None)
         use_ema = eng.ema_state is not None            # Config.WEIGHT_EMA: validate and save the average beside the raw weights
+        from . import bn_recal
+        recal_k = bn_recal.validate(cfg, world)        # Config.BN_RECAL_BATCHES: > 0 = the saved average gets BN statistics of its own
         history_full = BatchLogger(loss_weights=eng.learn_lw, weight_ema=use_ema)
         chief = rank == 0
         if chief:
@@ -520,7 +524,9 @@ class UrsoNet(object):
                         log("epoch %d  lamb trust  min %.3e  median %.3e  max %.3e  (%d kernels)" % (
                             epoch + 1, ts["min"], ts["median"], ts["max"], ts["tensors"]))
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))     # replicas are identical: one writer
-                if use_ema:                             # "ema_" in front: find_last / get_last_checkpoint keep finding the raw file
+                if use_ema and recal_k:                 # Config.BN_RECAL_BATCHES: the averaged weights with statistics of their own
+                    log(self._save_ema_recalibrated(ema_checkpoint_path(self.checkpoint_path.format(epoch=epoch + 1)), recal_k, train_feed, epoch + 1))
+                elif use_ema:                           # "ema_" in front: find_last / get_last_checkpoint keep finding the raw file
                     self.save_weights(ema_checkpoint_path(self.checkpoint_path.format(epoch=epoch + 1)), ema=True)
             if world > 1:
                 import torch.distributed as dist
@@ -530,6 +536,34 @@ class UrsoNet(object):
             val_feed.close()
         self.epoch = max(self.epoch, epochs)
         return history_full
+
+    def _save_ema_recalibrated(self, path, k, feed, epoch):
+        """Config.BN_RECAL_BATCHES: the next k batches of the training feeder through the engine under the averaged weights, their pooled
+        BN statistics (ursonet_amd/bn_recal.py) into the averaged checkpoint `path`, and the raw statistics back bit for bit.  Statistics
+        that are not finite are not written: the file then holds the shared ones, as without the key.  Returns the line to log."""
+        from . import bn_recal
+        from .graph import BN_EPS
+        eng = self._engine
+        raw = eng.flat_stats.detach().cpu().numpy().copy()
+        try:
+            with eng.ema_weights():
+                eng.bn_recal_begin()                    # (keeps the clone of flat_stats that bn_recal_abort puts back)
+                for _ in range(k):
+                    feed.next_into()
+                    eng.bn_recal_add()
+                eng.bn_recal_end()
+            after = eng.flat_stats.detach().cpu().numpy().copy()
+            finite = all(np.all(np.isfinite(after[o:o + n])) for o, n, _s in eng.stat_slices.values())
+            if not finite:
+                eng.bn_recal_abort()
+            self.save_weights(path, ema=True)
+        finally:
+            eng.bn_recal_abort()                        # the raw statistics, bit for bit, whatever happened
+        if not finite:
+            return "epoch %d  bn recal  %d batches x %d images: statistics not finite, the averaged file keeps the shared ones" % (epoch, k, eng.B)
+        rep = bn_recal.shift_report(eng.stat_slices, raw, after, BN_EPS)
+        return "epoch %d  bn recal  %d batches x %d images under the averaged weights  max mean shift / sigma %.3e  max var ratio %.3e  (%d BN layers)" % (
+            epoch, k, eng.B, max(v[0] for v in rep.values()), max(v[1] for v in rep.values()), len(rep))
 
     # ---------------------------------------------------------------- inference
     def _resized(self, images):
