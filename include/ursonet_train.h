@@ -97,6 +97,66 @@ int urso_bn_recal_add(int L, const urso_bn_recal_layer* layers_h, const urso_bn_
 int urso_bn_recal_settle(int L, const urso_bn_recal_layer* layers_h, const urso_bn_recal_layer* layers_d, int64_t n_stats,
                          const double* acc_d, float* stats_d, int64_t t, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * SWA: stochastic weight averaging and SWAG-diagonal (Config.SWA; ursonet_amd/swa.py is the same rule in NumPy and
+ * the written specification).  Behind the optimizer, every `period` performed steps after the first `start`, the weights go into an
+ * equal-weight running mean -- and, for SWAG-diagonal, their squares into a second one; a sample is mean + s * sd * z with
+ * sd = sqrt(max(sq - mean^2, 0)) and z standard normal.  The exchange of the average with the weights is urso_ema_swap's (ursonet_ext.h).
+ *
+ * state_d   int32_t [URSO_SWA_STATE] = {period, start, ticks, models, collected, variance, 0, 0}.  period, start and variance are set by
+ *           the host; urso_swa_update reads all and writes ticks, models and collected.
+ * ls_state_d is the loss-scale state of ursonet_loss_scale.h or NULL.  When it is set and state[URSO_LS_LAST_SKIPPED] != 0 the optimizer
+ *           skipped the step and urso_swa_update changes nothing, collected included.
+ *
+ *   ticks'  = min(ticks + 1, 2^31 - 1)
+ *   collect = period > 0 and ticks' > start and (ticks' - start) % period == 0 and models < URSO_SWA_MAX_MODELS
+ *   models' = models + 1 if collect;   collected = 1 if collect else 0
+ *
+ * urso_swa_update: every thread evaluates the gate.  Where it is shut no block touches w, mean or sq.  Where it is open, with m = models',
+ * every float32 operation rounded once (-ffp-contract=off):
+ *
+ *   m == 1:  mean = w (the bits)                     sq = w * w
+ *   m >  1:  r = fl32(1 / m)
+ *            mean = mean + ((w - mean) * r)           sq = sq + (((w * w) - sq) * r)
+ *
+ * reading w and reading and writing mean: 12 bytes per parameter, 20 with sq.  A one-thread kernel behind the pass on the same stream
+ * advances the state: by then every block has read it.  sq_d may be NULL: then only the mean is kept.  The state lives on the device, so
+ * whether sq_d agrees with state[URSO_SWA_VARIANCE] shows only there: a NULL sq_d with variance != 0, or the reverse, touches no buffer
+ * and no field but collected, which becomes URSO_SWA_REFUSED.
+ *
+ * urso_swag_sample: out[j] for j in [0, n) is the sample of element first + j of the flat buffer; mean_d, sq_d, out_d and z_out_d point at
+ * that element.  Elements 4 i .. 4 i + 3 of the flat buffer use the four words x of Philox-4x32-10 with counter
+ * (i mod 2^32, i >> 32, sample, 0) and key (seed mod 2^32, seed >> 32):
+ *
+ *   u = (x + 0.5) * 2^-32 (float64, exact)     (z0, z1) = sqrt(-2 log u0) * (cos, sin)(2 pi u1)     (z2, z3) likewise from u2, u3
+ *
+ * in float64, rounded to float32 at the end; then in float32, each operation rounded once, sqrtf correctly rounded:
+ *
+ *   d = sq - (mean * mean)     sd = sqrtf(d > 0 ? d : 0)     out = mean + ((s * sd) * z)
+ *
+ * z_out_d, when not NULL, receives z.  The values depend on first + j alone, not on the grid, the alignment or how a range is cut into
+ * launches.  s is the host's fl32(sqrt(var_scale)).
+ *
+ * Both streams: 256 threads per block, at most 4096 blocks with a grid stride, 16 bytes per lane and access where all buffers of the
+ * launch sit alike against the 16-byte boundary (a scalar head and tail around the vectors), scalars alone otherwise.  n == 0 launches
+ * nothing.  Nothing outside [0, n) is read or written.
+ * URSO_EINVAL, before any launch: a null pointer (sq_d of the update and z_out_d may be NULL); n < 0; a pointer off the 4-byte boundary;
+ * w, mean, sq (out or z_out and any other buffer) being one buffer or overlapping within n elements; first negative or no multiple of 4;
+ * s negative or not finite; sample < 0.
+ */
+#define URSO_SWA_STATE 8
+#define URSO_SWA_PERIOD 0
+#define URSO_SWA_START 1
+#define URSO_SWA_TICKS 2
+#define URSO_SWA_MODELS 3
+#define URSO_SWA_COLLECTED 4
+#define URSO_SWA_VARIANCE 5
+#define URSO_SWA_MAX_MODELS 16777216
+#define URSO_SWA_REFUSED (-1)
+int urso_swa_update(int64_t n, const float* w_d, float* mean_d, float* sq_d, int32_t* state_d, const float* ls_state_d, void* stream);
+int urso_swag_sample(int64_t n, int64_t first, const float* mean_d, const float* sq_d, float* out_d, float* z_out_d, float s, uint64_t seed,
+                     int sample, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

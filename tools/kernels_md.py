@@ -61,6 +61,9 @@ FAMILIES = [
     ("sam_ascend_kernel", "csrc_train/sam.hip", "elementwise grid-stride stream over three flat buffers, 16-byte accesses", "Config.SAM (opt-in): w0 = w, w += rho g / |g| between the step's two passes"),
     ("sam_descend_kernel", "csrc_train/sam.hip", "integer copy, 16-byte accesses", "Config.SAM (opt-in): w = w0 behind the second pass"),
     ("sam_settle_kernel", "csrc_train/sam.hip", "one thread", "Config.SAM with LOSS_SCALE: a skipped step leaves the ascent count as it was"),
+    ("swa_update_kernel", "csrc_train/swa.hip", "elementwise grid-stride stream over two or three flat buffers, 16-byte accesses; every block returns at once where the gate is shut", "Config.SWA (opt-in): the equal-weight running mean of the weights (and of their squares) behind the optimizer"),
+    ("swa_advance_kernel", "csrc_train/swa.hip", "one thread", "Config.SWA: ticks, models and collected of the device-side state"),
+    ("swag_sample_kernel", "csrc_train/swa.hip", "elementwise grid-stride stream, one Philox-4x32-10 call and two float64 Box-Muller pairs per 16-byte vector", "Config.SWA_VARIANCE: one weight set from the SWAG-diagonal Gaussian (never in the step)"),
     ("sqnorm", "pool_loss_optim.hip", "two-level reduction", "global gradient norm"),
 ]
 

@@ -96,6 +96,11 @@ class Config(object):
     # Not a reference field: BN statistics of their own for the averaged checkpoints (ursonet_amd/bn_recal.py).  The same
     # module's recalibrate_bn(model, dataset) re-estimates the statistics of any TRAIN_BN = None model on unlabelled frames and needs no key.
     BN_RECAL_BATCHES = 0          # 0 = off (nothing changes) | an int k > 0: before train() writes ema_weights_*.h5 it pools the BN statistics of k training batches under the averaged weights into that file; the raw statistics come back bit for bit.  Needs WEIGHT_EMA and TRAIN_BN = None.  One GPU only.
+    # Not reference fields: stochastic weight averaging and SWAG-diagonal on the device (ursonet_amd/swa.py).
+    SWA = None                    # None = off (nothing changes) | an int c > 0: every c performed optimizer steps the weights go into an equal-weight running mean (with CLR: c = 2 * CLR_STEP_SIZE, the low points of the cycle); train() also validates and saves the average.  One GPU only.
+    SWA_START = 0                 # an int >= 0: the number of performed optimizer steps before the counting begins
+    SWA_VARIANCE = False          # True = also keep the running mean of w * w (SWAG-diagonal): swag_weights() samples weight sets from N(mean, var_scale * diag(sq - mean^2))
+    SWA_RECAL_BATCHES = 0         # 0 = off | an int k > 0: before train() writes swa_weights_*.h5 it pools the BN statistics of k training batches under the averaged weights into that file; the raw statistics come back bit for bit.  Needs SWA and TRAIN_BN = None.
 
     def update(self):
         """Derived fields (config.py:151-166)."""

@@ -288,6 +288,8 @@ class DataParallelEngine(object):
             raise ValueError("LAMB is not supported under data parallelism (world size %d): leave Config.LAMB = None" % self.world)
         if self.world > 1 and getattr(engine, "sam_state", None) is not None:
             raise ValueError("SAM is not supported under data parallelism (world size %d): leave Config.SAM = None" % self.world)
+        if self.world > 1 and getattr(engine, "swa_state", None) is not None:
+            raise ValueError("SWA is not supported under data parallelism (world size %d): leave Config.SWA = None" % self.world)
         if getattr(engine, "mode", None) == "training":
             from . import grad_accum
             if grad_accum.validate(engine.config, self.world) > 1:      # (one rank too: this class replays graph cuts of its own)

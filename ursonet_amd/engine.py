@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import bn_recal, grad_accum, hip, lamb, lars, loss_scale, loss_weights, sam, weight_ema
+from . import bn_recal, grad_accum, hip, lamb, lars, loss_scale, loss_weights, sam, swa, weight_ema
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
@@ -98,6 +98,13 @@ class Engine(object):
         self.ema_swapped = False
         if weight_ema.enabled(config, mode):
             weight_ema.initial_state(config, self.world_size_hint())       # ValueError before anything is allocated
+        # Config.SWA: the equal-weight running mean of the weights collected every SWA performed steps (flat_swa), with
+        # SWA_VARIANCE the running mean of their squares (flat_swa_sq), and the int32 device-side state (ursonet_amd/swa.py); created once like
+        # hyper.  swa_swapped: flat_w holds the average right now (swap_swa); _swag_hold: the raw weights while a sample stands in flat_w
+        self.flat_swa = self.flat_swa_sq = self.swa_state = self._swa_init = self._swag_hold = None
+        self.swa_swapped = self._swag_active = False
+        if mode == "training":
+            swa.validate(config, self.world_size_hint())                   # ValueError before anything is allocated
         # Config.GRAD_ACCUM_STEPS: k > 1 = a second flat buffer that sums the gradients of k micro-steps and the host-side
         # index of the next micro-step; step() replays one captured graph per launch role (ursonet_amd/grad_accum.py).  1 = none of it exists
         self.flat_acc, self.accum_k, self.accum_micro, self.accum_ops, self._accum_roles = None, 1, 0, [], []
@@ -157,6 +164,10 @@ class Engine(object):
             self.flat_v = torch.zeros_like(self.flat_w)
             if weight_ema.enabled(self.config, self.mode):
                 self.flat_ema = torch.zeros_like(self.flat_w)          # set_weights below fills it: the average starts at the weights
+            if swa.enabled(self.config, self.mode):                    # (the first collected model is copied in: zeros until then)
+                self.flat_swa = torch.zeros_like(self.flat_w)
+                if getattr(self.config, "SWA_VARIANCE", False):
+                    self.flat_swa_sq = torch.zeros_like(self.flat_w)
         self.set_weights(initial_weights(g, seed, randomize_bn))
 
     def wview(self, ln, wn, buf=None):
@@ -173,8 +184,13 @@ class Engine(object):
 
     def set_weights(self, params, strict=True):
         """params: {layer: {weight: array}} in Keras layouts.  Missing layers are skipped unless strict.  With Config.WEIGHT_EMA the values
-        go into the average as well: a model that loads a checkpoint starts its average there (set_ema_weights loads another one)."""
+        go into the average as well: a model that loads a checkpoint starts its average there (set_ema_weights loads another one).  With
+        Config.SWA the collection starts afresh (ticks = models = 0): the models collected so far belong to other weights."""
         assert not getattr(self, "ema_swapped", False), "set_weights while the average is swapped in (swap_ema / ema_weights)"
+        assert not getattr(self, "swa_swapped", False) and not getattr(self, "_swag_active", False), \
+            "set_weights while the SWA average or a SWAG sample stands in for the weights (swap_swa / swa_weights / swag_weights)"
+        if getattr(self, "swa_state", None) is not None:
+            self.reset_swa()
         ema = getattr(self, "flat_ema", None)
         for ln, ws in self.graph.params.items():
             if ln not in params:
@@ -193,6 +209,10 @@ class Engine(object):
         """Load params (as set_weights takes them) into the average alone; the BN statistics, which both sets share, are not touched."""
         assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
         assert not self.ema_swapped, "set_ema_weights while the average is swapped in (swap_ema / ema_weights)"
+        self._load_trainable(params, self.flat_ema, strict)
+
+    def _load_trainable(self, params, buf, strict):
+        """params' trainable tensors into the flat buffer `buf` (an average's: set_ema_weights, set_swa_weights); BN statistics are skipped."""
         for ln, ws in self.graph.params.items():
             if ln not in params:
                 if strict:
@@ -204,14 +224,27 @@ class Engine(object):
                 a = np.asarray(params[ln][wn], dtype=np.float32)
                 if tuple(a.shape) != tuple(shape):
                     raise ValueError("layer %s weight %s: shape %s != expected %s" % (ln, wn, a.shape, shape))
-                self.wview(ln, wn, self.flat_ema).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+                self.wview(ln, wn, buf).copy_(torch.from_numpy(np.ascontiguousarray(a)))
 
-    def get_weights(self, ema=False):
+    def get_weights(self, ema=False, swa=False):
         """{layer: {weight: array}}.  ema=True: the averaged parameters (Config.WEIGHT_EMA) beside the BN statistics, which both sets share.
-        Either set is found wherever it lies: inside ema_weights() the two buffers have changed places."""
+        swa=True: the SWA mean (Config.SWA) likewise; swa="sq": the running mean of squares (SWA_VARIANCE) under the same names.
+        Every set is found wherever it lies: inside ema_weights() / swa_weights() two buffers have changed places.  Inside swag_weights()
+        the plain call returns the sample, which is then the model (so that save_weights() writes a sampled model)."""
         if ema:
             assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
-        buf = (self.flat_ema, self.flat_w)[bool(ema) == self.ema_swapped] if self.flat_ema is not None else None
+        if swa:
+            assert not ema, "ema and swa are two sets: ask for one"
+            assert self.flat_swa is not None, "Config.SWA is off"
+            if swa == "sq":
+                assert self.flat_swa_sq is not None, "Config.SWA_VARIANCE is off"
+                buf = self.flat_swa_sq
+            else:
+                buf = self.flat_w if self.swa_swapped else self.flat_swa
+        elif self.swa_swapped or self._swag_active:    # (neither nests with the EMA exchange)
+            buf = self.flat_ema if ema else (self.flat_swa if self.swa_swapped else self.flat_w)
+        else:
+            buf = (self.flat_ema, self.flat_w)[bool(ema) == self.ema_swapped] if self.flat_ema is not None else None
         out = OrderedDict()
         for ln, ws in self.graph.params.items():
             out[ln] = OrderedDict((wn, self.wview(ln, wn, buf).detach().cpu().numpy().copy()) for wn in ws)
@@ -284,6 +317,22 @@ class Engine(object):
             elif init != self._ema_init:               # the keys changed between plans: the schedule starts afresh, the average stays
                 self._ema_init = init
                 self.ema_state.copy_(torch.tensor(init, dtype=torch.float32))
+        # Config.SWA: None = no launch and no buffer.  Set: one more launch, the last of opt_ops (_plan_optimizer)
+        if training:
+            init = swa.initial_state(self.config, self.world_size)
+            if init is None:
+                self.swa_state = self._swa_init = None
+            else:
+                if self.flat_swa is None:              # the key was set after the engine was built
+                    self.flat_swa = torch.zeros_like(self.flat_w)
+                if bool(init[swa.VARIANCE]) != (self.flat_swa_sq is not None):
+                    self.flat_swa_sq = torch.zeros_like(self.flat_w) if init[swa.VARIANCE] else None
+                if self.swa_state is None:
+                    self._swa_init = init
+                    self.swa_state = torch.tensor(init, dtype=torch.int32, device=self.device)
+                elif init != self._swa_init:           # the keys changed between plans: the collection starts afresh, in the same buffer
+                    self._swa_init = init
+                    self.swa_state.copy_(torch.tensor(init, dtype=torch.int32))
         # Config.GRAD_ACCUM_STEPS: 1 = no launch and no buffer.  k > 1: one launch behind the backward pass of the
         # micro-steps that do not close (accum_ops) and one in front of the optimizer of the one that does (_plan_optimizer); a new plan
         # starts a new optimizer step
@@ -1039,6 +1088,9 @@ class Engine(object):
             self.opt_ops.append(_Launch(lambda: hip.loss_scale_update(self.ls_state, self.normsq), "loss_scale"))
         if self.ema_state is not None:                 # last: behind the optimizer, and behind loss_scale so that LAST_SKIPPED is this step's
             self.opt_ops.append(_Launch(lambda: hip.ema_update(n, self.flat_w, self.flat_ema, self.ema_state, ls=self.ls_state), "ema"))
+        if self.swa_state is not None:                 # Config.SWA: the very last, for the same reason; its gate is shut on most steps
+            self.opt_ops.append(_Launch(lambda: hip.swa_update(n, self.flat_w, self.flat_swa, self.flat_swa_sq, self.swa_state, ls=self.ls_state),
+                                        "swa"))
 
     def _plan_sam(self):
         """Config.SAM (ursonet_amd/sam.py): the three launches of the doubled chain.  Where `prep, forward, losses + backward` stand, the step
@@ -1847,6 +1899,8 @@ class Engine(object):
                 gr.replay()
             torch.cuda.synchronize(self.device)
             written = (self.flat_w, self.flat_g, self.flat_v, self.flat_stats) + ((self.flat_ema, self.ema_state) if self.ema_state is not None else ())
+            if self.swa_state is not None:
+                written += (self.flat_swa, self.swa_state) + ((self.flat_swa_sq,) if self.flat_swa_sq is not None else ())
             got = [t.clone() for t in written]
             self.restore_train_state(saved)
             self._single_chain = True
@@ -1888,6 +1942,8 @@ class Engine(object):
     def step(self):
         """Replay the captured training step (captures on first use)."""
         assert not self.ema_swapped, "step() while the average is swapped in: leave ema_weights() / call swap_ema() again first"
+        assert not self.swa_swapped and not self._swag_active, \
+            "step() while the SWA average or a SWAG sample stands in for the weights: leave swa_weights() / swag_weights() / call swap_swa() again first"
         if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the graph of this micro-step's role, captured on first use
             role = self._accum_roles[self.accum_micro]
             if self._graphs is None or role not in self._graphs:
@@ -2019,6 +2075,8 @@ class Engine(object):
             st.append(self.sam_state.clone())
         if self.ema_state is not None:                 # (in front of the loss-scale state, which restore_train_state finds at the end)
             st += [self.flat_ema.clone(), self.ema_state.clone()]
+        if self.swa_state is not None:                 # Config.SWA: the mean, the state and, with SWA_VARIANCE, the mean of squares
+            st += [self.flat_swa.clone(), self.swa_state.clone()] + ([self.flat_swa_sq.clone()] if self.flat_swa_sq is not None else [])
         if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the running sum and the index of the next micro-step
             st += [self.flat_acc.clone(), self.accum_micro]
         if self.ls_state is not None:
@@ -2039,13 +2097,20 @@ class Engine(object):
         if self.ema_state is not None:
             self.flat_ema.copy_(st[k]); self.ema_state.copy_(st[k + 1])
             k += 2
+        if self.swa_state is not None:
+            self.flat_swa.copy_(st[k]); self.swa_state.copy_(st[k + 1])
+            k += 2
+            if self.flat_swa_sq is not None:
+                self.flat_swa_sq.copy_(st[k])
+                k += 1
         if self.accum_k > 1:
             self.flat_acc.copy_(st[k]); self.accum_micro = int(st[k + 1])
         if self.ls_state is not None:
             self.ls_state.copy_(st[-1])
 
     def reset_optimizer(self):
-        """Zero the optimizer's moments (and restart the loss scale).  The weights' average and its schedule are no optimizer state: they stay.
+        """Zero the optimizer's moments (and restart the loss scale).  The weights' averages (Config.WEIGHT_EMA, Config.SWA) and their schedules
+        are no optimizer state: they stay, so staged training keeps one average (reset_swa() restarts SWA's by hand).
         Under Config.GRAD_ACCUM_STEPS > 1 a begun optimizer step is dropped: the next micro-step is a first one (a bit copy into flat_acc)."""
         self.flat_v.zero_()
         self.accum_micro = 0
@@ -2132,6 +2197,7 @@ class Engine(object):
         """Exchange flat_w and flat_ema in place (urso_ema_swap) and flip ema_swapped.  Every forward pass reads flat_w only through the prep
         pass, which evaluate() and the captured step both begin with, so nothing else has to move; the BN statistics are shared."""
         assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
+        assert not self.swa_swapped and not self._swag_active, "swap_ema while the SWA average or a SWAG sample stands in for the weights"
         hip.ema_swap(self.n_flat, self.flat_w, self.flat_ema)
         self.ema_swapped = not self.ema_swapped
 
@@ -2146,6 +2212,91 @@ class Engine(object):
 
             def __exit__(self, *exc):
                 eng.swap_ema()
+                return False
+        return _Ctx()
+
+    # ------------------------------------------------------------------ Config.SWA
+    def swa(self):
+        """{period, start, ticks, models, collected, variance} of the device-side SWA state, read once (one synchronising copy); None when
+        Config.SWA is off."""
+        if self.swa_state is None:
+            return None
+        return swa.as_dict(self.swa_state.detach().cpu().tolist())
+
+    def reset_swa(self):
+        """Restart the collection: ticks = models = 0.  The first model collected afterwards is copied in, so the buffers need no clearing."""
+        assert self.swa_state is not None, "Config.SWA is off"
+        assert not self.swa_swapped and not self._swag_active, "reset_swa while the SWA average or a SWAG sample stands in for the weights"
+        self.swa_state.copy_(torch.tensor(self._swa_init, dtype=torch.int32))
+
+    def set_swa_weights(self, params, sq_params=None, models=None, strict=True):
+        """Load params (as set_weights takes them) into the SWA mean and, with SWA_VARIANCE, sq_params into the mean of squares; `models`
+        (>= 1) is the number of models they average.  The collection goes on from there: ticks = start + models * period.  The BN statistics,
+        which all sets share, are not touched."""
+        assert self.swa_state is not None, "Config.SWA is off"
+        assert not self.swa_swapped and not self._swag_active, "set_swa_weights while the SWA average or a SWAG sample stands in for the weights"
+        if isinstance(models, (bool, np.bool_)) or not isinstance(models, (int, np.integer)) or not 1 <= models <= swa.MAX_MODELS:
+            raise ValueError("set_swa_weights: models must be an int in [1, 2^24], got %r" % (models,))
+        if (sq_params is not None) != (self.flat_swa_sq is not None):
+            raise ValueError("set_swa_weights: sq_params goes with Config.SWA_VARIANCE = True and only with it")
+        self._load_trainable(params, self.flat_swa, strict)
+        if sq_params is not None:
+            self._load_trainable(sq_params, self.flat_swa_sq, strict)
+        st = list(self._swa_init)
+        st[swa.MODELS] = int(models)
+        st[swa.TICKS] = min(st[swa.START] + int(models) * st[swa.PERIOD], swa.MAX_TICKS)
+        self.swa_state.copy_(torch.tensor(st, dtype=torch.int32))
+
+    def swap_swa(self):
+        """Exchange flat_w and flat_swa in place (urso_ema_swap: there is one exchange kernel) and flip swa_swapped; as swap_ema."""
+        assert self.flat_swa is not None, "Config.SWA is off"
+        assert not self.ema_swapped and not self._swag_active, "swap_swa while the EMA average or a SWAG sample stands in for the weights"
+        hip.ema_swap(self.n_flat, self.flat_w, self.flat_swa)
+        self.swa_swapped = not self.swa_swapped
+
+    def swa_weights(self):
+        """Context manager: the SWA mean is the model's inside (evaluate() and every forward pass), the raw weights are back after it."""
+        eng = self
+
+        class _Ctx(object):
+            def __enter__(self):
+                assert not eng.swa_swapped, "swa_weights() inside swa_weights() / swap_swa()"
+                eng.swap_swa()
+                return eng
+
+            def __exit__(self, *exc):
+                eng.swap_swa()
+                return False
+        return _Ctx()
+
+    def swag_weights(self, sample, seed=0, var_scale=0.5):
+        """Context manager (SWAG-diagonal; needs SWA_VARIANCE and at least two collected models): inside, flat_w holds sample number `sample`
+        of N(mean, var_scale * diag(sq - mean^2)) under `seed` (urso_swag_sample; ursonet_amd.swa.sample32 of swa.normals); the raw weights
+        wait in a hold buffer allocated on first use and come back bit for bit on exit, also after an exception."""
+        assert self.swa_state is not None and self.flat_swa_sq is not None, "swag_weights needs Config.SWA with SWA_VARIANCE = True"
+        for name, v, top in (("sample", sample, 2 ** 31), ("seed", seed, 2 ** 64)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+                raise ValueError("swag_weights: %s must be an int in [0, 2^%d), got %r" % (name, 31 if name == "sample" else 64, v))
+        s = swa.scale32(var_scale)                     # ValueError: not a finite float >= 0
+        eng = self
+
+        class _Ctx(object):
+            def __enter__(self):
+                assert not eng.ema_swapped and not eng.swa_swapped and not eng._swag_active, \
+                    "swag_weights() while an average or another sample stands in for the weights"
+                models = int(eng.swa_state[swa.MODELS].item())
+                if models < 2:
+                    raise ValueError("swag_weights needs at least 2 collected models (a variance), the average holds %d" % models)
+                if eng._swag_hold is None:
+                    eng._swag_hold = torch.empty_like(eng.flat_w)
+                eng._swag_hold.copy_(eng.flat_w)
+                eng._swag_active = True
+                hip.swag_sample(eng.n_flat, eng.flat_swa, eng.flat_swa_sq, eng.flat_w, s, int(seed), int(sample))
+                return eng
+
+            def __exit__(self, *exc):
+                eng.flat_w.copy_(eng._swag_hold)       # a copy of the same dtype: the bits
+                eng._swag_active = False
                 return False
         return _Ctx()
 

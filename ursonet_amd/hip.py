@@ -292,9 +292,13 @@ _TRAIN_SIGS = {
     "urso_bn_recal_plan": (_i, [_i, _vp, C.c_int64, _vp]),
     "urso_bn_recal_add": (_i, [_i, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "urso_bn_recal_settle": (_i, [_i, _vp, _vp, C.c_int64, _vp, _fp, C.c_int64, _vp]),
+    # SWA / SWAG-diagonal (ursonet_amd/swa.py): n, w, mean, sq | null, state, loss-scale state | n, first, mean, sq, out, z_out | null, s, seed, sample
+    "urso_swa_update": (_i, [C.c_int64, _fp, _fp, _fp, _vp, _fp, _vp]),
+    "urso_swag_sample": (_i, [C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, C.c_float, C.c_uint64, _i, _vp]),
 }
 TRAIN_SYMBOLS = sorted(_TRAIN_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
+SWA_STATE = 8                                                         # URSO_SWA_STATE int32s (ursonet_amd/swa.py names the fields)
 
 
 def _bind(lib, sigs):
@@ -895,6 +899,26 @@ def sam_settle(state, normsq, guard=True, stream=None):
     (ursonet_amd.sam.settle32)."""
     assert state.dtype == torch.float32 and state.numel() >= SAM_STATE and normsq.dtype == torch.float32
     _chk(train_lib().urso_sam_settle(ptr(state), ptr(normsq), 1 if guard else 0, stream_ptr(stream)), "urso_sam_settle")
+
+
+def swa_update(n, w, mean, sq, state, stream=None, ls=None):
+    """urso_swa_update (liburso_train.so): on the steps the int32 state collects, w goes into the running mean (and w * w into sq, which may
+    be None) over n fp32 elements; then the state advances (ursonet_amd.swa.collect32 / next_state on the device).  ls: the loss-scale
+    state; a step it marks as skipped changes nothing."""
+    assert w.dtype == torch.float32 and mean.dtype == torch.float32 and (sq is None or sq.dtype == torch.float32)
+    assert state.dtype == torch.int32 and state.numel() >= SWA_STATE
+    assert 0 <= n <= min(w.numel(), mean.numel()) and (sq is None or n <= sq.numel())
+    _chk(train_lib().urso_swa_update(n, ptr(w), ptr(mean), ptr(sq) if sq is not None else None, ptr(state),
+                                     _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_swa_update")
+
+
+def swag_sample(n, mean, sq, out, s, seed, sample, z_out=None, first=0, stream=None):
+    """urso_swag_sample (liburso_train.so): out = mean + (s * sd) * z over n fp32 elements, sd = sqrtf(max(sq - mean * mean, 0)) and z the
+    Philox normals of flat-buffer elements first .. first + n - 1 (ursonet_amd.swa.normals / sample32); z_out, when given, receives z."""
+    assert all(x is None or x.dtype == torch.float32 for x in (mean, sq, out, z_out))
+    assert 0 <= n <= min(x.numel() for x in (mean, sq, out) + ((z_out,) if z_out is not None else ()))
+    _chk(train_lib().urso_swag_sample(n, int(first), ptr(mean), ptr(sq), ptr(out), ptr(z_out) if z_out is not None else None, float(s),
+                                      int(seed), int(sample), stream_ptr(stream)), "urso_swag_sample")
 
 
 def grad_accum(n, g, acc, first, stream=None):

@@ -185,6 +185,15 @@ def ema_checkpoint_path(path):
     return os.path.join(os.path.dirname(path), "ema_" + os.path.basename(path))
 
 
+def swa_checkpoint_path(path, sqmean=False):
+    """The SWA twins of a checkpoint (Config.SWA): `swa_` in front of the file name for the mean, and for the mean of squares
+    (SWA_VARIANCE) `swa_sqmean` where the name says `weights`; in the same directory, never seen by find_last either."""
+    base = os.path.basename(path)
+    if sqmean:
+        base = "sqmean" + base[len("weights"):] if base.startswith("weights") else "sqmean_" + base
+    return os.path.join(os.path.dirname(path), "swa_" + base)
+
+
 class BatchLogger(object):
     """net.py:1106-1115 -- per-batch loss history returned by train()."""
 
@@ -241,6 +250,8 @@ class UrsoNet(object):
                 weight_ema.initial_state(config, world)     # ValueError: a bad WEIGHT_EMA, or one set under a data-parallel launcher
                 from . import bn_recal
                 bn_recal.validate(config, world)            # ValueError: a bad BN_RECAL_BATCHES, one without WEIGHT_EMA / with a frozen BN, or under a launcher
+                from . import swa
+                swa.validate(config, world)                 # ValueError: bad SWA keys, SWA_RECAL_BATCHES without SWA / with a frozen BN, or SWA under a launcher
             if mode == "training" and world > 1:
                 # under a launcher (`python -m torch.distributed.run --nproc-per-node N pose_estimator.py train ...`): one process per GPU, this
                 # rank's engine takes IMAGES_PER_GPU samples of every global batch of IMAGES_PER_GPU x WORLD_SIZE, the gradient exchange is
@@ -307,9 +318,29 @@ class UrsoNet(object):
                                          strict=False)
         self.set_log_dir(weights_out_path)
 
-    def save_weights(self, path, ema=False):
-        """ema=True (Config.WEIGHT_EMA): the averaged weights, as an ordinary weights file (the BN statistics are the ones both sets share)."""
+    def save_weights(self, path, ema=False, swa=False):
+        """ema=True (Config.WEIGHT_EMA): the averaged weights, as an ordinary weights file (the BN statistics are the ones both sets share).
+        swa=True (Config.SWA): the SWA mean likewise; swa="sq": the running mean of squares (SWA_VARIANCE) under the same names."""
+        if swa:
+            return write_weights_file(path, self._engine.get_weights(swa=swa))
         return write_weights_file(path, self._engine.get_weights(ema=True) if ema else self._engine.get_weights())
+
+    def swa_weights(self):
+        """Context manager (Config.SWA, training mode): inside it the engine runs on the SWA mean; as ema_weights()."""
+        return self._engine.swa_weights()
+
+    def swag_weights(self, sample, seed=0, var_scale=0.5):
+        """Context manager (Config.SWA with SWA_VARIANCE, at least two collected models): inside it the engine runs on sample number
+        `sample` of the SWAG-diagonal Gaussian (Engine.swag_weights), so that save_weights() writes a sampled model for predict() /
+        evaluate() -- followed where wanted by recalibrate_bn: the BN statistics are the raw weights'.  No training step may run inside."""
+        return self._engine.swag_weights(sample, seed=seed, var_scale=var_scale)
+
+    def load_swa(self, mean_path, sqmean_path=None, models=None):
+        """Restore an average that train() wrote: swa_weights_*.h5, with SWA_VARIANCE also swa_sqmean_*.h5, and the number of models they
+        hold (the `swa models N` of the log).  The collection goes on from there."""
+        keep = lambda params: OrderedDict((ln, ws) for ln, ws in params.items() if ln in self._graph.params)
+        self._engine.set_swa_weights(keep(read_weights_file(mean_path)),
+                                     keep(read_weights_file(sqmean_path)) if sqmean_path is not None else None, models=models, strict=False)
 
     def ema_weights(self):
         """Context manager (Config.WEIGHT_EMA, training mode): inside it the engine runs on the averaged weights -- for a custom evaluation
@@ -383,6 +414,12 @@ class UrsoNet(object):
         use_ema = eng.ema_state is not None            # Config.WEIGHT_EMA: validate and save the average beside the raw weights
         from . import bn_recal
         recal_k = bn_recal.validate(cfg, world)        # Config.BN_RECAL_BATCHES: > 0 = the saved average gets BN statistics of its own
+        # Config.SWA: once the average holds a model, validate and save it beside the raw weights (SWA_RECAL_BATCHES: with statistics of its own)
+        use_swa = getattr(eng, "swa_state", None) is not None
+        swa_recal_k = 0
+        if use_swa:
+            from . import swa as SWA
+            swa_recal_k = SWA.validate(cfg, world)[3]
         history_full = BatchLogger(loss_weights=eng.learn_lw, weight_ema=use_ema)
         chief = rank == 0
         if chief:
@@ -425,6 +462,7 @@ class UrsoNet(object):
         # validation history for the averaged weights, both device-side and read once per epoch
         ema_hist = torch.zeros(max(steps, 1), int(eng.ema_state.numel()), dtype=torch.float32, device=eng.device) if use_ema else None
         vhist_ema = torch.zeros(max(vsteps, 1), n_loss, dtype=torch.float32, device=eng.device) if use_ema else None
+        vhist_swa = torch.zeros(max(vsteps, 1), n_loss, dtype=torch.float32, device=eng.device) if use_swa else None
         clr_it = 0
         for epoch in range(self.epoch, epochs):
             for i in range(steps):
@@ -445,6 +483,8 @@ class UrsoNet(object):
                     ls_hist[i].copy_(eng.ls_state, non_blocking=True)
                 if lw_hist is not None:
                     lw_hist[i].copy_(lw_view, non_blocking=True)
+            swa_now = eng.swa() if use_swa else None    # read once per epoch (one synchronising copy)
+            swa_models = swa_now["models"] if swa_now else 0
             for i in range(vsteps):
                 val_feed.next_into()
                 eng.evaluate(read=False)
@@ -453,6 +493,10 @@ class UrsoNet(object):
                     with eng.ema_weights():
                         eng.evaluate(read=False)
                         vhist_ema[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
+                if swa_models >= 1:                     # and under the SWA mean, likewise
+                    with eng.swa_weights():
+                        eng.evaluate(read=False)
+                        vhist_swa[i].copy_(eng.loss_buf.view(-1), non_blocking=True)
             if world == 1 and eng.forked:
                 eng.verify_fork()                       # the forked backward pass against the single chain on this epoch's last batch (engine.py)
             if world > 1:
@@ -486,6 +530,9 @@ class UrsoNet(object):
                 if use_ema:
                     v = vhist_ema[:vsteps].cpu().numpy().mean(0)
                     val.update({"ema_loc_loss": v[0], "ema_k2_loss": v[2], "ema_k3_loss": v[3]} if kp else {"ema_loc_loss": v[0], "ema_ori_loss": v[1]})
+                if swa_models >= 1:
+                    v = vhist_swa[:vsteps].cpu().numpy().mean(0)
+                    val.update({"swa_loc_loss": v[0], "swa_k2_loss": v[2], "swa_k3_loss": v[3]} if kp else {"swa_loc_loss": v[0], "swa_ori_loss": v[1]})
             ls_text = ""
             if ls_hist is not None and steps:
                 from . import loss_scale as LS
@@ -505,6 +552,8 @@ class UrsoNet(object):
                 eh = ema_hist[:steps].cpu().numpy()
                 history_full.ema_decay_acc += [float(x) for x in eh[:, WE.NEXT_DECAY]]
                 ema_text = "  ema_decay %g" % float(eh[-1, WE.NEXT_DECAY])
+            if swa_models >= 1:
+                ema_text += "  swa models %d" % swa_models
             if chief:
                 log("epoch %d  loc_loss %.5f  %s%s%s%s" % (
                     epoch + 1, float(np.mean(h[:, 0])) if steps else float("nan"),
@@ -525,9 +574,18 @@ class UrsoNet(object):
                             epoch + 1, ts["min"], ts["median"], ts["max"], ts["tensors"]))
                 self.save_weights(self.checkpoint_path.format(epoch=epoch + 1))     # replicas are identical: one writer
                 if use_ema and recal_k:                 # Config.BN_RECAL_BATCHES: the averaged weights with statistics of their own
-                    log(self._save_ema_recalibrated(ema_checkpoint_path(self.checkpoint_path.format(epoch=epoch + 1)), recal_k, train_feed, epoch + 1))
+                    log(self._save_average_recalibrated(ema_checkpoint_path(self.checkpoint_path.format(epoch=epoch + 1)), recal_k, train_feed,
+                                                        epoch + 1, "ema"))
                 elif use_ema:                           # "ema_" in front: find_last / get_last_checkpoint keep finding the raw file
                     self.save_weights(ema_checkpoint_path(self.checkpoint_path.format(epoch=epoch + 1)), ema=True)
+                if swa_models >= 1:                     # "swa_" in front, for the same reason
+                    raw_path = self.checkpoint_path.format(epoch=epoch + 1)
+                    if swa_recal_k:                     # Config.SWA_RECAL_BATCHES: the SWA mean with statistics of its own
+                        log(self._save_average_recalibrated(swa_checkpoint_path(raw_path), swa_recal_k, train_feed, epoch + 1, "swa"))
+                    else:
+                        self.save_weights(swa_checkpoint_path(raw_path), swa=True)
+                    if eng.flat_swa_sq is not None:
+                        self.save_weights(swa_checkpoint_path(raw_path, sqmean=True), swa="sq")
             if world > 1:
                 import torch.distributed as dist
                 dist.barrier()                          # nobody runs ahead of the checkpoint (find_last on another rank sees it)
@@ -537,16 +595,17 @@ class UrsoNet(object):
         self.epoch = max(self.epoch, epochs)
         return history_full
 
-    def _save_ema_recalibrated(self, path, k, feed, epoch):
-        """Config.BN_RECAL_BATCHES: the next k batches of the training feeder through the engine under the averaged weights, their pooled
-        BN statistics (ursonet_amd/bn_recal.py) into the averaged checkpoint `path`, and the raw statistics back bit for bit.  Statistics
-        that are not finite are not written: the file then holds the shared ones, as without the key.  Returns the line to log."""
+    def _save_average_recalibrated(self, path, k, feed, epoch, which):
+        """Config.BN_RECAL_BATCHES (which = "ema") / Config.SWA_RECAL_BATCHES (which = "swa"): the next k batches of the training feeder
+        through the engine under that average, their pooled BN statistics (ursonet_amd/bn_recal.py) into the averaged checkpoint `path`,
+        and the raw statistics back bit for bit.  Statistics that are not finite are not written: the file then holds the shared ones, as
+        without the key.  Returns the line to log."""
         from . import bn_recal
         from .graph import BN_EPS
         eng = self._engine
         raw = eng.flat_stats.detach().cpu().numpy().copy()
         try:
-            with eng.ema_weights():
+            with (eng.ema_weights() if which == "ema" else eng.swa_weights()):
                 eng.bn_recal_begin()                    # (keeps the clone of flat_stats that bn_recal_abort puts back)
                 for _ in range(k):
                     feed.next_into()
@@ -556,7 +615,7 @@ class UrsoNet(object):
             finite = all(np.all(np.isfinite(after[o:o + n])) for o, n, _s in eng.stat_slices.values())
             if not finite:
                 eng.bn_recal_abort()
-            self.save_weights(path, ema=True)
+            self.save_weights(path, ema=which == "ema", swa=which == "swa")
         finally:
             eng.bn_recal_abort()                        # the raw statistics, bit for bit, whatever happened
         if not finite:
