@@ -17,7 +17,8 @@ those of the launches around a stage's first block (pair_shortcut64, pair_entry6
 (tiles_per_block), the pixel map of the compact / sampled forms (pixel_map_f32) and the Winograd operands (winograd_uv).
 
 The second half holds the float64 references and counted bounds of the step's tail (losses, global norm, optimizers, gradient
-finalisation, batch-statistics BatchNorm) that tests/test_step_tail_exact_gpu.py compares the kernels with.
+finalisation, batch-statistics BatchNorm) that tests/test_step_tail_exact_gpu.py compares the kernels with, and those of the weight
+preparation (fold64 / fold_bounds) and of the split reduction (reduce32 / reduce_bound) for tests/test_param_passes_exact_gpu.py.
 """
 import contextlib
 import math
@@ -775,40 +776,50 @@ def adam32(w, g, m, v, vhat, hyper, normsq, v_from_unclipped=False):
 
 
 # ---- parameter-gradient finalisation of a conv / dense layer with its frozen BatchNorm folded in
-def finalize64(dw_raw, colsum, W, b, gamma, mean, var, eps, wd, gamma_term=True):
+def finalize64(dw_raw, colsum, W, b, gamma, mean, var, eps, wd, gamma_term=True, dw_mag=None, cs_mag=None):
     """Closed form; s = gamma / sqrt(var + eps) (1 without BN), dw_raw [K][N] (the padded columns already dropped):
       gW = s dw_raw + 2 wd / (K N) W;  gb = s colsum + 2 wd / N b;
       ggamma = (sum_k W dw_raw + (b - mean) colsum) / sqrt(var + eps);  gbeta = colsum.
     b / gamma None: absent.  -> dict name -> (reference, magnitude of the terms).  (tests/test_exactprobe_cpu.py proves it
-    equal to float64 autograd through conv -> frozen BatchNorm + the L2 term.)"""
+    equal to float64 autograd through conv -> frozen BatchNorm + the L2 term.)
+    dw_mag / cs_mag: where dw_raw / colsum are themselves fp32 sums of split partials, the sums of the partials' magnitudes; they
+    replace |dw_raw| / |colsum| in the magnitudes (finalize_bounds(..., sum_depth) charges the partial sums' roundings to them)."""
     dw, cs, W = d64(dw_raw), d64(colsum), d64(W)
     K, N = W.shape
     eps, wd = f32v(eps), f32v(wd)
     rstd = torch.rsqrt(d64(var) + eps) if gamma is not None else None
     s = d64(gamma) * rstd if gamma is not None else torch.ones(N, dtype=torch.float64)
     regc, regb = 2 * wd / (float(K) * float(N)), 2 * wd / float(N)
-    out = {"gw": (s * dw + regc * W, (s * dw).abs() + (regc * W).abs())}
+    dwm = d64(dw_mag) if dw_mag is not None else dw.abs()
+    csm = d64(cs_mag) if cs_mag is not None else cs.abs()
+    out = {"gw": (s * dw + regc * W, s.abs() * dwm + (regc * W).abs())}
     if b is not None:
-        out["gb"] = (s * cs + regb * d64(b), (s * cs).abs() + (regb * d64(b)).abs())
+        out["gb"] = (s * cs + regb * d64(b), s.abs() * csm + (regb * d64(b)).abs())
     if gamma is not None:
         bm = (d64(b) if b is not None else 0.0) - d64(mean)
         extra = bm * cs if gamma_term else torch.zeros_like(cs)
-        out["ggamma"] = (rstd * ((W * dw).sum(0) + extra), rstd * ((W * dw).abs().sum(0) + (bm * cs).abs()))
-        out["gbeta"] = (cs.clone(), cs.abs())
+        out["ggamma"] = (rstd * ((W * dw).sum(0) + extra), rstd * ((W.abs() * dwm).sum(0) + torch.as_tensor(bm).abs() * csm))
+        out["gbeta"] = (cs.clone(), csm.clone())
     return out
 
 
-def finalize_bounds(ref, K, N, ldn, ks):
+BN_SCALE_ROUNDINGS = 4      # s = gamma rsqrt(var + eps) in fp32: addition 1, rsqrt 1 ulp = 2, product 1 (finalize_bounds, fold_bounds)
+
+
+def finalize_bounds(ref, K, N, ldn, ks, sum_depth=0):
     """Roundings (ks = row slabs of the launch, kb = ceil(K / ks) rows each; vector body when (N | ldn) % 4 == 0):
       gW, gb: s = gamma rsqrt(var + eps): addition 1, rsqrt 1 ulp = 2, product 1 = 4; s d 1; the L2 factor 2, its product 1;
               sum 1  ->  6 U on |s d| + |reg W|.
       ggamma: the dot sum_k W d: product 1 + ceil(kb / 16) additions per row lane + 15 lanes (vector) or ceil(kb / 4) + 3
               (scalar), + the slabs: ceil(ks / 4) + 2; (b - mean) colsum: 2; sum 1; rstd 3, product 1
               ->  (dot depth + 6) U on rstd (sum|W d| + |(b - mean) colsum|).
-      gbeta = colsum: exact.        All stored in fp32.  -> dict name -> bound."""
+      gbeta = colsum: exact.        All stored in fp32.  -> dict name -> bound.
+    sum_depth > 0 (the batched passes: d and colsum are fp32 sums of split partials, reduce_depth(splits) roundings on their longest
+    chain; `ref` then comes from finalize64(..., dw_mag, cs_mag)): every count grows by sum_depth -- gW, gb: 6 + sum_depth;
+    ggamma: dot depth + 6 + sum_depth; gbeta: sum_depth."""
     kb = -(-K // ks)
     ddot = 1 + ((-(-kb // 16) + 15) if ((N | ldn) & 3) == 0 else (-(-kb // 4) + 3)) + -(-ks // 4) + 2
-    cnt = {"gw": 6, "gb": 6, "ggamma": ddot + 6, "gbeta": 0}
+    cnt = {"gw": 6 + sum_depth, "gb": 6 + sum_depth, "ggamma": ddot + 6 + sum_depth, "gbeta": sum_depth}
     return {k: store_bound(r, cnt[k] * U32 * mag, 0) if cnt[k] else torch.zeros_like(r) for k, (r, mag) in ref.items()}
 
 
@@ -837,6 +848,200 @@ def finalize32(dw_raw, colsum, W, b, gamma, mean, var, eps, wd, gamma_term=True)
         out["ggamma"] = rstd * (pairwise_sum32(W * dw_raw, 0) + (bm * colsum if gamma_term else 0.0))
         out["gbeta"] = colsum.clone()
     return out
+
+
+# ---- weight preparation: the frozen BatchNorm folded into filter and bias, in the MFMA layouts (urso_conv_weight_prep, PB_PREP)
+def _bn_scale64(bn, eps, N):
+    if bn is None:
+        return torch.ones(N, dtype=torch.float64)
+    return d64(bn[0]) * torch.rsqrt(d64(bn[3]) + f32v(eps))
+
+
+def _folded_bias64(b, bn, eps, N):
+    """(b s + beta - mean s, the list of its terms' magnitudes) of one layer, [N] float64."""
+    s = _bn_scale64(bn, eps, N)
+    z = torch.zeros(N, dtype=torch.float64)
+    bs = d64(b) * s if b is not None else z
+    beta, ms = (d64(bn[1]), d64(bn[2]) * s) if bn is not None else (z, z)
+    return bs + beta - ms, (bs.abs(), beta.abs(), ms.abs())
+
+
+def fold_inputs(KH, KW, C, N, seed=0, tiny_block=None):
+    """(w [KH][KW][C][N], b [N], (gamma, beta, mean, var)) float32 of the preparation probes: BN tensors as the finalisation probes'
+    (gamma and var in [0.5, 1.5]: s is no power of two), random mean / beta / bias.  tiny_block = (n0, n1): the filters n0 .. n1 are
+    scaled so that |w s| there is around 3e-6, fp16 subnormals (a store that flushes them fails the bound)."""
+    g = torch.Generator().manual_seed(1000 * int(seed) + 7 * KH * KW * C + N)
+    w = torch.randn(KH, KW, C, N, generator=g) / (KH * KW * C) ** 0.5
+    b = torch.randn(N, generator=g)
+    bn = (torch.rand(N, generator=g) + 0.5, torch.randn(N, generator=g), torch.randn(N, generator=g), torch.rand(N, generator=g) + 0.5)
+    if tiny_block is not None:
+        n0, n1 = tiny_block
+        w[..., n0:n1] = torch.randn(KH, KW, C, n1 - n0, generator=g) * 3e-6
+    return w.contiguous(), b, bn
+
+
+def fold64(w, b, bn, eps, npad, extra=None):
+    """The definition of the weight preparation in float64.  w [KH][KW][C][N] (HWIO), b [N] or None, bn = (gamma, beta, mean, var)
+    or None, eps the fp32 value the entry point receives; s = gamma / sqrt(var + eps) (1 without BN):
+      wf [npad][KH][KW][C]: wf[n][tap][c] = w[tap][c][n] s[n];   wd [C][KH][KW][npad]: wd[c][taps - 1 - tap][n] = w[tap][c][n] s[n];
+      biasf [npad] = b s + beta - mean s (+ the folded bias of `extra` = another layer's (b, bn, N) for n < extra's N:
+      urso_param_desc::bias_from);   scale [npad] = s.
+    Filters N .. npad: wf / wd / biasf exactly 0, scale exactly 1.
+    -> dict name -> (reference, magnitude); biasf's magnitude is the TUPLE (|b s|, |beta|, |mean s|, |b' s'|, |beta'|, |mean' s'|)
+    of its terms (primes: extra's), each [npad], which fold_bounds charges one by one."""
+    w = d64(w)
+    KH, KW, C, N = w.shape
+    assert npad >= N
+    s = _bn_scale64(bn, eps, N)
+    p = w * s
+    wf = torch.zeros(npad, KH, KW, C, dtype=torch.float64)
+    wf[:N] = p.permute(3, 0, 1, 2)
+    wd = torch.zeros(C, KH, KW, npad, dtype=torch.float64)
+    wd[..., :N] = p.flip(0, 1).permute(2, 0, 1, 3)
+    pad = lambda t, v=0.0: torch.cat([t, torch.full((npad - N,), v, dtype=torch.float64)])
+    bf, terms = _folded_bias64(b, bn, eps, N)
+    z = torch.zeros(N, dtype=torch.float64)
+    eterms = (z, z, z)
+    if extra is not None:
+        eb, ebn, eN = extra
+        m = min(int(eN), N)
+        ebf, et = _folded_bias64(eb, ebn, eps, int(eN))
+        head = lambda t: torch.cat([t[:m], torch.zeros(N - m, dtype=torch.float64)])
+        bf = bf + head(ebf)
+        eterms = tuple(head(t) for t in et)
+    scale = pad(s, 1.0)
+    return {"wf": (wf, wf.abs()), "wd": (wd, wd.abs()), "biasf": (pad(bf), tuple(pad(t) for t in terms + eterms)),
+            "scale": (scale, torch.cat([s.abs(), torch.zeros(npad - N, dtype=torch.float64)]))}
+
+
+def fold_bounds(ref, dt, bias, bn, extra=None):
+    """Counted fp32 roundings of the preparation (derived from the operation, not measured); bias / bn: whether the layer has them,
+    extra: None or (extra has bias, extra has BN).  S = BN_SCALE_ROUNDINGS = 4 on s = gamma rsqrt(var + eps) (finalize_bounds'
+    count: addition 1, rsqrt 1 ulp = 2, product 1); without BN s is the constant 1 and a product with it is exact: 0.
+      scale = s:        S U |s|  (0 without BN; the padded filters' 1 is exact), stored in fp32.
+      wf, wd = w s:     S + the product 1 = 5 U |w s| (0 without BN), then rounded ONCE to `dt`: + half an ulp of `dt`.
+      biasf:            b s: S + product 1 = 5 U |b s| (0 without BN);  mean s: 5 U |mean s|;  beta - mean s: 1 U (|beta| + |mean s|);
+                        the sum of b s and that difference: 1 U (|b s| + |beta| + |mean s|), only when both are there;
+                        extra's folded bias, computed on its own: the same counts on ITS terms;  adding it: 1 U on all six terms.
+                        Stored in fp32.
+    A padded filter has magnitude 0 everywhere, so its bound is half an ulp at its reference (0, or 1 for scale): no other value of the
+    storage type lies inside it, and the definition's exact 0 / 1 is what is asserted."""
+    S = BN_SCALE_ROUNDINGS if bn else 0
+    out = {}
+    r, mag = ref["scale"]
+    out["scale"] = store_bound(r, S * U32 * mag, 0) if S else torch.zeros_like(r)
+    for k in ("wf", "wd"):
+        r, mag = ref[k]
+        out[k] = store_bound(r, ((S + 1) if bn else 0) * U32 * mag, dt)
+    r, (bs, beta, ms, ebs, ebeta, ems) = ref["biasf"]
+
+    def own(bs, beta, ms, has_b, has_bn):
+        if not has_bn:
+            return torch.zeros_like(bs)                      # b * 1 or nothing: exact
+        e = 5 * ms + (beta + ms)
+        if has_b:
+            e = e + 5 * bs + (bs + beta + ms)
+        return e
+    err = own(bs, beta, ms, bias, bn)
+    if extra is not None:
+        err = err + own(ebs, ebeta, ems, extra[0], extra[1]) + (bs + beta + ms + ebs + ebeta + ems)
+    out["biasf"] = store_bound(r, U32 * err, 0) if (bn or extra is not None) else torch.zeros_like(r)
+    return out
+
+
+def fold32(w, b, bn, eps, npad, dt, extra=None, flip=True, s_round=None, use_eps=True, use_extra=True, pad_scale=1.0):
+    """Plain fp32 restatement of the preparation (the simulated kernel) -> dict name -> tensor (wf / wd in `dt`, biasf / scale fp32).
+    Faults: flip=False leaves wd's taps unflipped; s_round = a 16-bit type rounds s to it before the products; use_eps=False leaves
+    eps out; use_extra=False leaves extra's folded bias out; pad_scale: scale of the padded filters."""
+    f = torch.float32
+    w = w.to(f)
+    KH, KW, C, N = w.shape
+    e = torch.tensor(eps if use_eps else 0.0, dtype=f)
+
+    def sc(bn_, n):
+        s_ = bn_[0].to(f) * torch.rsqrt(bn_[3].to(f) + e) if bn_ is not None else torch.ones(n)
+        return s_.to(s_round).to(f) if s_round is not None else s_
+
+    def fb(b_, bn_, n):
+        s_ = sc(bn_, n)
+        v = b_.to(f) * s_ if b_ is not None else torch.zeros(n)
+        return v + (bn_[1].to(f) - bn_[2].to(f) * s_) if bn_ is not None else v
+    s = sc(bn, N)
+    p = w * s
+    wf = torch.zeros(npad, KH, KW, C); wf[:N] = p.permute(3, 0, 1, 2)
+    wd = torch.zeros(C, KH, KW, npad); wd[..., :N] = (p.flip(0, 1) if flip else p).permute(2, 0, 1, 3)
+    bf = torch.zeros(npad); bf[:N] = fb(b, bn, N)
+    if extra is not None and use_extra:
+        m = min(int(extra[2]), N)
+        bf[:m] += fb(extra[0], extra[1], int(extra[2]))[:m]
+    scale = torch.full((npad,), pad_scale, dtype=f); scale[:N] = s
+    return {"wf": wf.to(tdtype(dt)), "wd": wd.to(tdtype(dt)), "biasf": bf, "scale": scale}
+
+
+# ---- the split reduction of weight-gradient partials (reduce_partials_body, conv_wgrad.hip) and the sums fused into the finalisation
+WGRAD_PART_PAD = 64                # URSO_WGRAD_PART_PAD: floats between consecutive partial tensors
+FUSE_REDUCE_MAX = 16               # URSO_FUSE_REDUCE_MAX: up to here the finalisation sums the partials itself
+
+
+PART_SENTINEL = 3.0e7              # finite filler of the gaps between partials and of the padded columns: must reach no gradient
+
+
+def partials_buffer(K, N, npad, splits, seed=0):
+    """Random weight-gradient partials in the documented workspace layout (urso_conv_wgrad_partial): one flat fp32 buffer holding
+    part[splits][K * npad + WGRAD_PART_PAD] followed by colpart[splits][npad]; the WGRAD_PART_PAD floats behind every partial and the
+    padded columns N .. npad of both hold PART_SENTINEL.  -> (flat, parts [splits][K][npad], colparts [splits][npad]), the last two
+    being copies in their logical shapes (sentinel columns included)."""
+    g = torch.Generator().manual_seed(100003 * int(seed) + 31 * K + 7 * npad + splits)
+    stride = K * npad + WGRAD_PART_PAD
+    parts = torch.full((splits, K, npad), PART_SENTINEL)
+    parts[:, :, :N] = torch.randn(splits, K, N, generator=g)
+    colparts = torch.full((splits, npad), PART_SENTINEL)
+    colparts[:, :N] = torch.randn(splits, N, generator=g) * 5
+    flat = torch.full((splits * stride + splits * npad,), PART_SENTINEL)
+    flat[:splits * stride].reshape(splits, stride)[:, :K * npad] = parts.reshape(splits, K * npad)
+    flat[splits * stride:] = colparts.reshape(-1)
+    return flat, parts, colparts
+
+
+def reduce_lanes(splits):
+    """urso_reduce_lanes (csrc/common.h): split-lanes of the reduction kernel."""
+    return 16 if splits > 384 else (8 if splits > 192 else (4 if splits > 96 else (2 if splits > 48 else 1)))
+
+
+def reduce32(parts, splits=None):
+    """Host fp32 emulation of reduce_partials_body's documented order over parts [splits][...] (fp32): SL = reduce_lanes(splits);
+    lane sl adds its contiguous run of ceil(splits / SL) partials in order, starting from +0; the lanes are then added in lane order
+    (one lane: its sum is the result).  Pure additions, so a kernel in that order matches bit for bit.  The sums the finalisation
+    fuses (2 .. 16 splits) are the one-lane case: sequential from +0."""
+    parts = parts.to(torch.float32)
+    splits = parts.shape[0] if splits is None else int(splits)
+    assert parts.shape[0] == splits
+    SL = reduce_lanes(splits)
+    per = -(-splits // SL)
+    lanes = []
+    for sl in range(SL):
+        t = torch.zeros_like(parts[0])
+        for k in range(sl * per, min(splits, (sl + 1) * per)):
+            t = t + parts[k]
+        lanes.append(t)
+    t = lanes[0]
+    for other in lanes[1:]:
+        t = t + other
+    return t
+
+
+def reduce_depth(splits):
+    """Roundings on the longest chain of reduce32: ceil(splits / SL) - 1 inside a lane (+0 + the first partial is exact) + SL - 1
+    additions of the lanes."""
+    SL = reduce_lanes(splits)
+    return -(-splits // SL) - 1 + SL - 1
+
+
+def reduce_bound(mag64, splits):
+    """|fp32 sum in reduce32's order - float64 sum| <= D U / (1 - D U) sum|terms|, D = reduce_depth(splits): every rounding is half
+    an ulp of a partial sum, none of which exceeds sum|terms|.  splits = 1: 0 (a copy)."""
+    D = reduce_depth(splits)
+    return d64(mag64) * (D * U32 / (1.0 - D * U32))
 
 
 # ---- batch-statistics BatchNorm over [M][N]

@@ -979,3 +979,178 @@ def test_winograd_operands_and_evaluation(shape):
         X.assert_exact(X.winograd_out(Ubad, V, Hq, Wq), ref, "winograd")
     worst = X.winograd_uv(torch.full((3, 3, 1, 1), 2.0), torch.tensor([2.0, -2.0]).repeat(4, 2).reshape(1, 4, 4, 1) * torch.tensor([1.0, 1, -1, -1]).reshape(1, 4, 1, 1))
     assert float(worst[0].abs().max()) == 4.5 and float(worst[1].abs().max()) <= 8
+
+
+# =====================================================================================================================
+# Weight preparation (fold64 / fold_bounds) and the split reduction (reduce32 / reduce_bound): each bound accepts a plain fp32
+# restatement and rejects the faults a preparation or reduction kernel can have.
+FOLD_SHAPES = [(1, 1, 1, 1, 1), (1, 1, 33, 31, 32), (3, 3, 40, 50, 56), (3, 3, 3, 5, 8), (1, 1, 64, 64, 64)]
+
+
+@pytest.mark.parametrize("t", [torch.bfloat16, torch.float16, torch.float32])
+def test_ulp_is_the_subnormal_spacing_below_the_smallest_normal(t):
+    """X.ulp below 2^emin: the constant subnormal spacing 2^(emin - (p - 1)) -- 2^-24 for fp16 -- down to 0; rounding a value there to the
+    type moves it by at most half of it, and the first normal binade has the same spacing."""
+    p, emin = X._SIG_BITS[t], X._EMIN[t]
+    sub = 2.0 ** (emin - (p - 1))
+    if t == torch.float16:
+        assert sub == 2.0 ** -24
+    v = torch.tensor([0.0, sub / 3, sub, 3e-6 if t == torch.float16 else 100 * sub, 2.0 ** emin * 0.999, 2.0 ** emin, 2.0 ** emin * 1.5],
+                     dtype=torch.float64)
+    assert torch.equal(X.ulp(v, t), torch.full_like(v, sub))
+    assert float(X.ulp(torch.tensor([2.0 ** (emin + 1)], dtype=torch.float64), t)) == 2 * sub
+    r = torch.rand(10000, dtype=torch.float64) * 2.0 ** emin
+    assert float((rne(r, t) - r).abs().max()) <= sub / 2 and float((rne(r, t) - r).abs().max()) > sub / 4
+    assert torch.equal(X.store_bound(torch.zeros(1, dtype=torch.float64), torch.zeros(1, dtype=torch.float64), t), torch.tensor([sub / 2], dtype=torch.float64))
+
+
+@pytest.mark.parametrize("dt", [0, 1, 2])
+@pytest.mark.parametrize("shape", FOLD_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_fold_bounds_accept_fp32_and_reject_faults(shape, dt):
+    KH, KW, Ci, Nn, npad = shape
+    eps = 1e-3
+    w, b, bn = X.fold_inputs(KH, KW, Ci, Nn, seed=1)
+    _, eb, ebn = X.fold_inputs(1, 1, 4, max(Nn - 2, 1), seed=2)
+    eN = max(Nn - 2, 1)
+    big = Nn >= 5
+    for bias in (True, False):
+        for has_bn in (True, False):
+            for extra in (None, (eb, ebn, eN), (None, ebn, eN), (eb, None, eN)):
+                b_, bn_ = (b if bias else None), (bn if has_bn else None)
+                ref = X.fold64(w, b_, bn_, eps, npad, extra)
+                bnd = X.fold_bounds(ref, dt, bias, has_bn, None if extra is None else (extra[0] is not None, extra[1] is not None))
+                got = X.fold32(w, b_, bn_, eps, npad, dt, extra)
+                for k in ref:
+                    assert X.violations(got[k], ref[k][0], bnd[k]) == 0, (k, bias, has_bn)
+                # the definition's exact values in the padded filters
+                assert float(ref["wf"][0][Nn:].abs().sum()) == 0 and float(ref["wd"][0][..., Nn:].abs().sum()) == 0
+                assert float(ref["biasf"][0][Nn:].abs().sum()) == 0 and bool((ref["scale"][0][Nn:] == 1).all())
+                if npad > Nn:
+                    bad = X.fold32(w, b_, bn_, eps, npad, dt, extra, pad_scale=0.0)
+                    assert X.violations(bad["scale"], ref["scale"][0], bnd["scale"]) >= (npad - Nn) / float(npad)
+                    bad = X.fold32(w, b_, bn_, eps, npad, dt, extra, pad_scale=1.0 + 2.0 ** -23)
+                    assert X.violations(bad["scale"], ref["scale"][0], bnd["scale"]) >= (npad - Nn) / float(npad)
+                if KH * KW > 1:
+                    bad = X.fold32(w, b_, bn_, eps, npad, dt, extra, flip=False)
+                    assert X.violations(bad["wd"], ref["wd"][0], bnd["wd"]) >= 0.5
+                    assert X.violations(bad["wf"], ref["wf"][0], bnd["wf"]) == 0
+                if extra is not None and big:
+                    bad = X.fold32(w, b_, bn_, eps, npad, dt, extra, use_extra=False)
+                    assert X.violations(bad["biasf"], ref["biasf"][0], bnd["biasf"]) >= 0.9 * eN / npad
+                if has_bn and big:
+                    for st in (torch.bfloat16, torch.float16):        # s rounded to 16 bits before the product: a double rounding
+                        bad = X.fold32(w, b_, bn_, eps, npad, dt, extra, s_round=st)
+                        # expected share: mean |shift of w s| / ulp of the store.  s rounded to the store's own type: a quarter of an ulp
+                        # on average -> ~0.25; fp16's s (2^-13 on average) under a bf16 store (ulp 2^-8 .. 2^-7): ~0.02; otherwise ~1
+                        floor = 0.01 if (dt == 1 and st == torch.float16) else (0.15 if X.tdtype(dt) == st else 0.5)
+                        assert X.violations(bad["wf"], ref["wf"][0], bnd["wf"]) >= floor * Nn / npad, (dt, st)
+                        assert X.violations(bad["wd"], ref["wd"][0], bnd["wd"]) >= floor * Nn / npad, (dt, st)
+                        assert X.violations(bad["scale"], ref["scale"][0], bnd["scale"]) >= 0.9 * Nn / npad
+                    bad = X.fold32(w, b_, bn_, eps, npad, dt, extra, use_eps=False)
+                    assert X.violations(bad["scale"], ref["scale"][0], bnd["scale"]) >= 0.9 * Nn / npad
+                    assert X.violations(bad["wf"], ref["wf"][0], bnd["wf"]) >= 0.01
+                    assert X.violations(bad["biasf"], ref["biasf"][0], bnd["biasf"]) >= 0.5 * Nn / npad
+
+
+def test_fold_bound_rejects_flushed_fp16_subnormals():
+    """|w s| around 3e-6 in a block of filters: fp16 subnormals (spacing 2^-24 = 6e-8).  A store rounding them is inside the bound, one
+    flushing them to zero is outside in nearly every element of the block."""
+    KH, KW, Ci, Nn, npad = 3, 3, 40, 50, 56
+    w, b, bn = X.fold_inputs(KH, KW, Ci, Nn, seed=3, tiny_block=(16, 40))
+    ref = X.fold64(w, b, bn, 1e-3, npad)
+    bnd = X.fold_bounds(ref, 2, True, True)
+    blk = ref["wf"][0][16:40]
+    assert float(blk.abs().max()) < 2.0 ** -14 and float(blk.abs().median()) > 1e-6
+    got = X.fold32(w, b, bn, 1e-3, npad, 2)
+    assert X.violations(got["wf"], ref["wf"][0], bnd["wf"]) == 0 and X.violations(got["wd"], ref["wd"][0], bnd["wd"]) == 0
+    f32 = X.fold32(w, b, bn, 1e-3, npad, 0)
+    flushed = flush16(f32["wf"].double(), torch.float16)
+    assert X.violations(flushed[16:40], blk, bnd["wf"][16:40]) >= 0.9
+    assert X.violations(flush16(f32["wd"].double(), torch.float16), ref["wd"][0], bnd["wd"]) >= 0.9 * 24 / npad
+
+
+def test_fold64_agrees_with_the_layout_test_of_the_suite():
+    """fold64 restates what tests/test_kernels_gpu.py::test_weight_prep_layouts builds by hand (1e-12), and X.stem_taps of it is the
+    packed stem filter of a folded 7x7 layer."""
+    KH, KW, Ci, Nn, NP = 3, 3, 40, 50, 56
+    w, b, bn = X.fold_inputs(KH, KW, Ci, Nn, seed=4)
+    d = lambda v: v.double()
+    s = d(bn[0]) / torch.sqrt(d(bn[3]) + X.f32v(1e-3))
+    wfr = torch.zeros(NP, KH, KW, Ci, dtype=torch.float64); wfr[:Nn] = (d(w) * s).permute(3, 0, 1, 2)
+    wdr = torch.zeros(Ci, KH, KW, NP, dtype=torch.float64); wdr[..., :Nn] = (d(w) * s).flip(0, 1).permute(2, 0, 1, 3)
+    ref = X.fold64(w, b, bn, 1e-3, NP)
+    assert float((ref["wf"][0] - wfr).abs().max()) <= 1e-12 and float((ref["wd"][0] - wdr).abs().max()) <= 1e-12
+    assert float((ref["biasf"][0][:Nn] - (s * d(b) + d(bn[1]) - d(bn[2]) * s)).abs().max()) <= 1e-12
+    assert bool((ref["biasf"][0].abs() <= sum(ref["biasf"][1]) * (1 + 1e-12)).all()) and len(ref["biasf"][1]) == 6
+    w7, b7, bn7 = X.fold_inputs(7, 7, 3, 5, seed=5)
+    r7 = X.fold64(w7, b7, bn7, 1e-3, 5)
+    taps = X.stem_taps(r7["wf"][0].permute(1, 2, 3, 0))
+    assert torch.equal(X.stem_untaps(taps), r7["wf"][0].permute(1, 2, 3, 0)) and float(taps[:, 0].abs().sum()) == 0 and float(taps[:, :, 3].abs().sum()) == 0
+
+
+REDUCE_SPLITS = [1, 2, 5, 16, 17, 49, 100, 200, 400, 733]
+
+
+def test_reduce_lanes_thresholds():
+    assert [X.reduce_lanes(s) for s in REDUCE_SPLITS] == [1, 1, 1, 1, 1, 2, 4, 8, 16, 16]
+    assert [X.reduce_lanes(s) for s in (48, 96, 192, 384)] == [1, 2, 4, 8]
+    assert [X.reduce_depth(s) for s in (1, 2, 16, 49, 733)] == [0, 1, 15, 25, 45 + 15]
+
+
+@pytest.mark.parametrize("splits", REDUCE_SPLITS)
+def test_reduce32_inside_bound_and_faults_rejected(splits):
+    """reduce32 over the documented workspace layout equals the float64 sum within reduce_bound; a dropped partial and partials read at
+    stride K npad (without WGRAD_PART_PAD) are outside it; the order matters to the bits (a sequential sum differs from the lane
+    order somewhere once there is more than one lane)."""
+    K, Nn, npad = 24, 13, 16
+    flat, parts, colparts = X.partials_buffer(K, Nn, npad, splits, seed=splits)
+    stride = K * npad + X.WGRAD_PART_PAD
+    assert flat.numel() == splits * stride + splits * npad
+    view = flat[:splits * stride].reshape(splits, stride)
+    assert torch.equal(view[:, :K * npad].reshape(splits, K, npad), parts) and bool((view[:, K * npad:] == X.PART_SENTINEL).all())
+    assert torch.equal(flat[splits * stride:].reshape(splits, npad), colparts)
+    for p in (parts, colparts):
+        ref, mag = p.double().sum(0), p.double().abs().sum(0)
+        bnd = X.reduce_bound(mag, splits)
+        got = X.reduce32(p, splits)
+        assert got.dtype == torch.float32 and X.violations(got, ref, bnd) == 0
+        X.assert_sensitive(ref, what="sum of partials")
+        if splits == 1:
+            assert torch.equal(got, p[0]) and float(bnd.abs().max()) == 0
+            continue
+        real = (slice(None), slice(0, Nn)) if p is parts else (slice(0, Nn),)
+        dropped = X.reduce32(torch.cat([p[:splits // 2], torch.zeros_like(p[:1]), p[splits // 2 + 1:]]), splits)
+        assert X.violations(dropped[real], ref[real], bnd[real]) >= 0.9
+    if splits > 1:
+        wrong = torch.stack([flat[q * K * npad:(q + 1) * K * npad] for q in range(splits)]).reshape(splits, K, npad)
+        ref, mag = parts.double().sum(0), parts.double().abs().sum(0)
+        assert X.violations(X.reduce32(wrong, splits)[:, :Nn], ref[:, :Nn], X.reduce_bound(mag, splits)[:, :Nn]) >= 0.9
+    if X.reduce_lanes(splits) > 1:
+        seq = torch.zeros_like(parts[0])
+        for q in range(splits):
+            seq = seq + parts[q]
+        assert not torch.equal(seq, X.reduce32(parts, splits))
+
+
+def test_finalize_bounds_widened_by_the_partial_sums():
+    """finalize64 with the partials' summed magnitudes + finalize_bounds(sum_depth) accepts the finalisation of an fp32 sum of partials
+    (reduce32's order) against the float64 sum's closed form, and rejects a dropped partial in every gradient."""
+    K, Nn, npad, splits = 144, 24, 24, 17
+    _, parts, colparts = X.partials_buffer(K, Nn, npad, splits, seed=9)
+    g = torch.Generator().manual_seed(5)
+    Wt, b = torch.randn(K, Nn, generator=g) / K ** 0.5, torch.randn(Nn, generator=g)
+    gamma, mean, var = torch.rand(Nn, generator=g) + 0.5, torch.randn(Nn, generator=g), torch.rand(Nn, generator=g) + 0.5
+    p64, c64 = parts.double()[:, :, :Nn], colparts.double()[:, :Nn]
+    ref = X.finalize64(p64.sum(0), c64.sum(0), Wt, b, gamma, mean, var, 1e-3, 1e-2, dw_mag=p64.abs().sum(0), cs_mag=c64.abs().sum(0))
+    plain = X.finalize64(p64.sum(0), c64.sum(0), Wt, b, gamma, mean, var, 1e-3, 1e-2)
+    for k in ref:
+        assert torch.equal(ref[k][0], plain[k][0]) and bool((ref[k][1] >= plain[k][1] * (1 - 1e-12)).all())
+    D = X.reduce_depth(splits)
+    assert D == 16
+    bnd = X.finalize_bounds(ref, K, Nn, npad, 1, sum_depth=D)
+    got = X.finalize32(X.reduce32(parts)[:, :Nn], X.reduce32(colparts)[:Nn], Wt, b, gamma, mean, var, 1e-3, 1e-2)
+    less = torch.cat([parts[:3], parts[4:]]), torch.cat([colparts[:3], colparts[4:]])
+    bad = X.finalize32(X.reduce32(less[0])[:, :Nn], X.reduce32(less[1])[:Nn], Wt, b, gamma, mean, var, 1e-3, 1e-2)
+    for k in ref:
+        assert X.violations(got[k], ref[k][0], bnd[k]) == 0, k
+        assert X.violations(bad[k], ref[k][0], bnd[k]) >= 0.9, k
