@@ -157,6 +157,79 @@ int urso_swa_update(int64_t n, const float* w_d, float* mean_d, float* sq_d, int
 int urso_swag_sample(int64_t n, int64_t first, const float* mean_d, const float* sq_d, float* out_d, float* z_out_d, float s, uint64_t seed,
                      int sample, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * Ensemble inference: the Bayesian model average of a classification head (predict / evaluate / test_and_submit with members=...,
+ * DESIGN.md section 24; ursonet_amd/ensemble.py, add64 / settle64, is the same rule in NumPy float64 and the written specification).
+ * The network runs once per member (weight set) over the dataset; urso_ens_add folds a member's softmax over one batch of logit rows into
+ * fp64 accumulators, urso_ens_settle turns accumulated rows into log-probabilities that urso_quat_wavg_decode, urso_quat_gmm_fit,
+ * urso_pose_decode and urso_pose_eval take in the place of logits, and into the uncertainty columns.  The average is the mean of the
+ * members' PMFs, decoded once -- not a mean of decoded poses.
+ *
+ * urso_ens_add, for every valid batch row b < n, r = row0 + b, z = logits + b * ld (K fp32 values); all arithmetic fp64, each operation
+ * rounded once (-ffp-contract=off), exp and log the device library's:
+ *
+ *   m   = max_i z_i, a NaN winning                 d_i = (double) z_i - (double) m              e_i = exp(d_i)
+ *   Z   = sum_i e_i                                S   = sum_i (e_i == 0 ? 0 : e_i * (-d_i))    (a vanished term adds exactly 0, also for d_i = -inf)
+ *   p_i = e_i / Z                                  H   = log(Z) + S / Z      the member's entropy in nats; both terms >= 0: no cancellation
+ *   first != 0:  acc[r][i]  = p_i                  stat[r] = {H, 1, 0, 0}      overwrites: the buffers need no clearing and may hold NaN
+ *   first == 0:  acc[r][i] += p_i                  stat[r][0] += H             stat[r][1] += 1
+ *
+ * A NaN or +inf logit makes the whole row NaN (m = +inf gives d = NaN).  Rows past n, columns past K and the padding between rows are
+ * never read or written.
+ *
+ * urso_ens_settle, for every b < n, r = row0 + b, over M members:
+ *
+ *   pbar_i     = acc[r][i] / (double) M
+ *   logp[b][i] = (float) log(pbar_i);  pbar_i == 0 gives -FLT_MAX, not -inf, so that z - max stays finite in every downstream kernel;
+ *                softmax(logp) is pbar up to fp32 rounding.  logp is [n][K]: the rows of this launch only
+ *   Hbar       = -sum_i (pbar_i == 0 ? 0 : pbar_i * log(pbar_i))
+ *   table[r]   = { H_MEAN = Hbar,  H_MEMBERS = stat[r][0] / M,  MI = max(Hbar - H_MEMBERS, 0) with a NaN staying NaN (the mutual information
+ *                  between the prediction and the member, BALD: the epistemic part),  PEAK = max_i pbar_i (a NaN winning),
+ *                  ARGMAX = the lowest index of the peak,  N_MEMBERS = stat[r][1] (the caller checks that it equals M),  0,  0 }
+ *
+ * Launch shape and reduction order, which are part of the result: one workgroup of 1024 threads (16 waves) per valid row.  Columns are
+ * dealt by their index alone: thread t owns the groups of four columns g = t, 1024 + t, 2048 + t, ... (columns 4 g .. 4 g + 3), and the
+ * ragged end K % 4 is the group behind the last whole one.  A thread adds its terms to its running sum in column order; the threads' sums
+ * are added by the xor shuffle 32, 16, .. 1 across a wave, then the 16 wave sums in wave order (the order urso_lars_norms documents).
+ * A group is one 16-byte load (store) where the row's first element sits on a 16-byte boundary and four 4-byte (8-byte) ones where it
+ * does not -- the same columns on the same thread, so every output is a function of the row's inputs alone: the same bits on a repeated
+ * launch, and for the same row whatever B, n, row0, ld, the alignment and its position in the batch.  The logits are read three times (max,
+ * sums, write; the second and third time from L2) and exp is computed twice: no e_i is kept.
+ *
+ * No allocation, no workspace, no host synchronisation.  n == 0 launches nothing.
+ * URSO_EINVAL, with a message, before any launch: a null struct or pointer; B <= 0, n outside [0, B] (settle: n < 0); row0 < 0; K < 1;
+ * ld < K; M outside [1, URSO_ENS_MAX_MEMBERS]; logits / logp off the 4-byte boundary; acc / stat / table off the 8-byte one.
+ */
+#define URSO_ENS_MAX_MEMBERS 64
+#define URSO_ENS_STAT 4
+#define URSO_ENS_COLS 8
+#define URSO_ENS_H_MEAN 0
+#define URSO_ENS_H_MEMBERS 1
+#define URSO_ENS_MI 2
+#define URSO_ENS_PEAK 3
+#define URSO_ENS_ARGMAX 4
+#define URSO_ENS_N_MEMBERS 5
+typedef struct urso_ens_add_args {
+    int32_t B, n;                    /* rows of logits, valid rows (0 <= n <= B) */
+    int64_t row0;                    /* accumulator row of batch row 0 */
+    int32_t K, ld;                   /* bins; floats between rows of logits (ld >= K) */
+    int32_t first, pad;              /* != 0: this is the first member (overwrite) */
+    const float* logits;             /* [B][ld] */
+    double* acc;                     /* [rows][K] */
+    double* stat;                    /* [rows][URSO_ENS_STAT] */
+} urso_ens_add_args;
+typedef struct urso_ens_settle_args {
+    int32_t n;                       /* rows of this launch */
+    int64_t row0;                    /* accumulator / table row of row 0 */
+    int32_t K, M;                    /* bins; members added */
+    const double* acc;               /* [rows][K] */
+    const double* stat;              /* [rows][URSO_ENS_STAT] */
+    float* logp;                     /* [n][K] */
+    double* table;                   /* [rows][URSO_ENS_COLS] */
+} urso_ens_settle_args;
+int urso_ens_add(const urso_ens_add_args* args, void* stream);
+int urso_ens_settle(const urso_ens_settle_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ import os
 
 import numpy as np
 
+from .ensemble import EnsemblePass, Members, eval_fields, no_member_fields
 from .infer import PosePass, eval_columns, fuse_columns, head_modes, loader_workers  # noqa: F401  (head_modes: its long-standing home is here)
 
 SUMMARY = ("Mean est. location error: ", "Mean est. orientation error: ", "ESA score: ", "Mean encoded location error: ")
@@ -30,12 +31,20 @@ class EvalResult(object):
     with multimodal, ori_err_soft (the soft-argmax estimate's error) and mode (index of the selected mode), else None.  The four
     summary means are computed on the host in fp64 from these arrays.  With views (fused=True: `table` is a FUSE table) the
     estimate and its four errors are the fused pose's, loc_spread, ori_spread (degrees), view_lambda and n_views say how well the views
-    agree (else None), and the encoded errors, which do not depend on the estimate, are None."""
+    agree (else None), and the encoded errors, which do not depend on the estimate, are None.  With members (ensemble: an
+    ensemble.EnsembleTables; `table` is not used) the estimate and its errors are the ensemble's, and n_members, member_loc_spread,
+    member_ori_spread, member_lambda and the entropies (ori_entropy, ori_member_entropy, ori_mi, loc_entropy, loc_member_entropy,
+    loc_mi) are set as on a PredictResult; else they are None."""
 
-    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal, fused=False):
+    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal, fused=False, *, ensemble=None):
         from . import hip
         self.image_ids = np.asarray(image_ids)
         self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
+        no_member_fields(self)
+        if ensemble is not None:
+            eval_fields(self, ensemble, loc_enc, ori_enc, multimodal)
+            self.dist = ensemble.fuse[:, hip.FUSE_DIST].copy()
+            return
         if fused:
             fuse_columns(self, table, True)
             self.loc_encoded_err = self.ori_encoded_err = self.ori_err_soft = self.mode = None
@@ -78,7 +87,15 @@ def write_csvs(out_dir, ori_err, loc_err, dist):
     return paths
 
 
-def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None, views=None):
+def ensemble_line(res):
+    """The line evaluate(members=...) prints behind the four of the reference: the mean mutual information of each classification head
+    (nats) and the mean spread of the members' decoded poses."""
+    mi = ["%s MI %s" % (k, np.mean(v)) for k, v in (("orientation", res.ori_mi), ("location", res.loc_mi)) if v is not None]
+    return "Ensemble of %d members: mean %smember spread %s (location) %s deg (orientation)" % (
+        res.n_members, "".join(m + ", " for m in mi), np.mean(res.member_loc_spread), np.mean(res.member_ori_spread))
+
+
+def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None, views=None, members=None, max_gb=16):
     """pose_estimator.evaluate(model, dataset): prints the reference's four summary lines (verbose > 0), writes ori_err.csv,
     loc_err.csv and dists_err.csv into out_dir and returns an EvalResult.  multimodal=True (soft classification only) fits up to
     three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 / 12, 5 iterations, nr_max_modes 4) and
@@ -87,7 +104,20 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     that the next call with it -- the next checkpoint, say -- loads no image again; the table is the same with and without it.
     views: [V,3] (pitch, yaw, roll) in degrees, as in predict(): the estimate and its errors are those of the pose fused from V rotated
     views of every image, and the result says how well the views agree; the encoded errors are not computed (run without views for
-    them: the fourth line prints nan).  ValueError as in predict()."""
+    them: the fourth line prints nan).  ValueError as in predict().
+    members, max_gb: as in predict() -- the estimate and its errors are those of the Bayesian model average of the listed weight sets
+    (the same estimate bits as predict(members=...)), the summary lines and CSV files are made from it, and one more line prints the
+    mean mutual information and the mean spread of the members.  multimodal fits the modes on the averaged PMF."""
+    if members is not None:
+        ms = Members(members, views, "evaluate")
+        out, loc_dtype = EnsemblePass(model, dataset, ms, multimodal, True, "evaluate", workers, cache, max_gb).run()
+        cfg = model.config
+        res = EvalResult(list(dataset.image_ids), None, not cfg.REGRESS_LOC, not (cfg.REGRESS_ORI or cfg.REGRESS_KEYPOINTS), multimodal, ensemble=out)
+        if verbose:
+            for line in summary_lines(res.means()) + [ensemble_line(res)]:
+                print(line)
+        write_csvs(out_dir, res.ori_err, res.loc_err, res.dist.astype(loc_dtype) if loc_dtype is not None else res.dist)
+        return res
     vs = None
     if views is not None:
         from .views import ViewSet

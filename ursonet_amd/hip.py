@@ -119,6 +119,23 @@ FUSE_LOC_SPREAD, FUSE_ORI_SPREAD, FUSE_VIEW_LAMBDA, FUSE_N_VIEWS, FUSE_COLS, FUS
 EMA_DECAY, EMA_WARMUP, EMA_UPDATES, EMA_NEXT_DECAY, EMA_FIELDS = 0, 1, 2, 3, 8       # URSO_EMA_* of include/ursonet_ext.h
 
 
+class EnsAddArgs(C.Structure):
+    """urso_ens_add_args (include/ursonet_train.h): one member's logits of one batch."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] + [(n, C.c_int32) for n in ("K", "ld", "first", "pad")] +
+                [(n, C.c_void_p) for n in ("logits", "acc", "stat")])
+
+
+class EnsSettleArgs(C.Structure):
+    """urso_ens_settle_args (include/ursonet_train.h): the accumulated rows of one chunk."""
+    _fields_ = ([("n", C.c_int32), ("row0", C.c_int64), ("K", C.c_int32), ("M", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("acc", "stat", "logp", "table")])
+
+
+# urso_ens_* sizes and table columns (include/ursonet_train.h)
+ENS_MAX_MEMBERS, ENS_STAT, ENS_COLS = 64, 4, 8
+ENS_H_MEAN, ENS_H_MEMBERS, ENS_MI, ENS_PEAK, ENS_ARGMAX, ENS_N_MEMBERS = range(6)
+
+
 class DenseWgradLayer(C.Structure):
     """urso_dense_wgrad_layer (include/ursonet_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("x", "dz", "part", "colpart")] + [(n, C.c_int32) for n in ("M", "K", "N")]
@@ -295,6 +312,9 @@ _TRAIN_SIGS = {
     # SWA / SWAG-diagonal (ursonet_amd/swa.py): n, w, mean, sq | null, state, loss-scale state | n, first, mean, sq, out, z_out | null, s, seed, sample
     "urso_swa_update": (_i, [C.c_int64, _fp, _fp, _fp, _vp, _fp, _vp]),
     "urso_swag_sample": (_i, [C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, C.c_float, C.c_uint64, _i, _vp]),
+    # ensemble inference (ursonet_amd/ensemble.py): urso_ens_add_args* | urso_ens_settle_args*
+    "urso_ens_add": (_i, [C.POINTER(EnsAddArgs), _vp]),
+    "urso_ens_settle": (_i, [C.POINTER(EnsSettleArgs), _vp]),
 }
 TRAIN_SYMBOLS = sorted(_TRAIN_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
@@ -919,6 +939,33 @@ def swag_sample(n, mean, sq, out, s, seed, sample, z_out=None, first=0, stream=N
     assert 0 <= n <= min(x.numel() for x in (mean, sq, out) + ((z_out,) if z_out is not None else ()))
     _chk(train_lib().urso_swag_sample(n, int(first), ptr(mean), ptr(sq), ptr(out), ptr(z_out) if z_out is not None else None, float(s),
                                       int(seed), int(sample), stream_ptr(stream)), "urso_swag_sample")
+
+
+def ens_add(B, n, row0, logits, acc, stat, first, stream=None):
+    """urso_ens_add (liburso_train.so): the softmax of the n valid rows of logits (fp32 [B, K] with contiguous rows; a view of the engine's
+    output is fine) goes into rows row0 .. of acc (fp64 [rows, K]) and its entropy into stat (fp64 [rows, ENS_STAT]); first overwrites
+    (ursonet_amd.ensemble.add64)."""
+    assert logits.dtype == torch.float32 and acc.dtype == torch.float64 and stat.dtype == torch.float64
+    assert acc.is_contiguous() and stat.is_contiguous() and logits.shape[0] >= B and acc.shape[1] == logits.shape[1] and stat.shape[1] == ENS_STAT
+    assert 0 <= n <= B and row0 >= 0 and row0 + n <= min(acc.shape[0], stat.shape[0])
+    a = EnsAddArgs()
+    a.B, a.n, a.row0, a.K, a.first, a.pad = int(B), int(n), int(row0), int(logits.shape[1]), 1 if first else 0, 0
+    a.logits, a.ld = _rows(logits)
+    a.acc, a.stat = ptr(acc), ptr(stat)
+    _chk(train_lib().urso_ens_add(C.byref(a), stream_ptr(stream)), "urso_ens_add")
+
+
+def ens_settle(n, row0, M, acc, stat, logp, table, stream=None):
+    """urso_ens_settle (liburso_train.so): rows row0 .. row0 + n - 1 of acc / stat over M members become logp (fp32 [>= n, K], this chunk's
+    rows) and rows row0 .. of table (fp64 [rows, ENS_COLS]) (ursonet_amd.ensemble.settle64)."""
+    assert acc.dtype == torch.float64 and stat.dtype == torch.float64 and table.dtype == torch.float64 and logp.dtype == torch.float32
+    assert acc.is_contiguous() and stat.is_contiguous() and table.is_contiguous() and logp.is_contiguous()
+    assert logp.shape[1] == acc.shape[1] and stat.shape[1] == ENS_STAT and table.shape[1] == ENS_COLS
+    assert 0 <= n <= logp.shape[0] and row0 >= 0 and row0 + n <= min(acc.shape[0], stat.shape[0], table.shape[0])
+    a = EnsSettleArgs()
+    a.n, a.row0, a.K, a.M = int(n), int(row0), int(acc.shape[1]), int(M)
+    a.acc, a.stat, a.logp, a.table = ptr(acc), ptr(stat), ptr(logp), ptr(table)
+    _chk(train_lib().urso_ens_settle(C.byref(a), stream_ptr(stream)), "urso_ens_settle")
 
 
 def grad_accum(n, g, acc, first, stream=None):

@@ -14,6 +14,7 @@ Under a launcher (world > 1) every process predicts the whole dataset; there is 
 """
 import numpy as np
 
+from .ensemble import EnsemblePass, Members, no_member_fields, predict_fields
 from .infer import PosePass, dec_columns, fuse_columns, loader_workers
 
 
@@ -25,11 +26,20 @@ class PredictResult(object):
     head does not define them.  With multimodal: modes [N,3,4], mode_priors [N,3] (descending; unused slots 0) and n_modes [N].
     With views (fused=True: `table` is a FUSE table): loc_est / q_est are the fused estimate, loc_spread, ori_spread (degrees: RMS
     deviation of the de-rotated views from it), view_lambda (1 when all views agree, 1/4 for a uniform spread) and n_views are set, and
-    loc_peak / ori_peak / ori_lambda, which are per-view quantities, are None.  Without views the four are None."""
+    loc_peak / ori_peak / ori_lambda, which are per-view quantities, are None.  Without views the four are None.
+    With members (ensemble: an ensemble.EnsembleTables; `table` is not used): loc_est / q_est are the ensemble's -- a classification
+    head's from the mean of the members' PMFs, a regression head's fused from the members' poses -- loc_peak / ori_peak / ori_lambda are
+    those of the averaged PMF, n_members is M, member_loc_spread, member_ori_spread (degrees) and member_lambda say how far the members'
+    decoded poses spread (urso_pose_fuse_views' columns), and per classification head, in nats: ori_entropy / loc_entropy (of the averaged
+    PMF), ori_member_entropy / loc_member_entropy (the mean of the members') and ori_mi / loc_mi (their difference, the mutual
+    information: the epistemic part).  Without members all of these are None."""
 
-    def __init__(self, image_ids, table, loc_class, soft, gmm=None, fused=False):
+    def __init__(self, image_ids, table, loc_class, soft, gmm=None, fused=False, *, ensemble=None):
         self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
-        if fused:
+        no_member_fields(self)
+        if ensemble is not None:
+            predict_fields(self, ensemble, loc_class, soft)
+        elif fused:
             fuse_columns(self, table, False)
             self.loc_peak = self.ori_peak = self.ori_lambda = None
         else:
@@ -38,7 +48,7 @@ class PredictResult(object):
         self.modes, self.mode_priors, self.n_modes = gmm if gmm is not None else (None, None, None)
 
 
-def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None):
+def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None, members=None, max_gb=16):
     """Pose estimates of every image of `dataset` -> PredictResult.  The dataset needs image_ids, load_image, image_info and, for
     the classification heads, histogram_3D_map / ori_histogram_map; no label loader is called.  multimodal=True (soft
     classification only) also fits up to three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 /
@@ -46,7 +56,19 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     frame_cache.FrameCache of the caller's that keeps the raw frames on the device between calls (Config.DEVICE_RESIZE only).
     views: [V,3] (pitch, yaw, roll) in degrees, e.g. views.ROLL_VIEWS(3, 30): every image is shown to the network once per view (the
     frame re-rendered through the rotated camera; needs dataset.camera), the estimates are rotated back and fused.  None: one pass, as ever.
-    ValueError: views with multimodal, a bad views array, no dataset.camera, IMAGE_RESIZE_MODE 'crop' / 'none'."""
+    ValueError: views with multimodal, a bad views array, no dataset.camera, IMAGE_RESIZE_MODE 'crop' / 'none'.
+    members: 1 .. 64 weight sets of this network (weights files, or {layer: {weight: array}} dicts), e.g. SWAG samples written with
+    swag_weights + save_weights: the Bayesian model average (ursonet_amd/ensemble.py).  The dataset is walked once per member; the
+    estimate of a classification head is decoded from the mean of the members' PMFs (multimodal: the modes are fitted on it), a regression
+    head's is fused from the members' poses, and the result carries the entropies and the members' spread.  The model's own weights are
+    back when the call returns or raises.  max_gb: the most device memory the whole-dataset accumulators may take.  ValueError: a bad
+    members list, a member that lacks a layer, views with members, accumulators above max_gb (the message names their size).  None: as ever."""
+    if members is not None:
+        ms = Members(members, views, "predict")
+        out, _dt = EnsemblePass(model, dataset, ms, multimodal, False, "predict", workers, cache, max_gb).run()
+        cfg = model.config
+        return PredictResult(list(dataset.image_ids), None, not cfg.REGRESS_LOC, not (cfg.REGRESS_ORI or cfg.REGRESS_KEYPOINTS), out.gmm,
+                             ensemble=out)
     vs = None
     if views is not None:
         from .views import ViewSet
