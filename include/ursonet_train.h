@@ -230,6 +230,92 @@ typedef struct urso_ens_settle_args {
 int urso_ens_add(const urso_ens_add_args* args, void* stream);
 int urso_ens_settle(const urso_ens_settle_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * Temperature scaling of the classification heads (calibrate(), predict / evaluate / test_and_submit with calibration=..., DESIGN.md
+ * section 25; ursonet_amd/calibrate.py, stats64 / reduce64 / scale32, is the same rule in NumPy float64 and the written specification).
+ * One scalar beta = 1 / T per head is fitted on held-out labelled data by minimising the head's own cross-entropy, and the head's logits
+ * are multiplied by it before every decode.  For a row of K fp32 logits z with the fp32 encoded target y (the PMF the training loss
+ * uses, which may be un-normalised)
+ *
+ *   CE(beta) = sy lse(beta) - beta yz      dCE/dbeta = sy m1(beta) - yz      d2CE/dbeta2 = sy var(beta) >= 0
+ *   sy = sum_i y_i    yz = sum_i y_i z_i    lse = log sum_i exp(beta z_i)    m1 = E_p[z]    var = Var_p[z]    p = softmax(beta z)
+ *
+ * urso_temp_stats, for every valid batch row b < n, z = logits + b * ld_z, y = target + b * ld_y, over the J inverse temperatures beta_j
+ * passed by value; all arithmetic fp64, each operation rounded once (-ffp-contract=off), exp and log the device library's:
+ *
+ *   sweep 1   m  = max_i z_i (fp32, a NaN winning)       sy = sum_i (double) y_i       yz = sum_i (y_i == 0 ? 0 : (double) y_i * (double) z_i)
+ *   sweep 2   d_i = (double) z_i - (double) m            e_ij = exp(beta_j * d_i)
+ *             Z_j = sum_i e_ij        A_j = sum_i (e_ij == 0 ? 0 : e_ij * d_i)        Q_j = sum_i (e_ij == 0 ? 0 : e_ij * (d_i * d_i))
+ *             (a vanished term adds exactly 0, also for d_i = -inf; a bin the target gives no weight adds nothing to yz, also at z_i = -inf)
+ *   close     r_j = A_j / Z_j         LSE_j = log(Z_j) + beta_j * m         M1_j = m + r_j         VAR_j = Q_j / Z_j - r_j * r_j
+ *             poison = 0 * (double) m  (0 for a finite m, NaN otherwise)      SY = sy + poison       YZ = yz + poison
+ *   out[row0 + b] = { SY, YZ, LSE_0, M1_0, VAR_0, .. LSE_(J-1), M1_(J-1), VAR_(J-1) }: 2 + 3 J of the row's URSO_TEMP_COLS doubles; the
+ *             columns behind them are not written
+ *
+ * A NaN or +inf logit, or a row of -inf alone, makes every written column of that row NaN and touches no other row.  The logits are read
+ * once per sweep for all J temperatures (the second time out of L2); the 3 J accumulators live in registers.  Rows >= n, rows of out
+ * outside [row0, row0 + n) and the padding behind K are never read or written.
+ *
+ * urso_temp_reduce, over rows 0 .. N - 1 of such a table, for j < J:
+ *
+ *   CE_rj = SY_r * LSE_rj - beta_j * YZ_r        g_rj = SY_r * M1_rj - YZ_r        h_rj = SY_r * VAR_rj       (products first, then the difference)
+ *   totals[j] = { sum_r CE_rj,  sum_r g_rj,  sum_r h_rj,  the number of rows r where one of SY, YZ, LSE_j, M1_j, VAR_j is not finite }
+ *
+ * One workgroup of 1024 threads: thread t adds rows t, t + 1024, .. in that order, then the order below.  Rows that are not finite are
+ * added like the others: the count says why a total is not finite.
+ *
+ * urso_temp_scale, for b < n and i < K:  out[b][i] = (float) ((double) in[b][i] * beta) -- the product is exact in fp64, so this is the
+ * correctly rounded fp32 product; beta == 1 gives the input's bits back, NaN and +-inf pass through.  in == out is allowed.
+ *
+ * Launch shape and reduction order of urso_temp_stats are urso_ens_add's and part of the result: one workgroup of 1024 threads (16 waves)
+ * per valid row; thread t owns the groups of four columns g = t, 1024 + t, .. and the ragged end K % 4 is the group behind the last whole
+ * one; a thread adds its terms in column order; the threads' sums are added by the xor shuffle 32, 16, .. 1 across a wave, then the 16
+ * wave sums in wave order.  A group is one 16-byte load where the row's first element sits on a 16-byte boundary and four 4-byte loads
+ * where it does not (logits and target each by their own alignment) -- the same columns on the same thread, so every output is a function
+ * of the row alone: the same bits on a repeated launch and whatever B, n, row0, the strides, the alignment, J's other temperatures and the
+ * row's position in the batch.  urso_temp_scale deals the same groups over a grid of (n, ceil((K / 4 + 1) / 1024)) workgroups, 16-byte
+ * loads and stores under the same rule.
+ *
+ * No allocation, no workspace, no host synchronisation.  n == 0 launches nothing.
+ * URSO_EINVAL, with a message, before any launch: a null struct or pointer; J outside [1, URSO_TEMP_MAX_J]; K < 1; a row stride < K;
+ * n outside [0, B]; row0 < 0; N < 1; a beta that is not finite and > 0; logits / target / in / out off the 4-byte boundary; the fp64
+ * tables off the 8-byte one.
+ */
+#define URSO_TEMP_MAX_J 8
+#define URSO_TEMP_COLS 26            /* 2 + 3 * URSO_TEMP_MAX_J */
+#define URSO_TEMP_SY 0
+#define URSO_TEMP_YZ 1
+#define URSO_TEMP_LSE 2              /* + 3 j */
+#define URSO_TEMP_M1 3               /* + 3 j */
+#define URSO_TEMP_VAR 4              /* + 3 j */
+#define URSO_TEMP_TOTALS 4           /* {CE, g, h, rows that are not finite} */
+typedef struct urso_temp_stats_args {
+    int32_t B, n;                    /* rows of logits and target, valid rows (0 <= n <= B) */
+    int64_t row0;                    /* table row of batch row 0 */
+    int32_t K, ld_z, ld_y, J;        /* bins; floats between rows of logits and of target (>= K); temperatures (1 .. 8) */
+    double beta[URSO_TEMP_MAX_J];    /* the first J are used */
+    const float* logits;             /* [B][ld_z] */
+    const float* target;             /* [B][ld_y] */
+    double* out;                     /* [rows][URSO_TEMP_COLS] */
+} urso_temp_stats_args;
+typedef struct urso_temp_reduce_args {
+    int64_t N;                       /* rows 0 .. N - 1 */
+    int32_t J, pad;
+    double beta[URSO_TEMP_MAX_J];    /* the temperatures the rows were written with */
+    const double* rows;              /* [N][URSO_TEMP_COLS] */
+    double* totals;                  /* [URSO_TEMP_MAX_J][URSO_TEMP_TOTALS]; rows j < J are written */
+} urso_temp_reduce_args;
+typedef struct urso_temp_scale_args {
+    int32_t B, n;                    /* rows, valid rows (0 <= n <= B) */
+    int32_t K, ld_in, ld_out, pad;   /* bins; floats between rows (>= K) */
+    double beta;
+    const float* in;                 /* [B][ld_in] */
+    float* out;                      /* [B][ld_out] */
+} urso_temp_scale_args;
+int urso_temp_stats(const urso_temp_stats_args* args, void* stream);
+int urso_temp_reduce(const urso_temp_reduce_args* args, void* stream);
+int urso_temp_scale(const urso_temp_scale_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

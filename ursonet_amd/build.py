@@ -25,7 +25,7 @@ OPT_SOURCES = ["lamb.hip"]
 # stays open, so the next one goes here.  Built and loaded as the other two.
 CSRC_TRAIN = os.path.join(HERE, "csrc_train")
 TRAIN_LIB = os.path.join(LIBDIR, "liburso_train.so")
-TRAIN_SOURCES = ["sam.hip", "bn_recal.hip", "swa.hip", "ensemble.hip"]
+TRAIN_SOURCES = ["sam.hip", "bn_recal.hip", "swa.hip", "ensemble.hip", "calibrate.hip"]
 
 
 def _hipcc():

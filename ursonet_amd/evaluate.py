@@ -18,6 +18,7 @@ import os
 
 import numpy as np
 
+from .calibrate import check_calibration
 from .ensemble import EnsemblePass, Members, eval_fields, no_member_fields
 from .infer import PosePass, eval_columns, fuse_columns, head_modes, loader_workers  # noqa: F401  (head_modes: its long-standing home is here)
 
@@ -95,7 +96,8 @@ def ensemble_line(res):
         res.n_members, "".join(m + ", " for m in mi), np.mean(res.member_loc_spread), np.mean(res.member_ori_spread))
 
 
-def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None, views=None, members=None, max_gb=16):
+def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None, views=None, members=None, max_gb=16,
+             calibration=None):
     """pose_estimator.evaluate(model, dataset): prints the reference's four summary lines (verbose > 0), writes ori_err.csv,
     loc_err.csv and dists_err.csv into out_dir and returns an EvalResult.  multimodal=True (soft classification only) fits up to
     three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 / 12, 5 iterations, nr_max_modes 4) and
@@ -107,7 +109,10 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     them: the fourth line prints nan).  ValueError as in predict().
     members, max_gb: as in predict() -- the estimate and its errors are those of the Bayesian model average of the listed weight sets
     (the same estimate bits as predict(members=...)), the summary lines and CSV files are made from it, and one more line prints the
-    mean mutual information and the mean spread of the members.  multimodal fits the modes on the averaged PMF."""
+    mean mutual information and the mean spread of the members.  multimodal fits the modes on the averaged PMF.
+    calibration: as in predict() -- the classification heads are decoded from their temperature-scaled logits (the same estimate bits as
+    predict(calibration=...)), and one more line prints the temperatures.  Not with members."""
+    check_calibration(calibration, members, "evaluate")
     if members is not None:
         ms = Members(members, views, "evaluate")
         out, loc_dtype = EnsemblePass(model, dataset, ms, multimodal, True, "evaluate", workers, cache, max_gb).run()
@@ -122,7 +127,7 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     if views is not None:
         from .views import ViewSet
         vs = ViewSet(views, multimodal, "evaluate").with_camera(dataset, model.config)
-    ps = PosePass(model, dataset, multimodal, views=vs)
+    ps = PosePass(model, dataset, multimodal, views=vs, calibration=calibration)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
@@ -143,7 +148,7 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     host = table[:N].cpu().numpy()                                              # the one device-to-host read
     res = EvalResult(ids, host, ps.loc_class, ps.soft, multimodal, fused=vs is not None)
     if verbose:
-        for line in summary_lines(res.means()):
+        for line in summary_lines(res.means()) + ([calibration.line()] if calibration is not None else []):
             print(line)
     dist = res.dist.astype(feed.loc_dtype) if feed.loc_dtype is not None else res.dist
     write_csvs(out_dir, res.ori_err, res.loc_err, dist)

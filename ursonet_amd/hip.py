@@ -134,6 +134,27 @@ class EnsSettleArgs(C.Structure):
 # urso_ens_* sizes and table columns (include/ursonet_train.h)
 ENS_MAX_MEMBERS, ENS_STAT, ENS_COLS = 64, 4, 8
 ENS_H_MEAN, ENS_H_MEMBERS, ENS_MI, ENS_PEAK, ENS_ARGMAX, ENS_N_MEMBERS = range(6)
+# urso_temp_* sizes and table columns (include/ursonet_train.h): LSE, M1 and VAR of temperature j are at + 3 j
+TEMP_MAX_J, TEMP_COLS, TEMP_TOTALS = 8, 26, 4
+TEMP_SY, TEMP_YZ, TEMP_LSE, TEMP_M1, TEMP_VAR = range(5)
+
+
+class TempStatsArgs(C.Structure):
+    """urso_temp_stats_args (include/ursonet_train.h): one batch of logits and encoded targets at J inverse temperatures."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] + [(n, C.c_int32) for n in ("K", "ld_z", "ld_y", "J")] +
+                [("beta", C.c_double * TEMP_MAX_J)] + [(n, C.c_void_p) for n in ("logits", "target", "out")])
+
+
+class TempReduceArgs(C.Structure):
+    """urso_temp_reduce_args (include/ursonet_train.h): the rows 0 .. N - 1 of a table of urso_temp_stats."""
+    _fields_ = ([("N", C.c_int64), ("J", C.c_int32), ("pad", C.c_int32), ("beta", C.c_double * TEMP_MAX_J)] +
+                [(n, C.c_void_p) for n in ("rows", "totals")])
+
+
+class TempScaleArgs(C.Structure):
+    """urso_temp_scale_args (include/ursonet_train.h): one batch of logits times beta."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "n", "K", "ld_in", "ld_out", "pad")] + [("beta", C.c_double)] +
+                [(n, C.c_void_p) for n in ("in_", "out")])
 
 
 class DenseWgradLayer(C.Structure):
@@ -315,6 +336,10 @@ _TRAIN_SIGS = {
     # ensemble inference (ursonet_amd/ensemble.py): urso_ens_add_args* | urso_ens_settle_args*
     "urso_ens_add": (_i, [C.POINTER(EnsAddArgs), _vp]),
     "urso_ens_settle": (_i, [C.POINTER(EnsSettleArgs), _vp]),
+    # temperature scaling (ursonet_amd/calibrate.py): urso_temp_stats_args* | urso_temp_reduce_args* | urso_temp_scale_args*
+    "urso_temp_stats": (_i, [C.POINTER(TempStatsArgs), _vp]),
+    "urso_temp_reduce": (_i, [C.POINTER(TempReduceArgs), _vp]),
+    "urso_temp_scale": (_i, [C.POINTER(TempScaleArgs), _vp]),
 }
 TRAIN_SYMBOLS = sorted(_TRAIN_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
@@ -966,6 +991,54 @@ def ens_settle(n, row0, M, acc, stat, logp, table, stream=None):
     a.n, a.row0, a.K, a.M = int(n), int(row0), int(acc.shape[1]), int(M)
     a.acc, a.stat, a.logp, a.table = ptr(acc), ptr(stat), ptr(logp), ptr(table)
     _chk(train_lib().urso_ens_settle(C.byref(a), stream_ptr(stream)), "urso_ens_settle")
+
+
+def _betas(field, betas):
+    J = len(betas)
+    assert 1 <= J <= TEMP_MAX_J
+    for j in range(TEMP_MAX_J):
+        field[j] = float(betas[j]) if j < J else 0.0
+    return J
+
+
+def temp_stats(B, n, row0, betas, logits, target, out, stream=None):
+    """urso_temp_stats (liburso_train.so): for the n valid rows of logits and target (fp32 [B, K] with contiguous rows) the fp64 statistics
+    {SY, YZ, then LSE, M1, VAR per beta} of the cross-entropy at the 1 .. 8 inverse temperatures `betas` go into rows row0 .. of out
+    (fp64 [rows, TEMP_COLS]) (ursonet_amd.calibrate.stats64)."""
+    assert logits.dtype == torch.float32 and target.dtype == torch.float32 and out.dtype == torch.float64 and out.is_contiguous()
+    assert logits.shape[0] >= B and target.shape[0] >= B and logits.shape[1] == target.shape[1] and out.shape[1] == TEMP_COLS
+    assert 0 <= n <= B and row0 >= 0 and row0 + n <= out.shape[0]
+    a = TempStatsArgs()
+    a.B, a.n, a.row0, a.K = int(B), int(n), int(row0), int(logits.shape[1])
+    a.J = _betas(a.beta, betas)
+    a.logits, a.ld_z = _rows(logits)
+    a.target, a.ld_y = _rows(target)
+    a.out = ptr(out)
+    _chk(train_lib().urso_temp_stats(C.byref(a), stream_ptr(stream)), "urso_temp_stats")
+
+
+def temp_reduce(N, betas, rows, totals, stream=None):
+    """urso_temp_reduce (liburso_train.so): totals[j] = {sum CE, sum g, sum h, rows that are not finite} over rows 0 .. N - 1 of a table of
+    temp_stats written with the same betas; totals fp64 [TEMP_MAX_J, TEMP_TOTALS] (ursonet_amd.calibrate.reduce64)."""
+    assert rows.dtype == torch.float64 and totals.dtype == torch.float64 and rows.is_contiguous() and totals.is_contiguous()
+    assert rows.shape[1] == TEMP_COLS and tuple(totals.shape) == (TEMP_MAX_J, TEMP_TOTALS) and 1 <= N <= rows.shape[0]
+    a = TempReduceArgs()
+    a.N, a.pad = int(N), 0
+    a.J = _betas(a.beta, betas)
+    a.rows, a.totals = ptr(rows), ptr(totals)
+    _chk(train_lib().urso_temp_reduce(C.byref(a), stream_ptr(stream)), "urso_temp_reduce")
+
+
+def temp_scale(B, n, beta, src, dst, stream=None):
+    """urso_temp_scale (liburso_train.so): dst = fl32(src * beta) over the n valid rows of fp32 [B, K] tensors with contiguous rows
+    (ursonet_amd.calibrate.scale32)."""
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and src.shape[1] == dst.shape[1]
+    assert 0 <= n <= B and src.shape[0] >= B and dst.shape[0] >= B
+    a = TempScaleArgs()
+    a.B, a.n, a.K, a.pad, a.beta = int(B), int(n), int(src.shape[1]), 0, float(beta)
+    a.in_, a.ld_in = _rows(src)
+    a.out, a.ld_out = _rows(dst)
+    _chk(train_lib().urso_temp_scale(C.byref(a), stream_ptr(stream)), "urso_temp_scale")
 
 
 def grad_accum(n, g, acc, first, stream=None):

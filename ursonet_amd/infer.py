@@ -3,6 +3,7 @@ device" and "this batch's rows are in the table".  A command builds one PosePass
   * run(images) uploads the batch by dtype and replays the inference graph as it is;
   * heads() splits the engine's outputs and, for the soft-classification head, runs urso_quat_wavg_decode on its logits (with the scatter
     matrix only for the DEC table, whose ORI_LAMBDA needs it: passing one selects another kernel variant) and, asked to, urso_quat_gmm_fit;
+    with a calibration (ursonet_amd/calibrate.py) the classification heads' logits first go through urso_temp_scale into buffers of the pass's;
   * eval_into() (labelled: estimates and errors, urso_pose_eval, EVAL columns) or decode_into() (no truth: estimates and confidences,
     urso_pose_decode, DEC columns) decodes every head and writes one fp64 row per image into a device table of the caller's.
 The two kernels share their device routines, so LOC_EST / Q_EST are the same bits whichever command produced them.  With views
@@ -93,9 +94,16 @@ class PosePass(object):
     """The per-call state of the pass: cfg, eng, B, dev, the head modes and, on the device, the bin maps loc_map (fp64) and hq (fp32),
     q_soft [B,4] and, with scatter=True, urso_quat_wavg_decode's scatter matrices [B,16].  `who`: the command, for check_heads' messages."""
 
-    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate", views=None):
-        """views: a views.ViewSet with its homographies (with_camera), for fuse_batch()."""
+    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate", views=None, calibration=None):
+        """views: a views.ViewSet with its homographies (with_camera), for fuse_batch().  calibration: a calibrate.Calibration whose
+        inverse temperatures heads() applies to the classification heads' logits (urso_temp_scale into buffers of the pass's: the engine's
+        outputs stay as they are); None, or a head whose beta is None: nothing is launched for it."""
         self.soft = check_heads(model, dataset, multimodal, who)
+        self.ori_beta = self.loc_beta = self.z_cal = self.loc_cal = None
+        if calibration is not None:
+            from .ensemble import head_bins
+            calibration.check_model(*head_bins(model), who=who)
+            self.ori_beta, self.loc_beta = calibration.ori_beta, calibration.loc_beta
         import torch
         from . import hip
         self.torch, self.hip = torch, hip
@@ -147,9 +155,19 @@ class PosePass(object):
         engine's output buffer) and ori their decoded quaternions; gmm: gmm_buffers' tuple, or views of n rows of it, to fit into."""
         loc, rest = self.eng.outputs()
         ori, ori2 = (rest[0], rest[1]) if self.cfg.REGRESS_KEYPOINTS else (rest, None)
+        if self.loc_beta is not None:                              # the calibrated location logits, in a buffer of the pass's
+            if self.loc_cal is None:
+                self.loc_cal = self.torch.zeros(self.B, loc.shape[1], dtype=self.torch.float32, device=self.dev)
+            self.hip.temp_scale(self.B, n, self.loc_beta, loc, self.loc_cal)
+            loc = self.loc_cal
         z = None
         if self.soft:
             z = ori[:n].contiguous()
+            if self.ori_beta is not None:
+                if self.z_cal is None:
+                    self.z_cal = self.torch.zeros(self.B, z.shape[1], dtype=self.torch.float32, device=self.dev)
+                self.hip.temp_scale(n, n, self.ori_beta, z, self.z_cal)
+                z = self.z_cal[:n]
             self.hip.quat_wavg_decode(n, z.shape[1], z, self.hq, self.q_soft, self.scatter)
             if gmm is not None:
                 self.hip.quat_gmm_fit(n, z.shape[1], z, False, self.hq, self.var, GMM_ITERATIONS, GMM_MAX_MODES, *gmm)

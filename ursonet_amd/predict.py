@@ -14,6 +14,7 @@ Under a launcher (world > 1) every process predicts the whole dataset; there is 
 """
 import numpy as np
 
+from .calibrate import check_calibration
 from .ensemble import EnsemblePass, Members, no_member_fields, predict_fields
 from .infer import PosePass, dec_columns, fuse_columns, loader_workers
 
@@ -48,7 +49,7 @@ class PredictResult(object):
         self.modes, self.mode_priors, self.n_modes = gmm if gmm is not None else (None, None, None)
 
 
-def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None, members=None, max_gb=16):
+def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None, members=None, max_gb=16, calibration=None):
     """Pose estimates of every image of `dataset` -> PredictResult.  The dataset needs image_ids, load_image, image_info and, for
     the classification heads, histogram_3D_map / ori_histogram_map; no label loader is called.  multimodal=True (soft
     classification only) also fits up to three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 /
@@ -62,7 +63,12 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     estimate of a classification head is decoded from the mean of the members' PMFs (multimodal: the modes are fitted on it), a regression
     head's is fused from the members' poses, and the result carries the entropies and the members' spread.  The model's own weights are
     back when the call returns or raises.  max_gb: the most device memory the whole-dataset accumulators may take.  ValueError: a bad
-    members list, a member that lacks a layer, views with members, accumulators above max_gb (the message names their size).  None: as ever."""
+    members list, a member that lacks a layer, views with members, accumulators above max_gb (the message names their size).  None: as ever.
+    calibration: a calibrate.Calibration (from calibrate(), Calibration.load() or built by hand): the logits of each classification head
+    are multiplied by its fitted inverse temperature (urso_temp_scale) before they are decoded, so loc_peak, ori_peak, ori_lambda, the
+    modes and the soft-argmax q_est are those of the calibrated PMF; views work, members do not (ValueError: calibrate and predict each
+    member on its own), nor does a calibration fitted on other bin counts.  None: the code of before, bit for bit."""
+    check_calibration(calibration, members, "predict")
     if members is not None:
         ms = Members(members, views, "predict")
         out, _dt = EnsemblePass(model, dataset, ms, multimodal, False, "predict", workers, cache, max_gb).run()
@@ -73,7 +79,7 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     if views is not None:
         from .views import ViewSet
         vs = ViewSet(views, multimodal, "predict").with_camera(dataset, model.config)
-    ps = PosePass(model, dataset, multimodal, scatter=vs is None, who="predict", views=vs)
+    ps = PosePass(model, dataset, multimodal, scatter=vs is None, who="predict", views=vs, calibration=calibration)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
