@@ -1,4 +1,4 @@
-"""Builds liburso_hip.so, the extension library liburso_ext.so, the optimizer library liburso_opt.so and the training library liburso_train.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
+"""Builds liburso_hip.so, the extension library liburso_ext.so, the optimizer library liburso_opt.so, the training library liburso_train.so and the inference library liburso_infer.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
 import os
 import subprocess
 import sys
@@ -26,6 +26,11 @@ OPT_SOURCES = ["lamb.hip"]
 CSRC_TRAIN = os.path.join(HERE, "csrc_train")
 TRAIN_LIB = os.path.join(LIBDIR, "liburso_train.so")
 TRAIN_SOURCES = ["sam.hip", "bn_recal.hip", "swa.hip", "ensemble.hip", "calibrate.hip"]
+# The inference library (include/ursonet_infer.h): inference features added after liburso_train.so's surface was pinned; its own surface
+# stays open.  Built and loaded as the other three.
+CSRC_INFER = os.path.join(HERE, "csrc_infer")
+INFER_LIB = os.path.join(LIBDIR, "liburso_infer.so")
+INFER_SOURCES = ["conformal.hip"]
 
 
 def _hipcc():
@@ -91,6 +96,11 @@ def train_source_hash():
     return _side_source_hash(CSRC_TRAIN, TRAIN_SOURCES)
 
 
+def infer_source_hash():
+    """source_hash() of the inference library."""
+    return _side_source_hash(CSRC_INFER, INFER_SOURCES)
+
+
 def _stale(lib, digest):
     if not os.path.exists(lib):
         return True
@@ -105,11 +115,12 @@ def needs_build():
     """Stale unless the hash recorded next to the .so equals the hash of the sources as they are now (mtimes are meaningless after a
     checkout or a snapshot push; a .so shipped without its hash file is rebuilt where a compiler exists and trusted where none does).
     True if any of the libraries is stale."""
-    return _stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash) or _stale(OPT_LIB, opt_source_hash) or _stale(TRAIN_LIB, train_source_hash)
+    return (_stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash) or _stale(OPT_LIB, opt_source_hash) or _stale(TRAIN_LIB, train_source_hash) or
+            _stale(INFER_LIB, infer_source_hash))
 
 
 def build(force=False, verbose=True):
-    """Compile every HIP source for gfx950 and link the four shared libraries, each only if it is stale (no GPU needed)."""
+    """Compile every HIP source for gfx950 and link the five shared libraries, each only if it is stale (no GPU needed)."""
     os.makedirs(LIBDIR, exist_ok=True)
     if force or _stale(LIB, source_hash):
         _compile_and_link(LIB, CSRC, SOURCES, FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split(), ("_" + VARIANT) if VARIANT else "", source_hash, verbose)
@@ -119,6 +130,8 @@ def build(force=False, verbose=True):
         _compile_and_link(OPT_LIB, CSRC_OPT, OPT_SOURCES, FLAGS, "_opt", opt_source_hash, verbose)
     if force or _stale(TRAIN_LIB, train_source_hash):
         _compile_and_link(TRAIN_LIB, CSRC_TRAIN, TRAIN_SOURCES, FLAGS, "_train", train_source_hash, verbose)
+    if force or _stale(INFER_LIB, infer_source_hash):
+        _compile_and_link(INFER_LIB, CSRC_INFER, INFER_SOURCES, FLAGS, "_infer", infer_source_hash, verbose)
     return LIB
 
 
@@ -148,4 +161,4 @@ def _compile_and_link(lib, srcdir, sources, flags, tag, digest, verbose):
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
-    print("built", LIB, EXT_LIB, OPT_LIB, TRAIN_LIB)
+    print("built", LIB, EXT_LIB, OPT_LIB, TRAIN_LIB, INFER_LIB)

@@ -19,6 +19,7 @@ import os
 import numpy as np
 
 from .calibrate import check_calibration
+from .conformal import bound_fields, check_conformal, no_bound_fields
 from .ensemble import EnsemblePass, Members, eval_fields, no_member_fields
 from .infer import PosePass, eval_columns, fuse_columns, head_modes, loader_workers  # noqa: F401  (head_modes: its long-standing home is here)
 
@@ -35,13 +36,16 @@ class EvalResult(object):
     agree (else None), and the encoded errors, which do not depend on the estimate, are None.  With members (ensemble: an
     ensemble.EnsembleTables; `table` is not used) the estimate and its errors are the ensemble's, and n_members, member_loc_spread,
     member_ori_spread, member_lambda and the entropies (ori_entropy, ori_member_entropy, ori_mi, loc_entropy, loc_member_entropy,
-    loc_mi) are set as on a PredictResult; else they are None."""
+    loc_mi) are set as on a PredictResult; else they are None.  With conformal (a conformal.Conformal; conformal_tables: the pass's score
+    and bound rows): ori_bound / loc_bound and the region fields as on a PredictResult, and ori_covered / loc_covered: whether the error is
+    within the bound -- for a classification head taken through the keys (the image's score is at most the level), which is exact; else None."""
 
-    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal, fused=False, *, ensemble=None):
+    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal, fused=False, *, ensemble=None, conformal=None, conformal_tables=None):
         from . import hip
         self.image_ids = np.asarray(image_ids)
         self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
         no_member_fields(self)
+        no_bound_fields(self, truth=True)
         if ensemble is not None:
             eval_fields(self, ensemble, loc_enc, ori_enc, multimodal)
             self.dist = ensemble.fuse[:, hip.FUSE_DIST].copy()
@@ -55,6 +59,8 @@ class EvalResult(object):
         self.ori_encoded_err = t[:, hip.EVAL_ORI_ENC_ERR].copy() if ori_enc else None
         self.ori_err_soft = t[:, hip.EVAL_ORI_ERR_SOFT].copy() if multimodal else None
         self.mode = t[:, hip.EVAL_MODE].astype(np.int32) if multimodal else None
+        if conformal is not None:
+            bound_fields(self, conformal, conformal_tables, len(self.image_ids), truth=True)
 
     def means(self):
         """The reference's four printed values (:451-454), in order."""
@@ -97,7 +103,7 @@ def ensemble_line(res):
 
 
 def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None, views=None, members=None, max_gb=16,
-             calibration=None):
+             calibration=None, conformal=None):
     """pose_estimator.evaluate(model, dataset): prints the reference's four summary lines (verbose > 0), writes ori_err.csv,
     loc_err.csv and dists_err.csv into out_dir and returns an EvalResult.  multimodal=True (soft classification only) fits up to
     three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 / 12, 5 iterations, nr_max_modes 4) and
@@ -111,8 +117,15 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     (the same estimate bits as predict(members=...)), the summary lines and CSV files are made from it, and one more line prints the
     mean mutual information and the mean spread of the members.  multimodal fits the modes on the averaged PMF.
     calibration: as in predict() -- the classification heads are decoded from their temperature-scaled logits (the same estimate bits as
-    predict(calibration=...)), and one more line prints the temperatures.  Not with members."""
+    predict(calibration=...)), and one more line prints the temperatures.  Not with members.
+    conformal: as in predict() -- the same bound bits as predict(conformal=...); urso_conf_score runs beside urso_conf_bound, the result
+    says per image whether the error is within the bound, and one more line prints the target, the empirical coverage and the mean and
+    median bound per head.  Not with members, views or multimodal (which picks the mode by the truth: not the estimate the levels are for)."""
     check_calibration(calibration, members, "evaluate")
+    check_conformal(conformal, members, views, calibration, "evaluate")
+    if conformal is not None and multimodal:
+        raise ValueError("evaluate: conformal=... cannot be combined with multimodal=True: the mode is picked by the truth, and the levels "
+                         "were fitted on the soft-argmax estimate")
     if members is not None:
         ms = Members(members, views, "evaluate")
         out, loc_dtype = EnsemblePass(model, dataset, ms, multimodal, True, "evaluate", workers, cache, max_gb).run()
@@ -127,7 +140,7 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     if views is not None:
         from .views import ViewSet
         vs = ViewSet(views, multimodal, "evaluate").with_camera(dataset, model.config)
-    ps = PosePass(model, dataset, multimodal, views=vs, calibration=calibration)
+    ps = PosePass(model, dataset, multimodal, views=vs, calibration=calibration, conformal=conformal)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
@@ -142,13 +155,17 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
                 ps.fuse_batch(table, bt)
                 continue
             ps.run(bt.images)
-            ps.eval_into(table, bt, ps.heads(bt.n, gmm), gmm)
+            heads = ps.heads(bt.n, gmm)
+            ps.eval_into(table, bt, heads, gmm)
+            ps.bounds(table, bt.n, bt.row0, heads, bt)
     finally:
         feed.close()
     host = table[:N].cpu().numpy()                                              # the one device-to-host read
-    res = EvalResult(ids, host, ps.loc_class, ps.soft, multimodal, fused=vs is not None)
+    res = EvalResult(ids, host, ps.loc_class, ps.soft, multimodal, fused=vs is not None, conformal=conformal,
+                     conformal_tables=ps.conformal_tables(N) if conformal is not None else None)
     if verbose:
-        for line in summary_lines(res.means()) + ([calibration.line()] if calibration is not None else []):
+        for line in (summary_lines(res.means()) + ([calibration.line()] if calibration is not None else []) +
+                     ([conformal.line(res)] if conformal is not None else [])):
             print(line)
     dist = res.dist.astype(feed.loc_dtype) if feed.loc_dtype is not None else res.dist
     write_csvs(out_dir, res.ori_err, res.loc_err, dist)

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "liburso_hip%s.so" % (("_" + _VARIANT) if 
 EXT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_ext.so")          # the extension library (include/ursonet_ext.h): loaded on first use
 OPT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_opt.so")          # the optimizer library (include/ursonet_opt.h): loaded on first use
 TRAIN_LIB_PATH = os.path.join(_HERE, "lib", "liburso_train.so")      # the training library (include/ursonet_train.h): loaded on first use
+INFER_LIB_PATH = os.path.join(_HERE, "lib", "liburso_infer.so")      # the inference library (include/ursonet_infer.h): loaded on first use
 
 F32, BF16, F16 = 0, 1, 2
 EPI_RELU, EPI_OUT_F32, EPI_MASK_BITS, EPI_EMIT_BITS, EPI_ADD_SRCGRID = 1, 2, 4, 8, 16
@@ -155,6 +156,26 @@ class TempScaleArgs(C.Structure):
     """urso_temp_scale_args (include/ursonet_train.h): one batch of logits times beta."""
     _fields_ = ([(n, C.c_int32) for n in ("B", "n", "K", "ld_in", "ld_out", "pad")] + [("beta", C.c_double)] +
                 [(n, C.c_void_p) for n in ("in_", "out")])
+
+
+class ConfScoreArgs(C.Structure):
+    """urso_conf_score_args (include/ursonet_infer.h): one batch of logits, the estimates' rows and the truth."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] +
+                [(n, C.c_int32) for n in ("K", "ld_z", "metric", "ld_est", "ld_ref", "pad")] +
+                [(n, C.c_void_p) for n in ("logits", "map", "est", "ref", "out")])
+
+
+class ConfBoundArgs(C.Structure):
+    """urso_conf_bound_args (include/ursonet_infer.h): one batch of logits and the estimates' rows at the level q."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] + [(n, C.c_int32) for n in ("K", "ld_z", "metric", "ld_est")] +
+                [("q", C.c_double)] + [(n, C.c_void_p) for n in ("logits", "map", "est", "out")])
+
+
+# urso_conf_* sizes, metrics and table columns (include/ursonet_infer.h)
+CONF_SHIFT, CONF_MAX_K, CONF_COLS, CONF_DIGIT, CONF_PASSES = 34, 1 << 18, 8, 11, 6
+CONF_ANGLE, CONF_EUCLID = 0, 1
+CONF_SCORE, CONF_C, CONF_W, CONF_KEY_REF, CONF_ERR, CONF_NEAR = range(6)
+CONF_BOUND, CONF_KEY, CONF_MASS, CONF_COUNT, CONF_BW = range(5)
 
 
 class DenseWgradLayer(C.Structure):
@@ -342,6 +363,13 @@ _TRAIN_SIGS = {
     "urso_temp_scale": (_i, [C.POINTER(TempScaleArgs), _vp]),
 }
 TRAIN_SYMBOLS = sorted(_TRAIN_SIGS)
+# the inference library liburso_infer.so, include/ursonet_infer.h: bound by infer_lib() on first use
+_INFER_SIGS = {
+    # conformal bounds (ursonet_amd/conformal.py): urso_conf_score_args* | urso_conf_bound_args*
+    "urso_conf_score": (_i, [C.POINTER(ConfScoreArgs), _vp]),
+    "urso_conf_bound": (_i, [C.POINTER(ConfBoundArgs), _vp]),
+}
+INFER_SYMBOLS = sorted(_INFER_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
 SWA_STATE = 8                                                         # URSO_SWA_STATE int32s (ursonet_amd/swa.py names the fields)
 
@@ -404,6 +432,23 @@ def train_lib():
         _bind(lib, _TRAIN_SIGS)
         _train = lib
     return _train
+
+
+_infer = None
+
+
+def infer_lib():
+    """liburso_infer.so, loaded and bound on first use, behind the main library as train_lib() loads its own."""
+    global _infer
+    if _infer is None:
+        if not os.path.exists(INFER_LIB_PATH):
+            raise ImportError("liburso_infer.so not found at %s -- build it with `python -m ursonet_amd.build` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % INFER_LIB_PATH)
+        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
+        lib = C.CDLL(INFER_LIB_PATH)
+        _bind(lib, _INFER_SIGS)
+        _infer = lib
+    return _infer
 
 
 def last_error():
@@ -1039,6 +1084,41 @@ def temp_scale(B, n, beta, src, dst, stream=None):
     a.in_, a.ld_in = _rows(src)
     a.out, a.ld_out = _rows(dst)
     _chk(train_lib().urso_temp_scale(C.byref(a), stream_ptr(stream)), "urso_temp_scale")
+
+
+def _conf_args(a, B, n, row0, metric, logits, bin_map, est, out):
+    """The fields urso_conf_score_args and urso_conf_bound_args share."""
+    D = 4 if metric == CONF_ANGLE else 3
+    assert metric in (CONF_ANGLE, CONF_EUCLID) and logits.dtype == torch.float32 and logits.shape[0] >= B and 0 <= n <= B and row0 >= 0
+    assert bin_map.dtype == (torch.float32 if metric == CONF_ANGLE else torch.float64) and bin_map.is_contiguous()
+    assert tuple(bin_map.shape) == (logits.shape[1], D), "the bin map does not fit the logits"
+    assert est.dtype == torch.float64 and est.shape[1] == D and row0 + n <= min(est.shape[0], out.shape[0])
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.shape[1] == CONF_COLS
+    a.B, a.n, a.row0, a.K, a.metric = int(B), int(n), int(row0), int(logits.shape[1]), int(metric)
+    a.logits, a.ld_z = _rows(logits)
+    a.est, a.ld_est = _rows(est)
+    a.map, a.out = ptr(bin_map), ptr(out)
+    return a, D
+
+
+def conf_score(B, n, row0, metric, logits, bin_map, est, ref, out, stream=None):
+    """urso_conf_score (liburso_infer.so): for the n valid rows of logits (fp32 [B, K] with contiguous rows) the mass of the bins strictly
+    closer to est than the truth is, into rows row0 .. of out (fp64 [rows, CONF_COLS]).  est: fp64 [rows, 4 | 3] with contiguous rows (a
+    column slice of a table is fine), row row0 + b for batch row b; ref: fp64 [B, 4 | 3], the truth; bin_map: fp32 [K, 4] (CONF_ANGLE) or
+    fp64 [K, 3] (CONF_EUCLID) (ursonet_amd.conformal.score64)."""
+    a, D = _conf_args(ConfScoreArgs(), B, n, row0, metric, logits, bin_map, est, out)
+    assert ref.dtype == torch.float64 and ref.shape[0] >= B and ref.shape[1] == D
+    a.ref, a.ld_ref = _rows(ref)
+    a.pad = 0
+    _chk(infer_lib().urso_conf_score(C.byref(a), stream_ptr(stream)), "urso_conf_score")
+
+
+def conf_bound(B, n, row0, metric, q, logits, bin_map, est, out, stream=None):
+    """urso_conf_bound (liburso_infer.so): for the n valid rows of logits the smallest ball around est that holds more than q of the PMF's
+    mass, into rows row0 .. of out (fp64 [rows, CONF_COLS]); arguments as conf_score's, q > 0 (ursonet_amd.conformal.bound64)."""
+    a, _D = _conf_args(ConfBoundArgs(), B, n, row0, metric, logits, bin_map, est, out)
+    a.q = float(q)
+    _chk(infer_lib().urso_conf_bound(C.byref(a), stream_ptr(stream)), "urso_conf_bound")
 
 
 def grad_accum(n, g, acc, first, stream=None):

@@ -94,11 +94,16 @@ class PosePass(object):
     """The per-call state of the pass: cfg, eng, B, dev, the head modes and, on the device, the bin maps loc_map (fp64) and hq (fp32),
     q_soft [B,4] and, with scatter=True, urso_quat_wavg_decode's scatter matrices [B,16].  `who`: the command, for check_heads' messages."""
 
-    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate", views=None, calibration=None):
+    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate", views=None, calibration=None, conformal=None):
         """views: a views.ViewSet with its homographies (with_camera), for fuse_batch().  calibration: a calibrate.Calibration whose
         inverse temperatures heads() applies to the classification heads' logits (urso_temp_scale into buffers of the pass's: the engine's
-        outputs stay as they are); None, or a head whose beta is None: nothing is launched for it."""
+        outputs stay as they are); None, or a head whose beta is None: nothing is launched for it.  conformal: a conformal.Conformal whose
+        levels bounds() applies behind the decode (urso_conf_bound per classification head into tables of the pass's); None: nothing."""
         self.soft = check_heads(model, dataset, multimodal, who)
+        self.conformal, self.conf = conformal, None
+        if conformal is not None:
+            from .ensemble import head_bins
+            conformal.check_model(*head_bins(model), who=who)
         self.ori_beta = self.loc_beta = self.z_cal = self.loc_cal = None
         if calibration is not None:
             from .ensemble import head_bins
@@ -187,6 +192,21 @@ class PosePass(object):
         loc, ori, ori2, z = heads
         self.hip.pose_decode(self.B, n, row0, self.loc_mode, self.ori_mode, loc, ori, table, ori2=ori2, loc_map=self.loc_map, ori_logits=z,
                              ori_map_rows=self.hq.shape[0] if self.soft else 0, ori_scatter=self.scatter)
+
+    def bounds(self, table, n, row0, heads, bt=None):
+        """With a conformal: behind eval_into / decode_into of the rows [row0, row0 + n) of `table`, urso_conf_bound per classification
+        head at the conformal's level, around the estimates just written, into tables of the pass's (as many rows as `table`); with the
+        EvalFeeder batch bt's truth, urso_conf_score as well.  conformal_tables() reads them, once, at the end."""
+        if self.conformal is None:
+            return
+        if self.conf is None:
+            from .conformal import ConformalPass
+            self.conf = ConformalPass(self, table.shape[0], levels=self.conformal, scores=bt is not None)
+        self.conf.launch(table, n, row0, heads, bt)
+
+    def conformal_tables(self, N):
+        """{head: (score rows or None, bound rows)} of the classification heads on the host ({} where no batch ran)."""
+        return {} if self.conf is None else self.conf.tables(N)
 
     def fuse_batch(self, table, bt):
         """The rows [bt.row0, bt.row0 + bt.n) of a FUSE table: the feeder batch bt once per view through the network -- the identity view

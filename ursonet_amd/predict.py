@@ -15,6 +15,7 @@ Under a launcher (world > 1) every process predicts the whole dataset; there is 
 import numpy as np
 
 from .calibrate import check_calibration
+from .conformal import bound_fields, check_conformal, no_bound_fields
 from .ensemble import EnsemblePass, Members, no_member_fields, predict_fields
 from .infer import PosePass, dec_columns, fuse_columns, loader_workers
 
@@ -33,11 +34,15 @@ class PredictResult(object):
     those of the averaged PMF, n_members is M, member_loc_spread, member_ori_spread (degrees) and member_lambda say how far the members'
     decoded poses spread (urso_pose_fuse_views' columns), and per classification head, in nats: ori_entropy / loc_entropy (of the averaged
     PMF), ori_member_entropy / loc_member_entropy (the mean of the members') and ori_mi / loc_mi (their difference, the mutual
-    information: the epistemic part).  Without members all of these are None."""
+    information: the epistemic part).  Without members all of these are None.
+    With conformal (a conformal.Conformal; conformal_tables: the pass's bound rows): ori_bound (degrees) and loc_bound (metres), the
+    error bounds that hold with probability 1 - alpha, and for a classification head ori_region_bins / loc_region_bins (the bins inside the
+    bound) and ori_region_mass / loc_region_mass (their PMF mass); None for a regression head, whose bound is a constant.  Without: None."""
 
-    def __init__(self, image_ids, table, loc_class, soft, gmm=None, fused=False, *, ensemble=None):
+    def __init__(self, image_ids, table, loc_class, soft, gmm=None, fused=False, *, ensemble=None, conformal=None, conformal_tables=None):
         self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
         no_member_fields(self)
+        no_bound_fields(self)
         if ensemble is not None:
             predict_fields(self, ensemble, loc_class, soft)
         elif fused:
@@ -47,9 +52,12 @@ class PredictResult(object):
             dec_columns(self, table, loc_class, soft)
         self.image_ids = np.asarray(image_ids)
         self.modes, self.mode_priors, self.n_modes = gmm if gmm is not None else (None, None, None)
+        if conformal is not None:
+            bound_fields(self, conformal, conformal_tables, len(self.image_ids))
 
 
-def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None, members=None, max_gb=16, calibration=None):
+def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None, members=None, max_gb=16, calibration=None,
+            conformal=None):
     """Pose estimates of every image of `dataset` -> PredictResult.  The dataset needs image_ids, load_image, image_info and, for
     the classification heads, histogram_3D_map / ori_histogram_map; no label loader is called.  multimodal=True (soft
     classification only) also fits up to three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 /
@@ -67,8 +75,13 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     calibration: a calibrate.Calibration (from calibrate(), Calibration.load() or built by hand): the logits of each classification head
     are multiplied by its fitted inverse temperature (urso_temp_scale) before they are decoded, so loc_peak, ori_peak, ori_lambda, the
     modes and the soft-argmax q_est are those of the calibrated PMF; views work, members do not (ValueError: calibrate and predict each
-    member on its own), nor does a calibration fitted on other bin counts.  None: the code of before, bit for bit."""
+    member on its own), nor does a calibration fitted on other bin counts.  None: the code of before, bit for bit.
+    conformal: a conformal.Conformal (from conformal() or Conformal.load()): behind the decode, urso_conf_bound gives every image the
+    smallest ball around its estimate that holds more than the fitted level of the head's PMF mass: ori_bound / loc_bound and the region
+    fields (a regression head gets its constant).  ValueError: with members or views, under calibration betas other than the ones the
+    levels were fitted under (the message names both), bin counts that do not fit the model.  None: nothing is launched."""
     check_calibration(calibration, members, "predict")
+    check_conformal(conformal, members, views, calibration, "predict")
     if members is not None:
         ms = Members(members, views, "predict")
         out, _dt = EnsemblePass(model, dataset, ms, multimodal, False, "predict", workers, cache, max_gb).run()
@@ -79,7 +92,7 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     if views is not None:
         from .views import ViewSet
         vs = ViewSet(views, multimodal, "predict").with_camera(dataset, model.config)
-    ps = PosePass(model, dataset, multimodal, scatter=vs is None, who="predict", views=vs, calibration=calibration)
+    ps = PosePass(model, dataset, multimodal, scatter=vs is None, who="predict", views=vs, calibration=calibration, conformal=conformal)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
@@ -94,9 +107,12 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
                 continue
             ps.run(bt.images)
             rows = [t[bt.row0:bt.row0 + bt.n] for t in gmm] if multimodal else None
-            ps.decode_into(table, bt.n, bt.row0, ps.heads(bt.n, rows))
+            heads = ps.heads(bt.n, rows)
+            ps.decode_into(table, bt.n, bt.row0, heads)
+            ps.bounds(table, bt.n, bt.row0, heads)
     finally:
         feed.close()
     host = table[:N].cpu().numpy()                                               # the one read of the table
     fit = tuple(gmm[i][:N].cpu().numpy() for i in (0, 2, 4)) if multimodal else None      # mean, prior, n_modes
-    return PredictResult(ids, host, ps.loc_class, ps.soft, fit, fused=vs is not None)
+    return PredictResult(ids, host, ps.loc_class, ps.soft, fit, fused=vs is not None, conformal=conformal,
+                         conformal_tables=ps.conformal_tables(N) if conformal is not None else None)

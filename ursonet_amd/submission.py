@@ -66,14 +66,15 @@ def submission_rows(result, dataset, config):
     return rows
 
 
-def test_and_submit(model, dataset_virtual, dataset_real, out_dir='', suffix='debug', views=None, members=None, calibration=None):
+def test_and_submit(model, dataset_virtual, dataset_real, out_dir='', suffix='debug', views=None, members=None, calibration=None, conformal=None):
     """pose_estimator.test_and_submit: predicts both label-free datasets, writes submission_<suffix>.csv into out_dir (rank 0
     only) and returns the two PredictResults.  views: as in predict() -- the submitted poses are the ones fused from rotated views.
     members: as in predict() -- the submitted poses are those of the ensemble of the listed weight sets.
-    calibration: as in predict() -- the classification heads are decoded from their temperature-scaled logits (not with members)."""
+    calibration: as in predict() -- the classification heads are decoded from their temperature-scaled logits (not with members).
+    conformal: as in predict() -- the two results carry the error bounds (the submission file does not)."""
     from .predict import predict
-    res_v = predict(model, dataset_virtual, views=views, members=members, calibration=calibration)
-    res_r = predict(model, dataset_real, views=views, members=members, calibration=calibration)
+    res_v = predict(model, dataset_virtual, views=views, members=members, calibration=calibration, conformal=conformal)
+    res_r = predict(model, dataset_real, views=views, members=members, calibration=calibration, conformal=conformal)
     from .dp import launcher_world                                               # (behind predict: its refusals need neither torch nor a GPU)
     if launcher_world()[0] == 0:
         sub = SubmissionWriter()
