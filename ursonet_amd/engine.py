@@ -2006,6 +2006,14 @@ class Engine(object):
         ori = self.q_out if self.quat_head else self.out_ori.data.view(self.B, -1)[:, :no]
         return loc, ori
 
+    def features(self):
+        """The bottleneck_layer output (Graph.feat), the tensor both head trunks read, as a [B, h, w, C] view in the engine's dtype: the
+        activations of the last forward pass (ursonet_amd/domain.py pools them).  A view of the plan's own buffer; nothing is launched."""
+        f = self.graph.feat
+        a = self.acts[f.id]
+        assert a.numel == self.B * f.h * f.w * f.c, "the bottleneck features are kept dense"
+        return a.data.view(self.B, f.h, f.w, f.c)
+
     def losses(self):
         """{'loc_loss','ori_loss'} (keypoint mode: {'loc_loss','k2_loss','k3_loss'}) weighted by LOSS_WEIGHTS, as in the
         Keras metrics (net.py:989-992, 1019-1028)."""

@@ -20,6 +20,7 @@ import numpy as np
 
 from .calibrate import check_calibration
 from .conformal import bound_fields, check_conformal, no_bound_fields
+from .domain import check_domain, domain_fields, no_domain_fields
 from .ensemble import EnsemblePass, Members, eval_fields, no_member_fields
 from .infer import PosePass, eval_columns, fuse_columns, head_modes, loader_workers  # noqa: F401  (head_modes: its long-standing home is here)
 
@@ -38,14 +39,20 @@ class EvalResult(object):
     member_ori_spread, member_lambda and the entropies (ori_entropy, ori_member_entropy, ori_mi, loc_entropy, loc_member_entropy,
     loc_mi) are set as on a PredictResult; else they are None.  With conformal (a conformal.Conformal; conformal_tables: the pass's score
     and bound rows): ori_bound / loc_bound and the region fields as on a PredictResult, and ori_covered / loc_covered: whether the error is
-    within the bound -- for a classification head taken through the keys (the image's score is at most the level), which is exact; else None."""
+    within the bound -- for a classification head taken through the keys (the image's score is at most the level), which is exact; else None.
+    With domain (a domain.Domain; domain_table: the pass's score rows): domain_score, domain_dist2, domain_zmax, domain_zarg and domain_p
+    as on a PredictResult; else None."""
 
-    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal, fused=False, *, ensemble=None, conformal=None, conformal_tables=None):
+    def __init__(self, image_ids, table, loc_enc, ori_enc, multimodal, fused=False, *, ensemble=None, conformal=None, conformal_tables=None,
+                 domain=None, domain_table=None):
         from . import hip
         self.image_ids = np.asarray(image_ids)
         self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
         no_member_fields(self)
         no_bound_fields(self, truth=True)
+        no_domain_fields(self)
+        if domain is not None:
+            domain_fields(self, domain, domain_table)
         if ensemble is not None:
             eval_fields(self, ensemble, loc_enc, ori_enc, multimodal)
             self.dist = ensemble.fuse[:, hip.FUSE_DIST].copy()
@@ -103,7 +110,7 @@ def ensemble_line(res):
 
 
 def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=None, cache=None, views=None, members=None, max_gb=16,
-             calibration=None, conformal=None):
+             calibration=None, conformal=None, domain=None):
     """pose_estimator.evaluate(model, dataset): prints the reference's four summary lines (verbose > 0), writes ori_err.csv,
     loc_err.csv and dists_err.csv into out_dir and returns an EvalResult.  multimodal=True (soft classification only) fits up to
     three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 / 12, 5 iterations, nr_max_modes 4) and
@@ -120,9 +127,13 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     predict(calibration=...)), and one more line prints the temperatures.  Not with members.
     conformal: as in predict() -- the same bound bits as predict(conformal=...); urso_conf_score runs beside urso_conf_bound, the result
     says per image whether the error is within the bound, and one more line prints the target, the empirical coverage and the mean and
-    median bound per head.  Not with members, views or multimodal (which picks the mode by the truth: not the estimate the levels are for)."""
+    median bound per head.  Not with members, views or multimodal (which picks the mode by the truth: not the estimate the levels are for).
+    domain: as in predict() -- the same score bits as predict(domain=...), and one more line prints the median and the 95th percentile of
+    the score, with a holdout the share of images with p < 0.05, and Spearman's rho of the score with ori_err and with loc_err.  Not with
+    members or views, nor under a data-parallel launcher."""
     check_calibration(calibration, members, "evaluate")
     check_conformal(conformal, members, views, calibration, "evaluate")
+    check_domain(domain, members, views, "evaluate")
     if conformal is not None and multimodal:
         raise ValueError("evaluate: conformal=... cannot be combined with multimodal=True: the mode is picked by the truth, and the levels "
                          "were fitted on the soft-argmax estimate")
@@ -140,7 +151,7 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
     if views is not None:
         from .views import ViewSet
         vs = ViewSet(views, multimodal, "evaluate").with_camera(dataset, model.config)
-    ps = PosePass(model, dataset, multimodal, views=vs, calibration=calibration, conformal=conformal)
+    ps = PosePass(model, dataset, multimodal, views=vs, calibration=calibration, conformal=conformal, domain=domain)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
@@ -155,6 +166,7 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
                 ps.fuse_batch(table, bt)
                 continue
             ps.run(bt.images)
+            ps.domain_scores(table, bt.n, bt.row0)
             heads = ps.heads(bt.n, gmm)
             ps.eval_into(table, bt, heads, gmm)
             ps.bounds(table, bt.n, bt.row0, heads, bt)
@@ -162,10 +174,11 @@ def evaluate(model, dataset, multimodal=False, out_dir=".", verbose=1, workers=N
         feed.close()
     host = table[:N].cpu().numpy()                                              # the one device-to-host read
     res = EvalResult(ids, host, ps.loc_class, ps.soft, multimodal, fused=vs is not None, conformal=conformal,
-                     conformal_tables=ps.conformal_tables(N) if conformal is not None else None)
+                     conformal_tables=ps.conformal_tables(N) if conformal is not None else None, domain=domain,
+                     domain_table=ps.domain_table(N) if domain is not None else None)
     if verbose:
         for line in (summary_lines(res.means()) + ([calibration.line()] if calibration is not None else []) +
-                     ([conformal.line(res)] if conformal is not None else [])):
+                     ([conformal.line(res)] if conformal is not None else []) + ([domain.line(res)] if domain is not None else [])):
             print(line)
     dist = res.dist.astype(feed.loc_dtype) if feed.loc_dtype is not None else res.dist
     write_csvs(out_dir, res.ori_err, res.loc_err, dist)

@@ -16,6 +16,7 @@ EXT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_ext.so")          # the exten
 OPT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_opt.so")          # the optimizer library (include/ursonet_opt.h): loaded on first use
 TRAIN_LIB_PATH = os.path.join(_HERE, "lib", "liburso_train.so")      # the training library (include/ursonet_train.h): loaded on first use
 INFER_LIB_PATH = os.path.join(_HERE, "lib", "liburso_infer.so")      # the inference library (include/ursonet_infer.h): loaded on first use
+FEAT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_feat.so")        # the feature library (include/ursonet_feat.h): loaded on first use
 
 F32, BF16, F16 = 0, 1, 2
 EPI_RELU, EPI_OUT_F32, EPI_MASK_BITS, EPI_EMIT_BITS, EPI_ADD_SRCGRID = 1, 2, 4, 8, 16
@@ -176,6 +177,29 @@ CONF_SHIFT, CONF_MAX_K, CONF_COLS, CONF_DIGIT, CONF_PASSES = 34, 1 << 18, 8, 11,
 CONF_ANGLE, CONF_EUCLID = 0, 1
 CONF_SCORE, CONF_C, CONF_W, CONF_KEY_REF, CONF_ERR, CONF_NEAR = range(6)
 CONF_BOUND, CONF_KEY, CONF_MASS, CONF_COUNT, CONF_BW = range(5)
+
+
+class FeatPoolArgs(C.Structure):
+    """urso_feat_pool_args (include/ursonet_feat.h): one batch of bottleneck features into rows of an fp64 table."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "C", "gh", "gw", "dtype")] +
+                [("ld", C.c_int64)] + [(n, C.c_void_p) for n in ("act", "out")])
+
+
+class FeatGramArgs(C.Structure):
+    """urso_feat_gram_args (include/ursonet_feat.h): rows of a feature table into the running sums s and G."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64), ("D", C.c_int32), ("pad", C.c_int32), ("ld_x", C.c_int64), ("ld_g", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("x", "centre", "s", "g")])
+
+
+class FeatMahaArgs(C.Structure):
+    """urso_feat_maha_args (include/ursonet_feat.h): a batch's feature rows against a mean and a transposed whitening matrix."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64), ("D", C.c_int32), ("pad", C.c_int32), ("ld_x", C.c_int64), ("ld_w", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("x", "mean", "wt", "out")])
+
+
+# urso_feat_* sizes and table columns (include/ursonet_feat.h)
+FEAT_MAX_D, FEAT_COLS, FEAT_MAHA_ROWS = 4096, 4, 8
+FEAT_SCORE, FEAT_DIST2, FEAT_ZMAX, FEAT_ZARG = range(4)
 
 
 class DenseWgradLayer(C.Structure):
@@ -370,6 +394,14 @@ _INFER_SIGS = {
     "urso_conf_bound": (_i, [C.POINTER(ConfBoundArgs), _vp]),
 }
 INFER_SYMBOLS = sorted(_INFER_SIGS)
+# the feature library liburso_feat.so, include/ursonet_feat.h: bound by feat_lib() on first use
+_FEAT_SIGS = {
+    # domain-shift scores (ursonet_amd/domain.py): urso_feat_pool_args* | urso_feat_gram_args* | urso_feat_maha_args*
+    "urso_feat_pool": (_i, [C.POINTER(FeatPoolArgs), _vp]),
+    "urso_feat_gram_add": (_i, [C.POINTER(FeatGramArgs), _vp]),
+    "urso_feat_maha": (_i, [C.POINTER(FeatMahaArgs), _vp]),
+}
+FEAT_SYMBOLS = sorted(_FEAT_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
 SWA_STATE = 8                                                         # URSO_SWA_STATE int32s (ursonet_amd/swa.py names the fields)
 
@@ -449,6 +481,23 @@ def infer_lib():
         _bind(lib, _INFER_SIGS)
         _infer = lib
     return _infer
+
+
+_feat = None
+
+
+def feat_lib():
+    """liburso_feat.so, loaded and bound on first use, behind the main library as train_lib() loads its own."""
+    global _feat
+    if _feat is None:
+        if not os.path.exists(FEAT_LIB_PATH):
+            raise ImportError("liburso_feat.so not found at %s -- build it with `python -m ursonet_amd.build` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % FEAT_LIB_PATH)
+        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
+        lib = C.CDLL(FEAT_LIB_PATH)
+        _bind(lib, _FEAT_SIGS)
+        _feat = lib
+    return _feat
 
 
 def last_error():
@@ -1119,6 +1168,54 @@ def conf_bound(B, n, row0, metric, q, logits, bin_map, est, out, stream=None):
     a, _D = _conf_args(ConfBoundArgs(), B, n, row0, metric, logits, bin_map, est, out)
     a.q = float(q)
     _chk(infer_lib().urso_conf_bound(C.byref(a), stream_ptr(stream)), "urso_conf_bound")
+
+
+def feat_pool(B, n, row0, grid, act, out, stream=None):
+    """urso_feat_pool (liburso_feat.so): the cell means of the n valid batch rows of act ([B, h, w, C] in the engine's dtype, contiguous)
+    over the grid (gh, gw) into rows row0 .. of out (fp64 [rows, >= D] with contiguous rows) (ursonet_amd.domain.pool64)."""
+    assert act.dim() == 4 and act.is_contiguous() and act.shape[0] >= B and act.dtype in DT_OF_TORCH and 0 <= n <= B and row0 >= 0
+    assert out.dtype == torch.float64 and row0 + n <= out.shape[0]
+    a = FeatPoolArgs()
+    a.B, a.n, a.row0, (a.gh, a.gw), a.dtype = int(B), int(n), int(row0), (int(grid[0]), int(grid[1])), DT_OF_TORCH[act.dtype]
+    a.h, a.w, a.C = (int(v) for v in act.shape[1:])
+    a.act = ptr(act)
+    a.out, a.ld = _rows(out)
+    assert out.shape[1] >= a.gh * a.gw * a.C, "the table is narrower than the feature row"
+    _chk(feat_lib().urso_feat_pool(C.byref(a), stream_ptr(stream)), "urso_feat_pool")
+
+
+def feat_gram_add(B, n, row0, x, centre, s, g, stream=None):
+    """urso_feat_gram_add (liburso_feat.so): rows [row0, row0 + n) of x (fp64 [rows, >= D], contiguous rows), centred on `centre` [D], into
+    the sums s [D] and the upper triangle of g (fp64 [D, >= D], contiguous rows) (ursonet_amd.domain.gram_add64)."""
+    D = int(s.numel())
+    assert all(t.dtype == torch.float64 for t in (x, centre, s, g)) and 0 <= n <= B and row0 >= 0 and row0 + n <= x.shape[0]
+    assert centre.numel() == D and x.shape[1] >= D and g.shape[0] >= D and g.shape[1] >= D
+    a = FeatGramArgs()
+    a.B, a.n, a.row0, a.D, a.pad = int(B), int(n), int(row0), D, 0
+    a.x, a.ld_x = _rows(x)
+    a.g, a.ld_g = _rows(g)
+    a.centre, a.s = ptr(centre), ptr(s)
+    _chk(feat_lib().urso_feat_gram_add(C.byref(a), stream_ptr(stream)), "urso_feat_gram_add")
+
+
+def feat_whiten_t(W, device):
+    """The storage urso_feat_maha reads: a lower-triangular whitening matrix W [D, D] (host, fp64) transposed, on the device."""
+    import numpy as np
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(W, dtype=np.float64).T)).to(device).contiguous()
+
+
+def feat_maha(B, n, row0, x, mean, wt, out, stream=None):
+    """urso_feat_maha (liburso_feat.so): the n valid rows of x (fp64 [B, >= D], the batch's feature rows) against mean [D] and wt
+    (feat_whiten_t: W transposed, [D, >= D]) into rows row0 .. of out (fp64 [rows, FEAT_COLS]) (ursonet_amd.domain.maha64)."""
+    D = int(mean.numel())
+    assert all(t.dtype == torch.float64 for t in (x, mean, wt, out)) and 0 <= n <= B and row0 >= 0 and x.shape[0] >= B and x.shape[1] >= D
+    assert wt.shape[0] >= D and wt.shape[1] >= D and out.is_contiguous() and out.shape[1] == FEAT_COLS and row0 + n <= out.shape[0]
+    a = FeatMahaArgs()
+    a.B, a.n, a.row0, a.D, a.pad = int(B), int(n), int(row0), D, 0
+    a.x, a.ld_x = _rows(x)
+    a.wt, a.ld_w = _rows(wt)
+    a.mean, a.out = ptr(mean), ptr(out)
+    _chk(feat_lib().urso_feat_maha(C.byref(a), stream_ptr(stream)), "urso_feat_maha")
 
 
 def grad_accum(n, g, acc, first, stream=None):

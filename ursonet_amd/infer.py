@@ -8,7 +8,8 @@ device" and "this batch's rows are in the table".  A command builds one PosePass
     urso_pose_decode, DEC columns) decodes every head and writes one fp64 row per image into a device table of the caller's.
 The two kernels share their device routines, so LOC_EST / Q_EST are the same bits whichever command produced them.  With views
 (ursonet_amd/views.py: predict / evaluate, views=...) fuse_batch() takes the place of the three: it runs the batch once per view, warped
-on the device, decodes every view into a table of the pass's and ends with one urso_pose_fuse_views into the caller's table.  Nothing here
+on the device, decodes every view into a table of the pass's and ends with one urso_pose_fuse_views into the caller's table.  With a
+domain (ursonet_amd/domain.py) domain_scores() pools the batch's bottleneck features and scores them behind run().  Nothing here
 synchronises or reads back, and torch, hip and the engine are touched only after check_heads() has passed (no GPU is needed to be
 refused).  The commands own their feeders, tables, GMM buffers, result types, prints, files and pictures.
 """
@@ -94,12 +95,18 @@ class PosePass(object):
     """The per-call state of the pass: cfg, eng, B, dev, the head modes and, on the device, the bin maps loc_map (fp64) and hq (fp32),
     q_soft [B,4] and, with scatter=True, urso_quat_wavg_decode's scatter matrices [B,16].  `who`: the command, for check_heads' messages."""
 
-    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate", views=None, calibration=None, conformal=None):
+    def __init__(self, model, dataset, multimodal=False, scatter=False, who="evaluate", views=None, calibration=None, conformal=None,
+                 domain=None):
         """views: a views.ViewSet with its homographies (with_camera), for fuse_batch().  calibration: a calibrate.Calibration whose
         inverse temperatures heads() applies to the classification heads' logits (urso_temp_scale into buffers of the pass's: the engine's
         outputs stay as they are); None, or a head whose beta is None: nothing is launched for it.  conformal: a conformal.Conformal whose
-        levels bounds() applies behind the decode (urso_conf_bound per classification head into tables of the pass's); None: nothing."""
+        levels bounds() applies behind the decode (urso_conf_bound per classification head into tables of the pass's); None: nothing.
+        domain: a domain.Domain whose statistics domain_scores() applies behind run() (urso_feat_pool and urso_feat_maha into a table of
+        the pass's); None: nothing."""
         self.soft = check_heads(model, dataset, multimodal, who)
+        self.domain, self.dom = domain, None
+        if domain is not None:
+            domain.check_model(model, who=who)
         self.conformal, self.conf = conformal, None
         if conformal is not None:
             from .ensemble import head_bins
@@ -207,6 +214,21 @@ class PosePass(object):
     def conformal_tables(self, N):
         """{head: (score rows or None, bound rows)} of the classification heads on the host ({} where no batch ran)."""
         return {} if self.conf is None else self.conf.tables(N)
+
+    def domain_scores(self, table, n, row0):
+        """With a domain: behind run(), the feature rows of the n valid images (urso_feat_pool on Engine.features()) and their scores
+        against the domain (urso_feat_maha) into rows [row0, row0 + n) of a table of the pass's (as many rows as `table`).
+        domain_table() reads it, once, at the end."""
+        if self.domain is None:
+            return
+        if self.dom is None:
+            from .domain import DomainPass
+            self.dom = DomainPass(self, table.shape[0], self.domain)
+        self.dom.launch(n, row0)
+
+    def domain_table(self, N):
+        """The score rows [N, FEAT_COLS] on the host (no rows where no batch ran)."""
+        return np.zeros((0, 4)) if self.dom is None else self.dom.table(N)
 
     def fuse_batch(self, table, bt):
         """The rows [bt.row0, bt.row0 + bt.n) of a FUSE table: the feeder batch bt once per view through the network -- the identity view

@@ -16,6 +16,7 @@ import numpy as np
 
 from .calibrate import check_calibration
 from .conformal import bound_fields, check_conformal, no_bound_fields
+from .domain import check_domain, domain_fields, no_domain_fields
 from .ensemble import EnsemblePass, Members, no_member_fields, predict_fields
 from .infer import PosePass, dec_columns, fuse_columns, loader_workers
 
@@ -37,12 +38,18 @@ class PredictResult(object):
     information: the epistemic part).  Without members all of these are None.
     With conformal (a conformal.Conformal; conformal_tables: the pass's bound rows): ori_bound (degrees) and loc_bound (metres), the
     error bounds that hold with probability 1 - alpha, and for a classification head ori_region_bins / loc_region_bins (the bins inside the
-    bound) and ori_region_mass / loc_region_mass (their PMF mass); None for a regression head, whose bound is a constant.  Without: None."""
+    bound) and ori_region_mass / loc_region_mass (their PMF mass); None for a regression head, whose bound is a constant.  Without: None.
+    With domain (a domain.Domain; domain_table: the pass's score rows): domain_score (the squared Mahalanobis distance of the image's
+    pooled bottleneck features to the source domain), domain_dist2 (the squared Euclidean distance to its mean), domain_zmax / domain_zarg
+    (the largest whitened component and its index) and domain_p (the conformal p-value against the domain's holdout scores; None without
+    a holdout).  Without: None."""
 
-    def __init__(self, image_ids, table, loc_class, soft, gmm=None, fused=False, *, ensemble=None, conformal=None, conformal_tables=None):
+    def __init__(self, image_ids, table, loc_class, soft, gmm=None, fused=False, *, ensemble=None, conformal=None, conformal_tables=None,
+                 domain=None, domain_table=None):
         self.loc_spread = self.ori_spread = self.view_lambda = self.n_views = None
         no_member_fields(self)
         no_bound_fields(self)
+        no_domain_fields(self)
         if ensemble is not None:
             predict_fields(self, ensemble, loc_class, soft)
         elif fused:
@@ -54,10 +61,12 @@ class PredictResult(object):
         self.modes, self.mode_priors, self.n_modes = gmm if gmm is not None else (None, None, None)
         if conformal is not None:
             bound_fields(self, conformal, conformal_tables, len(self.image_ids))
+        if domain is not None:
+            domain_fields(self, domain, domain_table)
 
 
 def predict(model, dataset, multimodal=False, workers=None, cache=None, views=None, members=None, max_gb=16, calibration=None,
-            conformal=None):
+            conformal=None, domain=None):
     """Pose estimates of every image of `dataset` -> PredictResult.  The dataset needs image_ids, load_image, image_info and, for
     the classification heads, histogram_3D_map / ori_histogram_map; no label loader is called.  multimodal=True (soft
     classification only) also fits up to three orientation modes per image (urso_quat_gmm_fit: var = (BETA / ORI_BINS_PER_DIM)^2 /
@@ -79,9 +88,14 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     conformal: a conformal.Conformal (from conformal() or Conformal.load()): behind the decode, urso_conf_bound gives every image the
     smallest ball around its estimate that holds more than the fitted level of the head's PMF mass: ori_bound / loc_bound and the region
     fields (a regression head gets its constant).  ValueError: with members or views, under calibration betas other than the ones the
-    levels were fitted under (the message names both), bin counts that do not fit the model.  None: nothing is launched."""
+    levels were fitted under (the message names both), bin counts that do not fit the model.  None: nothing is launched.
+    domain: a domain.Domain (from fit_domain() or Domain.load()): behind each batch's forward pass urso_feat_pool and urso_feat_maha
+    give every image its squared Mahalanobis distance to the source domain's feature statistics: domain_score, domain_dist2,
+    domain_zmax, domain_zarg, domain_p.  Works with calibration and conformal.  ValueError: with members or views, under a data-parallel
+    launcher, a model of another feature geometry.  None: nothing is launched, the code of before bit for bit."""
     check_calibration(calibration, members, "predict")
     check_conformal(conformal, members, views, calibration, "predict")
+    check_domain(domain, members, views, "predict")
     if members is not None:
         ms = Members(members, views, "predict")
         out, _dt = EnsemblePass(model, dataset, ms, multimodal, False, "predict", workers, cache, max_gb).run()
@@ -92,7 +106,8 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     if views is not None:
         from .views import ViewSet
         vs = ViewSet(views, multimodal, "predict").with_camera(dataset, model.config)
-    ps = PosePass(model, dataset, multimodal, scatter=vs is None, who="predict", views=vs, calibration=calibration, conformal=conformal)
+    ps = PosePass(model, dataset, multimodal, scatter=vs is None, who="predict", views=vs, calibration=calibration, conformal=conformal,
+                  domain=domain)
     from . import hip
     from .feeder import EvalFeeder
     ids = list(dataset.image_ids)
@@ -106,6 +121,7 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
                 ps.fuse_batch(table, bt)
                 continue
             ps.run(bt.images)
+            ps.domain_scores(table, bt.n, bt.row0)
             rows = [t[bt.row0:bt.row0 + bt.n] for t in gmm] if multimodal else None
             heads = ps.heads(bt.n, rows)
             ps.decode_into(table, bt.n, bt.row0, heads)
@@ -115,4 +131,5 @@ def predict(model, dataset, multimodal=False, workers=None, cache=None, views=No
     host = table[:N].cpu().numpy()                                               # the one read of the table
     fit = tuple(gmm[i][:N].cpu().numpy() for i in (0, 2, 4)) if multimodal else None      # mean, prior, n_modes
     return PredictResult(ids, host, ps.loc_class, ps.soft, fit, fused=vs is not None, conformal=conformal,
-                         conformal_tables=ps.conformal_tables(N) if conformal is not None else None)
+                         conformal_tables=ps.conformal_tables(N) if conformal is not None else None, domain=domain,
+                         domain_table=ps.domain_table(N) if domain is not None else None)
