@@ -1,4 +1,4 @@
-"""Builds liburso_hip.so, the extension library liburso_ext.so, the optimizer library liburso_opt.so, the training library liburso_train.so, the inference library liburso_infer.so and the feature library liburso_feat.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
+"""Builds liburso_hip.so, the extension library liburso_ext.so, the optimizer library liburso_opt.so, the training library liburso_train.so, the inference library liburso_infer.so, the feature library liburso_feat.so and the explanation library liburso_explain.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
 import os
 import subprocess
 import sys
@@ -36,6 +36,11 @@ INFER_SOURCES = ["conformal.hip"]
 CSRC_FEAT = os.path.join(HERE, "csrc_feat")
 FEAT_LIB = os.path.join(LIBDIR, "liburso_feat.so")
 FEAT_SOURCES = ["feat.hip"]
+# The explanation library (include/ursonet_explain.h): occlusion-sensitivity maps (ursonet_amd/explain.py); liburso_feat.so's surface was pinned
+# to its three names.  Built and loaded as the other five.
+CSRC_EXPLAIN = os.path.join(HERE, "csrc_explain")
+EXPLAIN_LIB = os.path.join(LIBDIR, "liburso_explain.so")
+EXPLAIN_SOURCES = ["explain.hip"]
 
 
 def _hipcc():
@@ -111,6 +116,11 @@ def feat_source_hash():
     return _side_source_hash(CSRC_FEAT, FEAT_SOURCES)
 
 
+def explain_source_hash():
+    """source_hash() of the explanation library."""
+    return _side_source_hash(CSRC_EXPLAIN, EXPLAIN_SOURCES)
+
+
 def _stale(lib, digest):
     if not os.path.exists(lib):
         return True
@@ -126,11 +136,11 @@ def needs_build():
     checkout or a snapshot push; a .so shipped without its hash file is rebuilt where a compiler exists and trusted where none does).
     True if any of the libraries is stale."""
     return (_stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash) or _stale(OPT_LIB, opt_source_hash) or _stale(TRAIN_LIB, train_source_hash) or
-            _stale(INFER_LIB, infer_source_hash) or _stale(FEAT_LIB, feat_source_hash))
+            _stale(INFER_LIB, infer_source_hash) or _stale(FEAT_LIB, feat_source_hash) or _stale(EXPLAIN_LIB, explain_source_hash))
 
 
 def build(force=False, verbose=True):
-    """Compile every HIP source for gfx950 and link the six shared libraries, each only if it is stale (no GPU needed)."""
+    """Compile every HIP source for gfx950 and link the seven shared libraries, each only if it is stale (no GPU needed)."""
     os.makedirs(LIBDIR, exist_ok=True)
     if force or _stale(LIB, source_hash):
         _compile_and_link(LIB, CSRC, SOURCES, FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split(), ("_" + VARIANT) if VARIANT else "", source_hash, verbose)
@@ -144,6 +154,8 @@ def build(force=False, verbose=True):
         _compile_and_link(INFER_LIB, CSRC_INFER, INFER_SOURCES, FLAGS, "_infer", infer_source_hash, verbose)
     if force or _stale(FEAT_LIB, feat_source_hash):
         _compile_and_link(FEAT_LIB, CSRC_FEAT, FEAT_SOURCES, FLAGS, "_feat", feat_source_hash, verbose)
+    if force or _stale(EXPLAIN_LIB, explain_source_hash):
+        _compile_and_link(EXPLAIN_LIB, CSRC_EXPLAIN, EXPLAIN_SOURCES, FLAGS, "_explain", explain_source_hash, verbose)
     return LIB
 
 
@@ -173,4 +185,4 @@ def _compile_and_link(lib, srcdir, sources, flags, tag, digest, verbose):
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
-    print("built", LIB, EXT_LIB, OPT_LIB, TRAIN_LIB, INFER_LIB, FEAT_LIB)
+    print("built", LIB, EXT_LIB, OPT_LIB, TRAIN_LIB, INFER_LIB, FEAT_LIB, EXPLAIN_LIB)

@@ -17,6 +17,7 @@ OPT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_opt.so")          # the optim
 TRAIN_LIB_PATH = os.path.join(_HERE, "lib", "liburso_train.so")      # the training library (include/ursonet_train.h): loaded on first use
 INFER_LIB_PATH = os.path.join(_HERE, "lib", "liburso_infer.so")      # the inference library (include/ursonet_infer.h): loaded on first use
 FEAT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_feat.so")        # the feature library (include/ursonet_feat.h): loaded on first use
+EXPLAIN_LIB_PATH = os.path.join(_HERE, "lib", "liburso_explain.so")  # the explanation library (include/ursonet_explain.h): loaded on first use
 
 F32, BF16, F16 = 0, 1, 2
 EPI_RELU, EPI_OUT_F32, EPI_MASK_BITS, EPI_EMIT_BITS, EPI_ADD_SRCGRID = 1, 2, 4, 8, 16
@@ -200,6 +201,32 @@ class FeatMahaArgs(C.Structure):
 # urso_feat_* sizes and table columns (include/ursonet_feat.h)
 FEAT_MAX_D, FEAT_COLS, FEAT_MAHA_ROWS = 4096, 4, 8
 FEAT_SCORE, FEAT_DIST2, FEAT_ZMAX, FEAT_ZARG = range(4)
+# urso_occl_* sizes and table columns (include/ursonet_explain.h): a head's KL, TV, DROP and ARGMAX are four columns in that order
+OCCL_COLS, OCCL_MAX_MAPS = 10, 8
+OCCL_D_ORI, OCCL_D_LOC, OCCL_ORI_KL, OCCL_ORI_TV, OCCL_ORI_DROP, OCCL_ORI_ARGMAX, OCCL_LOC_KL, OCCL_LOC_TV, OCCL_LOC_DROP, OCCL_LOC_ARGMAX = range(10)
+
+
+class OcclFillArgs(C.Structure):
+    """urso_occl_fill_args (include/ursonet_explain.h): one frame into n occluded rows of a batch."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "n", "H", "W", "C")] + [("fill", C.c_uint8 * 4)] + [(n, C.c_void_p) for n in ("src", "rects", "out")])
+
+
+class OcclScoreArgs(C.Structure):
+    """urso_occl_score_args (include/ursonet_explain.h): a batch's DEC rows and logits against the baseline's."""
+    _fields_ = ([("B", C.c_int32), ("n", C.c_int32), ("row0", C.c_int64)] + [(n, C.c_int32) for n in ("ori_K", "ori_ld", "loc_K", "loc_ld")] +
+                [(n, C.c_void_p) for n in ("dec0", "dec", "ori_z0", "ori_z", "loc_z0", "loc_z", "out")])
+
+
+class OcclSplatArgs(C.Structure):
+    """urso_occl_splat_args (include/ursonet_explain.h): chosen columns of a patch-score table into per-pixel maps of a window."""
+    _fields_ = ([(n, C.c_int32) for n in ("P", "M", "wy0", "wx0", "h", "w")] + [("cols", C.c_int32 * OCCL_MAX_MAPS), ("ld", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("scores", "rects", "out")])
+
+
+class HeatOverlayArgs(C.Structure):
+    """urso_heat_overlay_args (include/ursonet_explain.h): one map blended through a colour table onto a window of a picture."""
+    _fields_ = ([(n, C.c_int32) for n in ("h", "w", "alpha", "pad")] + [("ld_img", C.c_int64), ("lo", C.c_double), ("scale", C.c_double)] +
+                [(n, C.c_void_p) for n in ("map", "lut", "img")])
 
 
 class DenseWgradLayer(C.Structure):
@@ -402,6 +429,15 @@ _FEAT_SIGS = {
     "urso_feat_maha": (_i, [C.POINTER(FeatMahaArgs), _vp]),
 }
 FEAT_SYMBOLS = sorted(_FEAT_SIGS)
+# the explanation library liburso_explain.so, include/ursonet_explain.h: bound by explain_lib() on first use
+_EXPLAIN_SIGS = {
+    # occlusion sensitivity (ursonet_amd/explain.py): urso_occl_fill_args* | urso_occl_score_args* | urso_occl_splat_args* | urso_heat_overlay_args*
+    "urso_occl_fill_u8": (_i, [C.POINTER(OcclFillArgs), _vp]),
+    "urso_occl_score": (_i, [C.POINTER(OcclScoreArgs), _vp]),
+    "urso_occl_splat": (_i, [C.POINTER(OcclSplatArgs), _vp]),
+    "urso_heat_overlay_u8": (_i, [C.POINTER(HeatOverlayArgs), _vp]),
+}
+EXPLAIN_SYMBOLS = sorted(_EXPLAIN_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
 SWA_STATE = 8                                                         # URSO_SWA_STATE int32s (ursonet_amd/swa.py names the fields)
 
@@ -498,6 +534,23 @@ def feat_lib():
         _bind(lib, _FEAT_SIGS)
         _feat = lib
     return _feat
+
+
+_explain = None
+
+
+def explain_lib():
+    """liburso_explain.so, loaded and bound on first use, behind the main library as feat_lib() loads its own."""
+    global _explain
+    if _explain is None:
+        if not os.path.exists(EXPLAIN_LIB_PATH):
+            raise ImportError("liburso_explain.so not found at %s -- build it with `python -m ursonet_amd.build` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % EXPLAIN_LIB_PATH)
+        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
+        lib = C.CDLL(EXPLAIN_LIB_PATH)
+        _bind(lib, _EXPLAIN_SIGS)
+        _explain = lib
+    return _explain
 
 
 def last_error():
@@ -1216,6 +1269,73 @@ def feat_maha(B, n, row0, x, mean, wt, out, stream=None):
     a.wt, a.ld_w = _rows(wt)
     a.mean, a.out = ptr(mean), ptr(out)
     _chk(feat_lib().urso_feat_maha(C.byref(a), stream_ptr(stream)), "urso_feat_maha")
+
+
+def occl_fill_u8(src, rects, fill, out, n=None, stream=None):
+    """urso_occl_fill_u8 (liburso_explain.so): rows 0 .. n - 1 (default: one per rect) of out (uint8 [B, H, W, C], contiguous) become src
+    (uint8 [H, W, C], contiguous, outside out) with rect j (int32 [>= n, 4] on the device: y0, x0, y1, x1) painted with fill[:C]; rows >= n
+    stay (ursonet_amd.explain.occlude_host)."""
+    n = int(rects.shape[0]) if n is None else int(n)
+    assert src.dtype == out.dtype == torch.uint8 and rects.dtype == torch.int32 and src.dim() == 3 and out.dim() == 4
+    assert tuple(out.shape[1:]) == tuple(src.shape) and rects.dim() == 2 and rects.shape[1] == 4 and 0 <= n <= min(out.shape[0], rects.shape[0])
+    a = OcclFillArgs()
+    a.B, a.n, (a.H, a.W, a.C) = int(out.shape[0]), n, (int(v) for v in src.shape)
+    for c, v in enumerate(list(fill)[:4]):
+        a.fill[c] = int(v)
+    a.src, a.rects, a.out = ptr(src), ptr(rects), ptr(out)
+    _chk(explain_lib().urso_occl_fill_u8(C.byref(a), stream_ptr(stream)), "urso_occl_fill_u8")
+
+
+def occl_score(B, n, row0, dec0, dec, out, ori_z0=None, ori_z=None, loc_z0=None, loc_z=None, stream=None):
+    """urso_occl_score (liburso_explain.so): table rows [row0, row0 + n) of dec (fp64 [rows, DEC_COLS]) against the baseline's DEC row dec0
+    (fp64 [DEC_COLS]) and, per classification head given, the batch's logits z (fp32 [>= n, >= K], contiguous rows) against the
+    baseline's z0 (fp32 [K]) into the same rows of out (fp64 [rows, OCCL_COLS]) (ursonet_amd.explain.score64).  Columns of an absent head
+    keep what they held."""
+    assert dec0.dtype == dec.dtype == out.dtype == torch.float64 and dec0.numel() == DEC_COLS and dec.shape[1] == DEC_COLS and out.shape[1] == OCCL_COLS
+    assert 0 <= n <= B and row0 >= 0 and row0 + n <= min(dec.shape[0], out.shape[0])
+    a = OcclScoreArgs()
+    a.B, a.n, a.row0 = int(B), int(n), int(row0)
+    for head, z0, z in (("ori", ori_z0, ori_z), ("loc", loc_z0, loc_z)):
+        assert (z0 is None) == (z is None), "a head is its baseline logits and the batch's"
+        K = 0
+        if z0 is not None:
+            K = int(z0.numel())
+            assert z0.dtype == z.dtype == torch.float32 and z.shape[0] >= n and z.shape[1] >= K
+        zp, ld = _rows(z)
+        setattr(a, head + "_K", K)
+        setattr(a, head + "_ld", int(ld))
+        setattr(a, head + "_z0", ptr(z0))
+        setattr(a, head + "_z", zp)
+    a.dec0, a.dec, a.out = ptr(dec0), ptr(dec), ptr(out)
+    _chk(explain_lib().urso_occl_score(C.byref(a), stream_ptr(stream)), "urso_occl_score")
+
+
+def occl_splat(scores, cols, rects, window, out, stream=None):
+    """urso_occl_splat (liburso_explain.so): the columns `cols` of scores (fp64 [>= P, ld], contiguous rows) of the P patches rects (int32
+    [P, 4] on the device) into out (fp64 [M, h, w], contiguous), the maps of the window (y0, x0, y1, x1) (ursonet_amd.explain.splat64)."""
+    wy0, wx0, wy1, wx1 = (int(v) for v in window)
+    cols = [int(c) for c in cols]
+    assert scores.dtype == out.dtype == torch.float64 and rects.dtype == torch.int32 and rects.dim() == 2 and rects.shape[1] == 4
+    assert tuple(out.shape) == (len(cols), wy1 - wy0, wx1 - wx0) and scores.shape[0] >= rects.shape[0] and 1 <= len(cols) <= OCCL_MAX_MAPS
+    a = OcclSplatArgs()
+    a.P, a.M, a.wy0, a.wx0, a.h, a.w = int(rects.shape[0]), len(cols), wy0, wx0, wy1 - wy0, wx1 - wx0
+    for m, c in enumerate(cols):
+        a.cols[m] = c
+    a.scores, a.ld = _rows(scores)
+    a.rects, a.out = ptr(rects), ptr(out)
+    _chk(explain_lib().urso_occl_splat(C.byref(a), stream_ptr(stream)), "urso_occl_splat")
+
+
+def heat_overlay_u8(heat, lo, scale, lut, alpha, img, stream=None):
+    """urso_heat_overlay_u8 (liburso_explain.so): heat (fp64 [h, w], contiguous) through lut (uint8 [256, 3]) onto img (uint8 [h, w, 3], the
+    pixels of a row contiguous, any row stride) in place, at weight alpha / 256 (ursonet_amd.explain.overlay_host)."""
+    h, w = (int(v) for v in heat.shape)
+    assert heat.dtype == torch.float64 and lut.dtype == img.dtype == torch.uint8 and tuple(lut.shape) == (256, 3) and tuple(img.shape) == (h, w, 3)
+    assert img.is_cuda and img.stride(2) == 1 and img.stride(1) == 3, "expected a device picture whose rows are contiguous"
+    a = HeatOverlayArgs()
+    a.h, a.w, a.alpha, a.pad, a.ld_img, a.lo, a.scale = h, w, int(alpha), 0, int(img.stride(0)), float(lo), float(scale)
+    a.map, a.lut, a.img = ptr(heat), ptr(lut), img.data_ptr()
+    _chk(explain_lib().urso_heat_overlay_u8(C.byref(a), stream_ptr(stream)), "urso_heat_overlay_u8")
 
 
 def grad_accum(n, g, acc, first, stream=None):
