@@ -237,8 +237,8 @@ def test_argument_validation_without_gpu():
     """Every refusal of the three entry points.  Device pointers are made up and never dereferenced: each call is refused before the
     copy of the table or the launch."""
     import ursonet_amd.hip as hip
-    lib = hip.train_lib()
-    assert {"urso_bn_recal_plan", "urso_bn_recal_add", "urso_bn_recal_settle"} <= set(hip.TRAIN_SYMBOLS)
+    lib = hip.side_lib("train")
+    assert {"urso_bn_recal_plan", "urso_bn_recal_add", "urso_bn_recal_settle"} <= set(hip.SIDE_SYMBOLS["train"])
     assert ctypes.sizeof(hip.BnRecalLayer) == 48
     BM, BV, TAB, ACC, ST = (0x100000 * k for k in range(1, 6))
 

@@ -160,7 +160,7 @@ def test_the_plan_call_refuses_before_any_launch():
         with pytest.raises(hip.UrsoHipError, match="urso_bn_recal_plan: .*" + msg):
             hip.BnRecalPlan(layers, n, "cuda")
     # null and misaligned pointers, N <= 0: the raw call (a tensor cannot express them)
-    lib = hip.train_lib()
+    lib = hip.side_lib("train")
     tab = torch.zeros(6, dtype=torch.int64, device="cuda")
     for fields, msg in ((dict(bmean=None), "null"), (dict(bvar=None), "null"), (dict(bmean=m.data_ptr() + 2), "4-byte aligned"),
                         (dict(bvar=v.data_ptr() + 1), "4-byte aligned"), (dict(N=0), "N must be > 0"), (dict(N=-1), "N must be > 0")):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import tempref as R
+from libsurface import header_symbols
 from ursonet_amd import calibrate as Cal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -226,31 +227,17 @@ assert "torch" not in sys.modules and "ursonet_amd.hip" not in sys.modules and "
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
 def test_header_bindings_and_library_agree():
     import ursonet_amd.hip as hip
     from ursonet_amd import build
-    names, txt = _header_symbols()
-    assert names == set(hip.TRAIN_SYMBOLS) and TEMP_NAMES <= names and len(names) == 13
+    names, txt = header_symbols(HEADER)
+    assert names == set(hip.SIDE_SYMBOLS["train"]) and TEMP_NAMES <= names and len(names) == 13
+    assert "calibrate.hip" in build.SIDE_SOURCES["train"]
     for macro, v in (("MAX_J", Cal.MAX_J), ("COLS", Cal.COLS), ("TOTALS", Cal.TOTALS), ("SY", Cal.SY), ("YZ", Cal.YZ), ("LSE", Cal.LSE),
                      ("M1", Cal.M1), ("VAR", Cal.VAR)):
         assert re.search(r"#define\s+URSO_TEMP_%s\s+%d\b" % (macro, v), txt), macro
         assert getattr(hip, "TEMP_" + macro) == v
     assert Cal.COLS == 2 + 3 * Cal.MAX_J and len(Cal.GRID) == Cal.MAX_J and Cal.GRID[3] == 1.0
-    lib = hip.train_lib()                                                    # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in names)
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.TRAIN_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (urso_\w+)$", out, re.M)) == names
-    assert "calibrate.hip" in build.TRAIN_SOURCES and os.path.exists(os.path.join(build.CSRC_TRAIN, "calibrate.hip"))
-    assert sorted(os.listdir(build.CSRC_TRAIN)) == sorted(build.TRAIN_SOURCES)
-    for other in (hip.LIB_PATH, hip.EXT_LIB_PATH, hip.OPT_LIB_PATH):
-        sym = subprocess.run(["nm", "-D", "--defined-only", other], capture_output=True, text=True, check=True).stdout
-        assert not TEMP_NAMES & set(re.findall(r" T (urso_\w+)$", sym, re.M)), other
-    assert TEMP_NAMES.isdisjoint(hip.EXPORTED_SYMBOLS) and TEMP_NAMES.isdisjoint(hip.EXT_SYMBOLS) and TEMP_NAMES.isdisjoint(hip.OPT_SYMBOLS)
     # the argument structs are the header's: field order and sizes
     assert [f[0] for f in hip.TempStatsArgs._fields_] == ["B", "n", "row0", "K", "ld_z", "ld_y", "J", "beta", "logits", "target", "out"]
     assert [f[0] for f in hip.TempReduceArgs._fields_] == ["N", "J", "pad", "beta", "rows", "totals"]
@@ -263,7 +250,7 @@ def test_argument_validation_without_gpu():
     """Every refusal of the three entry points.  Device pointers are made up and never dereferenced: each call is refused before a
     launch, or has n = 0 and launches nothing."""
     import ursonet_amd.hip as hip
-    lib = hip.train_lib()
+    lib = hip.side_lib("train")
     Z, Y, O, T = (0x1000000 * k for k in range(1, 5))
 
     def fill(a, base, kw):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import confref as R
+from libsurface import header_symbols
 from ursonet_amd import conformal as Cf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,35 +220,16 @@ assert "torch" not in sys.modules and "ursonet_amd.hip" not in sys.modules and "
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
-def _defined(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return set(re.findall(r" T (urso_\w+)$", out, re.M))
-
-
 def test_header_bindings_and_library_agree():
     import ursonet_amd.hip as hip
     from ursonet_amd import build
-    names, txt = _header_symbols()
-    assert names == set(hip.INFER_SYMBOLS) == CONF_NAMES
+    names, txt = header_symbols(HEADER)
+    assert names == set(hip.SIDE_SYMBOLS["infer"]) == CONF_NAMES and build.SIDE_SOURCES["infer"] == ["conformal.hip"]
     for macro, v in (("SHIFT", Cf.SHIFT), ("MAX_K", Cf.MAX_K), ("COLS", Cf.COLS), ("ANGLE", Cf.ANGLE), ("EUCLID", Cf.EUCLID), ("SCORE", Cf.SCORE),
                      ("C", Cf.C_MASS), ("W", Cf.W_SUM), ("KEY_REF", Cf.KEY_REF), ("ERR", Cf.ERR), ("NEAR", Cf.NEAR), ("BOUND", Cf.BOUND),
                      ("KEY", Cf.KEY), ("MASS", Cf.MASS), ("COUNT", Cf.COUNT), ("BW", Cf.BOUND_W), ("DIGIT", 11), ("PASSES", 6)):
         assert re.search(r"#define\s+URSO_CONF_%s\s+%d\b" % (macro, v), txt), macro
         assert getattr(hip, "CONF_" + macro) == v
-    lib = hip.infer_lib()                                                    # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in names)
-    assert _defined(hip.INFER_LIB_PATH) == names
-    assert build.INFER_SOURCES == ["conformal.hip"] and sorted(os.listdir(build.CSRC_INFER)) == sorted(build.INFER_SOURCES)
-    assert os.path.basename(build.INFER_LIB) == "liburso_infer.so" == os.path.basename(hip.INFER_LIB_PATH)
-    for other in (hip.LIB_PATH, hip.EXT_LIB_PATH, hip.OPT_LIB_PATH, hip.TRAIN_LIB_PATH):
-        assert not CONF_NAMES & _defined(other), other
-    for table in (hip.EXPORTED_SYMBOLS, hip.EXT_SYMBOLS, hip.OPT_SYMBOLS, hip.TRAIN_SYMBOLS):
-        assert CONF_NAMES.isdisjoint(table)
     # the argument structs are the header's: field order and sizes
     assert [f[0] for f in hip.ConfScoreArgs._fields_] == ["B", "n", "row0", "K", "ld_z", "metric", "ld_est", "ld_ref", "pad", "logits", "map",
                                                           "est", "ref", "out"]
@@ -258,20 +240,6 @@ def test_header_bindings_and_library_agree():
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), txt, re.S).group(1)
         declared = re.findall(r"\b(\w+)\s*[,;]", re.sub(r"\b(const|int32_t|int64_t|float|double|void)\b|\*", " ", body))
         assert declared == [f[0] for f in fields], struct
-
-
-def test_the_build_knows_the_fifth_library(monkeypatch, tmp_path):
-    import ursonet_amd.hip as hip
-    from ursonet_amd import build
-    with open(build.INFER_LIB + ".srchash") as fh:
-        assert fh.read().strip() == build.infer_source_hash()                  # as built: the stamp is the hash of the sources
-    assert not build.needs_build()
-    monkeypatch.setattr(build, "INFER_LIB", str(tmp_path / "liburso_infer.so"))
-    assert build.needs_build()                                               # a missing fifth library makes the build stale
-    monkeypatch.setattr(hip, "_infer", None)
-    monkeypatch.setattr(hip, "INFER_LIB_PATH", str(tmp_path / "liburso_infer.so"))
-    with pytest.raises(ImportError, match="liburso_infer.so not found"):
-        hip.infer_lib()
 
 
 def test_header_is_plain_c99(tmp_path):
@@ -289,7 +257,7 @@ def test_argument_validation_without_gpu():
     """Every refusal of the two entry points.  Device pointers are made up and never dereferenced: each call is refused before a launch,
     or has n = 0 and launches nothing."""
     import ursonet_amd.hip as hip
-    lib = hip.infer_lib()
+    lib = hip.side_lib("infer")
     Z, M, E, RF, O = (0x1000000 * k for k in range(1, 6))
 
     def fill(a, base, kw):

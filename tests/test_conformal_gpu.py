@@ -171,7 +171,7 @@ def test_refusals_launch_nothing():
     z, m, est, ref = R.case(K, metric)
     case = _Case(K, metric, 9, 8, 0, K + 1, 1).load(z, m, est, ref)
     case.out.fill_(NAN)
-    lib = hip.infer_lib()
+    lib = hip.side_lib("infer")
 
     def args(cls, **kw):
         a = cls()

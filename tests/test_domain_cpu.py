@@ -16,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+from libsurface import header_symbols
 from ursonet_amd import domain as Dm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -301,34 +302,15 @@ assert sys.modules["torch"] is None and "ursonet_amd.hip" not in sys.modules and
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
-def _defined(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return set(re.findall(r" T (urso_\w+)$", out, re.M))
-
-
 def test_header_bindings_and_library_agree():
     import ursonet_amd.hip as hip
     from ursonet_amd import build
-    names, txt = _header_symbols()
-    assert names == set(hip.FEAT_SYMBOLS) == FEAT_NAMES
+    names, txt = header_symbols(HEADER)
+    assert names == set(hip.SIDE_SYMBOLS["feat"]) == FEAT_NAMES and build.SIDE_SOURCES["feat"] == ["feat.hip"]
     for macro, v in (("MAX_D", Dm.MAX_D), ("COLS", Dm.COLS), ("MAHA_ROWS", Dm.MAHA_ROWS), ("SCORE", Dm.SCORE), ("DIST2", Dm.DIST2),
                      ("ZMAX", Dm.ZMAX), ("ZARG", Dm.ZARG)):
         assert re.search(r"#define\s+URSO_FEAT_%s\s+%d\b" % (macro, v), txt), macro
         assert getattr(hip, "FEAT_" + macro) == v
-    lib = hip.feat_lib()                                                     # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in names)
-    assert _defined(hip.FEAT_LIB_PATH) == names
-    assert build.FEAT_SOURCES == ["feat.hip"] and sorted(os.listdir(build.CSRC_FEAT)) == sorted(build.FEAT_SOURCES)
-    assert os.path.basename(build.FEAT_LIB) == "liburso_feat.so" == os.path.basename(hip.FEAT_LIB_PATH)
-    for other in (hip.LIB_PATH, hip.EXT_LIB_PATH, hip.OPT_LIB_PATH, hip.TRAIN_LIB_PATH, hip.INFER_LIB_PATH):
-        assert not FEAT_NAMES & _defined(other), other
-    for table in (hip.EXPORTED_SYMBOLS, hip.EXT_SYMBOLS, hip.OPT_SYMBOLS, hip.TRAIN_SYMBOLS, hip.INFER_SYMBOLS):
-        assert FEAT_NAMES.isdisjoint(table)
     # the argument structs are the header's: field order and sizes
     fields = {"urso_feat_pool_args": (hip.FeatPoolArgs, ["B", "n", "row0", "h", "w", "C", "gh", "gw", "dtype", "ld", "act", "out"], 64),
               "urso_feat_gram_args": (hip.FeatGramArgs, ["B", "n", "row0", "D", "pad", "ld_x", "ld_g", "x", "centre", "s", "g"], 72),
@@ -339,21 +321,6 @@ def test_header_bindings_and_library_agree():
         declared = re.findall(r"\b(\w+)\s*[,;]", re.sub(r"\b(const|int32_t|int64_t|float|double|void)\b|\*", " ", body))
         assert declared == order, struct
     assert hip.FeatPoolArgs.ld.offset == 40 and hip.FeatPoolArgs.act.offset == 48 and hip.FeatGramArgs.ld_x.offset == 24 and hip.FeatMahaArgs.x.offset == 40
-
-
-def test_the_build_knows_the_sixth_library(monkeypatch, tmp_path):
-    import ursonet_amd.hip as hip
-    from ursonet_amd import build
-    with open(build.FEAT_LIB + ".srchash") as fh:
-        assert fh.read().strip() == build.feat_source_hash()                   # as built: the stamp is the hash of the sources
-    assert not build.needs_build()
-    assert "-ffp-contract=off" in build.FLAGS
-    monkeypatch.setattr(build, "FEAT_LIB", str(tmp_path / "liburso_feat.so"))
-    assert build.needs_build()                                               # a missing sixth library makes the build stale
-    monkeypatch.setattr(hip, "_feat", None)
-    monkeypatch.setattr(hip, "FEAT_LIB_PATH", str(tmp_path / "liburso_feat.so"))
-    with pytest.raises(ImportError, match="liburso_feat.so not found"):
-        hip.feat_lib()
 
 
 def test_header_is_plain_c99(tmp_path):
@@ -372,7 +339,7 @@ def test_argument_validation_without_gpu():
     """Every refusal of the three entry points.  Device pointers are made up and never dereferenced: each call is refused before a launch,
     or has n = 0 and launches nothing."""
     import ursonet_amd.hip as hip
-    lib = hip.feat_lib()
+    lib = hip.side_lib("feat")
     P = [0x1000000 * k for k in range(1, 6)]
 
     def call(fn, cls, base, kw):

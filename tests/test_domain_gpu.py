@@ -222,7 +222,7 @@ def test_maha_tie_returns_the_lower_index():
 def test_refusals_launch_nothing():
     import ctypes as C
     from ursonet_amd import hip
-    lib = hip.feat_lib()
+    lib = hip.side_lib("feat")
     D = 8
     x, mean, wt, out, s, g = _nan(4, D), _nan(D), _nan(D, D), _nan(6, Dm.COLS), _nan(D), _nan(D, D)
     act, tab = torch.full((4, 2, 2, 2), NAN, device="cuda"), _nan(6, D)

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+from libsurface import header_symbols
 from ursonet_amd import ensemble as E
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -210,29 +211,15 @@ def test_results_without_members_carry_none():
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
 def test_header_bindings_and_library_agree():
     import ursonet_amd.hip as hip
     from ursonet_amd import build
-    names, txt = _header_symbols()
-    assert names == set(hip.TRAIN_SYMBOLS) and ENS_NAMES <= names
+    names, txt = header_symbols(HEADER)
+    assert names == set(hip.SIDE_SYMBOLS["train"]) and ENS_NAMES <= names and "ensemble.hip" in build.SIDE_SOURCES["train"]
     for macro, v in (("MAX_MEMBERS", E.MAX_MEMBERS), ("STAT", E.STAT), ("COLS", E.COLS), ("H_MEAN", E.H_MEAN), ("H_MEMBERS", E.H_MEMBERS),
                      ("MI", E.MI), ("PEAK", E.PEAK), ("ARGMAX", E.ARGMAX), ("N_MEMBERS", E.N_MEMBERS)):
         assert re.search(r"#define\s+URSO_ENS_%s\s+%d\b" % (macro, v), txt), macro
         assert getattr(hip, "ENS_" + macro) == v
-    lib = hip.train_lib()                                                    # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in names)
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.TRAIN_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (urso_\w+)$", out, re.M)) == names
-    assert "ensemble.hip" in build.TRAIN_SOURCES and os.path.exists(os.path.join(build.CSRC_TRAIN, "ensemble.hip"))
-    for other in (hip.LIB_PATH, hip.EXT_LIB_PATH, hip.OPT_LIB_PATH):
-        sym = subprocess.run(["nm", "-D", "--defined-only", other], capture_output=True, text=True, check=True).stdout
-        assert not ENS_NAMES & set(re.findall(r" T (urso_\w+)$", sym, re.M)), other
-    assert ENS_NAMES.isdisjoint(hip.EXPORTED_SYMBOLS) and ENS_NAMES.isdisjoint(hip.EXT_SYMBOLS) and ENS_NAMES.isdisjoint(hip.OPT_SYMBOLS)
     # the argument structs are the header's: field order and sizes
     assert [f[0] for f in hip.EnsAddArgs._fields_] == ["B", "n", "row0", "K", "ld", "first", "pad", "logits", "acc", "stat"]
     assert [f[0] for f in hip.EnsSettleArgs._fields_] == ["n", "row0", "K", "M", "acc", "stat", "logp", "table"]
@@ -243,7 +230,7 @@ def test_argument_validation_without_gpu():
     """Every refusal of the two entry points.  Device pointers are made up and never dereferenced: each call is refused before a launch,
     or has n = 0 and launches nothing."""
     import ursonet_amd.hip as hip
-    lib = hip.train_lib()
+    lib = hip.side_lib("train")
     Z, A, S, L, T = (0x1000000 * k for k in range(1, 6))
 
     def add(**kw):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import occlref as R
+from libsurface import header_symbols
 from ursonet_amd import explain as X
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -284,36 +285,17 @@ assert sys.modules["torch"] is None and "ursonet_amd.hip" not in sys.modules and
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
-def _defined(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return set(re.findall(r" T (urso_\w+)$", out, re.M))
-
-
 def test_header_bindings_and_library_agree():
     import ursonet_amd.hip as hip
     from ursonet_amd import build
-    names, txt = _header_symbols()
-    assert names == set(hip.EXPLAIN_SYMBOLS) == NAMES
+    names, txt = header_symbols(HEADER)
+    assert names == set(hip.SIDE_SYMBOLS["explain"]) == NAMES and build.SIDE_SOURCES["explain"] == ["explain.hip"]
     for macro in ("COLS", "MAX_MAPS", "D_ORI", "D_LOC", "ORI_KL", "ORI_TV", "ORI_DROP", "ORI_ARGMAX", "LOC_KL", "LOC_TV", "LOC_DROP", "LOC_ARGMAX"):
         v = getattr(X, macro)
         assert re.search(r"#define\s+URSO_OCCL_%s\s+%d\b" % (macro, v), txt), macro
         assert getattr(hip, "OCCL_" + macro) == v
     assert (X.DEC_LOC_EST, X.DEC_Q_EST, X.DEC_COLS) == (hip.DEC_LOC_EST, hip.DEC_Q_EST, hip.DEC_COLS)
     assert X.ORI_KL + 4 == X.LOC_KL and X.LOC_KL + 4 == X.COLS and len(X.MAP_COLUMNS) == X.MAX_MAPS
-    lib = hip.explain_lib()                                                  # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in names)
-    assert _defined(hip.EXPLAIN_LIB_PATH) == names
-    assert build.EXPLAIN_SOURCES == ["explain.hip"] and sorted(os.listdir(build.CSRC_EXPLAIN)) == sorted(build.EXPLAIN_SOURCES)
-    assert os.path.basename(build.EXPLAIN_LIB) == "liburso_explain.so" == os.path.basename(hip.EXPLAIN_LIB_PATH)
-    for other in (hip.LIB_PATH, hip.EXT_LIB_PATH, hip.OPT_LIB_PATH, hip.TRAIN_LIB_PATH, hip.INFER_LIB_PATH, hip.FEAT_LIB_PATH):
-        assert not NAMES & _defined(other), other
-    for table in (hip.EXPORTED_SYMBOLS, hip.EXT_SYMBOLS, hip.OPT_SYMBOLS, hip.TRAIN_SYMBOLS, hip.INFER_SYMBOLS, hip.FEAT_SYMBOLS):
-        assert NAMES.isdisjoint(table)
     # the argument structs are the header's: field order and sizes
     fields = {"urso_occl_fill_args": (hip.OcclFillArgs, ["B", "n", "H", "W", "C", "fill", "src", "rects", "out"], 48),
               "urso_occl_score_args": (hip.OcclScoreArgs, ["B", "n", "row0", "ori_K", "ori_ld", "loc_K", "loc_ld", "dec0", "dec", "ori_z0", "ori_z",
@@ -328,21 +310,6 @@ def test_header_bindings_and_library_agree():
         assert declared == order, struct
     assert hip.OcclFillArgs.fill.offset == 20 and hip.OcclFillArgs.src.offset == 24 and hip.OcclScoreArgs.dec0.offset == 32
     assert hip.OcclSplatArgs.cols.offset == 24 and hip.OcclSplatArgs.ld.offset == 56 and hip.HeatOverlayArgs.lo.offset == 24
-
-
-def test_the_build_knows_the_seventh_library(monkeypatch, tmp_path):
-    import ursonet_amd.hip as hip
-    from ursonet_amd import build
-    with open(build.EXPLAIN_LIB + ".srchash") as fh:
-        assert fh.read().strip() == build.explain_source_hash()                # as built: the stamp is the hash of the sources
-    assert not build.needs_build()
-    assert "-ffp-contract=off" in build.FLAGS
-    monkeypatch.setattr(build, "EXPLAIN_LIB", str(tmp_path / "liburso_explain.so"))
-    assert build.needs_build()                                               # a missing seventh library makes the build stale
-    monkeypatch.setattr(hip, "_explain", None)
-    monkeypatch.setattr(hip, "EXPLAIN_LIB_PATH", str(tmp_path / "liburso_explain.so"))
-    with pytest.raises(ImportError, match="liburso_explain.so not found"):
-        hip.explain_lib()
 
 
 def test_header_is_plain_c99(tmp_path):
@@ -362,7 +329,7 @@ def test_argument_validation_without_gpu():
     """Every refusal of the four entry points.  Device pointers are made up and never dereferenced: each call is refused before a HIP
     call, or has n = 0 and launches nothing."""
     import ursonet_amd.hip as hip
-    lib = hip.explain_lib()
+    lib = hip.side_lib("explain")
     P = [0x1000000 * k for k in range(1, 9)]
 
     def call(fn, cls, base, kw):

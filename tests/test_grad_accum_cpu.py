@@ -164,9 +164,9 @@ def test_header_declares_and_bindings_hold_the_entry_points():
     assert re.search(r"\bint\s+urso_grad_accum_parts\s*\(\s*int64_t n\)", txt)
     assert re.search(r"\bint\s+urso_grad_accum_close\s*\(\s*int64_t n, float\* g_d, const float\* acc_d, float c, float\* sqpart_d, int nparts, "
                      r"void\* stream\)", txt)
-    assert NAMES <= set(hip.EXT_SYMBOLS) and not NAMES & set(hip.EXPORTED_SYMBOLS)
+    assert NAMES <= set(hip.SIDE_SYMBOLS["ext"]) and not NAMES & set(hip.EXPORTED_SYMBOLS)
     from ursonet_amd import build
-    assert "grad_accum.hip" in build.EXT_SOURCES and os.path.exists(os.path.join(build.CSRC_EXT, "grad_accum.hip"))
+    assert "grad_accum.hip" in build.SIDE_SOURCES["ext"] and os.path.exists(os.path.join(build.side_srcdir("ext"), "grad_accum.hip"))
 
 
 def test_parts_is_the_documented_grid():
@@ -178,7 +178,7 @@ def test_parts_is_the_documented_grid():
 
 def test_argument_validation_without_gpu():
     import ursonet_amd.hip as hip
-    lib = hip.ext_lib()
+    lib = hip.side_lib("ext")
     P, Q, S = 4096, 8192, 12288                                              # never dereferenced: every case fails validation or launches nothing
     bad_accum = [((8, None, Q, 0), "null"), ((8, P, None, 1), "null"), ((-1, P, Q, 0), "n must be >= 0"), ((-2 ** 40, P, Q, 1), "n must be >= 0"),
                  ((8, P + 1, Q, 0), "aligned"), ((8, P, Q + 2, 1), "aligned"), ((8, P, P, 0), "same buffer"), ((8, P, P, 1), "same buffer")]

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import lamb_layout as LAY
+from libsurface import header_symbols
 from ursonet_amd import lamb as B
 from ursonet_amd import lars as L
 from ursonet_amd.config import Config
@@ -258,25 +259,12 @@ def test_the_gpu_layout_lies_on_both_sides_of_the_clip_and_has_its_cases():
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
 def test_header_bindings_and_library_agree():
     import ursonet_amd.hip as hip
-    names, txt = _header_symbols()
-    assert names == NAMES == set(hip.OPT_SYMBOLS)
+    from ursonet_amd import build
+    names, txt = header_symbols(HEADER)
+    assert names == NAMES == set(hip.SIDE_SYMBOLS["opt"]) and build.SIDE_SOURCES["opt"] == ["lamb.hip"]
     assert re.search(r"#define\s+URSO_LAMB_STATE\s+3\b", txt) and len(hip.LAMB_STATE_INIT) == 3 and tuple(hip.LAMB_STATE_INIT) == B.STATE_INIT
-    lib = hip.opt_lib()                                                      # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in NAMES)
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.OPT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (urso_\w+)$", out, re.M)) == names
-    others = set(hip.EXT_SYMBOLS) | set(hip.EXPORTED_SYMBOLS) | set(hip.LOSS_SCALE_SYMBOLS)
-    for path in (hip.LIB_PATH, hip.EXT_LIB_PATH):
-        o = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        others |= set(re.findall(r" T (urso_\w+)$", o, re.M))
-    assert not names & others                                                # the other two libraries' surfaces did not grow
 
 
 def test_header_is_plain_c99(tmp_path):
@@ -291,20 +279,6 @@ def test_header_is_plain_c99(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
-def test_missing_library_is_an_error_and_the_build_knows_it(monkeypatch, tmp_path):
-    import ursonet_amd.hip as hip
-    from ursonet_amd import build
-    monkeypatch.setattr(hip, "_opt", None)
-    monkeypatch.setattr(hip, "OPT_LIB_PATH", str(tmp_path / "liburso_opt.so"))
-    with pytest.raises(ImportError, match="liburso_opt.so not found"):
-        hip.opt_lib()
-    assert build.OPT_SOURCES == ["lamb.hip"] and os.path.basename(build.OPT_LIB) == "liburso_opt.so"
-    with open(build.OPT_LIB + ".srchash") as fh:
-        assert fh.read().strip() == build.opt_source_hash()                    # as built: the stamp is the hash of the sources
-    monkeypatch.setattr(build, "OPT_LIB", str(tmp_path / "liburso_opt.so"))
-    assert build.needs_build()                                               # a missing third library makes the build stale
-
-
 def _i64(vals):
     return (ctypes.c_int64 * max(len(vals), 1))(*vals)
 
@@ -313,7 +287,7 @@ def test_argument_validation_without_gpu():
     """Every refusal of the three launches.  Device pointers are made up and never dereferenced: each call is refused before a launch, or
     has T = 0 / no blocks and launches nothing; the host tables are real."""
     import ursonet_amd.hip as hip
-    lib = hip.opt_lib()
+    lib = hip.side_lib("opt")
     W, G, M, V, H, TAB, MAP, PART, FIRST, ADAPT, HYP, ST, NSQ, TR, STAT, LS = (0x10000 * k for k in range(1, 17))
     off, n = _i64([0, 8, 4108]), _i64([5, 4097, 3])
     nb = 1 + 2 + 1

@@ -258,9 +258,9 @@ def test_header_declares_and_bindings_hold_the_entry_points():
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ursonet_ext.h")).read(), flags=re.S)
     declared = set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt))
     assert NAMES <= declared and len(declared) == 14
-    assert NAMES <= set(hip.EXT_SYMBOLS) and not NAMES & set(hip.EXPORTED_SYMBOLS) and not NAMES & set(hip.LOSS_SCALE_SYMBOLS)
+    assert NAMES <= set(hip.SIDE_SYMBOLS["ext"]) and not NAMES & set(hip.EXPORTED_SYMBOLS) and not NAMES & set(hip.LOSS_SCALE_SYMBOLS)
     assert re.search(r"#define\s+URSO_LARS_CHUNK\s+4096\b", txt)
-    lib = hip.ext_lib()
+    lib = hip.side_lib("ext")
     assert all(hasattr(lib, nm) for nm in NAMES)
 
 
@@ -270,7 +270,7 @@ def _i64(vals):
 
 def test_host_planning():
     import ursonet_amd.hip as hip
-    lib = hip.ext_lib()
+    lib = hip.side_lib("ext")
     assert lib.urso_lars_blocks(0, None) == 0
     sizes = [1, 3, 4, 5, 255, 1023, 4096, 4097, 2 * 4096 + 4, 3 * 4096, 0, 2 ** 33]
     n_h = _i64(sizes)
@@ -304,7 +304,7 @@ def test_argument_validation_without_gpu():
     """Every refusal of the three launches.  Device pointers are made up and never dereferenced: each call is refused before a launch, or
     has T = 0 and launches nothing; the host tables are real."""
     import ursonet_amd.hip as hip
-    lib = hip.ext_lib()
+    lib = hip.side_lib("ext")
     W, G, V, TAB, MAP, PART, FIRST, ADAPT, HYP, NSQ, TR, STAT, LS = (0x10000 * k for k in range(1, 14))
     off, n = _i64([0, 8, 4108]), _i64([5, 4097, 3])
     nb = 1 + 2 + 1

@@ -252,8 +252,8 @@ def test_checkpoint_round_trip_and_loading_across_modes(tmp_path):
 def test_extension_surface_lists_the_three_entry_points():
     import ursonet_amd.hip as hip
     names = {"urso_softmax_xent_fwd_bwd_lw", "urso_rel_l2_fwd_bwd_lw", "urso_absdot_fwd_bwd_lw"}
-    assert names <= set(hip.EXT_SYMBOLS) and not names & set(hip.EXPORTED_SYMBOLS) and not names & set(hip.LOSS_SCALE_SYMBOLS)
-    lib = hip.ext_lib()
+    assert names <= set(hip.SIDE_SYMBOLS["ext"]) and not names & set(hip.EXPORTED_SYMBOLS) and not names & set(hip.LOSS_SCALE_SYMBOLS)
+    lib = hip.side_lib("ext")
     # argument checks run before any launch: a null s is refused by name
     assert lib.urso_rel_l2_fwd_bwd_lw(2, 3, 8, None, None, 1.0, 0, None, None, None, None, None, None, None) != 0
     assert "urso_rel_l2_fwd_bwd_lw" in hip.last_error()

@@ -13,6 +13,7 @@ import types
 import numpy as np
 import pytest
 
+from libsurface import header_symbols
 from ursonet_amd import sam as S
 from ursonet_amd.config import Config
 from util import make_config
@@ -189,37 +190,21 @@ def test_state_records_the_ascent_and_a_skipped_step_is_settled():
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
-def _defined(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return set(re.findall(r" T (urso_\w+)$", out, re.M))
-
-
 def test_header_bindings_and_library_agree():
     """The three agree with each other and hold the SAM names; the set is not pinned to them: the next training feature goes here."""
     import ursonet_amd.hip as hip
-    names, txt = _header_symbols()
-    assert names == set(hip.TRAIN_SYMBOLS) and SAM_NAMES <= names
+    from ursonet_amd import build
+    names, txt = header_symbols(HEADER)
+    assert names == set(hip.SIDE_SYMBOLS["train"]) and SAM_NAMES <= names and "sam.hip" in build.SIDE_SOURCES["train"]
     assert re.search(r"#define\s+URSO_SAM_STATE\s+8\b", txt) and hip.SAM_STATE == S.STATE_LEN == 8
     for field in ("RHO", "EPS", "NORMSQ", "SCALE", "APPLIED", "APPLIED_TOTAL", "PENDING"):
         assert re.search(r"#define\s+URSO_SAM_%s\s+%d\b" % (field, getattr(S, field)), txt), field
-    lib = hip.train_lib()                                                    # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in names)
-    assert _defined(hip.TRAIN_LIB_PATH) == names
-    others = set(hip.EXT_SYMBOLS) | set(hip.EXPORTED_SYMBOLS) | set(hip.LOSS_SCALE_SYMBOLS) | set(hip.OPT_SYMBOLS)
-    for path in (hip.LIB_PATH, hip.EXT_LIB_PATH, hip.OPT_LIB_PATH):
-        others |= _defined(path)
-    assert others and not names & others                                     # no name of the other three libraries
 
 
 def test_header_is_plain_c99(tmp_path):
     if shutil.which("gcc") is None:
         pytest.skip("no gcc")
-    names, _ = _header_symbols()
+    names, _ = header_symbols(HEADER)
     src = tmp_path / "train_abi.c"
     src.write_text('#include "ursonet_train.h"\n#include <stddef.h>\ntypedef void (*fn)(void);\nfn table[] = {\n' +
                    "".join("    (fn)%s,\n" % n for n in sorted(names)) + "};\nsize_t count(void) { return sizeof(table) / sizeof(table[0]); }\n"
@@ -229,27 +214,11 @@ def test_header_is_plain_c99(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
-def test_missing_library_is_an_error_and_the_build_knows_it(monkeypatch, tmp_path):
-    import ursonet_amd.hip as hip
-    from ursonet_amd import build
-    monkeypatch.setattr(hip, "_train", None)
-    monkeypatch.setattr(hip, "TRAIN_LIB_PATH", str(tmp_path / "liburso_train.so"))
-    with pytest.raises(ImportError, match="liburso_train.so not found"):
-        hip.train_lib()
-    assert "sam.hip" in build.TRAIN_SOURCES and os.path.basename(build.TRAIN_LIB) == "liburso_train.so"
-    assert sorted(os.listdir(build.CSRC_TRAIN)) == sorted(build.TRAIN_SOURCES)
-    with open(build.TRAIN_LIB + ".srchash") as fh:
-        assert fh.read().strip() == build.train_source_hash()                  # as built: the stamp is the hash of the sources
-    assert not build.needs_build()
-    monkeypatch.setattr(build, "TRAIN_LIB", str(tmp_path / "liburso_train.so"))
-    assert build.needs_build()                                               # a missing fourth library makes the build stale
-
-
 def test_argument_validation_without_gpu():
     """Every refusal of the entry points.  Device pointers are made up and never dereferenced: each call is refused before a launch, or
     has n = 0 and launches nothing."""
     import ursonet_amd.hip as hip
-    lib = hip.train_lib()
+    lib = hip.side_lib("train")
     W, G, W0, ST, NSQ = (0x10000 * k for k in range(1, 6))
     good_a = dict(n=1000, w=W, g=G, w0=W0, state=ST)
     three = "three buffers"

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+from libsurface import header_symbols
 from ursonet_amd import swa as S
 from ursonet_amd.config import Config
 
@@ -258,34 +259,24 @@ def test_sample32_fixed_points_and_rule():
 
 
 # ------------------------------------------------------------------ the library's surface
-def _header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt)), txt
-
-
 def test_header_bindings_and_library_agree():
     import ursonet_amd.hip as hip
     from ursonet_amd import build
-    names, txt = _header_symbols()
-    assert names == set(hip.TRAIN_SYMBOLS) and SWA_NAMES <= names
+    names, txt = header_symbols(HEADER)
+    assert names == set(hip.SIDE_SYMBOLS["train"]) and SWA_NAMES <= names and "swa.hip" in build.SIDE_SOURCES["train"]
     assert re.search(r"#define\s+URSO_SWA_STATE\s+8\b", txt) and hip.SWA_STATE == S.FIELDS == 8
     for k, field in enumerate(S.FIELD_NAMES):
         assert re.search(r"#define\s+URSO_SWA_%s\s+%d\b" % (field.upper(), k), txt), field
     assert re.search(r"#define\s+URSO_SWA_MAX_MODELS\s+%d\b" % S.MAX_MODELS, txt)
     assert re.search(r"#define\s+URSO_SWA_REFUSED\s+\(%d\)" % S.REFUSED, txt)
-    lib = hip.train_lib()                                                    # loads and binds: a missing symbol raises
-    assert all(hasattr(lib, nm) for nm in names)
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.TRAIN_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (urso_\w+)$", out, re.M)) == names
-    assert "swa.hip" in build.TRAIN_SOURCES and os.path.exists(os.path.join(build.CSRC_TRAIN, "swa.hip"))
-    assert len(hip._TRAIN_SIGS["urso_swa_update"][1]) == 7 and len(hip._TRAIN_SIGS["urso_swag_sample"][1]) == 10
+    assert len(hip.SIDE_SIGS["train"]["urso_swa_update"][1]) == 7 and len(hip.SIDE_SIGS["train"]["urso_swag_sample"][1]) == 10
 
 
 def test_argument_validation_without_gpu():
     """Every refusal of the two entry points.  Device pointers are made up and never dereferenced: each call is refused before a launch,
     or has n = 0 and launches nothing."""
     import ursonet_amd.hip as hip
-    lib = hip.train_lib()
+    lib = hip.side_lib("train")
     W, M, Q, ST, LS, O, Z = (0x1000000 * k for k in range(1, 8))
 
     def call(fn, good, kw):

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from libsurface import header_symbols
 from oracle import pose_math as P
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,28 +18,11 @@ ROOT = os.path.dirname(HERE)
 EXT_HEADER = os.path.join(ROOT, "include", "ursonet_ext.h")
 
 
-def _ext_header_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(EXT_HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(urso_[a-z0-9_]+)\s*\(", txt))
-
-
-# ------------------------------------------------------------------ the extension's surface
-def test_extension_header_bindings_and_library_agree():
-    import ursonet_amd.hip as hip
-    names = _ext_header_symbols()
-    assert names and names == set(hip.EXT_SYMBOLS)
-    hip.ext_lib()                                                           # loads and binds: a missing symbol raises
-    out = subprocess.run(["nm", "-D", "--defined-only", hip.EXT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (urso_\w+)$", out, re.M)) == names
-    assert not names & set(hip.EXPORTED_SYMBOLS) and not names & set(hip.LOSS_SCALE_SYMBOLS)
-    main = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert not names & set(re.findall(r" T (urso_\w+)$", main, re.M))        # the main library's surface did not grow
-
-
+# ------------------------------------------------------------------ the extension's header (its surface: tests/test_side_libs_cpu.py)
 def test_extension_header_is_plain_c99(tmp_path):
     if shutil.which("gcc") is None:
         pytest.skip("no gcc")
-    names = sorted(_ext_header_symbols())
+    names = sorted(header_symbols(EXT_HEADER)[0])
     src = tmp_path / "ext_abi.c"
     src.write_text('#include "ursonet_ext.h"\n#include <stddef.h>\ntypedef void (*fn)(void);\nfn table[] = {\n' +
                    "".join("    (fn)%s,\n" % n for n in names) + "};\nsize_t count(void) { return sizeof(table) / sizeof(table[0]); }\n"
@@ -64,14 +48,6 @@ def test_header_constants_are_mirrored():
     assert ctypes.sizeof(hip.PoseFuseViewsArgs) == 80 and hip.PoseFuseViewsArgs.est.offset == 32 and hip.PoseFuseViewsArgs.table.offset == 72
 
 
-def test_missing_extension_library_is_an_error(monkeypatch, tmp_path):
-    import ursonet_amd.hip as hip
-    monkeypatch.setattr(hip, "_ext", None)
-    monkeypatch.setattr(hip, "EXT_LIB_PATH", str(tmp_path / "liburso_ext.so"))
-    with pytest.raises(ImportError, match=r"build it with `python -m ursonet_amd.build`"):
-        hip.ext_lib()
-
-
 # ------------------------------------------------------------------ argument validation
 def _args(**kw):
     import ursonet_amd.hip as hip
@@ -85,7 +61,7 @@ def _args(**kw):
 
 def test_pose_fuse_views_argument_validation_without_gpu():
     import ursonet_amd.hip as hip
-    lib = hip.ext_lib()
+    lib = hip.side_lib("ext")
     cases = [
         (dict(est=None), "null"), (dict(r=None), "null"), (dict(qr=None), "null"), (dict(table=None), "null"),
         (dict(loc_gt=4096), "both or neither"), (dict(q_gt=4096), "both or neither"),

@@ -151,15 +151,15 @@ def test_header_declares_and_bindings_hold_the_entry_points():
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ursonet_ext.h")).read(), flags=re.S)
     assert re.search(r"\bint\s+urso_ema_update\s*\(\s*int64_t n, const float\* w_d, float\* ema_d, float\* state_d, const float\* ls_state_d, void\* stream\)", txt)
     assert re.search(r"\bint\s+urso_ema_swap\s*\(\s*int64_t n, float\* a_d, float\* b_d, void\* stream\)", txt)
-    assert {"urso_ema_update", "urso_ema_swap"} <= set(hip.EXT_SYMBOLS)
+    assert {"urso_ema_update", "urso_ema_swap"} <= set(hip.SIDE_SYMBOLS["ext"])
     assert not {"urso_ema_update", "urso_ema_swap"} & set(hip.EXPORTED_SYMBOLS)
     from ursonet_amd import build
-    assert "weight_ema.hip" in build.EXT_SOURCES and os.path.exists(os.path.join(build.CSRC_EXT, "weight_ema.hip"))
+    assert "weight_ema.hip" in build.SIDE_SOURCES["ext"] and os.path.exists(os.path.join(build.side_srcdir("ext"), "weight_ema.hip"))
 
 
 def test_argument_validation_without_gpu():
     import ursonet_amd.hip as hip
-    lib = hip.ext_lib()
+    lib = hip.side_lib("ext")
     P, Q, S, L = 4096, 8192, 12288, 16384                                    # never dereferenced: every case fails validation or launches nothing
     bad_update = [((8, None, Q, S, None), "null"), ((8, P, None, S, None), "null"), ((8, P, Q, None, None), "null"),
                   ((-1, P, Q, S, None), "n must be >= 0"), ((-2 ** 40, P, Q, S, L), "n must be >= 0"),

@@ -159,16 +159,6 @@ class BNRecalResult(object):
         return out
 
 
-class _Subset(object):
-    """`dataset` with image_ids cut to the chosen ones; everything else is the dataset's."""
-
-    def __init__(self, dataset, ids):
-        self._dataset, self.image_ids = dataset, list(ids)
-
-    def __getattr__(self, name):
-        return getattr(self._dataset, name)
-
-
 def check_model(model):
     """ValueError unless `model` is a training-mode model on one GPU whose engine runs batch-statistics BatchNorm."""
     eng = getattr(model, "_engine", None)
@@ -206,12 +196,12 @@ def recalibrate_bn(model, dataset, nr_images=None, workers=None, cache=None, ema
     import torch
     from .feeder import EvalFeeder
     from .graph import BN_EPS
-    from .infer import loader_workers
+    from .infer import Subset, loader_workers
     cfg = model.config
     before = eng.flat_stats.detach().cpu().numpy().copy()
 
     def run():
-        feed = EvalFeeder(model, _Subset(dataset, used), cfg, workers=loader_workers(cfg, workers), labels=False, cache=cache)
+        feed = EvalFeeder(model, Subset(dataset, used), cfg, workers=loader_workers(cfg, workers), labels=False, cache=cache)
         eng.bn_recal_begin()
         try:
             for bt in feed:

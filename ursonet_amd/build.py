@@ -1,4 +1,3 @@
-"""Builds liburso_hip.so, the extension library liburso_ext.so, the optimizer library liburso_opt.so, the training library liburso_train.so, the inference library liburso_infer.so, the feature library liburso_feat.so and the explanation library liburso_explain.so (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."""
 import os
 import subprocess
 import sys
@@ -12,35 +11,29 @@ VARIANT = os.environ.get("URSO_LIB_VARIANT", "")
 LIB = os.path.join(LIBDIR, "liburso_hip%s.so" % (("_" + VARIANT) if VARIANT else ""))
 SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_pw.hip", "conv_pwx.hip", "conv_dense.hip", "conv_bneck.hip", "conv_halo.hip", "conv_halo2.hip", "conv_winograd.hip", "conv_pair.hip", "conv_pairw.hip", "conv_pairx.hip", "conv_pairs.hip", "conv_c3.hip", "conv_c3g.hip", "conv_hwgrad.hip", "conv_stem.hip", "conv_stemw.hip", "conv_wgrad.hip", "prep.hip", "pool_loss_optim.hip", "augment.hip", "resize.hip", "frame_cache.hip", "video.hip", "pmf_sheet.hip", "bn_train.hip", "comm.hip", "quat_gmm.hip", "pose_eval.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
-# The extension library (include/ursonet_ext.h): entry points added after liburso_hip.so's surface was frozen.  Same flags, no variant;
-# it calls into the main library (error text, launch profiler), which the loader resolves when it is loaded behind it (ursonet_amd/hip.py).
-CSRC_EXT = os.path.join(HERE, "csrc_ext")
-EXT_LIB = os.path.join(LIBDIR, "liburso_ext.so")
-EXT_SOURCES = ["pose_fuse.hip", "loss_weights.hip", "weight_ema.hip", "grad_accum.hip", "lars.hip"]
-# The optimizer library (include/ursonet_opt.h): entry points added after liburso_ext.so's surface was frozen too.  Built and loaded as that one.
-CSRC_OPT = os.path.join(HERE, "csrc_opt")
-OPT_LIB = os.path.join(LIBDIR, "liburso_opt.so")
-OPT_SOURCES = ["lamb.hip"]
-# The training library (include/ursonet_train.h): training features added after liburso_opt.so's surface was frozen as well; its own surface
-# stays open, so the next one goes here.  Built and loaded as the other two.
-CSRC_TRAIN = os.path.join(HERE, "csrc_train")
-TRAIN_LIB = os.path.join(LIBDIR, "liburso_train.so")
-TRAIN_SOURCES = ["sam.hip", "bn_recal.hip", "swa.hip", "ensemble.hip", "calibrate.hip"]
-# The inference library (include/ursonet_infer.h): inference features added after liburso_train.so's surface was pinned; its own surface
-# stays open.  Built and loaded as the other three.
-CSRC_INFER = os.path.join(HERE, "csrc_infer")
-INFER_LIB = os.path.join(LIBDIR, "liburso_infer.so")
-INFER_SOURCES = ["conformal.hip"]
-# The feature library (include/ursonet_feat.h): feature-space statistics of the bottleneck features (ursonet_amd/domain.py); liburso_infer.so's
-# surface was pinned to conformal's two names.  Built and loaded as the other four.
-CSRC_FEAT = os.path.join(HERE, "csrc_feat")
-FEAT_LIB = os.path.join(LIBDIR, "liburso_feat.so")
-FEAT_SOURCES = ["feat.hip"]
-# The explanation library (include/ursonet_explain.h): occlusion-sensitivity maps (ursonet_amd/explain.py); liburso_feat.so's surface was pinned
-# to its three names.  Built and loaded as the other five.
-CSRC_EXPLAIN = os.path.join(HERE, "csrc_explain")
-EXPLAIN_LIB = os.path.join(LIBDIR, "liburso_explain.so")
-EXPLAIN_SOURCES = ["explain.hip"]
+# The libraries behind the main one, in the order they were added: name -> sources.  Everything else follows from the name: the source
+# directory csrc_<name>, lib/liburso_<name>.so, the header include/ursonet_<name>.h and the object-file tag _<name>.  Same flags, no
+# variant; each calls into the main library (error text, launch profiler), which the loader resolves when it loads one behind it
+# (ursonet_amd/hip.py: side_lib).  A new library is a new row here and a row of signatures in hip.SIDE_SIGS.
+SIDE_SOURCES = {
+    "ext": ["pose_fuse.hip", "loss_weights.hip", "weight_ema.hip", "grad_accum.hip", "lars.hip"],   # entry points added after liburso_hip.so's surface was frozen
+    "opt": ["lamb.hip"],                                                                             # optimizers, after liburso_ext.so's was frozen too
+    "train": ["sam.hip", "bn_recal.hip", "swa.hip", "ensemble.hip", "calibrate.hip"],                # training features; its own surface stays open
+    "infer": ["conformal.hip"],                                                                      # conformal bounds (ursonet_amd/conformal.py)
+    "feat": ["feat.hip"],                                                                            # feature-space statistics (ursonet_amd/domain.py)
+    "explain": ["explain.hip"],                                                                      # occlusion-sensitivity maps (ursonet_amd/explain.py)
+}
+SIDE_LIBS = {name: os.path.join(LIBDIR, "liburso_%s.so" % name) for name in SIDE_SOURCES}           # patchable one library at a time
+__doc__ = ("Builds liburso_hip.so and, behind it, %s (gfx950) in-tree with hipcc.  `python -m ursonet_amd.build`."
+           % ", ".join("liburso_%s.so" % name for name in SIDE_SOURCES))
+
+
+def side_srcdir(name):
+    return os.path.join(HERE, "csrc_" + name)
+
+
+def side_header(name):
+    return os.path.join(HERE, "..", "include", "ursonet_%s.h" % name)
 
 
 def _hipcc():
@@ -73,12 +66,12 @@ def _hash_compiler(h):
         pass
 
 
-def _side_source_hash(srcdir, sources):
+def side_source_hash(name):
     """source_hash() of a library behind the main one: every file of its source directory, the headers of csrc/ it may include, the public
     headers, the compile flags and the compiler's version string."""
     import hashlib
     h = hashlib.sha256()
-    inc = os.path.join(HERE, "..", "include")
+    srcdir, inc = side_srcdir(name), os.path.join(HERE, "..", "include")
     files = (sorted(os.path.join(srcdir, f) for f in os.listdir(srcdir)) + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) +
              sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")))
     for f in files:
@@ -86,39 +79,9 @@ def _side_source_hash(srcdir, sources):
         with open(f, "rb") as fh:
             h.update(fh.read())
         h.update(b"\0")
-    h.update(" ".join(FLAGS + sources).encode())
+    h.update(" ".join(FLAGS + SIDE_SOURCES[name]).encode())
     _hash_compiler(h)
     return h.hexdigest()
-
-
-def ext_source_hash():
-    """source_hash() of the extension library."""
-    return _side_source_hash(CSRC_EXT, EXT_SOURCES)
-
-
-def opt_source_hash():
-    """source_hash() of the optimizer library."""
-    return _side_source_hash(CSRC_OPT, OPT_SOURCES)
-
-
-def train_source_hash():
-    """source_hash() of the training library."""
-    return _side_source_hash(CSRC_TRAIN, TRAIN_SOURCES)
-
-
-def infer_source_hash():
-    """source_hash() of the inference library."""
-    return _side_source_hash(CSRC_INFER, INFER_SOURCES)
-
-
-def feat_source_hash():
-    """source_hash() of the feature library."""
-    return _side_source_hash(CSRC_FEAT, FEAT_SOURCES)
-
-
-def explain_source_hash():
-    """source_hash() of the explanation library."""
-    return _side_source_hash(CSRC_EXPLAIN, EXPLAIN_SOURCES)
 
 
 def _stale(lib, digest):
@@ -131,31 +94,26 @@ def _stale(lib, digest):
         return True
 
 
+def side_stale(name):
+    return _stale(SIDE_LIBS[name], lambda: side_source_hash(name))
+
+
 def needs_build():
     """Stale unless the hash recorded next to the .so equals the hash of the sources as they are now (mtimes are meaningless after a
     checkout or a snapshot push; a .so shipped without its hash file is rebuilt where a compiler exists and trusted where none does).
     True if any of the libraries is stale."""
-    return (_stale(LIB, source_hash) or _stale(EXT_LIB, ext_source_hash) or _stale(OPT_LIB, opt_source_hash) or _stale(TRAIN_LIB, train_source_hash) or
-            _stale(INFER_LIB, infer_source_hash) or _stale(FEAT_LIB, feat_source_hash) or _stale(EXPLAIN_LIB, explain_source_hash))
+    return _stale(LIB, source_hash) or any(side_stale(name) for name in SIDE_SOURCES)
 
 
 def build(force=False, verbose=True):
-    """Compile every HIP source for gfx950 and link the seven shared libraries, each only if it is stale (no GPU needed)."""
+    """Compile every HIP source for gfx950 and link the main library and every library of SIDE_SOURCES, each only if it is stale (no GPU
+    needed)."""
     os.makedirs(LIBDIR, exist_ok=True)
     if force or _stale(LIB, source_hash):
         _compile_and_link(LIB, CSRC, SOURCES, FLAGS + os.environ.get("URSO_VARIANT_FLAGS", "").split(), ("_" + VARIANT) if VARIANT else "", source_hash, verbose)
-    if force or _stale(EXT_LIB, ext_source_hash):
-        _compile_and_link(EXT_LIB, CSRC_EXT, EXT_SOURCES, FLAGS, "_ext", ext_source_hash, verbose)
-    if force or _stale(OPT_LIB, opt_source_hash):
-        _compile_and_link(OPT_LIB, CSRC_OPT, OPT_SOURCES, FLAGS, "_opt", opt_source_hash, verbose)
-    if force or _stale(TRAIN_LIB, train_source_hash):
-        _compile_and_link(TRAIN_LIB, CSRC_TRAIN, TRAIN_SOURCES, FLAGS, "_train", train_source_hash, verbose)
-    if force or _stale(INFER_LIB, infer_source_hash):
-        _compile_and_link(INFER_LIB, CSRC_INFER, INFER_SOURCES, FLAGS, "_infer", infer_source_hash, verbose)
-    if force or _stale(FEAT_LIB, feat_source_hash):
-        _compile_and_link(FEAT_LIB, CSRC_FEAT, FEAT_SOURCES, FLAGS, "_feat", feat_source_hash, verbose)
-    if force or _stale(EXPLAIN_LIB, explain_source_hash):
-        _compile_and_link(EXPLAIN_LIB, CSRC_EXPLAIN, EXPLAIN_SOURCES, FLAGS, "_explain", explain_source_hash, verbose)
+    for name, sources in SIDE_SOURCES.items():
+        if force or side_stale(name):
+            _compile_and_link(SIDE_LIBS[name], side_srcdir(name), sources, FLAGS, "_" + name, lambda: side_source_hash(name), verbose)
     return LIB
 
 
@@ -185,4 +143,4 @@ def _compile_and_link(lib, srcdir, sources, flags, tag, digest, verbose):
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
-    print("built", LIB, EXT_LIB, OPT_LIB, TRAIN_LIB, INFER_LIB, FEAT_LIB, EXPLAIN_LIB)
+    print("built", LIB, *SIDE_LIBS.values())

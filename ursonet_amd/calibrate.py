@@ -19,9 +19,10 @@ refusal of calibrate() has passed.
 """
 import json
 import math
-import os
 
 import numpy as np
+
+from .infer import Subset, refuse_launcher
 
 MAX_J, COLS, TOTALS = 8, 26, 4                                   # URSO_TEMP_MAX_J, URSO_TEMP_COLS, URSO_TEMP_TOTALS (include/ursonet_train.h)
 SY, YZ, LSE, M1, VAR = range(5)                                  # URSO_TEMP_* columns; LSE, M1, VAR of temperature j at + 3 j
@@ -296,16 +297,6 @@ def check_size(N, k_ori, k_loc, max_gb, who="calibrate"):
     return need
 
 
-class _First(object):
-    """The first images of a dataset: image_ids is cut, everything else is the dataset's."""
-
-    def __init__(self, dataset, ids):
-        self._dataset, self.image_ids = dataset, ids
-
-    def __getattr__(self, name):
-        return getattr(self._dataset, name)
-
-
 def calibrate(model, dataset, nr_images=None, workers=None, cache=None, max_gb=16, *, members=None, views=None):
     """Fits the temperature of every classification head of an inference model on a labelled dataset -> Calibration.  The dataset is
     walked once (the first nr_images of dataset.image_ids; None: all) with evaluate()'s feeder and inference pass; each head's fp32
@@ -317,9 +308,7 @@ def calibrate(model, dataset, nr_images=None, workers=None, cache=None, max_gb=1
     if members is not None or views is not None:
         raise ValueError("%s: members=... and views=... are not supported: a temperature belongs to one weight set and the plain pass; "
                          "calibrate and predict each member on its own" % who)
-    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1 or getattr(model, "_dp", None) is not None or int(getattr(model, "_world", 1)) > 1:
-        raise ValueError("%s is not supported under a data-parallel launcher: each rank would fit the whole dataset; run it in a plain "
-                         "process" % who)
+    refuse_launcher(model, who, "fit the whole dataset")
     assert model.mode == "inference", "Create model in inference mode."
     cfg = model.config
     soft, loc_class = not (cfg.REGRESS_ORI or cfg.REGRESS_KEYPOINTS), not cfg.REGRESS_LOC
@@ -347,7 +336,7 @@ def calibrate(model, dataset, nr_images=None, workers=None, cache=None, max_gb=1
     f32 = dict(dtype=torch.float32, device=dev)
     z_ori, y_ori = (torch.empty(N, k_ori, **f32), torch.empty(N, k_ori, **f32)) if soft else (None, None)
     z_loc, y_loc = (torch.empty(N, k_loc, **f32), torch.empty(N, k_loc, **f32)) if loc_class else (None, None)
-    feed = EvalFeeder(model, _First(dataset, ids) if nr_images is not None else dataset, ps.cfg, enc_loc=loc_class, enc_ori=soft,
+    feed = EvalFeeder(model, Subset(dataset, ids) if nr_images is not None else dataset, ps.cfg, enc_loc=loc_class, enc_ori=soft,
                       workers=loader_workers(ps.cfg, workers), cache=cache)
     try:
         for bt in feed:

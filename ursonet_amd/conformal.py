@@ -17,9 +17,10 @@ conformal() has passed.
 """
 import json
 import math
-import os
 
 import numpy as np
+
+from .infer import Subset, refuse_launcher
 
 SHIFT, MAX_K, COLS = 34, 1 << 18, 8                               # URSO_CONF_SHIFT, URSO_CONF_MAX_K, URSO_CONF_COLS (include/ursonet_infer.h)
 ANGLE, EUCLID = 0, 1                                              # URSO_CONF_ANGLE, URSO_CONF_EUCLID
@@ -265,7 +266,7 @@ class ConformalPass(object):
                 self.heads.append((name, metric, col, D, ps.table(rows, hip.CONF_COLS) if scores else None,
                                    ps.table(rows, hip.CONF_COLS) if q is not None else None, q))
         assert hip.EVAL_Q_EST == hip.DEC_Q_EST and hip.EVAL_LOC_EST == hip.DEC_LOC_EST
-        hip.infer_lib()                                            # a missing library is an error here, not in the first batch
+        hip.side_lib("infer")                                      # a missing library is an error here, not in the first batch
         self.torch = torch
 
     def launch(self, table, n, row0, heads, bt=None):
@@ -324,10 +325,8 @@ def conformal(model, dataset, alpha=0.1, nr_images=None, workers=None, cache=Non
     alpha = _alpha(alpha, who)
     if members is not None or views is not None:
         raise ValueError("%s: members=... and views=... are not supported: the levels belong to the plain pass of one weight set" % who)
-    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1 or getattr(model, "_dp", None) is not None or int(getattr(model, "_world", 1)) > 1:
-        raise ValueError("%s is not supported under a data-parallel launcher: each rank would walk the whole dataset; run it in a plain "
-                         "process" % who)
-    from .calibrate import _First, check_calibration
+    refuse_launcher(model, who, "walk the whole dataset")
+    from .calibrate import check_calibration
     check_calibration(calibration, None, who)
     ids = list(dataset.image_ids)
     if nr_images is not None:
@@ -346,7 +345,7 @@ def conformal(model, dataset, alpha=0.1, nr_images=None, workers=None, cache=Non
     k_ori, k_loc = head_bins(model)
     table = ps.table(N, hip.EVAL_COLS)
     cp = ConformalPass(ps, N, scores=True)
-    feed = EvalFeeder(model, _First(dataset, ids) if nr_images is not None else dataset, ps.cfg, enc_loc=ps.loc_class, enc_ori=ps.soft,
+    feed = EvalFeeder(model, Subset(dataset, ids) if nr_images is not None else dataset, ps.cfg, enc_loc=ps.loc_class, enc_ori=ps.soft,
                       workers=loader_workers(ps.cfg, workers), cache=cache)
     try:
         for bt in feed:

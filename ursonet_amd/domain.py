@@ -13,9 +13,10 @@ one stated order, so the kernels equal the statements bit for bit.  The statisti
 batch size: the centre is a bit copy of the first image's feature row, and rows are added one behind the other.  Nothing here needs
 torch, the engine or the library before every refusal has passed.
 """
-import os
 
 import numpy as np
+
+from .infer import Subset, refuse_launcher
 
 MAX_D, COLS, MAHA_ROWS = 4096, 4, 8                               # URSO_FEAT_MAX_D, URSO_FEAT_COLS, URSO_FEAT_MAHA_ROWS (include/ursonet_feat.h)
 SCORE, DIST2, ZMAX, ZARG = range(4)                               # the score row
@@ -243,15 +244,8 @@ def check_domain(domain, members=None, views=None, who="predict"):
     if members is not None or views is not None:
         raise ValueError("%s: domain=... cannot be combined with members=... or views=...: the statistics were fitted on the plain pass of "
                          "one weight set" % who)
-    _no_launcher("%s: domain=..." % who)
+    refuse_launcher(None, "%s: domain=..." % who, "walk the whole dataset")
     return domain
-
-
-def _no_launcher(what, model=None):
-    if (int(os.environ.get("WORLD_SIZE", "1") or 1) > 1 or
-            (model is not None and (getattr(model, "_dp", None) is not None or int(getattr(model, "_world", 1)) > 1))):
-        raise ValueError("%s is not supported under a data-parallel launcher: each rank would walk the whole dataset; run it in a plain "
-                         "process" % what)
 
 
 def domain_fields(res, dom, table):
@@ -292,7 +286,7 @@ class DomainPass(object):
 
     def __init__(self, ps, rows, dom):
         hip, torch = ps.hip, ps.torch
-        hip.feat_lib()                                             # a missing library is an error here, not in the first batch
+        hip.side_lib("feat")                                       # a missing library is an error here, not in the first batch
         self.ps, self.hip, self.grid = ps, hip, dom.grid
         self.x = ps.table(ps.B, dom.D)
         self.out = ps.table(rows, hip.FEAT_COLS)
@@ -312,7 +306,7 @@ class DomainPass(object):
 def _plan(model, dataset, nr_images, grid, shrink, max_gb, who):
     """Every refusal of fit_domain() that needs no GPU -> (ids, geometry, grid, D)."""
     _shrink(shrink, who)
-    _no_launcher(who, model)
+    refuse_launcher(model, who, "walk the whole dataset")
     if model.mode != "inference":
         raise ValueError("%s needs a model created in inference mode (got mode %r): the features are those predict() computes" % (who, model.mode))
     geo = feature_geometry(model.config)
@@ -345,17 +339,16 @@ def fit_domain(model, dataset, holdout=None, nr_images=None, grid=(1, 1), shrink
     who = "fit_domain"
     ids, geo, grid, D = _plan(model, dataset, nr_images, grid, shrink, max_gb, who)
     N = len(ids)
-    from .calibrate import _First
     from .feeder import EvalFeeder
     from .infer import PosePass, loader_workers
     ps = PosePass(model, dataset, False, who=who)
     hip, torch = ps.hip, ps.torch
-    hip.feat_lib()
+    hip.side_lib("feat")
     f64 = dict(dtype=torch.float64, device=ps.dev)
     x, centre, s, G = ps.table(ps.B, D), torch.zeros(D, **f64), torch.zeros(D, **f64), torch.zeros(D, D, **f64)
     plan = []
     finite = torch.ones((N + ps.B - 1) // ps.B, dtype=torch.bool, device=ps.dev)
-    feed = EvalFeeder(model, _First(dataset, ids) if nr_images is not None else dataset, ps.cfg, workers=loader_workers(ps.cfg, workers),
+    feed = EvalFeeder(model, Subset(dataset, ids) if nr_images is not None else dataset, ps.cfg, workers=loader_workers(ps.cfg, workers),
                       labels=False, cache=cache)
     try:
         for bt in feed:

@@ -1115,7 +1115,7 @@ class Engine(object):
             self.flat_w0 = torch.zeros_like(self.flat_w)
         self.sam_loss = torch.zeros_like(self.loss_buf)                    # L(w + e), slot for slot as loss_buf
         self.sam_stats = torch.zeros_like(self.flat_stats) if self.train_bn else None
-        hip.train_lib()                                # a missing library is an error here, not at the first step
+        hip.side_lib("train")                          # a missing library is an error here, not at the first step
         nsq = self.sam_state[sam.NORMSQ:sam.NORMSQ + 1]
         sam_ws = torch.empty_like(self.sq_ws)          # (a workspace of its own: nothing of the optimizer's norm is shared)
 

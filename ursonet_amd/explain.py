@@ -26,11 +26,10 @@ finer than the patch is resolved.  Painting with the neutral value is itself off
 object the network never saw, and a large score can mean "this square disturbed the network" as well as "the evidence was here"; compare
 patch sizes, and read the maps next to domain_score.  The maps say where the estimate is read from, not whether it is right.
 """
-import os
 
 import numpy as np
 
-from .infer import check_heads, loader_workers
+from .infer import check_heads, loader_workers, refuse_launcher
 
 # table columns of urso_occl_score (include/ursonet_explain.h, URSO_OCCL_*; hip.OCCL_* are the same numbers)
 COLS, MAX_MAPS = 10, 8
@@ -244,12 +243,6 @@ def _fill_bytes(fill, cfg):
     return tuple(int(v) for v in vals)
 
 
-def _no_launcher(model):
-    if (int(os.environ.get("WORLD_SIZE", "1") or 1) > 1 or getattr(model, "_dp", None) is not None or int(getattr(model, "_world", 1)) > 1):
-        raise ValueError("explain is not supported under a data-parallel launcher: each rank would walk the whole dataset; run it in a plain "
-                         "process")
-
-
 def _u8_rgb(image):
     return getattr(image, "dtype", None) == np.uint8 and np.ndim(image) == 3 and np.shape(image)[-1] == 3
 
@@ -272,7 +265,7 @@ def explain(model, dataset, image_ids=None, nr_images=None, patch=32, stride=Non
     sink, into ExplainResult.pictures.  Per image P + 1 rows run in ceil((P + 1) / B) passes; the model's weights, statistics and input
     are not changed.  ValueError, before any GPU work: a training-mode model, what check_heads refuses, a data-parallel launcher, frames
     that are not uint8 RGB, a bad patch / stride / fill / lut / alpha / render, a resize mode without a window."""
-    _no_launcher(model)
+    refuse_launcher(model, "explain", "walk the whole dataset")
     if getattr(model, "mode", None) != "inference":
         raise ValueError("explain needs a model created in inference mode (got mode %r): the maps explain what predict() computes" % (getattr(model, "mode", None),))
     cfg = model.config

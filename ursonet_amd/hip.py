@@ -9,15 +9,9 @@ import os
 import numpy as np
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_VARIANT = os.environ.get("URSO_LIB_VARIANT", "")        # kernel experiments: see ursonet_amd/build.py
-LIB_PATH = os.path.join(_HERE, "lib", "liburso_hip%s.so" % (("_" + _VARIANT) if _VARIANT else ""))
-EXT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_ext.so")          # the extension library (include/ursonet_ext.h): loaded on first use
-OPT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_opt.so")          # the optimizer library (include/ursonet_opt.h): loaded on first use
-TRAIN_LIB_PATH = os.path.join(_HERE, "lib", "liburso_train.so")      # the training library (include/ursonet_train.h): loaded on first use
-INFER_LIB_PATH = os.path.join(_HERE, "lib", "liburso_infer.so")      # the inference library (include/ursonet_infer.h): loaded on first use
-FEAT_LIB_PATH = os.path.join(_HERE, "lib", "liburso_feat.so")        # the feature library (include/ursonet_feat.h): loaded on first use
-EXPLAIN_LIB_PATH = os.path.join(_HERE, "lib", "liburso_explain.so")  # the explanation library (include/ursonet_explain.h): loaded on first use
+from . import build as _build                              # the libraries' paths (it imports os, subprocess and sys only)
+
+LIB_PATH = _build.LIB                                      # the variant under URSO_LIB_VARIANT (kernel experiments: see ursonet_amd/build.py)
 
 F32, BF16, F16 = 0, 1, 2
 EPI_RELU, EPI_OUT_F32, EPI_MASK_BITS, EPI_EMIT_BITS, EPI_ADD_SRCGRID = 1, 2, 4, 8, 16
@@ -359,85 +353,77 @@ _LS_SIGS = {
     "urso_loss_scale_update": (_i, [_fp, _fp, _vp]),
 }
 LOSS_SCALE_SYMBOLS = sorted(_LS_SIGS)
-# the extension library liburso_ext.so, include/ursonet_ext.h: bound by ext_lib() on first use
-_EXT_SIGS = {
-    "urso_pose_fuse_views": (_i, [C.POINTER(PoseFuseViewsArgs), _vp]),
-    # learnable loss weights (ursonet_amd/loss_weights.py): the plain signatures + s, ds and the loss-scale state in front of the stream
-    "urso_softmax_xent_fwd_bwd_lw": (_i, [_i, _i, _fp, _fp, _f, _i, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
-    "urso_rel_l2_fwd_bwd_lw": (_i, [_i, _i, _i, _fp, _fp, _f, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
-    "urso_absdot_fwd_bwd_lw": (_i, [_i, _i, _i, _i, _fp, _fp, _f, _i, _fp, _fp, _vp, _fp, _fp, _fp, _vp]),
-    # the weights' moving average (ursonet_amd/weight_ema.py): n, w, ema, state, loss-scale state | n, a, b
-    "urso_ema_update": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
-    "urso_ema_swap": (_i, [C.c_int64, _fp, _fp, _vp]),
-    # gradient accumulation (ursonet_amd/grad_accum.py): n, g, acc, first | n | n, g, acc, c, sqpart, nparts
-    "urso_grad_accum": (_i, [C.c_int64, _fp, _fp, _i, _vp]),
-    "urso_grad_accum_parts": (_i, [C.c_int64]),
-    "urso_grad_accum_close": (_i, [C.c_int64, _fp, _fp, _f, _fp, _i, _vp]),
-    # layer-wise adaptive rate scaling (ursonet_amd/lars.py): T, n_h | T, n_h, NB, blockmap_h, first_h | T, off_h, n_h, tab, blockmap, NB, w, g,
-    # part | T, first, adapt, NB, part, hyper, normsq, eta, eps, clip mode, trust, stat, loss-scale state | ... w, g, v, trust, hyper, normsq, ls
-    "urso_lars_blocks": (_i, [_i, _vp]),
-    "urso_lars_plan": (_i, [_i, _vp, _i, _vp, _vp]),
-    "urso_lars_norms": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _vp]),
-    "urso_lars_trust": (_i, [_i, _vp, _vp, _i, _fp, _fp, _fp, C.c_double, C.c_double, _i, _fp, _vp, _fp, _vp]),
-    "urso_lars_sgd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+# the libraries behind the main one (build.SIDE_SOURCES): name -> signatures of include/ursonet_<name>.h, bound by side_lib(name) on first use
+SIDE_SIGS = {
+    "ext": {
+        "urso_pose_fuse_views": (_i, [C.POINTER(PoseFuseViewsArgs), _vp]),
+        # learnable loss weights (ursonet_amd/loss_weights.py): the plain signatures + s, ds and the loss-scale state in front of the stream
+        "urso_softmax_xent_fwd_bwd_lw": (_i, [_i, _i, _fp, _fp, _f, _i, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
+        "urso_rel_l2_fwd_bwd_lw": (_i, [_i, _i, _i, _fp, _fp, _f, _i, _fp, _vp, _fp, _fp, _fp, _fp, _vp]),
+        "urso_absdot_fwd_bwd_lw": (_i, [_i, _i, _i, _i, _fp, _fp, _f, _i, _fp, _fp, _vp, _fp, _fp, _fp, _vp]),
+        # the weights' moving average (ursonet_amd/weight_ema.py): n, w, ema, state, loss-scale state | n, a, b
+        "urso_ema_update": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
+        "urso_ema_swap": (_i, [C.c_int64, _fp, _fp, _vp]),
+        # gradient accumulation (ursonet_amd/grad_accum.py): n, g, acc, first | n | n, g, acc, c, sqpart, nparts
+        "urso_grad_accum": (_i, [C.c_int64, _fp, _fp, _i, _vp]),
+        "urso_grad_accum_parts": (_i, [C.c_int64]),
+        "urso_grad_accum_close": (_i, [C.c_int64, _fp, _fp, _f, _fp, _i, _vp]),
+        # layer-wise adaptive rate scaling (ursonet_amd/lars.py): T, n_h | T, n_h, NB, blockmap_h, first_h | T, off_h, n_h, tab, blockmap, NB, w, g,
+        # part | T, first, adapt, NB, part, hyper, normsq, eta, eps, clip mode, trust, stat, loss-scale state | ... w, g, v, trust, hyper, normsq, ls
+        "urso_lars_blocks": (_i, [_i, _vp]),
+        "urso_lars_plan": (_i, [_i, _vp, _i, _vp, _vp]),
+        "urso_lars_norms": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _vp]),
+        "urso_lars_trust": (_i, [_i, _vp, _vp, _i, _fp, _fp, _fp, C.c_double, C.c_double, _i, _fp, _vp, _fp, _vp]),
+        "urso_lars_sgd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+    },
+    "opt": {
+        # LAMB (ursonet_amd/lamb.py): T, off_h, n_h, tab, blockmap, NB, w, g, m, v, vhat, hyper, state, normsq, part, loss-scale state | T, first,
+        # adapt, NB, part, normsq, eta, eps, clip mode, trust, stat, ls | T, off_h, n_h, tab, blockmap, NB, w, m, vhat, trust, hyper, state, normsq, ls
+        "urso_lamb_moments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+        "urso_lamb_trust": (_i, [_i, _vp, _vp, _i, _fp, _fp, C.c_double, C.c_double, _i, _fp, _vp, _fp, _vp]),
+        "urso_lamb_apply": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+    },
+    "train": {
+        # SAM (ursonet_amd/sam.py): n, w, g, w0, state | n, w, w0 | state, normsq, guard
+        "urso_sam_ascend": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
+        "urso_sam_descend": (_i, [C.c_int64, _fp, _fp, _vp]),
+        "urso_sam_settle": (_i, [_fp, _fp, _i, _vp]),
+        # BN recalibration (ursonet_amd/bn_recal.py): L, layers_h, n_stats, layers_d | L, layers_h, layers_d, n_stats, acc, t | ... acc, stats, t
+        "urso_bn_recal_plan": (_i, [_i, _vp, C.c_int64, _vp]),
+        "urso_bn_recal_add": (_i, [_i, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+        "urso_bn_recal_settle": (_i, [_i, _vp, _vp, C.c_int64, _vp, _fp, C.c_int64, _vp]),
+        # SWA / SWAG-diagonal (ursonet_amd/swa.py): n, w, mean, sq | null, state, loss-scale state | n, first, mean, sq, out, z_out | null, s, seed, sample
+        "urso_swa_update": (_i, [C.c_int64, _fp, _fp, _fp, _vp, _fp, _vp]),
+        "urso_swag_sample": (_i, [C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, C.c_float, C.c_uint64, _i, _vp]),
+        # ensemble inference (ursonet_amd/ensemble.py): urso_ens_add_args* | urso_ens_settle_args*
+        "urso_ens_add": (_i, [C.POINTER(EnsAddArgs), _vp]),
+        "urso_ens_settle": (_i, [C.POINTER(EnsSettleArgs), _vp]),
+        # temperature scaling (ursonet_amd/calibrate.py): urso_temp_stats_args* | urso_temp_reduce_args* | urso_temp_scale_args*
+        "urso_temp_stats": (_i, [C.POINTER(TempStatsArgs), _vp]),
+        "urso_temp_reduce": (_i, [C.POINTER(TempReduceArgs), _vp]),
+        "urso_temp_scale": (_i, [C.POINTER(TempScaleArgs), _vp]),
+    },
+    "infer": {
+        # conformal bounds (ursonet_amd/conformal.py): urso_conf_score_args* | urso_conf_bound_args*
+        "urso_conf_score": (_i, [C.POINTER(ConfScoreArgs), _vp]),
+        "urso_conf_bound": (_i, [C.POINTER(ConfBoundArgs), _vp]),
+    },
+    "feat": {
+        # domain-shift scores (ursonet_amd/domain.py): urso_feat_pool_args* | urso_feat_gram_args* | urso_feat_maha_args*
+        "urso_feat_pool": (_i, [C.POINTER(FeatPoolArgs), _vp]),
+        "urso_feat_gram_add": (_i, [C.POINTER(FeatGramArgs), _vp]),
+        "urso_feat_maha": (_i, [C.POINTER(FeatMahaArgs), _vp]),
+    },
+    "explain": {
+        # occlusion sensitivity (ursonet_amd/explain.py): urso_occl_fill_args* | urso_occl_score_args* | urso_occl_splat_args* | urso_heat_overlay_args*
+        "urso_occl_fill_u8": (_i, [C.POINTER(OcclFillArgs), _vp]),
+        "urso_occl_score": (_i, [C.POINTER(OcclScoreArgs), _vp]),
+        "urso_occl_splat": (_i, [C.POINTER(OcclSplatArgs), _vp]),
+        "urso_heat_overlay_u8": (_i, [C.POINTER(HeatOverlayArgs), _vp]),
+    },
 }
-EXT_SYMBOLS = sorted(_EXT_SIGS)
-# the optimizer library liburso_opt.so, include/ursonet_opt.h: bound by opt_lib() on first use
-_OPT_SIGS = {
-    # LAMB (ursonet_amd/lamb.py): T, off_h, n_h, tab, blockmap, NB, w, g, m, v, vhat, hyper, state, normsq, part, loss-scale state | T, first,
-    # adapt, NB, part, normsq, eta, eps, clip mode, trust, stat, ls | T, off_h, n_h, tab, blockmap, NB, w, m, vhat, trust, hyper, state, normsq, ls
-    "urso_lamb_moments": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
-    "urso_lamb_trust": (_i, [_i, _vp, _vp, _i, _fp, _fp, C.c_double, C.c_double, _i, _fp, _vp, _fp, _vp]),
-    "urso_lamb_apply": (_i, [_i, _vp, _vp, _vp, _vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
-}
-OPT_SYMBOLS = sorted(_OPT_SIGS)
+SIDE_SYMBOLS = {name: sorted(sigs) for name, sigs in SIDE_SIGS.items()}
 LAMB_STATE_INIT = (1.0, 1.0, 0.0)                                     # URSO_LAMB_STATE floats {p1, p2, kt} before the first step
-# the training library liburso_train.so, include/ursonet_train.h: bound by train_lib() on first use
-_TRAIN_SIGS = {
-    # SAM (ursonet_amd/sam.py): n, w, g, w0, state | n, w, w0 | state, normsq, guard
-    "urso_sam_ascend": (_i, [C.c_int64, _fp, _fp, _fp, _fp, _vp]),
-    "urso_sam_descend": (_i, [C.c_int64, _fp, _fp, _vp]),
-    "urso_sam_settle": (_i, [_fp, _fp, _i, _vp]),
-    # BN recalibration (ursonet_amd/bn_recal.py): L, layers_h, n_stats, layers_d | L, layers_h, layers_d, n_stats, acc, t | ... acc, stats, t
-    "urso_bn_recal_plan": (_i, [_i, _vp, C.c_int64, _vp]),
-    "urso_bn_recal_add": (_i, [_i, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
-    "urso_bn_recal_settle": (_i, [_i, _vp, _vp, C.c_int64, _vp, _fp, C.c_int64, _vp]),
-    # SWA / SWAG-diagonal (ursonet_amd/swa.py): n, w, mean, sq | null, state, loss-scale state | n, first, mean, sq, out, z_out | null, s, seed, sample
-    "urso_swa_update": (_i, [C.c_int64, _fp, _fp, _fp, _vp, _fp, _vp]),
-    "urso_swag_sample": (_i, [C.c_int64, C.c_int64, _fp, _fp, _fp, _fp, C.c_float, C.c_uint64, _i, _vp]),
-    # ensemble inference (ursonet_amd/ensemble.py): urso_ens_add_args* | urso_ens_settle_args*
-    "urso_ens_add": (_i, [C.POINTER(EnsAddArgs), _vp]),
-    "urso_ens_settle": (_i, [C.POINTER(EnsSettleArgs), _vp]),
-    # temperature scaling (ursonet_amd/calibrate.py): urso_temp_stats_args* | urso_temp_reduce_args* | urso_temp_scale_args*
-    "urso_temp_stats": (_i, [C.POINTER(TempStatsArgs), _vp]),
-    "urso_temp_reduce": (_i, [C.POINTER(TempReduceArgs), _vp]),
-    "urso_temp_scale": (_i, [C.POINTER(TempScaleArgs), _vp]),
-}
-TRAIN_SYMBOLS = sorted(_TRAIN_SIGS)
-# the inference library liburso_infer.so, include/ursonet_infer.h: bound by infer_lib() on first use
-_INFER_SIGS = {
-    # conformal bounds (ursonet_amd/conformal.py): urso_conf_score_args* | urso_conf_bound_args*
-    "urso_conf_score": (_i, [C.POINTER(ConfScoreArgs), _vp]),
-    "urso_conf_bound": (_i, [C.POINTER(ConfBoundArgs), _vp]),
-}
-INFER_SYMBOLS = sorted(_INFER_SIGS)
-# the feature library liburso_feat.so, include/ursonet_feat.h: bound by feat_lib() on first use
-_FEAT_SIGS = {
-    # domain-shift scores (ursonet_amd/domain.py): urso_feat_pool_args* | urso_feat_gram_args* | urso_feat_maha_args*
-    "urso_feat_pool": (_i, [C.POINTER(FeatPoolArgs), _vp]),
-    "urso_feat_gram_add": (_i, [C.POINTER(FeatGramArgs), _vp]),
-    "urso_feat_maha": (_i, [C.POINTER(FeatMahaArgs), _vp]),
-}
-FEAT_SYMBOLS = sorted(_FEAT_SIGS)
-# the explanation library liburso_explain.so, include/ursonet_explain.h: bound by explain_lib() on first use
-_EXPLAIN_SIGS = {
-    # occlusion sensitivity (ursonet_amd/explain.py): urso_occl_fill_args* | urso_occl_score_args* | urso_occl_splat_args* | urso_heat_overlay_args*
-    "urso_occl_fill_u8": (_i, [C.POINTER(OcclFillArgs), _vp]),
-    "urso_occl_score": (_i, [C.POINTER(OcclScoreArgs), _vp]),
-    "urso_occl_splat": (_i, [C.POINTER(OcclSplatArgs), _vp]),
-    "urso_heat_overlay_u8": (_i, [C.POINTER(HeatOverlayArgs), _vp]),
-}
-EXPLAIN_SYMBOLS = sorted(_EXPLAIN_SIGS)
 SAM_STATE = 8                                                         # URSO_SAM_STATE floats (ursonet_amd/sam.py names the fields)
 SWA_STATE = 8                                                         # URSO_SWA_STATE int32s (ursonet_amd/swa.py names the fields)
 
@@ -450,107 +436,22 @@ def _bind(lib, sigs):
 
 
 _bind(_lib, dict(_SIGS, **_LS_SIGS))
-_ext = None
+_side = {}
 
 
-def ext_lib():
-    """liburso_ext.so, loaded and bound on first use.  It calls into the main library (error text, launch profiler), so that one's
+def side_lib(name):
+    """liburso_<name>.so, loaded and bound on first use.  It calls into the main library (error text, launch profiler), so that one's
     symbols are first made visible to later loads (RTLD_NOLOAD | RTLD_GLOBAL promotes the copy already loaded, whichever variant it is)."""
-    global _ext
-    if _ext is None:
-        if not os.path.exists(EXT_LIB_PATH):
-            raise ImportError("liburso_ext.so not found at %s -- build it with `python -m ursonet_amd.build` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % EXT_LIB_PATH)
+    if name not in _side:
+        path = _build.SIDE_LIBS[name]
+        if not os.path.exists(path):
+            raise ImportError("liburso_%s.so not found at %s -- build it with `python -m ursonet_amd.build` "
+                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % (name, path))
         C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
-        lib = C.CDLL(EXT_LIB_PATH)
-        _bind(lib, _EXT_SIGS)
-        _ext = lib
-    return _ext
-
-
-_opt = None
-
-
-def opt_lib():
-    """liburso_opt.so, loaded and bound on first use, behind the main library as ext_lib() loads its own."""
-    global _opt
-    if _opt is None:
-        if not os.path.exists(OPT_LIB_PATH):
-            raise ImportError("liburso_opt.so not found at %s -- build it with `python -m ursonet_amd.build` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % OPT_LIB_PATH)
-        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
-        lib = C.CDLL(OPT_LIB_PATH)
-        _bind(lib, _OPT_SIGS)
-        _opt = lib
-    return _opt
-
-
-_train = None
-
-
-def train_lib():
-    """liburso_train.so, loaded and bound on first use, behind the main library as opt_lib() loads its own."""
-    global _train
-    if _train is None:
-        if not os.path.exists(TRAIN_LIB_PATH):
-            raise ImportError("liburso_train.so not found at %s -- build it with `python -m ursonet_amd.build` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % TRAIN_LIB_PATH)
-        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
-        lib = C.CDLL(TRAIN_LIB_PATH)
-        _bind(lib, _TRAIN_SIGS)
-        _train = lib
-    return _train
-
-
-_infer = None
-
-
-def infer_lib():
-    """liburso_infer.so, loaded and bound on first use, behind the main library as train_lib() loads its own."""
-    global _infer
-    if _infer is None:
-        if not os.path.exists(INFER_LIB_PATH):
-            raise ImportError("liburso_infer.so not found at %s -- build it with `python -m ursonet_amd.build` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % INFER_LIB_PATH)
-        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
-        lib = C.CDLL(INFER_LIB_PATH)
-        _bind(lib, _INFER_SIGS)
-        _infer = lib
-    return _infer
-
-
-_feat = None
-
-
-def feat_lib():
-    """liburso_feat.so, loaded and bound on first use, behind the main library as train_lib() loads its own."""
-    global _feat
-    if _feat is None:
-        if not os.path.exists(FEAT_LIB_PATH):
-            raise ImportError("liburso_feat.so not found at %s -- build it with `python -m ursonet_amd.build` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % FEAT_LIB_PATH)
-        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
-        lib = C.CDLL(FEAT_LIB_PATH)
-        _bind(lib, _FEAT_SIGS)
-        _feat = lib
-    return _feat
-
-
-_explain = None
-
-
-def explain_lib():
-    """liburso_explain.so, loaded and bound on first use, behind the main library as feat_lib() loads its own."""
-    global _explain
-    if _explain is None:
-        if not os.path.exists(EXPLAIN_LIB_PATH):
-            raise ImportError("liburso_explain.so not found at %s -- build it with `python -m ursonet_amd.build` "
-                              "(hipcc --offload-arch=gfx950). There is no CPU fallback." % EXPLAIN_LIB_PATH)
-        C.CDLL(LIB_PATH, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL | os.RTLD_NOW)
-        lib = C.CDLL(EXPLAIN_LIB_PATH)
-        _bind(lib, _EXPLAIN_SIGS)
-        _explain = lib
-    return _explain
+        lib = C.CDLL(path)
+        _bind(lib, SIDE_SIGS[name])
+        _side[name] = lib
+    return _side[name]
 
 
 def last_error():
@@ -973,7 +874,7 @@ def softmax_xent(B, K, logits, labels, weight, relu_mask, dt, loss, dz, row_ws, 
     rounding to dt (the *_ls entry points); None: the plain entry point.
     lw (here and in rel_l2 / absdot) = (s, ds): the learnable-loss-weight form of liburso_ext.so (the *_lw entry points; ls may be set too)."""
     if lw is not None:
-        _chk(ext_lib().urso_softmax_xent_fwd_bwd_lw(B, K, ptr(logits), ptr(labels), weight, int(relu_mask), dt, ptr(loss), ptr(dz), ptr(row_ws),
+        _chk(side_lib("ext").urso_softmax_xent_fwd_bwd_lw(B, K, ptr(logits), ptr(labels), weight, int(relu_mask), dt, ptr(loss), ptr(dz), ptr(row_ws),
                                                     *_lw_ptrs(lw), _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)),
              "urso_softmax_xent_fwd_bwd_lw")
         return
@@ -996,7 +897,7 @@ def rel_l2_from_norms(B, D, ld, gt, pred, weight, gscale, dt, norms, loss, dpred
 
 def rel_l2(B, D, ld, gt, pred, weight, dt, loss, dpred, norms=None, stream=None, ls=None, lw=None):
     if lw is not None:
-        _chk(ext_lib().urso_rel_l2_fwd_bwd_lw(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), ptr(norms), *_lw_ptrs(lw),
+        _chk(side_lib("ext").urso_rel_l2_fwd_bwd_lw(B, D, ld, ptr(gt), ptr(pred), weight, dt, ptr(loss), ptr(dpred), ptr(norms), *_lw_ptrs(lw),
                                               _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_rel_l2_fwd_bwd_lw")
         return
     if ls is not None:
@@ -1009,7 +910,7 @@ def rel_l2(B, D, ld, gt, pred, weight, dt, loss, dpred, norms=None, stream=None,
 
 def absdot(B, D, ld, normalize, gt, x, weight, dt, q, loss, dx, stream=None, ls=None, lw=None):
     if lw is not None:
-        _chk(ext_lib().urso_absdot_fwd_bwd_lw(B, D, ld, int(normalize), ptr(gt), ptr(x), weight, dt, ptr(q), ptr(loss), ptr(dx), *_lw_ptrs(lw),
+        _chk(side_lib("ext").urso_absdot_fwd_bwd_lw(B, D, ld, int(normalize), ptr(gt), ptr(x), weight, dt, ptr(q), ptr(loss), ptr(dx), *_lw_ptrs(lw),
                                               _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_absdot_fwd_bwd_lw")
         return
     if ls is not None:
@@ -1057,19 +958,19 @@ def ema_update(n, w, ema, state, stream=None, ls=None):
     (ursonet_amd.weight_ema.update32 / next_state on the device).  ls: the loss-scale state; a step it marks as skipped changes nothing."""
     assert w.dtype == torch.float32 and ema.dtype == torch.float32 and state.dtype == torch.float32 and state.numel() >= EMA_FIELDS
     assert 0 <= n <= min(w.numel(), ema.numel())
-    _chk(ext_lib().urso_ema_update(n, ptr(w), ptr(ema), ptr(state), _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)),
+    _chk(side_lib("ext").urso_ema_update(n, ptr(w), ptr(ema), ptr(state), _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)),
          "urso_ema_update")
 
 
 def ema_swap(n, a, b, stream=None):
     """urso_ema_swap (liburso_ext.so): exchange the bit patterns of the first n elements of two 4-byte-element buffers in place."""
     assert a.element_size() == 4 and b.element_size() == 4 and 0 <= n <= min(a.numel(), b.numel())
-    _chk(ext_lib().urso_ema_swap(n, ptr(a), ptr(b), stream_ptr(stream)), "urso_ema_swap")
+    _chk(side_lib("ext").urso_ema_swap(n, ptr(a), ptr(b), stream_ptr(stream)), "urso_ema_swap")
 
 
 def grad_accum_parts(n):
     """urso_grad_accum_parts (liburso_ext.so): the slots urso_grad_accum_close writes for n elements (its block count; needs no GPU)."""
-    return int(ext_lib().urso_grad_accum_parts(int(n)))
+    return int(side_lib("ext").urso_grad_accum_parts(int(n)))
 
 
 def sam_ascend(n, w, g, w0, state, stream=None):
@@ -1077,20 +978,20 @@ def sam_ascend(n, w, g, w0, state, stream=None):
     with s = rho / (sqrtf(normsq) + eps); scale, applied and the counts go into state (ursonet_amd.sam.ascend32 / ascend_state32)."""
     assert all(x.dtype == torch.float32 for x in (w, g, w0, state)) and state.numel() >= SAM_STATE
     assert 0 <= n <= min(w.numel(), g.numel(), w0.numel())
-    _chk(train_lib().urso_sam_ascend(n, ptr(w), ptr(g), ptr(w0), ptr(state), stream_ptr(stream)), "urso_sam_ascend")
+    _chk(side_lib("train").urso_sam_ascend(n, ptr(w), ptr(g), ptr(w0), ptr(state), stream_ptr(stream)), "urso_sam_ascend")
 
 
 def sam_descend(n, w, w0, stream=None):
     """urso_sam_descend (liburso_train.so): w = w0, the bits, over n 4-byte elements."""
     assert w.element_size() == 4 and w0.element_size() == 4 and 0 <= n <= min(w.numel(), w0.numel())
-    _chk(train_lib().urso_sam_descend(n, ptr(w), ptr(w0), stream_ptr(stream)), "urso_sam_descend")
+    _chk(side_lib("train").urso_sam_descend(n, ptr(w), ptr(w0), stream_ptr(stream)), "urso_sam_descend")
 
 
 def sam_settle(state, normsq, guard=True, stream=None):
     """urso_sam_settle (liburso_train.so): a skipped step (guard and a non-finite normsq) takes its ascents out of applied_total; pending = 0
     (ursonet_amd.sam.settle32)."""
     assert state.dtype == torch.float32 and state.numel() >= SAM_STATE and normsq.dtype == torch.float32
-    _chk(train_lib().urso_sam_settle(ptr(state), ptr(normsq), 1 if guard else 0, stream_ptr(stream)), "urso_sam_settle")
+    _chk(side_lib("train").urso_sam_settle(ptr(state), ptr(normsq), 1 if guard else 0, stream_ptr(stream)), "urso_sam_settle")
 
 
 def swa_update(n, w, mean, sq, state, stream=None, ls=None):
@@ -1100,7 +1001,7 @@ def swa_update(n, w, mean, sq, state, stream=None, ls=None):
     assert w.dtype == torch.float32 and mean.dtype == torch.float32 and (sq is None or sq.dtype == torch.float32)
     assert state.dtype == torch.int32 and state.numel() >= SWA_STATE
     assert 0 <= n <= min(w.numel(), mean.numel()) and (sq is None or n <= sq.numel())
-    _chk(train_lib().urso_swa_update(n, ptr(w), ptr(mean), ptr(sq) if sq is not None else None, ptr(state),
+    _chk(side_lib("train").urso_swa_update(n, ptr(w), ptr(mean), ptr(sq) if sq is not None else None, ptr(state),
                                      _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_swa_update")
 
 
@@ -1109,7 +1010,7 @@ def swag_sample(n, mean, sq, out, s, seed, sample, z_out=None, first=0, stream=N
     Philox normals of flat-buffer elements first .. first + n - 1 (ursonet_amd.swa.normals / sample32); z_out, when given, receives z."""
     assert all(x is None or x.dtype == torch.float32 for x in (mean, sq, out, z_out))
     assert 0 <= n <= min(x.numel() for x in (mean, sq, out) + ((z_out,) if z_out is not None else ()))
-    _chk(train_lib().urso_swag_sample(n, int(first), ptr(mean), ptr(sq), ptr(out), ptr(z_out) if z_out is not None else None, float(s),
+    _chk(side_lib("train").urso_swag_sample(n, int(first), ptr(mean), ptr(sq), ptr(out), ptr(z_out) if z_out is not None else None, float(s),
                                       int(seed), int(sample), stream_ptr(stream)), "urso_swag_sample")
 
 
@@ -1124,7 +1025,7 @@ def ens_add(B, n, row0, logits, acc, stat, first, stream=None):
     a.B, a.n, a.row0, a.K, a.first, a.pad = int(B), int(n), int(row0), int(logits.shape[1]), 1 if first else 0, 0
     a.logits, a.ld = _rows(logits)
     a.acc, a.stat = ptr(acc), ptr(stat)
-    _chk(train_lib().urso_ens_add(C.byref(a), stream_ptr(stream)), "urso_ens_add")
+    _chk(side_lib("train").urso_ens_add(C.byref(a), stream_ptr(stream)), "urso_ens_add")
 
 
 def ens_settle(n, row0, M, acc, stat, logp, table, stream=None):
@@ -1137,7 +1038,7 @@ def ens_settle(n, row0, M, acc, stat, logp, table, stream=None):
     a = EnsSettleArgs()
     a.n, a.row0, a.K, a.M = int(n), int(row0), int(acc.shape[1]), int(M)
     a.acc, a.stat, a.logp, a.table = ptr(acc), ptr(stat), ptr(logp), ptr(table)
-    _chk(train_lib().urso_ens_settle(C.byref(a), stream_ptr(stream)), "urso_ens_settle")
+    _chk(side_lib("train").urso_ens_settle(C.byref(a), stream_ptr(stream)), "urso_ens_settle")
 
 
 def _betas(field, betas):
@@ -1161,7 +1062,7 @@ def temp_stats(B, n, row0, betas, logits, target, out, stream=None):
     a.logits, a.ld_z = _rows(logits)
     a.target, a.ld_y = _rows(target)
     a.out = ptr(out)
-    _chk(train_lib().urso_temp_stats(C.byref(a), stream_ptr(stream)), "urso_temp_stats")
+    _chk(side_lib("train").urso_temp_stats(C.byref(a), stream_ptr(stream)), "urso_temp_stats")
 
 
 def temp_reduce(N, betas, rows, totals, stream=None):
@@ -1173,7 +1074,7 @@ def temp_reduce(N, betas, rows, totals, stream=None):
     a.N, a.pad = int(N), 0
     a.J = _betas(a.beta, betas)
     a.rows, a.totals = ptr(rows), ptr(totals)
-    _chk(train_lib().urso_temp_reduce(C.byref(a), stream_ptr(stream)), "urso_temp_reduce")
+    _chk(side_lib("train").urso_temp_reduce(C.byref(a), stream_ptr(stream)), "urso_temp_reduce")
 
 
 def temp_scale(B, n, beta, src, dst, stream=None):
@@ -1185,7 +1086,7 @@ def temp_scale(B, n, beta, src, dst, stream=None):
     a.B, a.n, a.K, a.pad, a.beta = int(B), int(n), int(src.shape[1]), 0, float(beta)
     a.in_, a.ld_in = _rows(src)
     a.out, a.ld_out = _rows(dst)
-    _chk(train_lib().urso_temp_scale(C.byref(a), stream_ptr(stream)), "urso_temp_scale")
+    _chk(side_lib("train").urso_temp_scale(C.byref(a), stream_ptr(stream)), "urso_temp_scale")
 
 
 def _conf_args(a, B, n, row0, metric, logits, bin_map, est, out):
@@ -1212,7 +1113,7 @@ def conf_score(B, n, row0, metric, logits, bin_map, est, ref, out, stream=None):
     assert ref.dtype == torch.float64 and ref.shape[0] >= B and ref.shape[1] == D
     a.ref, a.ld_ref = _rows(ref)
     a.pad = 0
-    _chk(infer_lib().urso_conf_score(C.byref(a), stream_ptr(stream)), "urso_conf_score")
+    _chk(side_lib("infer").urso_conf_score(C.byref(a), stream_ptr(stream)), "urso_conf_score")
 
 
 def conf_bound(B, n, row0, metric, q, logits, bin_map, est, out, stream=None):
@@ -1220,7 +1121,7 @@ def conf_bound(B, n, row0, metric, q, logits, bin_map, est, out, stream=None):
     mass, into rows row0 .. of out (fp64 [rows, CONF_COLS]); arguments as conf_score's, q > 0 (ursonet_amd.conformal.bound64)."""
     a, _D = _conf_args(ConfBoundArgs(), B, n, row0, metric, logits, bin_map, est, out)
     a.q = float(q)
-    _chk(infer_lib().urso_conf_bound(C.byref(a), stream_ptr(stream)), "urso_conf_bound")
+    _chk(side_lib("infer").urso_conf_bound(C.byref(a), stream_ptr(stream)), "urso_conf_bound")
 
 
 def feat_pool(B, n, row0, grid, act, out, stream=None):
@@ -1234,7 +1135,7 @@ def feat_pool(B, n, row0, grid, act, out, stream=None):
     a.act = ptr(act)
     a.out, a.ld = _rows(out)
     assert out.shape[1] >= a.gh * a.gw * a.C, "the table is narrower than the feature row"
-    _chk(feat_lib().urso_feat_pool(C.byref(a), stream_ptr(stream)), "urso_feat_pool")
+    _chk(side_lib("feat").urso_feat_pool(C.byref(a), stream_ptr(stream)), "urso_feat_pool")
 
 
 def feat_gram_add(B, n, row0, x, centre, s, g, stream=None):
@@ -1248,7 +1149,7 @@ def feat_gram_add(B, n, row0, x, centre, s, g, stream=None):
     a.x, a.ld_x = _rows(x)
     a.g, a.ld_g = _rows(g)
     a.centre, a.s = ptr(centre), ptr(s)
-    _chk(feat_lib().urso_feat_gram_add(C.byref(a), stream_ptr(stream)), "urso_feat_gram_add")
+    _chk(side_lib("feat").urso_feat_gram_add(C.byref(a), stream_ptr(stream)), "urso_feat_gram_add")
 
 
 def feat_whiten_t(W, device):
@@ -1268,7 +1169,7 @@ def feat_maha(B, n, row0, x, mean, wt, out, stream=None):
     a.x, a.ld_x = _rows(x)
     a.wt, a.ld_w = _rows(wt)
     a.mean, a.out = ptr(mean), ptr(out)
-    _chk(feat_lib().urso_feat_maha(C.byref(a), stream_ptr(stream)), "urso_feat_maha")
+    _chk(side_lib("feat").urso_feat_maha(C.byref(a), stream_ptr(stream)), "urso_feat_maha")
 
 
 def occl_fill_u8(src, rects, fill, out, n=None, stream=None):
@@ -1283,7 +1184,7 @@ def occl_fill_u8(src, rects, fill, out, n=None, stream=None):
     for c, v in enumerate(list(fill)[:4]):
         a.fill[c] = int(v)
     a.src, a.rects, a.out = ptr(src), ptr(rects), ptr(out)
-    _chk(explain_lib().urso_occl_fill_u8(C.byref(a), stream_ptr(stream)), "urso_occl_fill_u8")
+    _chk(side_lib("explain").urso_occl_fill_u8(C.byref(a), stream_ptr(stream)), "urso_occl_fill_u8")
 
 
 def occl_score(B, n, row0, dec0, dec, out, ori_z0=None, ori_z=None, loc_z0=None, loc_z=None, stream=None):
@@ -1307,7 +1208,7 @@ def occl_score(B, n, row0, dec0, dec, out, ori_z0=None, ori_z=None, loc_z0=None,
         setattr(a, head + "_z0", ptr(z0))
         setattr(a, head + "_z", zp)
     a.dec0, a.dec, a.out = ptr(dec0), ptr(dec), ptr(out)
-    _chk(explain_lib().urso_occl_score(C.byref(a), stream_ptr(stream)), "urso_occl_score")
+    _chk(side_lib("explain").urso_occl_score(C.byref(a), stream_ptr(stream)), "urso_occl_score")
 
 
 def occl_splat(scores, cols, rects, window, out, stream=None):
@@ -1323,7 +1224,7 @@ def occl_splat(scores, cols, rects, window, out, stream=None):
         a.cols[m] = c
     a.scores, a.ld = _rows(scores)
     a.rects, a.out = ptr(rects), ptr(out)
-    _chk(explain_lib().urso_occl_splat(C.byref(a), stream_ptr(stream)), "urso_occl_splat")
+    _chk(side_lib("explain").urso_occl_splat(C.byref(a), stream_ptr(stream)), "urso_occl_splat")
 
 
 def heat_overlay_u8(heat, lo, scale, lut, alpha, img, stream=None):
@@ -1335,13 +1236,13 @@ def heat_overlay_u8(heat, lo, scale, lut, alpha, img, stream=None):
     a = HeatOverlayArgs()
     a.h, a.w, a.alpha, a.pad, a.ld_img, a.lo, a.scale = h, w, int(alpha), 0, int(img.stride(0)), float(lo), float(scale)
     a.map, a.lut, a.img = ptr(heat), ptr(lut), img.data_ptr()
-    _chk(explain_lib().urso_heat_overlay_u8(C.byref(a), stream_ptr(stream)), "urso_heat_overlay_u8")
+    _chk(side_lib("explain").urso_heat_overlay_u8(C.byref(a), stream_ptr(stream)), "urso_heat_overlay_u8")
 
 
 def grad_accum(n, g, acc, first, stream=None):
     """urso_grad_accum (liburso_ext.so): acc = g (first: the bits) or acc += g over n fp32 elements (ursonet_amd.grad_accum.first32 / add32)."""
     assert g.dtype == torch.float32 and acc.dtype == torch.float32 and 0 <= n <= min(g.numel(), acc.numel())
-    _chk(ext_lib().urso_grad_accum(n, ptr(g), ptr(acc), 1 if first else 0, stream_ptr(stream)), "urso_grad_accum")
+    _chk(side_lib("ext").urso_grad_accum(n, ptr(g), ptr(acc), 1 if first else 0, stream_ptr(stream)), "urso_grad_accum")
 
 
 def grad_accum_close(n, g, acc, c, sqpart, stream=None):
@@ -1349,7 +1250,7 @@ def grad_accum_close(n, g, acc, c, sqpart, stream=None):
     sum of squares of what it stored into sqpart (grad_accum_parts(n) slots, for sqnorm_final)."""
     assert g.dtype == torch.float32 and acc.dtype == torch.float32 and sqpart.dtype == torch.float32
     assert 0 <= n <= min(g.numel(), acc.numel())
-    _chk(ext_lib().urso_grad_accum_close(n, ptr(g), ptr(acc), float(c), ptr(sqpart), sqpart.numel(), stream_ptr(stream)),
+    _chk(side_lib("ext").urso_grad_accum_close(n, ptr(g), ptr(acc), float(c), ptr(sqpart), sqpart.numel(), stream_ptr(stream)),
          "urso_grad_accum_close")
 
 
@@ -1364,7 +1265,7 @@ class LarsPlan(object):
         T = self.T = len(self.tensors)
         self.off_h = (C.c_int64 * max(T, 1))(*[o for o, _, _ in self.tensors])
         self.n_h = (C.c_int64 * max(T, 1))(*[n for _, n, _ in self.tensors])
-        lib = ext_lib()
+        lib = side_lib("ext")
         nb = lib.urso_lars_blocks(T, self.n_h)
         _chk(min(nb, 0), "urso_lars_blocks")
         self.nblocks = int(nb)
@@ -1384,19 +1285,19 @@ class LarsPlan(object):
     def norms(self, w, g, stream=None):
         """part[b] = (sum of w^2, sum of g^2) over block b's chunk (ursonet_amd.lars.slot_sums32)."""
         assert w.dtype == torch.float32 and g.dtype == torch.float32
-        _chk(ext_lib().urso_lars_norms(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g),
+        _chk(side_lib("ext").urso_lars_norms(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g),
                                        ptr(self.part), stream_ptr(stream)), "urso_lars_norms")
 
     def trust_ratios(self, hyper, normsq, eta, eps, clip_mode, stream=None, ls=None):
         """trust[t] and stat[t] = (|w|, |g|, q) from the slots (ursonet_amd.lars.norms64 / trust32); ls: the loss-scaled form."""
-        _chk(ext_lib().urso_lars_trust(self.T, ptr(self.first), ptr(self.adapt), self.nblocks, ptr(self.part), ptr(hyper), ptr(normsq),
+        _chk(side_lib("ext").urso_lars_trust(self.T, ptr(self.first), ptr(self.adapt), self.nblocks, ptr(self.part), ptr(hyper), ptr(normsq),
                                        float(eta), float(eps), 1 if clip_mode else 0, ptr(self.trust), ptr(self.stat),
                                        _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_lars_trust")
 
     def sgd(self, w, g, v, hyper, normsq, stream=None, ls=None):
         """The update with each tensor's trust (ursonet_amd.lars.update32); ls: the loss-scaled form."""
         assert w.dtype == torch.float32 and g.dtype == torch.float32 and v.dtype == torch.float32
-        _chk(ext_lib().urso_lars_sgd(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(v),
+        _chk(side_lib("ext").urso_lars_sgd(self.T, self.off_h, self.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(v),
                                      ptr(self.trust), ptr(hyper), ptr(normsq), _ls_ptr(ls) if ls is not None else None,
                                      stream_ptr(stream)), "urso_lars_sgd")
 
@@ -1422,7 +1323,7 @@ class BnRecalPlan(object):
             assert m.dtype == torch.float32 and v.dtype == torch.float32 and m.numel() == v.numel()
             row.bmean, row.bvar, row.N, row.M, row.off_mean, row.off_var = ptr(m), ptr(v), m.numel(), M, om, ov
         self.table = torch.zeros(max(L, 1) * C.sizeof(BnRecalLayer) // 8, dtype=torch.int64, device=device)
-        _chk(train_lib().urso_bn_recal_plan(L, C.addressof(self.table_h), self.n_stats, ptr(self.table)), "urso_bn_recal_plan")
+        _chk(side_lib("train").urso_bn_recal_plan(L, C.addressof(self.table_h), self.n_stats, ptr(self.table)), "urso_bn_recal_plan")
         self.acc = torch.zeros(max(self.n_stats, 1), dtype=torch.float64, device=device)
         self.t = 0
 
@@ -1433,14 +1334,14 @@ class BnRecalPlan(object):
 
     def add(self, stream=None):
         """One more batch: the layers' bmean / bvar as they are now go into acc (ursonet_amd.bn_recal.pool_add64); t advances."""
-        _chk(train_lib().urso_bn_recal_add(self.L, C.addressof(self.table_h), ptr(self.table), self.n_stats, ptr(self.acc), self.t,
+        _chk(side_lib("train").urso_bn_recal_add(self.L, C.addressof(self.table_h), ptr(self.table), self.n_stats, ptr(self.acc), self.t,
                                            stream_ptr(stream)), "urso_bn_recal_add")
         self.t += 1
 
     def settle(self, stats, stream=None):
         """stats[slices] = the pooled float32 statistics (ursonet_amd.bn_recal.pool_settle32); refused before anything was added."""
         assert stats.dtype == torch.float32 and stats.numel() >= self.n_stats
-        _chk(train_lib().urso_bn_recal_settle(self.L, C.addressof(self.table_h), ptr(self.table), self.n_stats, ptr(self.acc), ptr(stats),
+        _chk(side_lib("train").urso_bn_recal_settle(self.L, C.addressof(self.table_h), ptr(self.table), self.n_stats, ptr(self.acc), ptr(stats),
                                               self.t, stream_ptr(stream)), "urso_bn_recal_settle")
 
 
@@ -1456,7 +1357,7 @@ class LambPlan(object):
         self.tab, self.blockmap, self.first, self.adapt = tb.tab, tb.blockmap, tb.first, tb.adapt
         self.part, self.trust, self.stat = tb.part, tb.trust, tb.stat          # (allocated there, written by these launches alone)
         self.state = torch.tensor(LAMB_STATE_INIT, dtype=torch.float32, device=device)
-        opt_lib()                                                            # a missing library is an error here, not at the first step
+        side_lib("opt")                                                            # a missing library is an error here, not at the first step
 
     def reset(self):
         """state = {1, 1, 0}: before the first step."""
@@ -1467,13 +1368,13 @@ class LambPlan(object):
         direction32); ls: the loss-scaled form."""
         assert all(x.dtype == torch.float32 for x in (w, g, m, v, vhat, hyper)) and hyper.numel() >= 8
         tb = self.tables
-        _chk(opt_lib().urso_lamb_moments(self.T, tb.off_h, tb.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(m),
+        _chk(side_lib("opt").urso_lamb_moments(self.T, tb.off_h, tb.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(g), ptr(m),
                                          ptr(v), ptr(vhat), ptr(hyper), ptr(self.state), ptr(normsq), ptr(self.part),
                                          _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_lamb_moments")
 
     def trust_ratios(self, normsq, eta, eps, clip_mode, stream=None, ls=None):
         """trust[t] and stat[t] = (|w|, |r|, q) from the slots (ursonet_amd.lars.norms64, ursonet_amd.lamb.trust32)."""
-        _chk(opt_lib().urso_lamb_trust(self.T, ptr(self.first), ptr(self.adapt), self.nblocks, ptr(self.part), ptr(normsq), float(eta),
+        _chk(side_lib("opt").urso_lamb_trust(self.T, ptr(self.first), ptr(self.adapt), self.nblocks, ptr(self.part), ptr(normsq), float(eta),
                                        float(eps), 1 if clip_mode else 0, ptr(self.trust), ptr(self.stat),
                                        _ls_ptr(ls) if ls is not None else None, stream_ptr(stream)), "urso_lamb_trust")
 
@@ -1481,7 +1382,7 @@ class LambPlan(object):
         """w = w - (lr * trust) * r with each tensor's trust (ursonet_amd.lamb.apply32)."""
         assert w.dtype == torch.float32 and m.dtype == torch.float32 and vhat.dtype == torch.float32
         tb = self.tables
-        _chk(opt_lib().urso_lamb_apply(self.T, tb.off_h, tb.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(m), ptr(vhat),
+        _chk(side_lib("opt").urso_lamb_apply(self.T, tb.off_h, tb.n_h, ptr(self.tab), ptr(self.blockmap), self.nblocks, ptr(w), ptr(m), ptr(vhat),
                                        ptr(self.trust), ptr(hyper), ptr(self.state), ptr(normsq), _ls_ptr(ls) if ls is not None else None,
                                        stream_ptr(stream)), "urso_lamb_apply")
 
@@ -1567,7 +1468,7 @@ def pose_fuse_views(B, n, row0, est, r, qr, table, loc_gt=None, q_gt=None, est_v
     a.est_view_rows = int(B if est_view_rows is None else est_view_rows)
     assert est.shape[0] >= (a.V - 1) * a.est_view_rows + a.B and table.shape[0] >= a.row0 + a.n and table.shape[1] == FUSE_COLS
     a.r, a.qr, a.loc_gt, a.q_gt, a.table = ptr(r), ptr(qr), ptr(loc_gt), ptr(q_gt), ptr(table)
-    _chk(ext_lib().urso_pose_fuse_views(C.byref(a), stream_ptr(stream)), "urso_pose_fuse_views")
+    _chk(side_lib("ext").urso_pose_fuse_views(C.byref(a), stream_ptr(stream)), "urso_pose_fuse_views")
 
 
 def warp_perspective(B, H, W, Cc, interp, src, m, dst, stream=None):

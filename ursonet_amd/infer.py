@@ -55,6 +55,23 @@ def loader_workers(cfg, workers=None):
     return int(getattr(cfg, "LOADER_WORKERS", min(8, os.cpu_count() or 1))) if workers is None else workers
 
 
+def refuse_launcher(model, who, reason):
+    """ValueError under a data-parallel launcher (WORLD_SIZE > 1, or a model built under one; model may be None): the commands that walk
+    a whole dataset in one process.  `reason` is what each rank would do."""
+    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1 or getattr(model, "_dp", None) is not None or int(getattr(model, "_world", 1)) > 1:
+        raise ValueError("%s is not supported under a data-parallel launcher: each rank would %s; run it in a plain process" % (who, reason))
+
+
+class Subset(object):
+    """`dataset` with image_ids cut to the chosen ones; everything else is the dataset's."""
+
+    def __init__(self, dataset, ids):
+        self._dataset, self.image_ids = dataset, list(ids)
+
+    def __getattr__(self, name):
+        return getattr(self._dataset, name)
+
+
 def eval_columns(res, table, loc_class):
     """Sets the fields every result of an EVAL table has on `res`; returns the table as fp64 [N, EVAL_COLS] for the caller's own."""
     from . import hip
