@@ -193,13 +193,8 @@ def _batch(seed, keypoints=False):
 
 
 def _state_buffers(eng):
-    names = ["flat_w", "flat_v", "flat_g", "normsq", "flat_stats"]
-    if eng.adam:
-        names += ["flat_v2", "flat_vhat", "hyper"]
-    for name in ("lamb_state", "flat_ema", "ema_state", "flat_acc", "ls_state"):
-        if getattr(eng, name, None) is not None:
-            names.append(name)
-    return names
+    """The engine's own table of persistent state (Engine.train_state) and what a step leaves beside it."""
+    return [name for name, _ in eng.train_state()] + ["flat_g", "normsq"]
 
 
 def _unfused_normsq(eng):

@@ -24,6 +24,7 @@ from . import bn_recal, grad_accum, hip, lamb, lars, loss_scale, loss_weights, s
 from .config import compute_dtype_name
 from .graph import BN_EPS, build_graph, conv_flops
 from .plan_state import _Act, _Conv, _Launch, _PendingLaunches, _round_up
+from .train_state import weights_location
 
 BN_MOMENTUM = 0.99          # Keras BatchNormalization default (net.py:60-76 passes none)
 
@@ -60,6 +61,40 @@ class _no_gc(object):
         return False
 
 
+def _checked_params(graph, params, strict, only=None):
+    """(layer, weight, host float32 tensor) of every tensor of `graph` that params {layer: {weight: array}} holds, in the graph's order,
+    as the loaders copy them.  A missing layer is a KeyError if strict and skipped otherwise; a wrong shape is a ValueError.  only: a
+    container of (layer, weight) outside which tensors are passed over unread (Engine.slices: the trainable ones)."""
+    for ln, ws in graph.params.items():
+        if ln not in params:
+            if strict:
+                raise KeyError("missing layer %r" % ln)
+            continue
+        for wn, shape in ws.items():
+            if only is not None and (ln, wn) not in only:
+                continue
+            a = np.asarray(params[ln][wn], dtype=np.float32)
+            if tuple(a.shape) != tuple(shape):
+                raise ValueError("layer %s weight %s: shape %s != expected %s" % (ln, wn, a.shape, shape))
+            yield ln, wn, torch.from_numpy(np.ascontiguousarray(a))
+
+
+class _StandIn(object):
+    """Context manager of Engine.ema_weights() / swa_weights() / swag_weights(): `enter` puts another set of weights into flat_w, `leave`
+    brings the raw ones back -- also after an exception inside the block, which goes on to the caller.  Yields the engine."""
+
+    def __init__(self, eng, enter, leave):
+        self.eng, self.enter, self.leave = eng, enter, leave
+
+    def __enter__(self):
+        self.enter()
+        return self.eng
+
+    def __exit__(self, *exc):
+        self.leave()
+        return False
+
+
 class Engine(object):
     def __init__(self, config, mode, batch=None, seed=1234, device=None, randomize_bn=False, grad_bucket_bytes=1 << 40):
         assert mode in ("training", "inference")
@@ -90,47 +125,24 @@ class Engine(object):
         self._graphs = None
         # state that outlives a re-plan (set_trainable, ursonet_amd/dp.py); halo_ws: its first 4 KiB of flags must stay zero
         self.plan_version, self.halo_ws, self.rel_scale = 0, None, None
+        # the persistent training state: train_state() lists it, _plan_device_state() creates the small states once,
+        # _stand_in says which set of weights lies in flat_w.  None / 1 / [] = the feature is off and none of it exists
         self.hyper = self.flat_v2 = self.flat_vhat = None
-        self.ls_state = self._ls_init = None           # Config.LOSS_SCALE: the device-side loss-scale state (ursonet_amd/loss_scale.py), created once like hyper
-        # Config.WEIGHT_EMA: a second flat buffer that follows flat_w behind every optimizer step, and its device-side
-        # schedule state (ursonet_amd/weight_ema.py); both created once like hyper.  ema_swapped: flat_w holds the average right now (swap_ema)
-        self.flat_ema = self.ema_state = self._ema_init = None
-        self.ema_swapped = False
-        if weight_ema.enabled(config, mode):
-            weight_ema.initial_state(config, self.world_size_hint())       # ValueError before anything is allocated
-        # Config.SWA: the equal-weight running mean of the weights collected every SWA performed steps (flat_swa), with
-        # SWA_VARIANCE the running mean of their squares (flat_swa_sq), and the int32 device-side state (ursonet_amd/swa.py); created once like
-        # hyper.  swa_swapped: flat_w holds the average right now (swap_swa); _swag_hold: the raw weights while a sample stands in flat_w
-        self.flat_swa = self.flat_swa_sq = self.swa_state = self._swa_init = self._swag_hold = None
-        self.swa_swapped = self._swag_active = False
-        if mode == "training":
-            swa.validate(config, self.world_size_hint())                   # ValueError before anything is allocated
-        # Config.GRAD_ACCUM_STEPS: k > 1 = a second flat buffer that sums the gradients of k micro-steps and the host-side
-        # index of the next micro-step; step() replays one captured graph per launch role (ursonet_amd/grad_accum.py).  1 = none of it exists
-        self.flat_acc, self.accum_k, self.accum_micro, self.accum_ops, self._accum_roles = None, 1, 0, [], []
-        if mode == "training":
-            grad_accum.validate(config, self.world_size_hint())            # ValueError before anything is allocated
-        # Config.LARS: the tables and outputs of the three launches that stand where the plain SGD launch stands
-        # (hip.LarsPlan, rebuilt with every plan); None = none of it exists
-        self.lars_plan = None
-        if mode == "training":
-            lars.validate(config, self.world_size_hint())                  # ValueError before anything is allocated
-        # Config.LAMB: the same for the three launches that stand where the plain Adam launch stands (hip.LambPlan);
-        # its state {p1, p2, kt} is created ONCE, like hyper: a later set_trainable() rebuilds the plan and must not restart the tick
-        self.lamb_plan, self.lamb_state = None, None
-        if mode == "training":
-            lamb.validate(config, self.world_size_hint())                  # ValueError before anything is allocated
-        # Config.SAM: the step runs its forward / backward pass twice, around the ascent to w + rho g / |g|.  flat_w0 keeps
-        # the weights meanwhile (pure scratch); sam_state {rho, eps, normsq, scale, applied, applied_total, pending, 0} is created ONCE, like hyper;
-        # sam_ops are the three launches between and behind the passes (_plan_sam).  None / [] = none of it exists
-        self.sam_state, self._sam_keys, self.flat_w0, self.sam_loss, self.sam_stats, self.sam_ops = None, None, None, None, None, []
-        if mode == "training":
-            sam.validate(config, self.world_size_hint())                   # ValueError before anything is allocated
-        # Config.BN_RECAL_BATCHES: train()'s recalibration of the averaged weights' BN statistics; the engine only
-        # refuses a bad key.  _recal_plan: (plan_version, hip.BnRecalPlan) once bn_recal_begin() ran; _recal_stats: its clone of flat_stats
-        self._recal_plan = self._recal_stats = None
-        if mode == "training":
-            bn_recal.validate(config, self.world_size_hint())              # ValueError before anything is allocated
+        self._state_init = {}                          # attribute of a small device state -> the initial values it last started from
+        self._stand_in = None                          # None | "ema" | "swa" | "swag": what stands in flat_w for the raw weights right now
+        self.ls_state = None                           # Config.LOSS_SCALE
+        self.flat_ema = self.ema_state = None          # Config.WEIGHT_EMA (section 17)
+        self.flat_acc, self.accum_k, self.accum_micro, self.accum_ops, self._accum_roles = None, 1, 0, [], []      # GRAD_ACCUM_STEPS (section 18)
+        self.lars_plan = None                          # Config.LARS (section 19): hip.LarsPlan, rebuilt with every plan
+        self.lamb_plan, self.lamb_state = None, None   # Config.LAMB (section 20): hip.LambPlan likewise, and its state {p1, p2, kt}
+        self.sam_state, self._sam_keys, self.flat_w0, self.sam_loss, self.sam_stats, self.sam_ops = None, None, None, None, None, []   # Config.SAM (section 21)
+        self._recal_plan = self._recal_stats = None    # BN_RECAL_BATCHES (section 22): (plan_version, hip.BnRecalPlan), the clone of flat_stats
+        self.flat_swa = self.flat_swa_sq = self.swa_state = self._swag_hold = None     # Config.SWA (section 23); _swag_hold: the raw weights under a sample
+        if mode == "training":                         # a bad key is a ValueError before anything is allocated: the first one in this order
+            if weight_ema.enabled(config, mode):
+                weight_ema.initial_state(config, self.world_size_hint())
+            for feature in (swa, grad_accum, lars, lamb, sam, bn_recal):
+                feature.validate(config, self.world_size_hint())
         self.input_u8, self.in_images_u8, self.adam = False, None, False
         self.wgrad_stream, self._single_chain, self._single_chain_always, self.fork_checks = None, False, False, 0
         self._alloc_params(seed, randomize_bn)
@@ -186,51 +198,39 @@ class Engine(object):
         """params: {layer: {weight: array}} in Keras layouts.  Missing layers are skipped unless strict.  With Config.WEIGHT_EMA the values
         go into the average as well: a model that loads a checkpoint starts its average there (set_ema_weights loads another one).  With
         Config.SWA the collection starts afresh (ticks = models = 0): the models collected so far belong to other weights."""
-        assert not getattr(self, "ema_swapped", False), "set_weights while the average is swapped in (swap_ema / ema_weights)"
-        assert not getattr(self, "swa_swapped", False) and not getattr(self, "_swag_active", False), \
+        stand_in = getattr(self, "_stand_in", None)    # (getattr: tests/test_loss_weights_cpu.py calls this on a host stand-in of its own)
+        assert stand_in != "ema", "set_weights while the average is swapped in (swap_ema / ema_weights)"
+        assert stand_in not in ("swa", "swag"), \
             "set_weights while the SWA average or a SWAG sample stands in for the weights (swap_swa / swa_weights / swag_weights)"
         if getattr(self, "swa_state", None) is not None:
             self.reset_swa()
         ema = getattr(self, "flat_ema", None)
-        for ln, ws in self.graph.params.items():
-            if ln not in params:
-                if strict:
-                    raise KeyError("missing layer %r" % ln)
-                continue
-            for wn, shape in ws.items():
-                a = np.asarray(params[ln][wn], dtype=np.float32)
-                if tuple(a.shape) != tuple(shape):
-                    raise ValueError("layer %s weight %s: shape %s != expected %s" % (ln, wn, a.shape, shape))
-                self.wview(ln, wn).copy_(torch.from_numpy(np.ascontiguousarray(a)))
-                if ema is not None and (ln, wn) in self.slices:
-                    self.wview(ln, wn, ema).copy_(self.wview(ln, wn))
+        for ln, wn, t in _checked_params(self.graph, params, strict):
+            self.wview(ln, wn).copy_(t)
+            if ema is not None and (ln, wn) in self.slices:
+                self.wview(ln, wn, ema).copy_(self.wview(ln, wn))
 
     def set_ema_weights(self, params, strict=True):
         """Load params (as set_weights takes them) into the average alone; the BN statistics, which both sets share, are not touched."""
         assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
-        assert not self.ema_swapped, "set_ema_weights while the average is swapped in (swap_ema / ema_weights)"
+        assert self._stand_in != "ema", "set_ema_weights while the average is swapped in (swap_ema / ema_weights)"
         self._load_trainable(params, self.flat_ema, strict)
 
     def _load_trainable(self, params, buf, strict):
         """params' trainable tensors into the flat buffer `buf` (an average's: set_ema_weights, set_swa_weights); BN statistics are skipped."""
-        for ln, ws in self.graph.params.items():
-            if ln not in params:
-                if strict:
-                    raise KeyError("missing layer %r" % ln)
-                continue
-            for wn, shape in ws.items():
-                if (ln, wn) not in self.slices:
-                    continue
-                a = np.asarray(params[ln][wn], dtype=np.float32)
-                if tuple(a.shape) != tuple(shape):
-                    raise ValueError("layer %s weight %s: shape %s != expected %s" % (ln, wn, a.shape, shape))
-                self.wview(ln, wn, buf).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        for ln, wn, t in _checked_params(self.graph, params, strict, only=self.slices):
+            self.wview(ln, wn, buf).copy_(t)
+
+    # what stands in flat_w, as the three yes / no facts callers and tests ask for; _stand_in alone holds it
+    ema_swapped = property(lambda self: self._stand_in == "ema", doc="flat_w holds the EMA average right now (swap_ema)")
+    swa_swapped = property(lambda self: self._stand_in == "swa", doc="flat_w holds the SWA mean right now (swap_swa)")
+    _swag_active = property(lambda self: self._stand_in == "swag", doc="flat_w holds a SWAG sample right now (swag_weights)")
 
     def get_weights(self, ema=False, swa=False):
         """{layer: {weight: array}}.  ema=True: the averaged parameters (Config.WEIGHT_EMA) beside the BN statistics, which both sets share.
         swa=True: the SWA mean (Config.SWA) likewise; swa="sq": the running mean of squares (SWA_VARIANCE) under the same names.
-        Every set is found wherever it lies: inside ema_weights() / swa_weights() two buffers have changed places.  Inside swag_weights()
-        the plain call returns the sample, which is then the model (so that save_weights() writes a sampled model)."""
+        Every set is found wherever it lies (train_state.weights_location): inside ema_weights() / swa_weights() two buffers have changed
+        places.  Inside swag_weights() the plain call returns the sample, which is then the model (so that save_weights() writes a sampled model)."""
         if ema:
             assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
         if swa:
@@ -238,13 +238,9 @@ class Engine(object):
             assert self.flat_swa is not None, "Config.SWA is off"
             if swa == "sq":
                 assert self.flat_swa_sq is not None, "Config.SWA_VARIANCE is off"
-                buf = self.flat_swa_sq
-            else:
-                buf = self.flat_w if self.swa_swapped else self.flat_swa
-        elif self.swa_swapped or self._swag_active:    # (neither nests with the EMA exchange)
-            buf = self.flat_ema if ema else (self.flat_swa if self.swa_swapped else self.flat_w)
-        else:
-            buf = (self.flat_ema, self.flat_w)[bool(ema) == self.ema_swapped] if self.flat_ema is not None else None
+        which = ("sq" if swa == "sq" else "swa") if swa else ("ema" if ema else "raw")
+        where = weights_location(self._stand_in, which, self.flat_ema is not None)
+        buf = getattr(self, where) if where is not None else None
         out = OrderedDict()
         for ln, ws in self.graph.params.items():
             out[ln] = OrderedDict((wn, self.wview(ln, wn, buf).detach().cpu().numpy().copy()) for wn in ws)
@@ -272,6 +268,20 @@ class Engine(object):
             return None
         return self.wview(ln, wn).reshape(-1)
 
+    def _plan_device_state(self, attr, init, dtype):
+        """The rule of a feature's small device-side state (ls_state, ema_state, swa_state), "created once, like hyper": init None (the
+        keys are off) drops it; the first plan that has the keys creates it from `init`; a later plan keeps the buffer -- the counts go on
+        across set_trainable() -- unless the keys changed, and then the new values are copied into the SAME buffer."""
+        if init is None:
+            setattr(self, attr, None)
+            self._state_init.pop(attr, None)
+            return
+        if getattr(self, attr) is None:
+            setattr(self, attr, torch.tensor(init, dtype=dtype, device=self.device))
+        elif init != self._state_init[attr]:
+            getattr(self, attr).copy_(torch.tensor(init, dtype=dtype))
+        self._state_init[attr] = init
+
     def _build_plan(self):
         training = self.mode == "training"
         self.plan_version += 1                         # ursonet_amd/dp.py re-derives its graph cuts when this moves
@@ -293,46 +303,25 @@ class Engine(object):
         # their gradients by the scale in front of the rounding to the engine dtype, every finalisation that writes flat_g divides it out again
         # before weight decay / BN derivation / squared norm, the optimizer skips a step whose norm is not finite and one more launch moves the scale
         if training:
-            init = loss_scale.initial_state(self.config, self.world_size)
-            if init is None:
-                self.ls_state = self._ls_init = None
-            elif self.ls_state is None:
-                self._ls_init = init
-                self.ls_state = torch.tensor(init, dtype=torch.float32, device=self.device)
-            elif init != self._ls_init:                # the keys changed between plans: the new settings start afresh, in the same buffer
-                self._ls_init = init
-                self.ls_state.copy_(torch.tensor(init, dtype=torch.float32))
+            self._plan_device_state("ls_state", loss_scale.initial_state(self.config, self.world_size), torch.float32)
         if training and self.learn_lw:
             loss_weights.validate(self.config, self.world_size)
-        # Config.WEIGHT_EMA: None = no launch and no buffer.  Set: one more launch at the end of opt_ops (_plan_optimizer)
+        # Config.WEIGHT_EMA: None = no launch and no buffer.  Set: one more launch at the end of opt_ops (_plan_optimizer).
+        # Changed keys start the schedule afresh; the average stays
         if training:
-            init = weight_ema.initial_state(self.config, self.world_size)
-            if init is None:
-                self.ema_state = self._ema_init = None
-            elif self.ema_state is None:
-                self._ema_init = init
-                self.ema_state = torch.tensor(init, dtype=torch.float32, device=self.device)
-                if self.flat_ema is None:              # the key was set after the engine was built: the average starts at the weights of now
-                    self.flat_ema = self.flat_w.clone()
-            elif init != self._ema_init:               # the keys changed between plans: the schedule starts afresh, the average stays
-                self._ema_init = init
-                self.ema_state.copy_(torch.tensor(init, dtype=torch.float32))
-        # Config.SWA: None = no launch and no buffer.  Set: one more launch, the last of opt_ops (_plan_optimizer)
+            self._plan_device_state("ema_state", weight_ema.initial_state(self.config, self.world_size), torch.float32)
+            if self.ema_state is not None and self.flat_ema is None:       # the key was set after the engine was built: the average starts
+                self.flat_ema = self.flat_w.clone()                        # at the weights of now
+        # Config.SWA: None = no launch and no buffer.  Set: one more launch, the last of opt_ops (_plan_optimizer).
+        # Changed keys start the collection afresh
         if training:
             init = swa.initial_state(self.config, self.world_size)
-            if init is None:
-                self.swa_state = self._swa_init = None
-            else:
+            if init is not None:
                 if self.flat_swa is None:              # the key was set after the engine was built
                     self.flat_swa = torch.zeros_like(self.flat_w)
                 if bool(init[swa.VARIANCE]) != (self.flat_swa_sq is not None):
                     self.flat_swa_sq = torch.zeros_like(self.flat_w) if init[swa.VARIANCE] else None
-                if self.swa_state is None:
-                    self._swa_init = init
-                    self.swa_state = torch.tensor(init, dtype=torch.int32, device=self.device)
-                elif init != self._swa_init:           # the keys changed between plans: the collection starts afresh, in the same buffer
-                    self._swa_init = init
-                    self.swa_state.copy_(torch.tensor(init, dtype=torch.int32))
+            self._plan_device_state("swa_state", init, torch.int32)
         # Config.GRAD_ACCUM_STEPS: 1 = no launch and no buffer.  k > 1: one launch behind the backward pass of the
         # micro-steps that do not close (accum_ops) and one in front of the optimizer of the one that does (_plan_optimizer); a new plan
         # starts a new optimizer step
@@ -1887,8 +1876,10 @@ class Engine(object):
     def _verify_forked_graph(self, gr, replays=None):
         """The captured graph with its second branch against the same launches issued eagerly on one chain: `replays` steps each from the same
         state (URSO_FORK_VERIFY_REPLAYS, default 4; the second replay is the first that shows a node run early: the first reads what the
-        warm-up step left), compared bit for bit on EVERYTHING a step writes: weights, gradients, momentum / Adam moments, BN statistics.
-        A graph executor that fails this (see _fork_weight_gradients) costs the engine its side branch, not its results.
+        warm-up step left), compared bit for bit on flat_g and the FORK_COMPARED part of train_state(): weights, gradients, momentum, BN
+        statistics, the averages and their states.  NOT compared: Adam's flat_v2 / flat_vhat and hyper (its step counter), lamb_state; a
+        forked Adam step is checked through the weights and first moments alone.  (ls_state, sam_state and flat_acc never meet a fork:
+        _fork_weight_gradients.)  A graph executor that fails this (see _fork_weight_gradients) costs the engine its side branch, not its results.
         Cost: 2 x replays training steps and two clones of the training state per capture (and per re-capture: set_input_u8 toggles,
         set_trainable).  It runs again wherever verify_fork() is called (UrsoNet.train: once per epoch; tests/test_model_gpu.py holds a
         200-replay stress test); bench.py repeats the comparison with two fresh engines before it times anything."""
@@ -1898,9 +1889,7 @@ class Engine(object):
             for _ in range(n):
                 gr.replay()
             torch.cuda.synchronize(self.device)
-            written = (self.flat_w, self.flat_g, self.flat_v, self.flat_stats) + ((self.flat_ema, self.ema_state) if self.ema_state is not None else ())
-            if self.swa_state is not None:
-                written += (self.flat_swa, self.swa_state) + ((self.flat_swa_sq,) if self.flat_swa_sq is not None else ())
+            written = [self.flat_g] + [t for name, t in self.train_state() if name in self.FORK_COMPARED]
             got = [t.clone() for t in written]
             self.restore_train_state(saved)
             self._single_chain = True
@@ -1941,8 +1930,8 @@ class Engine(object):
 
     def step(self):
         """Replay the captured training step (captures on first use)."""
-        assert not self.ema_swapped, "step() while the average is swapped in: leave ema_weights() / call swap_ema() again first"
-        assert not self.swa_swapped and not self._swag_active, \
+        assert self._stand_in != "ema", "step() while the average is swapped in: leave ema_weights() / call swap_ema() again first"
+        assert self._stand_in not in ("swa", "swag"), \
             "step() while the SWA average or a SWAG sample stands in for the weights: leave swa_weights() / swag_weights() / call swap_swa() again first"
         if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the graph of this micro-step's role, captured on first use
             role = self._accum_roles[self.accum_micro]
@@ -2072,49 +2061,41 @@ class Engine(object):
     def set_lr(self, lr):
         self.hyper[0] = float(lr)
 
-    def save_train_state(self):
-        """Weights + optimizer state (incl. Adam's device-side step counter), for the warm-up step before graph capture."""
-        st = [self.flat_w.clone(), self.flat_v.clone(), self.flat_stats.clone()]
-        if self.adam:
-            st += [self.flat_v2.clone(), self.flat_vhat.clone(), self.hyper.clone()]
-        if self.lamb_state is not None:                # Config.LAMB: the tick's running products and kt
-            st.append(self.lamb_state.clone())
-        if self.sam_state is not None:                 # Config.SAM: rho, the last step's record and the counts (flat_w0 is scratch)
-            st.append(self.sam_state.clone())
-        if self.ema_state is not None:                 # (in front of the loss-scale state, which restore_train_state finds at the end)
-            st += [self.flat_ema.clone(), self.ema_state.clone()]
-        if self.swa_state is not None:                 # Config.SWA: the mean, the state and, with SWA_VARIANCE, the mean of squares
-            st += [self.flat_swa.clone(), self.swa_state.clone()] + ([self.flat_swa_sq.clone()] if self.flat_swa_sq is not None else [])
-        if self.accum_k > 1:                           # Config.GRAD_ACCUM_STEPS: the running sum and the index of the next micro-step
-            st += [self.flat_acc.clone(), self.accum_micro]
+    FORK_COMPARED = ("flat_w", "flat_v", "flat_stats", "flat_ema", "ema_state", "flat_swa", "swa_state", "flat_swa_sq")      # _verify_forked_graph
+
+    def train_state(self):
+        """[(name, tensor)] of the persistent device state of training under the current plan, in the order save_train_state() keeps
+        (DESIGN.md section 30): everything a step writes and the next step reads.  Scratch (flat_g, flat_w0, _swag_hold) is not in it."""
+        names = ["flat_w", "flat_v", "flat_stats"]
+        if self.adam:                                  # the moments and hyper, which holds Adam's device-side step counter
+            names += ["flat_v2", "flat_vhat", "hyper"]
+        names += [n for n in ("lamb_state", "sam_state") if getattr(self, n) is not None]
+        if self.ema_state is not None:
+            names += ["flat_ema", "ema_state"]
+        if self.swa_state is not None:
+            names += ["flat_swa", "swa_state"] + (["flat_swa_sq"] if self.flat_swa_sq is not None else [])
+        if self.accum_k > 1:
+            names.append("flat_acc")
         if self.ls_state is not None:
-            st.append(self.ls_state.clone())
+            names.append("ls_state")
+        return [(n, getattr(self, n)) for n in names]
+
+    def save_train_state(self):
+        """Clones of train_state(), for the warm-up step before graph capture.  Under Config.GRAD_ACCUM_STEPS the host-side index of the next
+        micro-step rides behind flat_acc."""
+        st = []
+        for name, t in self.train_state():
+            st.append(t.clone())
+            if name == "flat_acc":
+                st.append(self.accum_micro)
         return st
 
     def restore_train_state(self, st):
-        self.flat_w.copy_(st[0]); self.flat_v.copy_(st[1]); self.flat_stats.copy_(st[2])
-        if self.adam:
-            self.flat_v2.copy_(st[3]); self.flat_vhat.copy_(st[4]); self.hyper.copy_(st[5])
-        k = 6 if self.adam else 3
-        if self.lamb_state is not None:
-            self.lamb_state.copy_(st[k])
-            k += 1
-        if self.sam_state is not None:
-            self.sam_state.copy_(st[k])
-            k += 1
-        if self.ema_state is not None:
-            self.flat_ema.copy_(st[k]); self.ema_state.copy_(st[k + 1])
-            k += 2
-        if self.swa_state is not None:
-            self.flat_swa.copy_(st[k]); self.swa_state.copy_(st[k + 1])
-            k += 2
-            if self.flat_swa_sq is not None:
-                self.flat_swa_sq.copy_(st[k])
-                k += 1
-        if self.accum_k > 1:
-            self.flat_acc.copy_(st[k]); self.accum_micro = int(st[k + 1])
-        if self.ls_state is not None:
-            self.ls_state.copy_(st[-1])
+        it = iter(st)
+        for name, t in self.train_state():
+            t.copy_(next(it))
+            if name == "flat_acc":
+                self.accum_micro = int(next(it))
 
     def reset_optimizer(self):
         """Zero the optimizer's moments (and restart the loss scale).  The weights' averages (Config.WEIGHT_EMA, Config.SWA) and their schedules
@@ -2127,7 +2108,7 @@ class Engine(object):
         if self.lamb_plan is not None:                 # Config.LAMB: {p1, p2, kt} = {1, 1, 0}, with t = 0 above
             self.lamb_plan.reset()
         if self.ls_state is not None:
-            self.ls_state.copy_(torch.tensor(self._ls_init, dtype=torch.float32))
+            self.ls_state.copy_(torch.tensor(self._state_init["ls_state"], dtype=torch.float32))
         if self.sam_state is not None:                 # Config.SAM: the last step's record and the counts; rho and eps stay
             self.sam_state[sam.NORMSQ:].zero_()
 
@@ -2155,24 +2136,19 @@ class Engine(object):
         table: the float64 norms the trust ratios were computed from (of the weights BEFORE the step and of the finalised gradient) and
         the float32 trust the update used.  adapting_only: the kernels alone, without the tensors whose trust is 1 by rule.  None when
         Config.LARS is off; zeros and trust 1 before the first step."""
-        lp = self.lars_plan
-        if lp is None:
-            return None
-        stat, trust = lp.stat.detach().cpu().numpy(), lp.trust.detach().cpu().numpy()
-        return OrderedDict((key, (float(stat[t, 0]), float(stat[t, 1]), float(trust[t])))
-                           for t, key in enumerate(self.slices) if lp.tensors[t][2] or not adapting_only)
+        return self._trust_report(self.lars_plan, adapting_only)
 
     def lamb_report(self, adapting_only=False):
-        """{(layer, weight): (|w|, |r|, trust)} of the last optimizer step under Config.LAMB, one synchronising read of the device-side
-        table: the float64 norms the trust ratios were computed from (of the weights BEFORE the step and of the Adam direction r) and the
-        float32 trust the update used.  adapting_only: the kernels alone.  None when Config.LAMB is off; zeros and trust 1 before the
-        first step."""
-        bp = self.lamb_plan
-        if bp is None:
+        """The same under Config.LAMB, {(layer, weight): (|w|, |r|, trust)}: the second norm is that of the Adam direction r.  None when
+        Config.LAMB is off."""
+        return self._trust_report(self.lamb_plan, adapting_only)
+
+    def _trust_report(self, plan, adapting_only):
+        if plan is None:
             return None
-        stat, trust = bp.stat.detach().cpu().numpy(), bp.trust.detach().cpu().numpy()
+        stat, trust = plan.stat.detach().cpu().numpy(), plan.trust.detach().cpu().numpy()
         return OrderedDict((key, (float(stat[t, 0]), float(stat[t, 1]), float(trust[t])))
-                           for t, key in enumerate(self.slices) if bp.tensors[t][2] or not adapting_only)
+                           for t, key in enumerate(self.slices) if plan.tensors[t][2] or not adapting_only)
 
     def set_sam_rho(self, rho):
         """Config.SAM's radius from the next step on: the device field, so a captured graph needs no re-capture."""
@@ -2205,23 +2181,13 @@ class Engine(object):
         """Exchange flat_w and flat_ema in place (urso_ema_swap) and flip ema_swapped.  Every forward pass reads flat_w only through the prep
         pass, which evaluate() and the captured step both begin with, so nothing else has to move; the BN statistics are shared."""
         assert self.flat_ema is not None, "Config.WEIGHT_EMA is off"
-        assert not self.swa_swapped and not self._swag_active, "swap_ema while the SWA average or a SWAG sample stands in for the weights"
+        assert self._stand_in not in ("swa", "swag"), "swap_ema while the SWA average or a SWAG sample stands in for the weights"
         hip.ema_swap(self.n_flat, self.flat_w, self.flat_ema)
-        self.ema_swapped = not self.ema_swapped
+        self._stand_in = None if self._stand_in == "ema" else "ema"
 
     def ema_weights(self):
         """Context manager: the averaged weights are the model's inside (evaluate() and every forward pass), the raw ones are back after it."""
-        eng = self
-
-        class _Ctx(object):
-            def __enter__(self):
-                eng.swap_ema()
-                return eng
-
-            def __exit__(self, *exc):
-                eng.swap_ema()
-                return False
-        return _Ctx()
+        return _StandIn(self, self.swap_ema, self.swap_ema)
 
     # ------------------------------------------------------------------ Config.SWA
     def swa(self):
@@ -2234,15 +2200,15 @@ class Engine(object):
     def reset_swa(self):
         """Restart the collection: ticks = models = 0.  The first model collected afterwards is copied in, so the buffers need no clearing."""
         assert self.swa_state is not None, "Config.SWA is off"
-        assert not self.swa_swapped and not self._swag_active, "reset_swa while the SWA average or a SWAG sample stands in for the weights"
-        self.swa_state.copy_(torch.tensor(self._swa_init, dtype=torch.int32))
+        assert self._stand_in not in ("swa", "swag"), "reset_swa while the SWA average or a SWAG sample stands in for the weights"
+        self.swa_state.copy_(torch.tensor(self._state_init["swa_state"], dtype=torch.int32))
 
     def set_swa_weights(self, params, sq_params=None, models=None, strict=True):
         """Load params (as set_weights takes them) into the SWA mean and, with SWA_VARIANCE, sq_params into the mean of squares; `models`
         (>= 1) is the number of models they average.  The collection goes on from there: ticks = start + models * period.  The BN statistics,
         which all sets share, are not touched."""
         assert self.swa_state is not None, "Config.SWA is off"
-        assert not self.swa_swapped and not self._swag_active, "set_swa_weights while the SWA average or a SWAG sample stands in for the weights"
+        assert self._stand_in not in ("swa", "swag"), "set_swa_weights while the SWA average or a SWAG sample stands in for the weights"
         if isinstance(models, (bool, np.bool_)) or not isinstance(models, (int, np.integer)) or not 1 <= models <= swa.MAX_MODELS:
             raise ValueError("set_swa_weights: models must be an int in [1, 2^24], got %r" % (models,))
         if (sq_params is not None) != (self.flat_swa_sq is not None):
@@ -2250,7 +2216,7 @@ class Engine(object):
         self._load_trainable(params, self.flat_swa, strict)
         if sq_params is not None:
             self._load_trainable(sq_params, self.flat_swa_sq, strict)
-        st = list(self._swa_init)
+        st = list(self._state_init["swa_state"])
         st[swa.MODELS] = int(models)
         st[swa.TICKS] = min(st[swa.START] + int(models) * st[swa.PERIOD], swa.MAX_TICKS)
         self.swa_state.copy_(torch.tensor(st, dtype=torch.int32))
@@ -2258,24 +2224,16 @@ class Engine(object):
     def swap_swa(self):
         """Exchange flat_w and flat_swa in place (urso_ema_swap: there is one exchange kernel) and flip swa_swapped; as swap_ema."""
         assert self.flat_swa is not None, "Config.SWA is off"
-        assert not self.ema_swapped and not self._swag_active, "swap_swa while the EMA average or a SWAG sample stands in for the weights"
+        assert self._stand_in not in ("ema", "swag"), "swap_swa while the EMA average or a SWAG sample stands in for the weights"
         hip.ema_swap(self.n_flat, self.flat_w, self.flat_swa)
-        self.swa_swapped = not self.swa_swapped
+        self._stand_in = None if self._stand_in == "swa" else "swa"
 
     def swa_weights(self):
         """Context manager: the SWA mean is the model's inside (evaluate() and every forward pass), the raw weights are back after it."""
-        eng = self
-
-        class _Ctx(object):
-            def __enter__(self):
-                assert not eng.swa_swapped, "swa_weights() inside swa_weights() / swap_swa()"
-                eng.swap_swa()
-                return eng
-
-            def __exit__(self, *exc):
-                eng.swap_swa()
-                return False
-        return _Ctx()
+        def enter():
+            assert self._stand_in != "swa", "swa_weights() inside swa_weights() / swap_swa()"
+            self.swap_swa()
+        return _StandIn(self, enter, self.swap_swa)
 
     def swag_weights(self, sample, seed=0, var_scale=0.5):
         """Context manager (SWAG-diagonal; needs SWA_VARIANCE and at least two collected models): inside, flat_w holds sample number `sample`
@@ -2286,27 +2244,22 @@ class Engine(object):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
                 raise ValueError("swag_weights: %s must be an int in [0, 2^%d), got %r" % (name, 31 if name == "sample" else 64, v))
         s = swa.scale32(var_scale)                     # ValueError: not a finite float >= 0
-        eng = self
 
-        class _Ctx(object):
-            def __enter__(self):
-                assert not eng.ema_swapped and not eng.swa_swapped and not eng._swag_active, \
-                    "swag_weights() while an average or another sample stands in for the weights"
-                models = int(eng.swa_state[swa.MODELS].item())
-                if models < 2:
-                    raise ValueError("swag_weights needs at least 2 collected models (a variance), the average holds %d" % models)
-                if eng._swag_hold is None:
-                    eng._swag_hold = torch.empty_like(eng.flat_w)
-                eng._swag_hold.copy_(eng.flat_w)
-                eng._swag_active = True
-                hip.swag_sample(eng.n_flat, eng.flat_swa, eng.flat_swa_sq, eng.flat_w, s, int(seed), int(sample))
-                return eng
+        def enter():
+            assert self._stand_in is None, "swag_weights() while an average or another sample stands in for the weights"
+            models = int(self.swa_state[swa.MODELS].item())
+            if models < 2:
+                raise ValueError("swag_weights needs at least 2 collected models (a variance), the average holds %d" % models)
+            if self._swag_hold is None:
+                self._swag_hold = torch.empty_like(self.flat_w)
+            self._swag_hold.copy_(self.flat_w)
+            self._stand_in = "swag"
+            hip.swag_sample(self.n_flat, self.flat_swa, self.flat_swa_sq, self.flat_w, s, int(seed), int(sample))
 
-            def __exit__(self, *exc):
-                eng.flat_w.copy_(eng._swag_hold)       # a copy of the same dtype: the bits
-                eng._swag_active = False
-                return False
-        return _Ctx()
+        def leave():
+            self.flat_w.copy_(self._swag_hold)         # a copy of the same dtype: the bits
+            self._stand_in = None
+        return _StandIn(self, enter, leave)
 
     def flops(self):
         return conv_flops(self.graph, self.B)
