@@ -21,89 +21,11 @@ import re
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+from layerref import DeviceTensors, _l2_rel, _max_rel, _pad_for, forward_layer_errors      # noqa: F401  (re-exported)
 from util import make_config, synthetic_batch
 
 pytestmark = pytest.mark.gpu
-
-
-def _max_rel(a, b, valid=None):
-    a, b = a.double(), b.double()
-    d = (a - b).abs()
-    if valid is not None:
-        d = d * valid
-        b = b * valid
-    return float(d.max() / (b.abs().max() + 1e-30))
-
-
-def _l2_rel(a, b, valid=None):
-    a, b = a.double(), b.double()
-    if valid is not None:
-        a, b = a * valid, b * valid
-    return float(torch.linalg.vector_norm(a - b) / (torch.linalg.vector_norm(b) + 1e-30))
-
-
-class DeviceTensors(object):
-    """Reads the engine's activation / gradient buffers back as dense fp32 NCHW tensors (+ the mask of the pixels the device computes)."""
-
-    def __init__(self, eng):
-        self.eng, self.B = eng, eng.B
-        self.npad = {}
-        for c in eng.convs.values():
-            self.npad[c.dst.spec.id] = c.npad
-        # a projection shortcut computed inside the fused forward pair (conv_pairs.hip) has no output tensor
-        self.never_stored = {eng.convs[nm].dst.spec.id for nm in getattr(eng, "shortcut_folded", [])}
-        self.producer = {c.dst.spec.id: c for c in eng.convs.values()}
-        self.pool_of_stem = {}
-        for n in eng.graph.nodes:
-            if n.op == "pool":
-                self.npad[n.dst.id] = n.dst.c
-                self.pool_of_stem[n.src.id] = n
-
-    def _even(self, X):
-        m = torch.zeros(1, 1, X.spec.h, X.spec.w)
-        m[:, :, ::2, ::2] = 1
-        return m
-
-    def _nchw(self, flat, X, h, w):
-        C = self.npad[X.spec.id]
-        return flat.float().cpu().view(self.B, h, w, C)[..., :X.spec.c].permute(0, 3, 1, 2).contiguous()
-
-    def values(self, X):
-        """(values [B, C, H, W] with zeros where the device computes nothing, valid-pixel mask or None = all) -- None when the tensor is never stored."""
-        s = X.spec
-        if getattr(X, "fused_pool", False) or X.spec.id in self.never_stored:
-            return None
-        if getattr(X, "fwd_sampled", False):                     # computed at the even pixels only, stored compact
-            v = torch.zeros(self.B, s.c, s.h, s.w)
-            v[:, :, ::2, ::2] = self._nchw(X.data_compact, X, s.h // 2, s.w // 2)
-            return v, self._even(X)
-        v = self._nchw(X.data, X, s.h, s.w)
-        if getattr(X, "fwd_scattered", False):                   # even pixels written, the rest of the buffer is whatever the allocator left
-            m = self._even(X)
-            return torch.where(m.bool().expand_as(v), v, torch.zeros_like(v)), m
-        return v, None
-
-    def grad(self, X):
-        """dL/d(pre-activation of X's producer) as the device stored it, dense; None when it never reaches memory in full."""
-        if X.grad is None or not X.grad_written or getattr(X.grad, "_urso_on_chip", False):
-            return None
-        s = X.spec
-        if X.compact is not None:                                # [B, H/2, W/2, C]: zero off the even grid
-            g = torch.zeros(self.B, s.c, s.h, s.w)
-            g[:, :, ::2, ::2] = self._nchw(X.grad, X, s.h // 2, s.w // 2)
-            return g
-        return self._nchw(X.grad, X, s.h, s.w)
-
-
-def _pad_for(n, x):
-    """Explicit zero padding of node n (graph.py keeps (top, left); bottom / right follow from the output size): ZeroPadding2D(3) of the
-    stem, 'same' of the 3x3 layers, TF-SAME of the stride-2 bottleneck_layer (net.py:170, 106, 639)."""
-    pt, pl = n.pad
-    pb = (n.dst.h - 1) * n.stride + n.kh - x.shape[2] - pt
-    pr = (n.dst.w - 1) * n.stride + n.kw - x.shape[3] - pl
-    return F.pad(x, (pl, max(pr, 0), pt, max(pb, 0)))
 
 
 BN_MOMENTUM = 0.99           # Keras BatchNormalization default (net.py:60-76 passes none)
@@ -193,14 +115,14 @@ def layerwise_errors(eng, w0, img, cfg, dtype, only=None):
     Returns {check name: {layer or tensor: (max-norm error, Euclidean error)}} and the lists of what could not be read.
     ('stats' and 'dbias' hold (largest |error| / bound, largest |error|) instead: their gates are elementwise bounds.)
     only: a regular expression; layers whose name it does not match (re.search) are left out, and so is every activation gradient
-    one of them contributes to."""
+    one of them contributes to.
+    The forward half -- the oracle's single layer on the device's operands and the 'fwd' entries -- is layerref.forward_layer_errors,
+    the walk the inference plan is checked with as well (tests/test_inference_layerwise_gpu.py); what is added here, layer by layer
+    through its hook, is the backward half (and the normalisation half of a batch-statistics layer, which reads the layer's stored z)."""
     from oracle import graph_ref as G
-    q = G.StorageRounding(dtype, unstored=getattr(eng, "shortcut_folded", ()))
     rnd = lambda t: t.to(dtype).float()
     dev = DeviceTensors(eng)
-    P = G.to_torch(w0)
     grads_dev = eng.get_grads()
-    B = eng.B
     wd = float(cfg.WEIGHT_DECAY)
     out = {"fwd": {}, "dkernel": {}, "dvec": {}, "dx": {}, "z": {}, "dz": {}, "stats": {}, "dbias": {}, "dz_absmax": {}}
     skipped = {"fwd": [], "bwd": [], "dx": []}
@@ -215,90 +137,40 @@ def layerwise_errors(eng, w0, img, cfg, dtype, only=None):
             contrib[i] = t if i not in contrib else contrib[i] + t
         complete[i] = complete.get(i, True) and ok
 
-    for c in eng.convs.values():
-        n = c.node
-        if only is not None and not re.search(only, n.name):
-            if not n.stem:
-                add_contrib(c.src, None, False)
-            if c.res is not None:
-                add_contrib(c.res, None, False)
-            continue
-        Pc = P[n.name]
-        Pb = P[n.bn] if n.bn else None
-        # ---- the device's stored operands
-        if n.stem:
-            x = rnd(torch.tensor(img)).permute(0, 3, 1, 2).contiguous()
-            xvalid = None
-        else:
-            xv = dev.values(c.src)
-            if xv is None:
-                skipped["fwd"].append(n.name); continue
-            x, xvalid = xv
-        if c.batch_bn:
-            assert xvalid is None and not n.dense
-            xt = x.clone().requires_grad_(True)
-            z4c = G.conv2d(_pad_for(n, xt), {"kernel": q.weight(Pc["kernel"]), **({"bias": Pc["bias"]} if "bias" in Pc else {})}, stride=n.stride)
-            _bn_layer_errors(eng, dev, c, P, w0, w1, grads_dev, z4c, xt, rnd, wd, out, skipped, add_contrib)
-            continue
-        res = None
+    def no_gradient_through(c):
+        if not c.node.stem:
+            add_contrib(c.src, None, False)
         if c.res is not None:
-            rv = dev.values(c.res)
-            if rv is None and c.res.spec.id in dev.never_stored:
-                # the shortcut lives inside this layer's fused launch as 64 more columns of its GEMM, added in fp32 and never rounded to
-                # storage: the oracle's shortcut layer on ITS device input, unrounded
-                Sc = dev.producer[c.res.spec.id]
-                sx = dev.values(Sc.src)[0]
-                with torch.no_grad():
-                    res = G.conv_bn(_pad_for(Sc.node, sx), P[Sc.node.name], P[Sc.node.bn] if Sc.node.bn else None, False,
-                                    stride=Sc.node.stride, padding="valid", q=q)
-            elif rv is None:
-                skipped["fwd"].append(n.name); continue
-            else:
-                res = rv[0]
-        xt = x.clone().requires_grad_(True)
-        # ---- the oracle's single layer on them
-        if n.dense:
-            feat = xt.permute(0, 2, 3, 1).reshape(B, -1) if xt.dim() == 4 and xt.shape[2] * xt.shape[3] > 1 else xt.reshape(B, -1)
-            z = G._qdense(feat, Pc, q)
-            z4 = z.view(B, -1, 1, 1)
-        else:
-            z4 = G.conv_bn(_pad_for(n, xt), Pc, Pb, False, stride=n.stride, padding="valid", q=q)
-        if res is not None:
-            z4 = z4 + res
-        y = torch.relu(z4) if n.relu else z4
-        y = y if n.out_f32 else rnd(y.detach())
-        # ---- forward: the layer's stored output
-        dv = dev.values(c.dst)
-        if dv is None and c.dst.spec.id in dev.never_stored:     # the folded shortcut: checked through the layer that adds it (above); its dz is that layer's
-            dzs = dev.grad(c.dst)
-            if dzs is None:
-                skipped["bwd"].append(n.name); add_contrib(c.src, None, False); continue
-            dv = (None, None)
-        elif dv is None:                                         # conv1 inside urso_stem_conv_pool: only the pooled tensor exists
-            pool = dev.pool_of_stem[c.dst.spec.id]
-            pd = dev.values(acts_by_id[pool.dst.id])[0]
-            yp = G.maxpool_3x3_s2_same(y.detach())
-            out["fwd"][n.name + "+maxpool"] = (_max_rel(yp, pd), _l2_rel(yp, pd))
-        elif dv[0] is not None:
-            out["fwd"][n.name] = (_max_rel(y.detach(), dv[0], dv[1]), _l2_rel(y.detach(), dv[0], dv[1]))
+            add_contrib(c.res, None, False)
+
+    def backward_half(event, L):
+        c = L.c
+        n = c.node
+        if event == "unselected":
+            no_gradient_through(c)
+            return
+        if event == "batch_bn":
+            _bn_layer_errors(eng, dev, c, L.P, w0, w1, grads_dev, L.z4c, L.xt, rnd, wd, out, skipped, add_contrib)
+            return
+        Pc, Pb, xt, z4 = L.Pc, L.Pb, L.xt, L.z4
         # ---- backward: the device's dz through the layer
-        if dv is None:
+        if L.stored == "pooled":
             pool = dev.pool_of_stem[c.dst.spec.id]
             dzp = dev.grad(acts_by_id[pool.dst.id])
             if dzp is None:
-                skipped["bwd"].append(n.name); continue
+                skipped["bwd"].append(n.name); return
             yr = torch.relu(z4)
             yy = yr + (rnd(yr.detach()) - yr.detach())           # the pool picks its arg-max among the STORED (rounded) values; the gradient is the ReLU's
             obj = (G.maxpool_3x3_s2_same(yy) * dzp).sum()
         else:
-            dz = dev.grad(c.dst)
+            dz = dev.grad(c.dst)                                 # (a folded shortcut: its dz is that of the layer that adds it)
             if dz is None:
                 skipped["bwd"].append(n.name)
-                if not n.stem:
+                if L.stored == "folded":
                     add_contrib(c.src, None, False)
-                if c.res is not None:
-                    add_contrib(c.res, None, False)
-                continue
+                else:
+                    no_gradient_through(c)
+                return
             obj = (z4 * dz).sum()
             if c.res is not None:
                 add_contrib(c.res, dz, True)                      # Add: the residual operand receives dz itself
@@ -315,6 +187,10 @@ def layerwise_errors(eng, w0, img, cfg, dtype, only=None):
         for (wn, _), g in zip(bnl, gs[1 + len(leaves):]):
             gd = torch.tensor(grads_dev[n.bn][wn])
             out["dvec"][n.bn + "/" + wn] = (_max_rel(gd, g), _l2_rel(gd, g))
+
+    fwd, skipped_fwd = forward_layer_errors(eng, w0, img, cfg, dtype, only=only, hook=backward_half, dev=dev)
+    out["fwd"].update(fwd)
+    skipped["fwd"][:0] = skipped_fwd
     # ---- activation gradients: sum over the consumers, ReLU mask of the tensor's own stored values, one rounding
     for i, t in contrib.items():
         X = acts_by_id[i]

@@ -85,19 +85,25 @@ def test_f16_config_runs_fp16_path():
     assert float((go.cpu() - ref_o).abs().max() / ref_o.abs().max()) < 5e-2
 
 
-def test_uint8_input_path_equals_molded_float_path():
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16", "float16"])
+@pytest.mark.parametrize("backbone", ["resnet18", "resnet50"])
+def test_uint8_input_path_equals_molded_float_path(backbone, dtype):
     """Engine.load_batch_u8 (mean subtraction inside urso_mold_images, net.py:1337-1348) gives bit-identical network inputs and
-    outputs to molding on the host; detect() takes that path for uint8 frames."""
+    outputs to molding on the host, in every engine dtype (the 16-bit ones round the molded value inside the kernel); detect() and the
+    other commands take that path for uint8 frames."""
     from ursonet_amd.engine import Engine
-    cfg = make_config("resnet18", 64, 128, batch=3, regress_ori=True, dtype="float32")
+    cfg = make_config(backbone, 64, 128, batch=3, regress_ori=True, dtype=dtype)
     eng = Engine(cfg, "inference", seed=4, randomize_bn=True)
     rng = np.random.default_rng(1)
     u8 = rng.integers(0, 256, size=(3, 64, 128, 3), dtype=np.uint8)
     eng.load_batch(u8.astype(np.float32) - np.asarray(cfg.MEAN_PIXEL, dtype=np.float32)); eng.forward(); torch.cuda.synchronize()
     a = [t.clone() for t in eng.outputs()]
+    x0 = eng.acts[eng.graph.tensors[0].id]
+    xa = x0.data.clone()
     eng.load_batch_u8(u8); eng.forward(); torch.cuda.synchronize()
     b = eng.outputs()
-    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    assert torch.equal(xa, x0.data) and float(xa.float().abs().max()) > 0
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and bool(torch.isfinite(a[0]).all())
     eng.set_input_u8(False)
     eng.load_batch(u8.astype(np.float32) - np.asarray(cfg.MEAN_PIXEL, dtype=np.float32)); eng.forward(); torch.cuda.synchronize()
     assert torch.equal(a[0], eng.outputs()[0])
