@@ -122,6 +122,7 @@ for (cls, famname), g in sorted(groups.items(), key=lambda kv: kv[1]["first"]):
     print("| %s | %d | `%s` | %.1f | %s | %s | %s | %.2f |" % (cls, g["n"], famname, ms / g["n"] * 1e3, ("%.0f" % (g["fl"] / (ms * 1e9))) if g["fl"] else "-",
                                                      ("%.0f" % (g["by"] / (ms * 1e6))) if g["by"] else "-", bound if (g["fl"] or g["by"]) else "-", frac))
 print("\n## Kernel families\n")
+print("Every fused ReLU below is `relu_f` (common.h): IEEE 754-2019 maximum, `__builtin_elementwise_maximum(y, 0.f)`, one `v_maximum3_f32`; it stores a NaN where `fmaxf(y, 0)` would store 0 (DESIGN.md section 31).\n")
 print("| kernel | file | tile / waves / LDS / residency | used for | launches | ms per step | share |")
 print("|---|---|---|---|---|---|---|")
 byfam = {}

@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(size_t nvec, int N, const
         for (int q = 0; q < VE; ++q) {
             float v = (Elem<T>::to_f(ez[q]) - m_[q]) * s_[q] + b_[q];
             if (res) v += Elem<T>::to_f(er[q]);
-            eo[q] = Elem<T>::from_f(relu ? fmaxf(v, 0.f) : v);
+            eo[q] = Elem<T>::from_f(relu ? relu_f(v) : v);
         }
         i32x4_t ov; __builtin_memcpy(&ov, eo, 16);
         return ov;

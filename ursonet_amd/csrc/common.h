@@ -104,6 +104,11 @@ template <> struct Elem<_Float16> {
     static __device__ __forceinline__ _Float16 from_f(float v) { return (_Float16)v; }
 };
 
+// The ReLU of every fused epilogue.  fmaxf(y, 0) is C's maxNum and returns 0 for a NaN; IEEE 754-2019 maximum keeps the NaN, sends -inf,
+// negatives and -0 to +0 and leaves the rest, so on finite data it stores the bits fmaxf stored (DESIGN.md "Non-finite values").  One
+// v_maximum3_f32 on gfx950, as v_max_f32 was; the select y <= 0 ? 0 : y is the same function in two instructions and measurably slower.
+__device__ __forceinline__ float relu_f(float y) { return __builtin_elementwise_maximum(y, 0.f); }
+
 // One MFMA "chunk-group step": every lane supplies one 16-byte chunk of its A row and one of
 // its B row (lane = 16*g + r: row r of the 16-row sub-tile, chunk g of the 4-chunk K group).
 //   D[i][j] += sum_k A[i][k] * B[j][k],  D layout: lane holds D[i = 4*(lane>>4) + reg][j = lane&15].

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(1024) void bneck_fwd_kernel(const BnfArgs a) {
     float v[4] = {y.x, y.y, y.z, y.w};
     T o[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { if (a.relu) v[r] = fmaxf(v[r], 0.f); o[r] = Elem<T>::from_f(v[r]); }
+    for (int r = 0; r < 4; ++r) { if (a.relu) v[r] = relu_f(v[r]); o[r] = Elem<T>::from_f(v[r]); }
     *(i32x2_t*)((T*)a.dst + (size_t)m * a.N + nb) = *(i32x2_t*)o;
 }
 

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void c3_kernel(const C3Args a) {
             for (int v = 0; v < 2; ++v) {
                 T o[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { float y = acc[r][8 * v + e]; y = a.relu ? fmaxf(y, 0.f) : y; o[e] = Elem<T>::from_f(y); }
+                for (int e = 0; e < 8; ++e) { float y = acc[r][8 * v + e]; y = a.relu ? relu_f(y) : y; o[e] = Elem<T>::from_f(y); }
                 i32x4_t ov; __builtin_memcpy(&ov, o, 16);
                 *(i32x4_t*)(sO + px * 128 + (((4 * cw + 2 * h + v) ^ ((px >> 1) & 7)) << 4)) = ov;
             }
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(512, 2) void c3w_kernel(const C3Args a) {
                     const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
                     T o[8];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { float y = fin[rr][8 * v + e] + bb[e]; y = a.relu ? fmaxf(y, 0.f) : y; o[e] = Elem<T>::from_f(y); }
+                    for (int e = 0; e < 8; ++e) { float y = fin[rr][8 * v + e] + bb[e]; y = a.relu ? relu_f(y) : y; o[e] = Elem<T>::from_f(y); }
                     i32x4_t ov; __builtin_memcpy(&ov, o, 16);
                     *(i32x4_t*)(sO + px * 256 + (((4 * fq + 2 * h + v) ^ (px & 15)) << 4)) = ov;
                 }
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(512, 2) void c3v_kernel(const C3Args a) {
             for (int r = 0; r < 8; ++r) {
                 const int px = 16 * r + fr;
                 float y0v = acc[r].x + bq.x, y1v = acc[r].y + bq.y, y2v = acc[r].z + bq.z, y3v = acc[r].w + bq.w;
-                if (a.relu) { y0v = fmaxf(y0v, 0.f); y1v = fmaxf(y1v, 0.f); y2v = fmaxf(y2v, 0.f); y3v = fmaxf(y3v, 0.f); }
+                if (a.relu) { y0v = relu_f(y0v); y1v = relu_f(y1v); y2v = relu_f(y2v); y3v = relu_f(y3v); }
                 T o[4] = {Elem<T>::from_f(y0v), Elem<T>::from_f(y1v), Elem<T>::from_f(y2v), Elem<T>::from_f(y3v)};
                 i32x2_t ov; __builtin_memcpy(&ov, o, 8);
                 *(i32x2_t*)(sO + px * 256 + ((((2 * wave + (fg >> 1)) ^ (px & 15))) << 4) + (fg & 1) * 8) = ov;

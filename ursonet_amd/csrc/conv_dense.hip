@@ -78,7 +78,7 @@ __global__ __launch_bounds__(512) void dense_kernel(const DnArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (a.add) v[r] += Elem<T>::to_f(ea[r]);
-            if (a.relu) v[r] = fmaxf(v[r], 0.f);
+            if (a.relu) v[r] = relu_f(v[r]);
             if (a.mask) v[r] = (Elem<T>::to_f(em[r]) > 0.f) ? v[r] : 0.f;
         }
         if constexpr (OUT32) *(f32x4_t*)((float*)a.dst + e) = f32x4_t{v[0], v[1], v[2], v[3]};
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(NW * 64) void dense_multi_kernel(const DnmArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (L.add) v[r] += Elem<T>::to_f(ea[r]);
-            if (L.relu) v[r] = fmaxf(v[r], 0.f);
+            if (L.relu) v[r] = relu_f(v[r]);
             if (L.mask) v[r] = (Elem<T>::to_f(em[r]) > 0.f) ? v[r] : 0.f;
         }
         if (L.out32) *(f32x4_t*)((float*)L.dst + e) = f32x4_t{v[0], v[1], v[2], v[3]};

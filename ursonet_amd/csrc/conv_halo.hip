@@ -334,7 +334,7 @@ __global__ __launch_bounds__(512, 2) void hconv_kernel(const HcArgs a) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             float y = acc[i][j][8 * hf + e] + bv[e];
-                            y = a.relu ? fmaxf(y, 0.f) : y;
+                            y = a.relu ? relu_f(y) : y;
                             eo[e] = Elem<T>::from_f(y);
                         }
                         i32x4_t ov; __builtin_memcpy(&ov, eo, 16);

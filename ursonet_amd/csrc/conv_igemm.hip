@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
                         const int c = v * VE + e;                               // = 4*j + r: sub-tile j, D register r
                         float y = acc[i][c >> 2][c & 3] + bv[c];                // an absent bias reads as 0
                         if constexpr (HAS_ADD) y += Elem<T>::to_f(ea[e]);
-                        y = relu ? fmaxf(y, 0.f) : y;
+                        y = relu ? relu_f(y) : y;
                         if constexpr (HAS_MASK) y = (Elem<T>::to_f(em[e]) > 0.f) ? y : 0.f;
                         if constexpr (MASK == 2) y = ((rbit[i * NV + v] >> e) & 1u) ? y : 0.f;
                         eo[e] = Elem<T>::from_f(y);
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
                 }
                 if (relu) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
+                    for (int q = 0; q < 4; ++q) v[q] = relu_f(v[q]);
                 }
                 if (a.mask) {
                     const T* mp = (const T*)a.mask + o;
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
                     float x = v[q];
                     if (a.bias) x += a.bias[nbj + q];
                     if (a.add) x += Elem<T>::to_f(((const T*)a.add)[o + q]);
-                    if (relu) x = fmaxf(x, 0.f);
+                    if (relu) x = relu_f(x);
                     if (a.mask && !(Elem<T>::to_f(((const T*)a.mask)[o + q]) > 0.f)) x = 0.f;
                     if (outf32) ((float*)a.dst)[o + q] = x; else ((T*)a.dst)[o + q] = Elem<T>::from_f(x);
                 }
@@ -378,7 +378,7 @@ __global__ void splitk_finish_kernel(size_t n4, int N, int S, size_t slice_elems
         for (int q = 0; q < 4; ++q) {
             float y = v[q] + (bias ? bias[n + q] : 0.f);
             if (add) y += Elem<T>::to_f(add[e + q]);
-            if (relu) y = fmaxf(y, 0.f);
+            if (relu) y = relu_f(y);
             if (mask && !(Elem<T>::to_f(mask[e + q]) > 0.f)) y = 0.f;
             if (outf32) ((float*)dst)[e + q] = y; else ((T*)dst)[e + q] = Elem<T>::from_f(y);
         }

@@ -292,7 +292,7 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         float x = acc[pt][c2][8 * v + e] + Elem<T>::to_f(res[e]);
-                        if constexpr (MODE == 0) x = (VAR == 0 || a.relu1) ? fmaxf(x, 0.f) : x;
+                        if constexpr (MODE == 0) x = (VAR == 0 || a.relu1) ? relu_f(x) : x;
                         else x = ((mbits >> (8 * v + e)) & 1u) ? x : 0.f;
                         out[e] = Elem<T>::from_f(x);
                         if constexpr (MODE == 0 && EMIT) obits |= (Elem<T>::to_f(out[e]) > 0.f ? 1u : 0u) << (8 * v + e);
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(S::NW * 64, 2) void pair_kernel(const PairArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float x = acc2[pt][r];
-                if constexpr (MODE == 0) x = fmaxf(x, 0.f);
+                if constexpr (MODE == 0) x = relu_f(x);
                 out[r] = Elem<T>::from_f(x);
             }
             i32x2_t pk;

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
                     T out[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        out[e] = Elem<T>::from_f(fmaxf(acc[c2][8 * v + e], 0.f));
+                        out[e] = Elem<T>::from_f(relu_f(acc[c2][8 * v + e]));
                         if constexpr (EMIT) obits |= (Elem<T>::to_f(out[e]) > 0.f ? 1u : 0u) << (8 * v + e);
                     }
                     __builtin_memcpy(&rv[v], out, 16);
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void pairs_kernel(const PairsArgs a) {
         for (int pt = 0; pt < 4; ++pt) {
             T out[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) out[r] = Elem<T>::from_f(fmaxf(acc2[pt][r], 0.f));
+            for (int r = 0; r < 4; ++r) out[r] = Elem<T>::from_f(relu_f(acc2[pt][r]));
             i32x2_t pk;
             __builtin_memcpy(&pk, out, 8);
             *(i32x2_t*)(sA + e2[pt]) = pk;                     // the src tile of this stage: every wave is past GEMM 1

@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? URSO_PW_OCC : 2)) void pw_kernel(c
                     const int c = v * VE + e;
                     float y = acc[i][c >> 2][c & 3] + bv[c];
                     if constexpr (HAS_ADD) y += Elem<T>::to_f(ea[e]);
-                    y = a.relu ? fmaxf(y, 0.f) : y;
+                    y = a.relu ? relu_f(y) : y;
                     if constexpr (HAS_MASK) y = (Elem<T>::to_f(em[e]) > 0.f) ? y : 0.f;
                     if constexpr (MASKK == 2) y = ((rbit[i * NV + v] >> (8 * fg + e)) & 1u) ? y : 0.f;
                     eo[e] = Elem<T>::from_f(y);

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(512, 2) void pwx_kernel(const PxArgs a) {
                     const int c = v * VE + e;
                     float y = acc[i][c >> 2][c & 3] + bv[c];
                     if constexpr (HAS_ADD) y += Elem<T>::to_f(ea[e]);
-                    y = a.relu ? fmaxf(y, 0.f) : y;
+                    y = a.relu ? relu_f(y) : y;
                     if constexpr (HAS_MASK) y = (Elem<T>::to_f(em[e]) > 0.f) ? y : 0.f;
                     if constexpr (MASKK == 2) y = ((rbit[i * NV + v] >> (8 * fg + e)) & 1u) ? y : 0.f;
                     eo[e] = Elem<T>::from_f(y);

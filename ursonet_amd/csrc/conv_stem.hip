@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void stem_kernel(const StemArgs a) {
             for (int v = 0; v < 2; ++v) {
                 T o[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { float y = acc[r][8 * v + e]; y = a.relu ? fmaxf(y, 0.f) : y; o[e] = Elem<T>::from_f(y); }
+                for (int e = 0; e < 8; ++e) { float y = acc[r][8 * v + e]; y = a.relu ? relu_f(y) : y; o[e] = Elem<T>::from_f(y); }
                 i32x4_t ov; __builtin_memcpy(&ov, o, 16);
                 *(i32x4_t*)(sO + px * 128 + (((4 * cw + 2 * h + v) ^ ((px >> 1) & 7)) << 4)) = ov;
             }
@@ -184,8 +184,10 @@ int urso_stem_launch(const urso_conv_geom* g, int dt, int relu, const void* src,
 //     as three register groups of three rows with the patch-row fragment reuse of stem_kernel;
 //   * pooling works on integer KEYS: key = (16-bit value << 16) | priority, priority = 8 - (3 ky + kx) of the window tap the element
 //     would be.  For values >= 0 the 16-bit float patterns order like integers, so a signed max over the nine keys of a window is the
-//     window maximum AND its FIRST arg-max (the strict `>` scan of maxpool_fwd_kernel) in one v_max; negative values give negative keys
-//     and the ReLU is the final clamp max(key, 8).  Rows first: the three conv rows of a pooled row are other registers of the same lane
+//     window maximum AND its FIRST arg-max (the strict `>` scan of maxpool_fwd_kernel) in one v_max; the ReLU runs before the keys
+//     are built (relu_f: negatives become +0, a NaN stays) and a NaN's sign bit is cleared, so that its key is the largest of all and
+//     the window stores NaN as maxpool_fwd_kernel does; the final clamp max(key, 8) gives a window of zeros its first tap.
+//     Rows first: the three conv rows of a pooled row are other registers of the same lane
 //     (max3 of row 2p + 6, row 2p+1 with its +3 built in, row 2p+2); then the column neighbours over DPP wave_shl:1 fused into v_max_i32
 //     (lane = conv column): T(odd l) = max(P(l), P(l+1)), window(even l) = max(P(l) + 2, T(l+1)); filters 8..15 then move into the idle odd
 //     lanes so that the packing runs on 8 registers with every lane at work;
@@ -339,7 +341,10 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StempArgs a) {
                 const int c = (((base + r) & 1) ? cL + 3 : cL) | (cy0 + base + r >= a.OH ? (int)0x80000000 : 0);
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
-                    const uint32_t p = sp_pack2<T>(acc[r][e], acc[r][e + 1]);
+                    // the ReLU first (negatives -> +0: their keys tie below the window's first tap, as under the final clamp; a NaN stays),
+                    // so that a sign bit left in the pair is a NaN's; cleared, its key is above every other (+inf included), the window
+                    // keeps it and the clamp leaves it -- with the bit set the key would be negative and the clamp would store 0
+                    const uint32_t p = sp_pack2<T>(relu_f(acc[r][e]), relu_f(acc[r][e + 1])) & 0x7FFF7FFFu;
                     K[r][e] = (int)((p << 16) | (uint32_t)c);
                     K[r][e + 1] = (int)((p & 0xFFFF0000u) | (uint32_t)c);
                 }

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void wino_out_kernel(const float* __restrict__
             const float bb = bias ? bias[n8 * 8 + e] : 0.f;
             y0[e] = s[r][0][e] + s[r][1][e] + s[r][2][e] + bb;
             y1[e] = s[r][1][e] - s[r][2][e] - s[r][3][e] + bb;
-            if (relu) { y0[e] = fmaxf(y0[e], 0.f); y1[e] = fmaxf(y1[e], 0.f); }
+            if (relu) { y0[e] = relu_f(y0[e]); y1[e] = relu_f(y1[e]); }
         }
         const int yy = 2 * ty + r, x0 = 2 * tx;
         if (yy < H) {

@@ -33,7 +33,8 @@ __global__ void maxpool_fwd_kernel(int B, int H, int W, int C, const T* __restri
                 i32x4_t raw = *(const i32x4_t*)(x + (((size_t)b * H + iy) * W + ix) * C + cv * VE);
                 T e[VE]; __builtin_memcpy(e, &raw, 16);
 #pragma unroll
-                for (int q = 0; q < VE; ++q) { float v = Elem<T>::to_f(e[q]); if (v > best[q]) { best[q] = v; arg[q] = ky * 3 + kx; } }
+                // a NaN is taken (v != v) and then kept: nothing compares greater than it and no later tap is itself taken unless NaN
+                for (int q = 0; q < VE; ++q) { float v = Elem<T>::to_f(e[q]); if (v > best[q] || v != v) { best[q] = v; arg[q] = ky * 3 + kx; } }
             }
         }
         T o[VE]; uint8_t ab[VE];
